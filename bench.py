@@ -12,6 +12,12 @@ return code.  `--dry-run-launch` prints the child commands and their environment
 One step = dropout-mask generation + forward + 3-term loss + backward + [all-reduce] + global-norm clip + Adam on one
 synthetic batch of 32 utterances per GPU (SURVEY.md section 8d shapes, vanilla-lj-hifi-stop dims: 4 speaker tokens,
 fp32, random-init weights).  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the headline line, nothing else.  `--full` adds the secondary
+measurements: the HIP-event breakdown of the timed steps and its roofline, every rank's record, the all-reduce alone and in its
+other mode, the steps at float32_matmul_precision=high, the decode rates and the CPU-oracle baseline.  `--dump-outputs DIR` writes
+what the last timed step computed (rank 0's shard) as DIR/<name>.npy; inputs, weights and dropout masks are seeded, and that step
+starts from the run's initial state, so two runs - or two builds - with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -128,6 +134,35 @@ def cpu_baseline(dims, batch, t_cap=200, b_cap=32, timed_steps=3, n_inf=100):
                 decode_sample=f"{n_inf} autoregressive steps, batch {b_cap}, includes encoder and postnet of the call, {dti:.1f} s")
 
 
+DUMP_MAX_ELEMS = 3 * 2 ** 20       # per dumped output; larger ones are written as a fixed, seeded sample (whole dump < 64 MB)
+DUMP_STATE_ELEMS = 2 ** 20         # sample of the flat parameter and gradient buffers (28 M values each at the bench dims)
+
+
+def dump_outputs(out_dir, loss3, outs, ps) -> dict:
+    """What the last timed step computed, as float32 / float64 .npy files: its loss terms, its forward outputs (the model's
+    return values) and the state the step leaves behind (parameters after Adam, their gradients, the BatchNorm running
+    statistics).  Returns {name: "full" | "sample of N"}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(loss=loss3, mel_outputs=outs[0], mel_outputs_postnet=outs[1], gate_outputs=outs[2], alignments=outs[3],
+                  params=ps.flat, grads=ps.grad, bn_running_stats=ps.buf_flat)
+    written, nbytes = {}, 0
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        cap = DUMP_STATE_ELEMS if name in ("params", "grads") else DUMP_MAX_ELEMS
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(1000 + i).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+            written[name] = f"sample of {cap} of {t.numel()} values (flat indices drawn with numpy seed {1000 + i})"
+        else:
+            written[name] = "full"
+        nbytes += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert nbytes <= 64 * 2 ** 20, nbytes
+    return written
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -242,7 +277,14 @@ def main():
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="with --gpus N and no launcher: print the N child commands / environments as one JSON line and exit (no GPU call)")
     ap.add_argument("--launch-timeout", type=float, default=0.0, help="launcher: seconds after which all ranks are ended (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements (segment breakdown and roofline, per-rank records, all-reduce alone and in the "
+                         "other mode, float32_matmul_precision=high, decode rates, CPU baseline; the --no-* flags still drop theirs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed on rank 0 as DIR/<name>.npy (float32 / float64, < 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_run_launch):
         sys.exit(launch_ranks(args, sys.argv[1:]))     # this process is the launcher: it never touches the GPU
@@ -300,26 +342,52 @@ def main():
         torch.cuda.synchronize()
 
     # do the engine's two streams run side by side in THIS process (GPU_MAX_HW_QUEUES, tacotron2_amd/__init__.py)?  Trainer checks
-    # it when data-parallel (a live communicator brings streams of its own); measured here at N = 1 too, reported in the line
+    # it when data-parallel (a live communicator brings streams of its own); measured here at N = 1 too, reported in the line.  Part
+    # of a plain run's set-up: a failed check replaces the side stream, and the timed steps run on the one that passed
     qc = tr.queue_check or tr.engine.ensure_concurrent_streams()
+
+    # --dump-outputs: the last timed step starts again from the state this run started from (weights, BatchNorm statistics, zero
+    # Adam moments, step counter - so also the first step's dropout masks and learning rate).  Two runs then hand that step the
+    # same inputs; without it the last-bit differences of the split-K atomics, carried through W + K - 1 Adam updates, make two
+    # runs of one build write outputs that drift apart.  The restore is device copies on the main stream in front of that step
+    # (after the previous step's Adam, which all of its side-stream work precedes), no host synchronisation.
+    start = None
+    if args.dump_outputs:
+        start = dict(flat=ps.flat.clone(), buf=ps.buf_flat.clone(), nbt=dict(ps.num_batches_tracked), step=tr.global_step)
+
+    def restore_start():
+        ps.flat.copy_(start["flat"])
+        ps.buf_flat.copy_(start["buf"])
+        if ps.exp_avg is not None:
+            ps.exp_avg.zero_()
+            ps.exp_avg_sq.zero_()
+        ps.num_batches_tracked.update(start["nbt"])
+        tr.global_step = start["step"]
 
     # (the batch is fixed and already at the global shape: no per-step shape negotiation - it would put a host read of an
     #  all-reduce result in front of every step)
     for _ in range(args.warmup):
         tr.train_step(batch, padded=True)
     sync()
-    tr.engine.profile = True
+    tr.engine.profile = args.full            # HIP events at the segment boundaries of the timed steps: --full only
     step_marks = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss3, _ = tr.train_step(batch, padded=True)
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1:
+            restore_start()
+        loss3, outs = tr.train_step(batch, padded=True)
         step_marks.append(tr.engine.marks)   # (train_step starts a new list per step; the events are read after the timed region)
     t_enq = time.perf_counter() - t0         # host: all steps enqueued (far below dt when the GPU is the bound, as it should be)
     sync()
     dt = time.perf_counter() - t0
     tr.engine.profile = False
     tr.engine.check_persistent_kernels()     # (after the timed region: a host read of the persistent launches' timeout flag)
-    seg = tr.engine.segment_times_ms()       # last timed step (events recorded inside the timed region)
+    # the last timed step's results, before anything else runs: loss3 is an engine workspace that later steps overwrite
+    loss_last = [float(x) for x in loss3.cpu()]
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, loss3, outs, ps)
+        print(f"[bench] wrote {len(dumped)} arrays of the last timed step to {args.dump_outputs}: {dumped}", file=sys.stderr, flush=True)
+    seg = tr.engine.segment_times_ms()       # last timed step (events recorded inside the timed region; empty without --full)
     # per rank, over all timed steps: GPU time of a step on the main stream (first to last mark), of which the gradient all-reduce
     # segment (RCCL: the wire AND the wait for the slowest rank's backward) - so that "a rank was slow" (its own_step_ms - allreduce_ms
     # is the largest) and "the wire was slow" (allreduce_ms large on every rank) can be told apart in a scaling run
@@ -332,7 +400,7 @@ def main():
                 gpu_step_ms=sum(gpu_ms) / max(len(gpu_ms), 1), allreduce_ms=sum(ar_ms) / max(len(ar_ms), 1),
                 valid_frames=float(batch["mel_spectrogram_len"].sum()), queue_check_ok=(qc or {}).get("ok"))
     per_rank = [mine]
-    if world > 1:
+    if world > 1 and args.full:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -343,7 +411,7 @@ def main():
     # ... and the gradient all-reduce ALONE, behind a barrier (nobody waits for a slower rank's backward): the wire time of the 112.5 MB
     # buffer, to set against the `allreduce` segment of the step (wire + waiting)
     allreduce_alone = None
-    if tr.dp:
+    if args.full and tr.dp:
         sync()
         ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dist.all_reduce(ps.grad)
@@ -364,7 +432,7 @@ def main():
     # behind the frame loop) for a few steps, outside the judged region: the default was chosen at world size 1, where the collective
     # is a device-local pass; a real multi-GPU run is the only place the choice can be measured.  Every rank takes part.
     other_mode = None
-    if tr.dp and not tr.sync_bn:
+    if args.full and tr.dp and not tr.sync_bn:
         was = tr.overlap_allreduce
         tr.overlap_allreduce = not was
         tr.engine.grad_tail_hook = tr._start_tail_allreduce if tr.overlap_allreduce else None
@@ -389,7 +457,7 @@ def main():
     # "high", run/train.py:170: three of the six bf16 partial products; mel L1 against the fp32 oracle stays < 1e-4,
     # tests/test_gpu_fullsize.py).  Reported beside the judged fp32-exact line, never as `value`.
     high = None
-    if rank == 0 and world == 1 and args.matmul_precision == "highest" and not args.no_high:
+    if args.full and rank == 0 and world == 1 and args.matmul_precision == "highest" and not args.no_high:
         set_float32_matmul_precision("high")
         for _ in range(2):
             tr.train_step(batch, padded=True)
@@ -408,7 +476,7 @@ def main():
     # fixed 860 frames with the stop checks live (random weights never emit a stop), rank 0 only, outside the timed region
     decode = None
     decode_b1 = None
-    if rank == 0 and world == 1 and not args.no_decode:      # (reported by the N = 1 run only: the other ranks would idle)
+    if args.full and rank == 0 and world == 1 and not args.no_decode:      # (reported by the N = 1 run only: the other ranks would idle)
         ib = ljspeech_batch(64, seed=4321, num_speakers=4)
         eng = tr.engine
         ci, cl, spk = ib["chars_idx"].to(dev), ib["chars_idx_len"].to(dev), ib["speaker_id"].to(dev)
@@ -475,19 +543,13 @@ def main():
         decode["sorted_by_length_steps_per_s"] = n_dec / (time.perf_counter() - t2)
 
     if rank == 0:
-        Ef = 512
         ms_step = dt / args.steps * 1e3
         value = float(frames[0]) * args.steps / dt
-        # roofline of the teacher-forced decoder frame loop (north_star's "fused decoder step"): T decoder steps are
-        # executed by {pre_att GEMM, attention chain, pre_dec GEMM, decoder-LSTM chain, projection GEMM}
-        dec_fwd_ms = sum(v for k, v in seg.items() if k.startswith("fwd.dec."))
-        alg = decoder_step_bytes(B, L, Ef) * T
-        achieved = alg / (dec_fwd_ms * 1e-3) / 1e9 if dec_fwd_ms > 0 else 0.0
         out = dict(metric="mel-frames/sec (node), LJSpeech-shaped teacher-forced train step, b=32/GPU, fp32",
                    value=value, unit="mel-frames/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
                    ms_per_step=ms_step, higher_is_better=True, scaling="weak", vs_baseline=None,
                    dtype="f32" if args.matmul_precision == "highest" else f"f32 (GEMMs at float32_matmul_precision={args.matmul_precision})",
-                   data="synthetic",
+                   data="synthetic", full=args.full,
                    config=dict(workload="LJSpeech single-speaker train (vanilla-lj-hifi-stop.json dims), batch 32 per GPU, fp32",
                                global_batch=B * world, L=L, T=T, valid_frames_per_step=float(frames[0]),
                                padded_frames_per_step=float(frames[1]), parallelism=f"dp{world}",
@@ -503,24 +565,32 @@ def main():
                                                  "over its own gloo group while step k runs: nothing on the step path either)",
                                predicted_unmeasured=PREDICTED_SCALING),
                    padded_frames_per_s=float(frames[1]) * args.steps / dt,
-                   loss=[float(x) for x in loss3.cpu()],
-                   roofline=dict(bound="hbm", kernel="teacher-forced decoder frame loop, forward (pre_att GEMM + attention "
-                                 "chain + pre_dec GEMM + decoder-LSTM chain + projection GEMM = T fused decoder steps)",
-                                 achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
-                                 traffic=None, algorithmic_bytes_per_step=decoder_step_bytes(B, L, Ef),
-                                 us_per_decoder_step=dec_fwd_ms * 1e3 / T if T else None),
-                   segments_ms={k: round(v, 3) for k, v in seg.items()},
-                   per_rank=[{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in per_rank],
-                   allreduce_alone=allreduce_alone, other_allreduce_mode=other_mode, decode=decode, decode_b1=decode_b1, matmul_precision_high=high)
-        # HBM-side bytes of the same kernels from rocprofv3 PMC passes (FETCH_SIZE x2-corrected + WRITE_SIZE, profiles/):
-        # recorded offline because counters cannot be collected inside this process
-        tj = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tj):
-            with open(tj) as f:
-                tinfo = json.load(f)
-            if tinfo.get("L") == L and tinfo.get("B") == B:
-                out["roofline"]["traffic"] = tinfo["bytes_per_decoder_step_fwd"] * T
-        if world == 1 and not args.no_cpu_baseline:
+                   loss=loss_last)
+        if args.full:
+            # roofline of the teacher-forced decoder frame loop (north_star's "fused decoder step"): T decoder steps are
+            # executed by {pre_att GEMM, attention chain, pre_dec GEMM, decoder-LSTM chain, projection GEMM}
+            Ef = 512
+            dec_fwd_ms = sum(v for k, v in seg.items() if k.startswith("fwd.dec."))
+            alg = decoder_step_bytes(B, L, Ef) * T
+            achieved = alg / (dec_fwd_ms * 1e-3) / 1e9 if dec_fwd_ms > 0 else 0.0
+            out.update(roofline=dict(bound="hbm", kernel="teacher-forced decoder frame loop, forward (pre_att GEMM + attention "
+                                     "chain + pre_dec GEMM + decoder-LSTM chain + projection GEMM = T fused decoder steps)",
+                                     achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
+                                     traffic=None, algorithmic_bytes_per_step=decoder_step_bytes(B, L, Ef),
+                                     us_per_decoder_step=dec_fwd_ms * 1e3 / T if T else None),
+                       segments_ms={k: round(v, 3) for k, v in seg.items()},
+                       per_rank=[{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in per_rank],
+                       allreduce_alone=allreduce_alone, other_allreduce_mode=other_mode, decode=decode, decode_b1=decode_b1,
+                       matmul_precision_high=high)
+            # HBM-side bytes of the same kernels from rocprofv3 PMC passes (FETCH_SIZE x2-corrected + WRITE_SIZE, profiles/):
+            # recorded offline because counters cannot be collected inside this process
+            tj = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tj):
+                with open(tj) as f:
+                    tinfo = json.load(f)
+                if tinfo.get("L") == L and tinfo.get("B") == B:
+                    out["roofline"]["traffic"] = tinfo["bytes_per_decoder_step_fwd"] * T
+        if args.full and world == 1 and not args.no_cpu_baseline:
             dims = {k: v for k, v in VANILLA.items()}
             print("[bench] GPU timing done; timing the CPU oracle baseline (bounded sample)...", file=sys.stderr, flush=True)
             out["cpu_baseline"] = cpu_baseline(dims, cpu_batch, t_cap=200, b_cap=min(32, args.batch))

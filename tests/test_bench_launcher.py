@@ -12,7 +12,9 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 
 def _env():
-    return {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    # (without GPU_MAX_HW_QUEUES: the launch plan carries the package's own default unless the caller sets one)
+    return {k: v for k, v in os.environ.items()
+            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "GPU_MAX_HW_QUEUES")}
 
 
 def test_dry_run_launch_prints_one_child_per_rank_and_touches_no_gpu():

@@ -206,7 +206,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     rank; the 8-GPU run is the driver's)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "4", "--backend", "gloo", "--share-gpu"]
+           "--batch", "4", "--backend", "gloo", "--share-gpu", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -235,7 +235,7 @@ def test_bench_four_ranks_rehearsal_on_one_gpu(tmp_path):
     every rank padded to the global shape, the two-bucket all-reduce (`--overlap-allreduce`), one JSON line from rank 0."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", "29614", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-           "--batch", "3", "--backend", "gloo", "--share-gpu", "--overlap-allreduce"]
+           "--batch", "3", "--backend", "gloo", "--share-gpu", "--overlap-allreduce", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-12000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -245,6 +245,45 @@ def test_bench_four_ranks_rehearsal_on_one_gpu(tmp_path):
     assert d["value"] > 0 and d["scaling"] == "weak" and all(np.isfinite(d["loss"]))
     assert d["config"]["sync_batchnorm"] is False and d["config"]["allreduce"] == "2 buckets, tail overlapped with the encoder backward"
     assert "cpu_baseline" not in d and d["decode"] is None                     # N = 1 only
+
+
+def _bench_dump(out, steps, warmup):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--batch", "4", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    return r
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the plain run times exactly K steps, prints the headline line
+    without the secondary (`--full`) measurements, and writes the last timed step's loss, outputs and state as float32 / float64
+    arrays, 64 MB at most.  That step starts from the run's initial state, so another run - here one of a single step with no
+    warm-up, in another process - writes the same arrays to rounding (the split-K atomics' last bits)."""
+    out = tmp_path / "dump"
+    r = _bench_dump(out, 3, 1)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["n_gpus"] == 1
+    assert d["unit"] == "mel-frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    frames = d["config"]["valid_frames_per_step"]
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - frames) < 1e-6 * frames          # ms_per_step is the time of ONE timed step
+    assert not {"segments_ms", "roofline", "per_rank", "decode", "decode_b1", "matmul_precision_high", "cpu_baseline"} & set(d)
+    arrays = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(arrays) == {"loss", "mel_outputs", "mel_outputs_postnet", "gate_outputs", "alignments", "params", "grads",
+                           "bn_running_stats"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert arrays["loss"].tolist() == d["loss"]
+    T, L = d["config"]["T"], d["config"]["L"]
+    assert arrays["mel_outputs"].shape == arrays["mel_outputs_postnet"].shape == (4, T, 80) and arrays["gate_outputs"].shape == (4, T, 1)
+    assert arrays["alignments"].shape == (4, T, L) and arrays["params"].size == arrays["grads"].size == 2 ** 20
+    _bench_dump(tmp_path / "dump1", 1, 0)
+    for name, a in arrays.items():
+        b = np.load(tmp_path / "dump1" / (name + ".npy"))
+        # (Adam's first update is lr * g / (|g| + eps): a last-bit change of a tiny gradient moves its parameter more)
+        tol = (1e-4 if name == "params" else 1e-5) * max(1.0, float(np.abs(a).max()))
+        assert b.shape == a.shape and float(np.abs(a - b).max()) <= tol, (name, float(np.abs(a - b).max()), tol)
 
 
 def test_cli_vanilla_ljspeech_stop_config_batch2_ten_steps(tmp_path):

@@ -30,10 +30,12 @@ def test_dp_step_over_rccl_world1_is_the_single_process_step(extra):
 def test_bench_force_dp_runs_the_rccl_path_at_one_gpu():
     """`bench.py --gpus 1 --force-dp`: the driver's multi-GPU command line minus the launcher - process group over RCCL, both
     gradient buckets, the `allreduce` segment in the breakdown - so that the 8-GPU run is not the first time RCCL sees this code."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29655")
+    # the queue count is the package's own default (tacotron2_amd/__init__.py), not one the calling environment happens to set
+    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29655")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dp", "--overlap-allreduce", "--steps", "2",
-                        "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--no-decode", "--no-high"], cwd=ROOT, capture_output=True, text=True,
-                       timeout=900, env=env)
+                        "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline", "--no-decode", "--no-high"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["allreduce"].startswith("2 buckets") and "allreduce" in d["segments_ms"]

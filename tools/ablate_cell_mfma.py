@@ -22,7 +22,7 @@ for keep in (4, 2, 1):
         print(r.stderr[-1500:])
     for b in (32, 64):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--batch", str(b),
-                            "--no-cpu-baseline", "--no-decode", "--no-high"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--no-decode", "--no-high"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
         js = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if js:
             d = json.loads(js[-1]); s = d["segments_ms"]
