@@ -233,7 +233,19 @@ int t2_lstm_seq_bwd(const T2LstmBwdStep* base, const T2LstmBwdStride* inc, int n
  *                      to L4 = round_up(L,4) floats (16-byte aligned; must be 16-byte aligned itself)
  * Any text length whose per-sample images fit the 160 KB of LDS (energies kernel: 24 bytes per position - about 6,000 characters);
  * the kernels walk texts above 256 positions in rounds.
- * Writes w_out (new attention weights = the alignments row), cum_out = cum_prev + w, ctx_out (context). */
+ * Writes w_out (new attention weights = the alignments row), cum_out = cum_prev + w, ctx_out (context).
+ *
+ * Windowed attention (inference only; ESPnet's attention constraint, Mozilla TTS's `windowing`): with win_peak != NULL,
+ * win_back, win_fwd >= 0, frame t of utterance b attends only to the positions
+ *     max(0, m[b] - win_back) <= l <= min(len[b] - 1, m[b] + win_fwd),   m[b] = win_peak[0][b] = the previous frame's peak
+ * (every other position gets energy -inf before the softmax: its weight is exactly 0 and w_out / cum_out are not written
+ * there).  The step then writes win_peak[0][b] = m_t[b], the argmax of its weights (lowest position on ties, as torch.argmax).
+ * Before the first frame the caller zero-fills row 0 (m_{-1} = 0).  Row 1 is the step's own hand-off from the energies to the
+ * context launch (the previous peak: a launch's readers of the old peak and its writer of the new one are different workgroups).
+ * The location features still read w_prev / cum_prev over the full row (the window +- (Kl-1)/2 positions), so w_prev must be
+ * the previous frame's full weights row (zero outside its window).  Energies, softmax and context touch only the window: the
+ * work and bytes per frame follow its width, not L.  The cumulative weights are updated in place (cum_out == cum_prev
+ * required), th_out must be NULL.  A window as wide as the text (win_back, win_fwd >= L) is the unconstrained step. */
 typedef struct {
     int B, L, A, Ad, Ef, Kl;
     const float* att_h; int64_t ldh;
@@ -247,6 +259,8 @@ typedef struct {
     float* ctxt_out; int ctxt_col0;          /* optional x16-tiled copy of the context (see T2LstmStep) */
     uint64_t* clk;                           /* diagnostic, normally NULL: 32 device words; workgroup (0,0) stamps the shader
                                                 clock (s_memtime) at phase boundaries: energies [0..3], context [8..13] */
+    int win_back, win_fwd;                   /* attention window (with win_peak): see "Windowed attention" above */
+    int32_t* win_peak;                       /* NULL = unconstrained (the whole text); else [2][B] int32 device words */
 } T2AttnStep;
 int t2_attn_fold_location(const float* Wd, const float* Wc, float* U, int Ad, int F, int Kl, void* stream);
 int t2_attn_step_fwd(const T2AttnStep* s, void* stream);
@@ -440,6 +454,10 @@ typedef struct {
     int32_t* done; int32_t* state;
     const float* dec_pre;            /* optional [B][4D]: per-utterance term added to the decoder-LSTM pre-activations of
                                         every frame (controls . W_ih[:, A+Ef:]^T, model/decoder.py:94-99) */
+    int win_back, win_fwd;           /* attention window (T2AttnStep), >= 0; only read when win_peak != NULL */
+    int32_t* win_peak;               /* NULL = unconstrained attention (as before); else [2][B] int32, zero-filled by the caller
+                                        before frame 0: the windowed attention step of every frame (T2AttnStep), with the
+                                        cumulative weights kept in place in cum slot 0 (slot 1 unused) */
 } T2Infer;
 int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream);
 /* proj[g] [nframes][Bg[g]][ld_proj] for g < ngroups (<= 64 groups of up to 64 utterances) -> lengths [sum Bg] int64,

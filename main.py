@@ -3,16 +3,38 @@
 
     python main.py --config C --device N train --speech-dir S [--results-dir R] [--resume-ckpt K] [--finetune --finetune-steps n]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
+                                                  [--attention-window BACK,FWD]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
+                                                  [--attention-window BACK,FWD]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
+                                                  [--attention-window BACK,FWD]
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
 
 Other reference sub-commands (preprocess, server) are data preparation / demo tooling outside the hot-path scope
 (SURVEY.md section 2).  Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N
 main.py --config C train ...` (one process per GPU, RCCL gradient all-reduce)."""
+import re
+
 import click
 
 from tacotron2_amd.run.common import load_config
+
+
+def parse_attention_window(ctx, param, value):
+    """--attention-window BACK,FWD -> (back, fwd): two integers >= 0, anything else a usage error."""
+    if value is None:
+        return None
+    parts = [p.strip() for p in value.split(",")]
+    if len(parts) != 2 or not all(re.fullmatch(r"[0-9]+", p) for p in parts):
+        raise click.BadParameter(f"expected BACK,FWD (two integers >= 0, e.g. 1,3), got {value!r}")
+    return int(parts[0]), int(parts[1])
+
+
+attention_window_option = click.option(
+    "--attention-window", required=False, type=str, default=None, callback=parse_attention_window, metavar="BACK,FWD",
+    help="Windowed (monotonic) attention: each decoder frame attends only to the text positions from BACK before to FWD after "
+         "the previous frame's attention peak (ESPnet's attention constraint; 1,3 is the usual value). Default: off, the whole "
+         "text.")
 
 
 @click.group()
@@ -59,7 +81,8 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--speaker-id", required=False, type=int, default=None, help="Speaker ID for a multi-speaker model")
 @click.option("--controls", required=False, type=str, default=None, help="If controls are enabled, a comma-separated list of values to pass into the model. Defaults to all 0 values.")
 @click.option("--description", required=False, type=str, default=None, help="Path of a precomputed description embedding (.pt / .npy, pooler_output of bert-base-uncased); raw text needs the BERT weights (unavailable offline)")
-def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description):
+@attention_window_option
+def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window):
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for speech!")
     from tacotron2_amd.run.say import do_say
@@ -67,7 +90,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
     do_say(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
            extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, text=text, output=out,
            speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
-           description=description)
+           description=description, attention_window=attention_window)
 
 
 @main.command()
@@ -79,7 +102,8 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
 @click.option("--batch-size", required=False, type=int, default=8, help="Utterances decoded together (reference: 8; up to 64 per decode group).")
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit", required=False, type=int, default=None, help="Only the first n utterances of the test manifest.")
-def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit):
+@attention_window_option
+def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window):
     """Synthesise the test manifest (run/test.py of the reference): one wav per utterance + failures.csv."""
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
@@ -87,7 +111,8 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
     c = ctx.obj["config"]
     do_test(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
             extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
-            hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit)
+            hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit,
+            attention_window=attention_window)
 
 
 @main.command()
@@ -99,13 +124,16 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
 @click.option("--samples-per-speaker", required=False, type=int, default=200, help="Utterances drawn per speaker (reference: 200).")
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit-overrides", required=False, type=int, default=None, help="Only the first n of the 51 control overrides.")
-def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides):
+@attention_window_option
+def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides,
+                     attention_window):
     """The test manifest under 51 control-vector overrides (run/test_correlation.py of the reference)."""
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
     from tacotron2_amd.run.test_correlation import do_test_correlation
     c = ctx.obj["config"]
-    do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
+    model_config = c["model"] if attention_window is None else dict(c["model"], attention_window=list(attention_window))
+    do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=model_config,
                         extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
                         hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, samples_per_speaker=samples_per_speaker,
                         max_len=max_len, limit_overrides=limit_overrides)

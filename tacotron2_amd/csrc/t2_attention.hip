@@ -38,6 +38,7 @@ struct AttnK {
     float* ctx_out; long ldctx; float* ctx_out2; long ldctx2;
     float* ctxt_out; int ctxt_col0; long ctxt_cs;
     unsigned long long* clk;   // diagnostic: shader-clock stamps of workgroup (0,0) (T2AttnStep.clk), or null
+    int win_back, win_fwd; int32_t* win_peak;   // windowed kernels only (T2AttnStep.win_*): bounds clamped to [0, L]
 };
 // In-kernel phase stamps exist in the DIAGNOSTIC build only (-DT2_STAMPS, tacotron2_amd/build.py --stamps): each one is a branch
 // that ends a basic block, and the instruction scheduler does not move loads or MFMAs of the next phase across it.
@@ -61,7 +62,9 @@ template <int NTH>
 struct StageRegs { float uv[1024 / NTH]; float iv[1024 / NTH]; };
 
 // DO_INP / DO_U: which of the two images a kernel needs (the matrix-pipe ds kernel takes its filter operand from global memory)
-template <int NTH, bool DO_INP = true, bool DO_U = true>
+// WIN: a separate instantiation for the windowed energies kernel (run-time position offset), so that the constant offsets of
+// the other callers are still propagated into theirs
+template <int NTH, bool DO_INP = true, bool DO_U = true, bool WIN = false>
 __device__ __forceinline__ void stage_issue(StageRegs<NTH>& r, const float* w_prev, long ldw, const float* cum_prev, long ldcum,
                                             const float* U, const float* dummy, int b, int j, int L, int Lp, int tid, int kpad = KPAD,
                                             int loff = 0 /* text position of image index kpad (position tiles of long texts) */) {
@@ -161,7 +164,7 @@ __device__ __forceinline__ Bf3 t2_split1(float v) {
     return s;
 }
 
-template <int NTH, bool DO_U = true>
+template <int NTH, bool DO_U = true, bool WIN = false>
 __device__ __forceinline__ void stage_commit_split(const StageRegs<NTH>& r, unsigned* PX, unsigned* UX, const float* w_prev, long ldw,
                                                    const float* cum_prev, long ldcum, const float* dummy, int b, int L, int Lp, int tid,
                                                    int kpad = KPAD, int loff = 0) {
@@ -211,6 +214,18 @@ __device__ __forceinline__ void stage_commit_split(const StageRegs<NTH>& r, unsi
     }
 }
 
+// Attention window of utterance b for this frame (WIN kernels): text positions [lo, lo + W) with lo = max(0, m - back),
+// lo + W - 1 = min(len - 1, m + fwd), m = the previous frame's peak (clamped into the text, so that no index leaves it).
+__device__ __forceinline__ void attn_window(const AttnK& p, int m, int len, int& lo, int& W) {
+    m = imin(imax(m, 0), p.L - 1);
+    lo = imax(m - p.win_back, 0);
+    const int hi = imax(imin(imin(len, p.L) - 1, m + p.win_fwd), lo);
+    W = hi - lo + 1;
+}
+
+// WIN: the windowed form - only the W positions of the window [lo, lo + W) are computed (their energies land at their text
+// positions of e_part); the location inputs are staged over the window plus KPAD positions on either side.
+template <bool WIN>
 __device__ __forceinline__ void attn_energy_body(const AttnK& p, const int b, const int j, float* sm) {
     const int tid = threadIdx.x, lane = tid & 63;
     [[maybe_unused]] const bool stamp = b == 0 && j == 0 && tid == 0;
@@ -218,15 +233,23 @@ __device__ __forceinline__ void attn_energy_body(const AttnK& p, const int b, co
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7
     const int n = lane & 15, q = lane >> 4;                   // MFMA column = dim of the slice (also this lane's A row), row group
     const int a = j * 16 + n;
-    const int L = p.L, NG = (L + 3) >> 2, L4 = 4 * NG, NT = (L + 15) >> 4, Lp = 4 * NG + 48;
+    const int Lt = p.L;                                       // text length (row strides)
+    int lo = 0, Lw = Lt;                                      // positions computed: lo .. lo + Lw - 1
+    if constexpr (WIN) {
+        const int m = p.win_peak[b];
+        attn_window(p, m, p.len[b], lo, Lw);
+        if (j == 0 && tid == 0) p.win_peak[p.B + b] = m;     // the previous peak, handed to this frame's context launch
+    }
+    const int L = Lw, NG = (L + 3) >> 2, L4 = 4 * NG, NT = (L + 15) >> 4, Lp = 4 * NG + 48;
     float* qs = sm;                                           // [16]
     unsigned* PX = reinterpret_cast<unsigned*>(qs + 16);      // [3][2*Lp]  haloed (w_prev, cum_prev) at index l + 15, neighbour pairs
     unsigned* UX = PX + 6 * Lp;                               // [3][16*40] folded location filter rows of this slice (tap 31 = 0)
-    const long rowoff = ((long)b * p.Ad + a) * L;
+    const long rowoff = ((long)b * p.Ad + a) * Lt + lo;
 
     // ---- issue first: the haloed location inputs and filter rows (the only loads the convolution waits for) ----
     StageRegs<ENT> sr;
-    stage_issue<ENT>(sr, p.w_prev, p.ldw, p.cum_prev, p.ldcum, p.U, p.pmT, b, j, L, Lp, tid);
+    if constexpr (WIN) stage_issue<ENT, true, true, true>(sr, p.w_prev, p.ldw, p.cum_prev, p.ldcum, p.U, p.pmT, b, j, Lt, Lp, tid, KPAD, lo);
+    else stage_issue<ENT>(sr, p.w_prev, p.ldw, p.cum_prev, p.ldcum, p.U, p.pmT, b, j, L, Lp, tid);
     // ---- issue: processed-memory values of this wave's first two position tiles (mt = w, w + 8) + v ----
     float pmv[2][4];
     const float va = p.v[a];
@@ -248,7 +271,8 @@ __device__ __forceinline__ void attn_energy_body(const AttnK& p, const int b, co
 #pragma unroll
         for (int aa = 0; aa < 2; ++aa) wv[aa][i] = *reinterpret_cast<const f32x4*>(wq0 + (long)aa * p.A + k);
     }
-    stage_commit_split<ENT>(sr, PX, UX, p.w_prev, p.ldw, p.cum_prev, p.ldcum, p.pmT, b, L, Lp, tid);
+    if constexpr (WIN) stage_commit_split<ENT, true, true>(sr, PX, UX, p.w_prev, p.ldw, p.cum_prev, p.ldcum, p.pmT, b, Lt, Lp, tid, KPAD, lo);
+    else stage_commit_split<ENT>(sr, PX, UX, p.w_prev, p.ldw, p.cum_prev, p.ldcum, p.pmT, b, L, Lp, tid);
     __syncthreads();   // planes visible
     T2_STAMP(p, stamp, 1);
     // ---- fragments: filter rows of this lane's dim (B: taps 8q .. 8q+7 of channel c) and a tile's Toeplitz rows
@@ -332,7 +356,7 @@ __device__ __forceinline__ void attn_energy_body(const AttnK& p, const int b, co
             if (l < L) th4[i] = t2_tanh(qa + acc[i] + pm4[i]);
         }
         // tanh stash rows are padded to 4*NG floats: one aligned 16-byte store per lane
-        if (p.th_out && lg < NG) *reinterpret_cast<f32x4*>(p.th_out + ((long)b * p.Ad + a) * L4 + 4 * lg) = th4;
+        if (!WIN && p.th_out && lg < NG) *reinterpret_cast<f32x4*>(p.th_out + ((long)b * p.Ad + a) * L4 + 4 * lg) = th4;
         // Sum over the slice's 16 dims = the 16 lanes of this row group, for 4 positions at once: two exchange steps leave lane
         // (n & 3) = i with position i's sum over its quad, two rotations add the four quads (4 DPP adds instead of 16).
         const float e0 = va * th4[0], e1 = va * th4[1], e2 = va * th4[2], e3 = va * th4[3];
@@ -346,7 +370,7 @@ __device__ __forceinline__ void attn_energy_body(const AttnK& p, const int b, co
         s += t2_dpp<0x124, 0xf>(0.f, s);                   // row_ror:4
         s += t2_dpp<0x128, 0xf>(0.f, s);                   // row_ror:8 -> lane n holds position (n & 3)'s sum over all 16 dims
         const int lw = 4 * lg + n;
-        if (n < 4 && lw < L) p.e_part[((long)b * (p.Ad >> 4) + j) * L + lw] = s;
+        if (n < 4 && lw < L) p.e_part[((long)b * (p.Ad >> 4) + j) * Lt + lo + lw] = s;
     };
     if (w < NT) epilogue(w, loc[0], pmv[0]);
     if (w + 8 < NT) epilogue(w + 8, loc[1], pmv[1]);
@@ -364,15 +388,28 @@ __device__ __forceinline__ void attn_energy_body(const AttnK& p, const int b, co
 __global__ __launch_bounds__(ENT, 4) void attn_energy_kernel(AttnK p) {
     T2_CHAIN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    attn_energy_body(p, blockIdx.x, blockIdx.y, sm);
+    attn_energy_body<false>(p, blockIdx.x, blockIdx.y, sm);
+}
+
+__global__ __launch_bounds__(ENT, 4) void attn_energy_win_kernel(AttnK p) {
+    T2_CHAIN_PRIO();
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    attn_energy_body<true>(p, blockIdx.x, blockIdx.y, sm);
 }
 
 
+// WIN: softmax and weighted sum over the window [lo, lo + W) only (every window position is < len); slice 0 writes the weights
+// and the cumulative weights of the window (cum in place: each position is read and written by the same thread) and the
+// frame's peak m_t = the lowest window position of the largest weight (torch.argmax) into win_peak[b].
+template <bool WIN>
 __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, const int es0, float* sm) {
     const int tid = threadIdx.x;
     [[maybe_unused]] const bool stamp = b == 0 && es0 == 0 && tid == 0;
     T2_STAMP(p, stamp, 8);
-    const int L = p.L, NA = p.Ad >> 4;
+    const int Lt = p.L, NA = p.Ad >> 4;
+    int lo = 0, Lw = Lt;
+    if constexpr (WIN) attn_window(p, p.win_peak[p.B + b], p.len[b], lo, Lw);
+    const int L = Lw;
     constexpr int NR = 24;
     const int WS = imax((L + 3) & ~3, 8 * NR);
     float* ws = sm;                       // [max(L rounded to 4, 8*NR)] softmax weights, zero past L
@@ -387,11 +424,11 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
     {
         const int lc = imin(tid, L - 1);
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) ev0[jj] = p.e_part[((long)b * NA + imin(jj, NA - 1)) * L + lc];
+        for (int jj = 0; jj < 8; ++jj) ev0[jj] = p.e_part[((long)b * NA + imin(jj, NA - 1)) * Lt + lo + lc];
     }
     __builtin_amdgcn_sched_barrier(0);   // keep these loads in front (the scheduler otherwise sinks them behind the rows below)
     // ---- issue: encoder-memory slice of the first 192 positions (independent of the softmax, consumed after it) ----
-    const float* mp = p.memory + (long)b * L * p.Ef + es0 + el;
+    const float* mp = p.memory + ((long)b * Lt + lo) * p.Ef + es0 + el;
     float mv[NR];
 #pragma unroll
     for (int i = 0; i < NR; ++i) mv[i] = mp[(long)imin(lg + 8 * i, L - 1) * p.Ef];
@@ -406,13 +443,13 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
                 for (int jj = 0; jj < 8; ++jj) ev[jj] = ev0[jj];
             } else {
 #pragma unroll
-                for (int jj = 0; jj < 8; ++jj) ev[jj] = p.e_part[((long)b * NA + imin(j0 + jj, NA - 1)) * L + lc];
+                for (int jj = 0; jj < 8; ++jj) ev[jj] = p.e_part[((long)b * NA + imin(j0 + jj, NA - 1)) * Lt + lo + lc];
             }
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) e += (j0 + jj) < NA ? ev[jj] : 0.f;
         }
         if (l < L) {
-            if (l >= len) e = -INFINITY;
+            if (!WIN && l >= len) e = -INFINITY;
             ws[l] = e;
             mx = fmaxf(mx, e);
         }
@@ -420,7 +457,7 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
     float cprev[2] = {0.f, 0.f};   // previous cumulative weights for the (<= 2) positions this thread writes
     if (es0 == 0 && p.cum_prev) {
 #pragma unroll
-        for (int r = 0; r < 2; ++r) cprev[r] = p.cum_prev[(long)b * p.ldcum + imin(tid + 256 * r, L - 1)];
+        for (int r = 0; r < 2; ++r) cprev[r] = p.cum_prev[(long)b * p.ldcum + lo + imin(tid + 256 * r, L - 1)];
     }
     T2_STAMP(p, stamp, 9);
     // Softmax with ONE workgroup exchange: every wave exponentiates against its own maximum and publishes (max, sum); the global
@@ -443,18 +480,34 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
     for (int ww = 0; ww < 4; ++ww) S += red[4 + ww] * (red[ww] == -INFINITY ? 0.f : expf(red[ww] - M));
     const float scale = (mw == -INFINITY ? 0.f : expf(mw - M)) / S;
     T2_STAMP(p, stamp, 10);
+    [[maybe_unused]] float bw = -1.f;
+    [[maybe_unused]] int bl = 0;
     for (int l = tid, r = 0; l < L; l += 256, ++r) {
         const float wv = ws[l] * scale;
         ws[l] = wv;
         if (es0 == 0) {
-            p.w_out[(long)b * p.ldwo + l] = wv;
+            p.w_out[(long)b * p.ldwo + lo + l] = wv;
             if (p.cum_out) {
-                const float cp = r < 2 ? cprev[r] : (p.cum_prev ? p.cum_prev[(long)b * p.ldcum + l] : 0.f);
-                p.cum_out[(long)b * p.ldco + l] = cp + wv;
+                const float cp = r < 2 ? cprev[r] : (p.cum_prev ? p.cum_prev[(long)b * p.ldcum + lo + l] : 0.f);
+                p.cum_out[(long)b * p.ldco + lo + l] = cp + wv;
+            }
+            if (WIN && wv > bw) { bw = wv; bl = l; }   // positions ascend: the first of equal weights stays
+        }
+    }
+    if constexpr (WIN) {
+        if (es0 == 0) {   // (value, position) maximum over the wave, lower position on ties; one pair per wave into red
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const float ov = __shfl_xor(bw, o);
+                const int ol = __shfl_xor(bl, o);
+                if (ov > bw || (ov == bw && ol < bl)) { bw = ov; bl = ol; }
             }
         }
     }
     __syncthreads();
+    if constexpr (WIN) {
+        if (es0 == 0 && (tid & 63) == 0) { red[tid >> 6] = bw; reinterpret_cast<int*>(red)[4 + (tid >> 6)] = bl; }
+    }
     T2_STAMP(p, stamp, 11);
     // all 24 weights are read from LDS before the first use (a guarded `load -> wait -> fma` chain costs 24 LDS latencies)
     float wv24[NR];
@@ -475,6 +528,18 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
         p.ctx_out[(long)b * p.ldctx + es0 + tid] = s2;
         if (p.ctx_out2) p.ctx_out2[(long)b * p.ldctx2 + es0 + tid] = s2;
         if (p.ctxt_out) { const int col = p.ctxt_col0 + es0 + tid; p.ctxt_out[(long)(col >> 4) * p.ctxt_cs + b * 16 + (col & 15)] = s2; }
+        if constexpr (WIN) {
+            if (es0 == 0 && tid == 0) {
+                float v = red[0];
+                int at = reinterpret_cast<const int*>(red)[4];
+                for (int ww = 1; ww < 4; ++ww) {
+                    const float ov = red[ww];
+                    const int ol = reinterpret_cast<const int*>(red)[4 + ww];
+                    if (ov > v || (ov == v && ol < at)) { v = ov; at = ol; }
+                }
+                p.win_peak[b] = lo + at;
+            }
+        }
     }
     T2_STAMP(p, stamp, 13);
 }
@@ -482,7 +547,13 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
 __global__ __launch_bounds__(256, 1) void attn_context_kernel(AttnK p) {
     T2_CHAIN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    attn_context_body(p, blockIdx.x, blockIdx.y * 32, sm);
+    attn_context_body<false>(p, blockIdx.x, blockIdx.y * 32, sm);
+}
+
+__global__ __launch_bounds__(256, 1) void attn_context_win_kernel(AttnK p) {
+    T2_CHAIN_PRIO();
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    attn_context_body<true>(p, blockIdx.x, blockIdx.y * 32, sm);
 }
 
 // U[a][c][k] = sum_f Wd[a][f] * Wc[f][c][k]
@@ -502,6 +573,12 @@ int check_attn(const T2AttnStep& s) {
     T2_REQUIRE(s.ldh % 4 == 0 && t2_aligned16(s.att_h) && t2_aligned16(s.Wq), "attention: att_h/Wq alignment");
     T2_REQUIRE(s.e_part && s.w_out && s.ctx_out && s.pmT && s.memory && s.len && s.U && s.v, "attention: null operand");
     T2_REQUIRE(!s.th_out || t2_aligned16(s.th_out), "attention: th_out must be 16-byte aligned (rows are padded to 4 floats)");
+    if (s.win_peak) {
+        T2_REQUIRE(s.win_back >= 0 && s.win_fwd >= 0, "attention: window bounds must be >= 0");
+        T2_REQUIRE(!s.th_out, "attention: the windowed step has no tanh stash (inference only)");
+        T2_REQUIRE(s.cum_prev && s.cum_out == s.cum_prev && s.ldco == s.ldcum,
+                   "attention: the windowed step updates the cumulative weights in place (cum_out == cum_prev)");
+    }
     return T2_OK;
 }
 
@@ -514,16 +591,28 @@ void to_ak(const T2AttnStep& s, AttnK& k) {
     k.ctx_out = s.ctx_out; k.ldctx = s.ldctx; k.ctx_out2 = s.ctx_out2; k.ldctx2 = s.ldctx2;
     k.ctxt_out = s.ctxt_out; k.ctxt_col0 = s.ctxt_col0; k.ctxt_cs = (long)((s.B + 15) / 16 * 16) * 16;
     k.clk = (unsigned long long*)s.clk;
+    k.win_back = s.win_back < s.L ? s.win_back : s.L; k.win_fwd = s.win_fwd < s.L ? s.win_fwd : s.L; k.win_peak = s.win_peak;
 }
 
 int launch_attn(const T2AttnStep& s, hipStream_t st) {
     AttnK k;
     to_ak(s, k);
-    const int NG = (s.L + 3) >> 2, Lp = 4 * NG + 48;
+    const bool win = s.win_peak != nullptr;
+    // the LDS images cover the widest window: the whole text, or back + 1 + fwd positions
+    const int Lw = win && k.win_back + k.win_fwd + 1 < s.L ? k.win_back + k.win_fwd + 1 : s.L;
+    const int NG = (Lw + 3) >> 2, Lp = 4 * NG + 48;
     const size_t sm_e = (size_t)(16 + 6 * Lp + 3 * 640) * sizeof(float);
-    const int wsn = ((s.L + 3) & ~3) > 192 ? ((s.L + 3) & ~3) : 192;
+    const int wsn = ((Lw + 3) & ~3) > 192 ? ((Lw + 3) & ~3) : 192;
     const size_t sm_c = (size_t)(wsn + 8 + 256) * sizeof(float);
     // (no fixed length limit: what bounds a text is the 160 KB of LDS - 24 bytes per position in the energies kernel)
+    if (win) {
+        T2_REQUIRE(t2_allow_lds(attn_energy_win_kernel, sm_e) && t2_allow_lds(attn_context_win_kernel, sm_c),
+                   "attention: the window is too wide for the LDS images of the attention kernels");
+        hipLaunchKernelGGL(attn_energy_win_kernel, dim3(s.B, s.Ad / 16), dim3(ENT), sm_e, st, k);
+        hipLaunchKernelGGL(attn_context_win_kernel, dim3(s.B, s.Ef / 32), dim3(256), sm_c, st, k);
+        T2_CHECK_LAUNCH();
+        return T2_OK;
+    }
     T2_REQUIRE(t2_allow_lds(attn_energy_kernel, sm_e) && t2_allow_lds(attn_context_kernel, sm_c),
                "attention: the text is too long for the LDS images of the attention kernels");
     hipLaunchKernelGGL(attn_energy_kernel, dim3(s.B, s.Ad / 16), dim3(ENT), sm_e, st, k);

@@ -13,6 +13,7 @@ the hardware:
 """
 from __future__ import annotations
 
+import numbers
 from typing import Dict, Optional
 
 import torch
@@ -72,6 +73,20 @@ def gemm_fill(A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, bias=None):
         gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=a_k, b_k=b_k, bias=bias, accumulate=2, splitk=2)
     else:
         gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=a_k, b_k=b_k, bias=bias)
+
+
+def check_attention_window(window):
+    """None, or (back, fwd) as two integers >= 0 -> the same as a tuple of ints; anything else raises ValueError."""
+    if window is None:
+        return None
+    try:
+        back, fwd = window
+    except (TypeError, ValueError):
+        raise ValueError(f"attention_window must be (back, fwd), got {window!r}") from None
+    for v in (back, fwd):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0:
+            raise ValueError(f"attention_window must be two integers >= 0, got {window!r}")
+    return int(back), int(fwd)
 
 
 def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
@@ -1234,7 +1249,8 @@ class Engine:
     # =============================================================================================
     # autoregressive inference: forward(teacher_forcing=False, max_len_override=N)  (model/tacotron2.py:262-325)
     # =============================================================================================
-    def _infer_group(self, g, enc, chars_len, Tcap, speaker_id, description_embeddings, training, prenet_masks, controls):
+    def _infer_group(self, g, enc, chars_len, Tcap, speaker_id, description_embeddings, training, prenet_masks, controls,
+                     attention_window=None):
         """Conditioning and decode-loop operands of one group of <= 64 utterances (workspaces prefixed inf<g>.); `enc` is the
         group's slice of the encoder output, computed for the WHOLE batch by the caller."""
         d, P, ps = self.d, self.ps.P, self.ps
@@ -1285,7 +1301,11 @@ class Engine:
             pm = self.buf(pf + "pmask", Tcap, 2, B, Pd)
         else:
             pm = None
-        a = make("T2Infer", B=B, L=L, A=A, D=D, Ef=Ef, Ad=Ad, P=Pd, M=M, Kl=KL, Tcap=Tcap,
+        win = {}
+        if attention_window is not None:     # [2][B] peaks, row 0 zero-filled: m_{-1} = 0 (include/tacotron2_amd.h)
+            win = dict(win_back=int(attention_window[0]), win_fwd=int(attention_window[1]),
+                       win_peak=self.buf(pf + "win_peak", 2, B, dtype=torch.int32, zero=True))
+        a = make("T2Infer", B=B, L=L, A=A, D=D, Ef=Ef, Ad=Ad, P=Pd, M=M, Kl=KL, Tcap=Tcap, **win,
                  W_comb=self._w_comb, b_comb=self._b_comb, row_comb=row_comb, W_pre2=P["prenet.3.weight"],
                  W_comb_t=self._w_comb_t, W_pre2_t=self._w_pre2_t, p1_t=self.buf(pf + "p1_t", Pd // 16, Bp, 16, zero=True),
                  wp_att=self._wp_att_inf, b_att_ih=P["decoder.att_rnn.bias_ih"], b_att_hh=P["decoder.att_rnn.bias_hh"],
@@ -1296,13 +1316,17 @@ class Engine:
         return dict(a=a, B=B, proj=proj, align=align, state=state, pm=pm, philox=prenet_masks is None and pm is not None)
 
     def infer(self, chars_idx, chars_len, max_len, speaker_id=None, description_embeddings=None, training=False,
-              prenet_masks=None, seed=0, check_every=32, controls=None):
+              prenet_masks=None, seed=0, check_every=32, controls=None, attention_window=None):
         """Returns (mels, mels_post, gates, alignments, lengths) exactly as the reference's non-teacher-forced forward: ONE loop
         over the whole batch that ends when every utterance has produced a negative stop logit (model/tacotron2.py:319-322).
         Batches above 64 utterances are decoded as groups of 64 in lock-step chunks of `check_every` frames; the break frame
         and `lengths` are taken from the stored stop logits of all groups (t2_stop_scan).
-        prenet_masks: optional [n][2][B][P] scale masks (parity tests); otherwise Philox masks (AlwaysDropout)."""
+        prenet_masks: optional [n][2][B][P] scale masks (parity tests); otherwise Philox masks (AlwaysDropout).
+        attention_window: optional (back, fwd), integers >= 0 - frame t attends only to the positions
+        max(0, m - back) .. min(len - 1, m + fwd) around the previous frame's attention peak m (0 before the first frame); the
+        other alignments are exactly 0 (include/tacotron2_amd.h, "Windowed attention").  None: the whole text, as before."""
         d, P, ps = self.d, self.ps.P, self.ps
+        attention_window = check_attention_window(attention_window)
         B, L = chars_idx.shape
         assert B <= 4096, "engine.infer handles up to 4096 utterances per call (64 groups of 64)"
         self.generation += 1          # the encoder / postnet workspaces are shared with forward_tf
@@ -1352,7 +1376,7 @@ class Engine:
                 speaker_id[sl] if speaker_id is not None else None,
                 description_embeddings[sl].contiguous() if description_embeddings is not None else None, training,
                 prenet_masks[:, :, sl].contiguous() if (prenet_masks is not None and B > 64) else prenet_masks,
-                controls[sl] if controls is not None else None))
+                controls[sl] if controls is not None else None, attention_window))
         p = float(d["dropout"])
         t0 = 0
         self.mark("inf.encoder")

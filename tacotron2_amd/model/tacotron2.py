@@ -9,13 +9,13 @@ There is no CPU fallback: the module can be constructed and (de)serialised anywh
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from .._lib import call
-from ..engine import Engine, _stream
+from ..engine import Engine, _stream, check_attention_window
 from ..init import init_parameters
 from ..params import ParamStore
 
@@ -157,7 +157,14 @@ class Tacotron2(nn.Module):
                 mel_spectrogram: Optional[Tensor] = None, mel_spectrogram_len: Optional[Tensor] = None,
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
-                dropout_masks: Optional[dict] = None):
+                dropout_masks: Optional[dict] = None, attention_window: Optional[Tuple[int, int]] = None):
+        """attention_window (autoregressive decoding only): (back, fwd) integers >= 0 - each frame attends only to the positions
+        max(0, m - back) .. min(len - 1, m + fwd) around the previous frame's attention peak m (ESPnet's `use_att_constraint`);
+        None attends to the whole text, as the reference does."""
+        if attention_window is not None:
+            if teacher_forcing:
+                raise ValueError("attention_window applies to autoregressive decoding only (teacher_forcing=False)")
+            attention_window = check_attention_window(attention_window)
         if teacher_forcing:
             assert mel_spectrogram is not None, "Ground-truth Mel spectrogram is required for teacher forcing"
             assert mel_spectrogram_len is not None, "Ground-truth Mel spectrogram lengths are required for teacher forcing"
@@ -186,7 +193,8 @@ class Tacotron2(nn.Module):
             o = self._engine.infer(chars_idx.contiguous(), chars_idx_len, int(max_len_override), speaker_id=speaker_id,
                                    description_embeddings=description_embeddings.contiguous().float()
                                    if description_embeddings is not None else None,
-                                   training=self.training, prenet_masks=pm, seed=self._seed + self._calls, controls=controls)
+                                   training=self.training, prenet_masks=pm, seed=self._seed + self._calls, controls=controls,
+                                   attention_window=attention_window)
             self._calls += 1
         return o[:4]
 

@@ -4,7 +4,7 @@ Adam + MultiStepLR (:78-91).  run/train.py drives the fused HIP step (tacotron2_
 validation_step keep the reference's batch format for external loops."""
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -60,6 +60,8 @@ class TTSModel(nn.Module):
         self.scheduler_milestones = list(scheduler_milestones)
         self.speaker_tokens, self.controls = speaker_tokens, controls
         self.max_len_override, self.description_embeddings = max_len_override, description_embeddings
+        # (back, fwd) windowed attention of predict_step and the run drivers' decoding (run/test.py); None = the whole text
+        self.attention_window: Optional[Tuple[int, int]] = None
         self.tacotron2 = Tacotron2(num_chars=num_chars, encoded_dim=encoded_dim, encoder_kernel_size=encoder_kernel_size,
                                    num_mels=num_mels, prenet_dim=prenet_dim, att_rnn_dim=att_rnn_dim, att_dim=att_dim,
                                    rnn_hidden_dim=rnn_hidden_dim, postnet_dim=postnet_dim, dropout=dropout,
@@ -78,11 +80,12 @@ class TTSModel(nn.Module):
     def forward(self, chars_idx: Tensor, chars_idx_len: Tensor, teacher_forcing: bool = True,
                 mel_spectrogram: Optional[Tensor] = None, mel_spectrogram_len: Optional[Tensor] = None,
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
-                max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None):
+                max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
+                attention_window: Optional[Tuple[int, int]] = None):
         return self.tacotron2(chars_idx=chars_idx, chars_idx_len=chars_idx_len, teacher_forcing=teacher_forcing,
                               mel_spectrogram=mel_spectrogram, mel_spectrogram_len=mel_spectrogram_len,
                               speaker_id=speaker_id, controls=controls, max_len_override=max_len_override,
-                              description_embeddings=description_embeddings)
+                              description_embeddings=description_embeddings, attention_window=attention_window)
 
     def _args(self, meta):
         args = {}
@@ -119,7 +122,8 @@ class TTSModel(nn.Module):
         data, meta = batch[0], batch[1]
         with torch.no_grad():
             return self(chars_idx=data["chars_idx"], chars_idx_len=meta["chars_idx_len"], teacher_forcing=False,
-                        max_len_override=self.max_len_override or 5000, **self._args(meta))
+                        max_len_override=self.max_len_override or 5000, attention_window=self.attention_window,
+                        **self._args(meta))
 
     # Lightning-style checkpoint exchange: {"state_dict": {"tacotron2.<name>": tensor}, "hyper_parameters": {...}}
     def checkpoint(self, extra: Optional[dict] = None) -> dict:

@@ -5,12 +5,13 @@ run/say.py:161-171 takes without a HiFi-GAN checkpoint), or HiFi-GAN audio with 
 run/say.py:66-86,153-159)."""
 from __future__ import annotations
 
-from typing import List, Optional, Union
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
+from ..engine import check_attention_window
 from ..model.tts_model import TTSModel
 from .common import model_kwargs
 
@@ -40,7 +41,7 @@ def load_description(description: Optional[str], dim: int, n: int, dev) -> torch
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
-           description: Optional[str] = None, max_len: int = 5000):
+           description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None):
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
@@ -54,6 +55,9 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     model.eval()
     if random_seed is not None:
         model.tacotron2._seed = int(random_seed)
+    if attention_window is None:       # the config's model.attention_window, if any (as load_test_model does)
+        attention_window = model_config.get("attention_window")
+    model.attention_window = check_attention_window(attention_window)
     kw = {}
     if model.speaker_tokens:
         kw["speaker_id"] = torch.full((len(texts),), int(speaker_id or 0), dtype=torch.int32, device=dev)
@@ -66,7 +70,8 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         assert len(vals) == n_ctl, f"--controls needs {n_ctl} comma-separated values"
         kw["controls"] = torch.tensor([vals] * len(texts), dtype=torch.float32, device=dev)
     with torch.no_grad():
-        _, post, gates, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len, **kw)
+        _, post, gates, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
+                                  attention_window=model.attention_window, **kw)
     post = post.cpu().numpy()
     # run/say.py:155,161 keeps mel_spectrogram_post[:, :-1]: all emitted frames but the last.  The stop frame itself is already
     # masked (gate -1000 from `lengths` on), so an utterance that stopped keeps its `lengths` = n - 1 frames; one that ran into

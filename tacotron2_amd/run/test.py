@@ -17,18 +17,22 @@ from __future__ import annotations
 import csv
 import datetime
 import os
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
+from ..engine import check_attention_window
 from ..model.tts_model import TTSModel
 from .common import model_kwargs
 
 
-def load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed=None):
-    """TTSModel.load_from_checkpoint as run/test.py:116-130 calls it (max_len_override 5000, no scheduler), in eval mode."""
+def load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed=None,
+                    attention_window=None):
+    """TTSModel.load_from_checkpoint as run/test.py:116-130 calls it (max_len_override 5000, no scheduler), in eval mode.
+    attention_window: (back, fwd) of the windowed attention the model decodes with (TTSModel.attention_window); None takes the
+    config's `model.attention_window` if there is one (`main.py --attention-window` puts it there for test-correlation), else off."""
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
     kw["scheduler_milestones"] = []
@@ -36,6 +40,9 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
     model.eval()
     if random_seed is not None:
         model.tacotron2._seed = int(random_seed)
+    if attention_window is None:
+        attention_window = model_config.get("attention_window")
+    model.attention_window = check_attention_window(attention_window)
     return model
 
 
@@ -72,7 +79,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     receptive field spans many frames, so the last samples of an utterance depend on what follows it.
     zero_length: what is written for an utterance that never stopped (mel_length 0): "test" = run/test.py:176-193 (wav_length
     becomes -1 and is applied twice: the row minus its last two samples); "correlation" = run/test_correlation.py:196-209 (an
-    empty file).  Both log the utterance.  Griffin-Lim (librosa raises on an empty spectrogram): logged, nothing written."""
+    empty file).  Both log the utterance.  Griffin-Lim (librosa raises on an empty spectrogram): logged, nothing written.
+    The decode uses the model's attention window (TTSModel.attention_window, set by load_test_model; None = off)."""
     from ..vocoder import write_wav
     dev = model.tacotron2.store.device
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
@@ -107,7 +115,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                     if desc_paths[j] is not None else torch.zeros(dim) for j in sel]
             args["description_embeddings"] = torch.stack(rows).to(dev)
         with torch.no_grad():
-            _, post, gate, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len, **args)
+            _, post, gate, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
+                                     attention_window=model.attention_window, **args)
         mel_lengths = (gate[:, :, 0] < 0).to(torch.int64).argmax(dim=-1).cpu().tolist()
         for k, j in enumerate(sel):
             i += 1
@@ -134,7 +143,7 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
 def do_test(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
             speech_dir: Optional[str], checkpoint: str, hifi_gan_checkpoint: Optional[str] = None,
             results_dir: Optional[str] = None, batch_size: int = 8, max_len: int = 5000, limit: Optional[int] = None,
-            random_seed: Optional[int] = None) -> List[str]:
+            random_seed: Optional[int] = None, attention_window: Optional[Tuple[int, int]] = None) -> List[str]:
     import pandas as pd
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
@@ -144,7 +153,8 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
         df = df[df.speaker_id == extensions_config["speaker_tokens"]["force_speaker"]].reset_index(drop=True)
     if limit is not None:
         df = df.iloc[:int(limit)].reset_index(drop=True)
-    model = load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed)
+    model = load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
+                            attention_window)
     ctl_cfg = extensions_config.get("controls", {"active": False})
     feats = df[ctl_cfg["features"]].values.tolist() if model.controls else None
     if results_dir is None:
