@@ -19,6 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
+from . import guard as _guard
 from ._lib import call, make
 from .params import ParamStore
 
@@ -214,6 +215,10 @@ class Engine:
                                       # so only the LATEST forward can be back-propagated (checked in backward_tf)
         self.profile = False          # when True, mark() records HIP events at segment boundaries
         self.marks = []; self.spans = []               # [(name, event)] of the current step
+        self.guard_bytes = _guard.DEFAULT_BYTES  # > 0 (tests): guard bands of this many bytes on both sides of every workspace and
+                                                 # output, each sized exactly to its request (tacotron2_amd/guard.py, guard_check)
+        self._guards: Dict[str, tuple] = {}      # name -> (backing, g, n, short) of the guarded allocations
+        self._guard_short: Dict[str, int] = {}   # test hook: name -> elements by which that buffer's after-band overlaps its view
 
     def persist_resident(self, D: int, B: int, n: int = 1) -> bool:
         """True when the persistent LSTM launch (n cells x H/4 workgroups that wait for each other) is fully co-resident on this
@@ -234,10 +239,26 @@ class Engine:
 
     def check_persistent_kernels(self):
         """Host-synchronising check of the persistent launches' timeout flag (bounded spins end the launch early instead of
-        hanging): raises if a wait timed out.  Tests and the bench call it after a step."""
+        hanging): raises if a wait timed out.  Tests and the bench call it after a step.  With guard bands on, it also raises when a
+        band was overwritten (guard_check)."""
         if self._persist_sync is not None and int(self._persist_sync[256].item()) != 0:
             self._persist_sync[256:272].zero_()       # the flag is sticky on the device: cleared here, reported once
             raise _lib.T2Error("t2_lstm_seq_fwd_persist: an inter-workgroup wait timed out (outputs of that forward are invalid)")
+        if self.guard_bytes > 0 or self.ps.guard_bytes > 0:
+            hits = self.guard_check()
+            if hits:
+                raise _lib.T2Error("guard bands overwritten: " + _guard.describe(hits))
+
+    def guard_check(self) -> list:
+        """Synchronises the device and compares every guard band of this engine's workspaces and outputs and of its ParamStore's flat
+        buffers bitwise against its pattern: [(buffer name, "before" | "after", offset of the first bad element from the view's first
+        element, count, first values)]; [] when every band is intact or guards are off."""
+        if self.dev.type == "cuda":
+            torch.cuda.synchronize(self.dev)
+        hits = []
+        for name, (backing, g, n, short) in self._guards.items():
+            hits += _guard.scan(name, backing, g, n, short)
+        return hits + self.ps.guard_check()
 
     def side_stream(self):
         if self._side is None:
@@ -353,13 +374,36 @@ class Engine:
         for s in shape:
             n *= s
         t = self._ws.get(name)
-        if t is None or t.numel() < n or t.dtype != dtype:
+        if self.guard_bytes > 0:
+            # guard mode: exactly n elements, so the after-band starts where the view ends (never a larger earlier tensor)
+            if t is None or t.numel() != n or t.dtype != dtype:
+                assert not self._prez.get(name), \
+                    f"workspace {name}: prezero() and the buf(zero=True) that follows it ask for different sizes"
+                t = self._ws[name] = self._guarded(name, n, dtype)
+        elif t is None or t.numel() < n or t.dtype != dtype:
             t = torch.empty(max(n, 1), dtype=dtype, device=self.dev)
             self._ws[name] = t
         v = t[:n].view(*shape)
         if zero and not self._prez.pop(name, False):
             zero_later(v)       # cleared by the next t2_zero_regions launch, in front of the next library call
         return v
+
+    def _guarded(self, name: str, n: int, dtype) -> torch.Tensor:
+        short = self._guard_short.get(name, 0)
+        backing, v, g = _guard.alloc(n, dtype, self.dev, self.guard_bytes, short)
+        self._guards[name] = (backing, g, n, short)
+        return v
+
+    def out(self, name: str, *shape, zero: bool = False) -> torch.Tensor:
+        """A float32 tensor handed to the caller, fresh on every call: torch.empty / torch.zeros - or, with guard bands on, a guarded
+        allocation checked under `out.<name>` (the latest one of that name)."""
+        if self.guard_bytes <= 0:
+            return (torch.zeros if zero else torch.empty)(*shape, dtype=torch.float32, device=self.dev)
+        n = 1
+        for s in shape:
+            n *= s
+        v = self._guarded("out." + name, n, torch.float32)
+        return (v.zero_() if zero else v).view(*shape)
 
     def workspace_report(self, top: int = 8) -> dict:
         """Device memory of the named workspaces as allocated so far (after a step at the largest shape seen): total bytes, count
@@ -415,8 +459,17 @@ class Engine:
     def persist_counters(self, nblocks: int) -> int:
         """Device address of `nblocks` fresh 256-word arrival-counter blocks (cleared by begin_phase; one per row block of a
         persistent launch: t2_lstm_seq_fwd_persist_pz)."""
-        assert self._persist_next + nblocks <= self.PERSIST_RING, "persistent launches per forward exceed the counter ring"
-        a = self.persist_sync().data_ptr() + 4 * (self.PERSIST_RING0 + 256 * self._persist_next)
+        ring = self.persist_sync()
+        if self._persist_next + nblocks > self.PERSIST_RING:
+            # More blocks since the last begin_phase than the ring holds: a forward of more than ~95 pipeline chunks (long
+            # utterances, short chunks, two 32-row blocks per launch), or encoder_fwd driven without a phase (model/submodules.py).
+            # The ring starts over, cleared again on the CURRENT stream in front of this launch.  Every earlier user of a block is
+            # ordered before that clear: the decoder-LSTM launches run on the side stream one after the other, and the side stream
+            # first waits for a main-stream event recorded behind the forward's encoder launch; outside a phase the launches share
+            # the caller's stream.
+            zero_later(ring[self.PERSIST_RING0:])
+            self._persist_next = 0
+        a = ring.data_ptr() + 4 * (self.PERSIST_RING0 + 256 * self._persist_next)
         self._persist_next += nblocks
         return a
 
@@ -672,7 +725,7 @@ class Engine:
         # 288 GB of HBM (a backward that recomputes them instead was built and measured in round 3: +1.0 ms per step,
         # profiles/r03_ab_tanh_recompute.txt)
         th = self.buf("th", T, B, Ad, (L + 3) // 4 * 4) if save_for_backward else None
-        align = torch.empty(B, T, L, dtype=torch.float32, device=self.dev)
+        align = self.out("align", B, T, L)
         e_part = self.buf("e_part", B, Ad // 16, L)
         # packed in the column order of the xdec row [att_h | ctx], so each step reads ONE contiguous activation segment
         wp_att = self.pack_fwd("att", [(P["decoder.att_rnn.weight_hh"], A, A),
@@ -785,8 +838,8 @@ class Engine:
             # reads the loss anyway (check_persistent_kernels).
             call("t2_guard_poison", self._persist_sync.data_ptr() + 4 * 256, proj, R * (M + 1), st)
         self.mark("fwd.dec.proj_gemm")
-        mels = torch.empty(B, T, M, dtype=torch.float32, device=self.dev)
-        gates = torch.empty(B, T, 1, dtype=torch.float32, device=self.dev)
+        mels = self.out("mels", B, T, M)
+        gates = self.out("gates", B, T, 1)
         post_in = self.buf("post.x0", B, T + 4, M)
         call("t2_finalize_fwd", proj, M + 1, mlen32, mels, gates, post_in, B, T, M, st)
 
@@ -795,7 +848,7 @@ class Engine:
         chans = [M, Pn, Pn, Pn, Pn, M]
         post_drop = masks.get("post_drop")
         x = post_in
-        post = torch.empty(B, T, M, dtype=torch.float32, device=self.dev)
+        post = self.out("post", B, T, M)
         for li in range(5):
             last = li == 4
             x = self.conv_bn_fwd(f"post.conv{li}", x, P[f"postnet.postnet.{4 * li}.weight"], None,
@@ -1285,7 +1338,7 @@ class Engine:
         p1 = self.buf(pf + "p1", B, Pd)
         e_part = self.buf(pf + "e_part", B, Ad // 16, L)
         proj = self.buf(pf + "proj", Tcap, B, ldo)
-        align = torch.zeros(B, Tcap, L, dtype=torch.float32, device=self.dev)
+        align = self.out(pf + "align", B, Tcap, L, zero=True)
         done = self.buf(pf + "done", B, dtype=torch.int32, zero=True)
         state = self.buf(pf + "state", 2, dtype=torch.int32, zero=True)
         _, cterm, cmel1 = self.controls_terms(controls, B)
@@ -1361,7 +1414,7 @@ class Engine:
         # linear's K chunks in the order [ctx | dec_h] of the tiled state
         Nc = Pd + M + 1
         Ncp = (Nc + 15) // 16 * 16
-        wc = torch.zeros(Ncp, ldp, device=self.dev)
+        wc = self.out("inf.w_comb_cols", Ncp, ldp, zero=True)
         wc[:Nc, :Ef] = self._w_comb[:, D:]; wc[:Nc, Ef:] = self._w_comb[:, :D]
         self._w_comb_t = wc.view(Ncp, ldp // 16, 16).permute(1, 0, 2).contiguous()
         self._w_pre2_t = P["prenet.3.weight"].view(Pd, Pd // 16, 16).permute(1, 0, 2).contiguous()
@@ -1421,8 +1474,8 @@ class Engine:
         self.check_persistent_kernels()      # (the encoder recurrence is a persistent launch; the host has just synchronised anyway)
         # outputs: mask by the counted lengths, postnet on the unmasked mels (model/tacotron2.py:327-345)
         mlen32 = lengths.to(torch.int32)
-        mels = torch.empty(B, n, M, dtype=torch.float32, device=self.dev)
-        gates = torch.empty(B, n, 1, dtype=torch.float32, device=self.dev)
+        mels = self.out("inf.mels", B, n, M)
+        gates = self.out("inf.gates", B, n, 1)
         post_in = self.buf("post.x0", B, n + 4, M)
         for G, b0 in zip(groups, range(0, B, 64)):
             Bg = G["B"]
@@ -1431,7 +1484,7 @@ class Engine:
         Pn = d["postnet_dim"]
         chans = [M, Pn, Pn, Pn, Pn, M]
         x = post_in
-        post = torch.empty(B, n, M, dtype=torch.float32, device=self.dev)
+        post = self.out("inf.post", B, n, M)
         pctx: dict = {}
         for li in range(5):
             last = li == 4

@@ -13,6 +13,25 @@ from .._lib import call
 from .tacotron2 import Tacotron2
 
 
+def check_loss_inputs(mel, post, gate, mel_tgt, gate_tgt, mel_len) -> None:
+    """The loss kernel reads raw pointers with the strides of `mel`: a target of another shape would be read with the wrong stride
+    or past its end, a tensor on another device would be a foreign pointer inside the kernel.  Raises ValueError instead."""
+    if mel.dim() != 3:
+        raise ValueError(f"loss: mels must be (B, T, M), got shape {tuple(mel.shape)}")
+    B, T, M = mel.shape
+    if tuple(post.shape) != (B, T, M) or gate.numel() != B * T:
+        raise ValueError(f"loss: mels_post {tuple(post.shape)} and gates {tuple(gate.shape)} do not match mels {(B, T, M)}")
+    if tuple(mel_tgt.shape) != (B, T, M):
+        raise ValueError(f"loss: the mel target has shape {tuple(mel_tgt.shape)}, the model output {(B, T, M)}")
+    if gate_tgt.numel() != B * T:
+        raise ValueError(f"loss: the gate target has {gate_tgt.numel()} elements, the output has B * T = {B * T}")
+    if mel_len.numel() != B:
+        raise ValueError(f"loss: {mel_len.numel()} mel lengths for a batch of {B}")
+    for name, t in (("mels_post", post), ("gates", gate), ("mel target", mel_tgt), ("gate target", gate_tgt), ("mel lengths", mel_len)):
+        if t.device != mel.device:
+            raise ValueError(f"loss: the {name} is on {t.device}, the mels on {mel.device}")
+
+
 class _LossTermsFn(torch.autograd.Function):
     """(gate BCE-with-logits, mel MSE, post MSE) of model/tts_model.py:197-199 - plain means over the padded tensors - as ONE
     device kernel (t2_loss_terms); with autograd on, the same launch also writes the three dense gradients, which backward scales
@@ -20,6 +39,7 @@ class _LossTermsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mel, post, gate, mel_tgt, gate_tgt, mel_len):
+        check_loss_inputs(mel, post, gate, mel_tgt, gate_tgt, mel_len)
         B, T, M = mel.shape
         need = any(ctx.needs_input_grad[:3])
         mel, post, gate = mel.contiguous().float(), post.contiguous().float(), gate.contiguous().float()

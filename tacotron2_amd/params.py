@@ -10,9 +10,11 @@ in ONE contiguous fp32 device buffer, each tensor 16-byte aligned, so that
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
+
+from . import guard as _guard
 
 
 def param_manifest(d: dict) -> "OrderedDict[str, tuple]":
@@ -112,9 +114,13 @@ def _numel(shape) -> int:
 class ParamStore:
     """Owns the flat parameter, gradient and Adam-moment buffers and the name -> view tables."""
 
-    def __init__(self, d: dict, device, with_grad: bool = True):
+    def __init__(self, d: dict, device, with_grad: bool = True, guard_bytes: Optional[int] = None):
+        """guard_bytes (tests; default T2_GUARD_BYTES, else 0): guard bands of that many bytes at both ends of flat, grad,
+        exp_avg, exp_avg_sq and buf_flat (tacotron2_amd/guard.py) - the views and offsets between parameters do not change."""
         self.dims = dict(d)
         self.device = torch.device(device)
+        self.guard_bytes = _guard.DEFAULT_BYTES if guard_bytes is None else int(guard_bytes)
+        self._guards: Dict[str, tuple] = {}
         man = param_manifest(d)
         offs, off = OrderedDict(), 0
         for name, shp in man.items():
@@ -123,8 +129,8 @@ class ParamStore:
             off += n if name in _GLUED else (n + 3) // 4 * 4
         self.numel = (off + 3) // 4 * 4
         self.offsets, self.shapes = offs, man
-        self.flat = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
-        self.grad = torch.zeros(self.numel, dtype=torch.float32, device=self.device) if with_grad else None
+        self.flat = self._zeros("flat", self.numel)
+        self.grad = self._zeros("grad", self.numel) if with_grad else None
         self.exp_avg = None
         self.exp_avg_sq = None
         self.P: Dict[str, torch.Tensor] = {}
@@ -136,7 +142,7 @@ class ParamStore:
                 self.G[name] = self.grad[offs[name]:offs[name] + n].view(shp)
         bman = buffer_manifest(d)
         nb = sum((_numel(s) + 3) // 4 * 4 for s in bman.values())
-        self.buf_flat = torch.zeros(nb, dtype=torch.float32, device=self.device)
+        self.buf_flat = self._zeros("buf_flat", nb)
         self.Bf: Dict[str, torch.Tensor] = {}
         o = 0
         for name, shp in bman.items():
@@ -166,8 +172,23 @@ class ParamStore:
 
     def init_adam(self):
         if self.exp_avg is None:
-            self.exp_avg = torch.zeros_like(self.flat)
-            self.exp_avg_sq = torch.zeros_like(self.flat)
+            self.exp_avg = self._zeros("exp_avg", self.numel)
+            self.exp_avg_sq = self._zeros("exp_avg_sq", self.numel)
+
+    # --- guard bands (tests) ------------------------------------------------------------------------
+    def _zeros(self, name: str, n: int) -> torch.Tensor:
+        if self.guard_bytes <= 0:
+            return torch.zeros(n, dtype=torch.float32, device=self.device)
+        backing, v, g = _guard.alloc(n, torch.float32, self.device, self.guard_bytes)
+        self._guards[name] = (backing, g, n)
+        return v.zero_()
+
+    def guard_check(self) -> list:
+        """Band hits of the flat buffers (the caller synchronises): [(name, side, offset, count, first values)]."""
+        hits = []
+        for name, (backing, g, n) in self._guards.items():
+            hits += _guard.scan("ps." + name, backing, g, n)
+        return hits
 
     # --- state_dict exchange (reference layout, SURVEY.md Appendix A) -----------------------------
     def load_state_dict(self, sd: Dict[str, torch.Tensor], prefix: str = "", strict: bool = True):

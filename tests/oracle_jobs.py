@@ -197,9 +197,57 @@ def _decode_full(spec=""):
                 kind="decode_full")
 
 
+def edge_lengths_case(d, B, L, T, seed):
+    """random_case with the edge lengths in the batch: row 0 the full text and ONE frame, the last row ONE character and all T frames
+    (tests/test_gpu_guarded_edges.py)."""
+    ci, lens, mel, tl, gate, masks = random_case(d, B, L, T, seed)
+    if B >= 2:
+        lens[B - 1] = 1
+        tl[0] = 1
+        for b in (0, B - 1):
+            ci[b, lens[b]:] = 0
+            mel[b, tl[b]:] = 0
+            gate[b] = 0
+            gate[b, :tl[b] - 1] = 1.0
+    return ci, lens, mel, tl, gate, masks
+
+
+def _guard_tiny(spec):
+    """spec "B-L-T-chain": a TINY-dims training step at a batch size around the step kernels' row blocks, edge lengths in the batch
+    (the decoder-LSTM chain variant only names the job: the oracle side is the same)."""
+    B, L, T = (int(x) for x in spec.split("-")[:3])
+    d = R.default_dims(**TINY)
+    P = R.init_params(d, seed=B + L)
+    return dict(d=d, P=P, case=edge_lengths_case(d, B, L, T, 1000 + B + L + T), kw={}, kind="train")
+
+
+def _guard_full(spec):
+    """spec "B": the shipped sizes (E = 512, LSTMs 1024, 4 speaker tokens) at B = 33 / 65 / 129, L = 25, T = 12, edge lengths."""
+    B = int(spec)
+    d = R.default_dims(speaker_tokens=True, num_speakers=4)
+    P = R.init_params(d, seed=500 + B)
+    spk = torch.randint(0, 4, (B,), generator=torch.Generator().manual_seed(B), dtype=torch.int32)
+    return dict(d=d, P=P, case=edge_lengths_case(d, B, 25, 12, 5000 + B), kw=dict(speaker_id=spk), kind="train")
+
+
+def _ring_step():
+    """TINY, B = 33, T = 760 with 16-frame chunks: 51 persistent decoder-LSTM launches of two 32-row blocks - more counter blocks than
+    the ring of 96 holds."""
+    d = R.default_dims(**TINY)
+    P = R.init_params(d, seed=760)
+    return dict(d=d, P=P, case=random_case(d, 33, 9, 760, 7600), kw={}, kind="train")
+
+
+def _ring_fwd():
+    """TINY, B = 33, T = 2900 with the default 64-frame chunks: 49 launches of two blocks (about 34 s of audio)."""
+    d = R.default_dims(**TINY)
+    P = R.init_params(d, seed=2900)
+    return dict(d=d, P=P, case=random_case(d, 33, 9, 2900, 29000), kw={}, kind="fwd")
+
+
 CASES = dict(judged_fwd=_judged_fwd, judged_step=_judged_step, judged_fwd_b64=_judged_fwd_b64, libritts4=_libritts4, decode_full=_decode_full, judged4=_judged4, libritts_fwd=_libritts_fwd, bench_len_vanilla=_bench_len_vanilla,
              bench_len_desc=_bench_len_desc, b64_step=_b64_step, long_text=_long_text, tile_edge=_tile_edge,
-             decode_ragged=_decode_ragged)
+             decode_ragged=_decode_ragged, guard_tiny=_guard_tiny, guard_full=_guard_full, ring_step=_ring_step, ring_fwd=_ring_fwd)
 
 
 def case(name: str) -> dict:

@@ -27,9 +27,11 @@ from tests.oracle_jobs import case as job_case, oracle_train as _oracle_train  #
 from tests.oracle_pool import oracle, release  # noqa: E402
 
 
-def _hip_train_and_compare(d, P, case, dev, kw_cpu=None, kw_dev=None, grad_tol=3e-4, check_engine=None, job=None):
+def _hip_train_and_compare(d, P, case, dev, kw_cpu=None, kw_dev=None, grad_tol=3e-4, check_engine=None, job=None, guard_bytes=None,
+                           check_ctx=None):
     """job: name of the tests/oracle_jobs.py job that runs the oracle side of THIS case (same builder, same dekinked masks) in a
-    background CPU process; None: the oracle runs here."""
+    background CPU process; None: the oracle runs here.  guard_bytes: guard bands on engine and ParamStore (build_engine), checked
+    clean after the step.  check_ctx: called with the forward's ctx (which paths the step took)."""
     ci, lens, mel, tl, gate, masks = case
     if job is not None:
         o = oracle(job)
@@ -39,14 +41,18 @@ def _hip_train_and_compare(d, P, case, dev, kw_cpu=None, kw_dev=None, grad_tol=3
     else:
         masks, _ = dekink_masks(P, d, ci, mel, masks)      # ReLU-kink elements out of both sides (tests/helpers.py)
         ref, loss, grads, new_stats = _oracle_train(P, d, ci, lens, mel, tl, gate, masks, **(kw_cpu or {}))
-    eng, ps = build_engine(d, P, dev)
+    eng, ps = build_engine(d, P, dev, guard_bytes=guard_bytes)
     if check_engine is not None:
         check_engine(eng)
     outs, ctx = eng.forward_tf(ci.to(dev), lens.to(dev), mel.to(dev), tl.to(dev), training=True,
                                masks=masks_to_device(masks, dev), **(kw_dev or {}))
+    if check_ctx is not None:
+        check_ctx(ctx)
     ps.grad.zero_()
     loss3 = eng.loss_and_grads(outs, ctx, mel.to(dev), gate.to(dev))
     torch.cuda.synchronize()
+    if guard_bytes:
+        assert eng.guard_check() == []
     eng.check_persistent_kernels()
     assert l1(outs[0], ref[0]) < MEL_L1_TOL and l1(outs[1], ref[1]) < MEL_L1_TOL, (l1(outs[0], ref[0]), l1(outs[1], ref[1]))
     assert mx(outs[0], ref[0]) < 1e-3 and mx(outs[1], ref[1]) < 2e-3

@@ -34,12 +34,17 @@ def masks_to_device(m, dev):
     return out
 
 
-def build_engine(d, P, dev):
+def build_engine(d, P, dev, guard_bytes=None):
+    """guard_bytes: guard bands on the engine's workspaces and the ParamStore's flat buffers (tacotron2_amd/guard.py); None: the
+    process default (T2_GUARD_BYTES, else none)."""
     from tacotron2_amd.engine import Engine
     from tacotron2_amd.params import ParamStore
-    ps = ParamStore(d, dev)
+    ps = ParamStore(d, dev, guard_bytes=guard_bytes)
     ps.load_state_dict(P)
-    return Engine(ps), ps
+    eng = Engine(ps)
+    if guard_bytes is not None:
+        eng.guard_bytes = guard_bytes
+    return eng, ps
 
 
 def l1(a, b):
@@ -447,14 +452,15 @@ def test_edge_shapes_match_oracle(B, L, T, lens, tls):
     dev = _dev()
     d = R.default_dims(num_chars=39, encoded_dim=64, prenet_dim=32, att_rnn_dim=64, att_dim=32, rnn_hidden_dim=64,
                        postnet_dim=64, num_mels=80, dropout=0.5)
+    from tests.oracle_jobs import oracle_train
     P = R.init_params(d, seed=B)
     ci, cl, mel, tl, gate, masks = random_case(d, B, L, T, 300 + B, dev)
     if lens is not None:
         cl = torch.tensor(lens); tl = torch.tensor(tls, dtype=torch.int32)
         for b in range(B):
             ci[b, lens[b]:] = 0; mel[b, tls[b]:] = 0
-    with torch.no_grad():
-        ref = R.tacotron2_fwd(P, d, ci, cl, True, mel, tl, training=True, masks=masks)
+    masks, _ = dekink_masks(P, d, ci, mel, masks)      # ReLU-kink elements out of both sides of the gradient comparison
+    ref, loss, grads, _ = oracle_train(P, d, ci, cl, mel, tl, gate, masks)
     eng, ps = build_engine(d, P, dev)
     (mels, post, gates, al), ctx = eng.forward_tf(ci.to(dev), cl.to(dev), mel.to(dev), tl.to(dev), training=True,
                                                   masks=masks_to_device(masks, dev))
@@ -463,6 +469,9 @@ def test_edge_shapes_match_oracle(B, L, T, lens, tls):
     torch.cuda.synchronize()
     assert l1(mels, ref[0]) < MEL_L1_TOL and l1(post, ref[1]) < MEL_L1_TOL and mx(al, ref[3]) < 2e-5
     assert torch.isfinite(ps.grad).all() and torch.isfinite(loss3).all()
+    # every gradient against the oracle's autograd - B = 100 ends in a 36-row block (ADVICE round 4's out-of-bounds read was there)
+    assert abs(float(loss3.sum()) - loss) < 2e-5 * max(1.0, abs(loss))
+    _grad_check(ps, grads)
 
 
 @pytest.mark.oracle("long_text:{L}")
