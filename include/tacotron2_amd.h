@@ -328,6 +328,13 @@ typedef struct {
     float* ws_bd;                    /* workspace of (Ad/16) * 16896 floats: the per-slice kernel runs its two correlations (dU, d_in)
                                         on the bf16 matrix pipe with exactly split operands (six products, fp32 accuracy); the
                                         workspace receives the d_in filter operand in fragment layout, rewritten by every call */
+    const float* dalign;             /* optional upstream gradient w.r.t. the alignments AS RETURNED (each w_t after the softmax, before
+                                        it is added into the cumulative weights), layout of `align`: frame t of utterance b at
+                                        dalign + (b*T + t)*L, every frame (also those behind an utterance's mel length).  It joins the
+                                        softmax backward of the frame's first launch, de[l] = w[l] * (dw[l] + dwx[l] + da[l] - sigma)
+                                        with sigma = sum_l w[l] * (dw[l] + dwx[l] + da[l]), and nothing else: not the
+                                        cumulative-weights carry G.  NULL = no such gradient (the same loads and arithmetic as without
+                                        the operand) */
 } T2AttnSeqBwd;
 int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream);
 
@@ -398,6 +405,15 @@ int t2_loss_fwd_bwd(const float* mels, const float* post, const float* gates, co
 int t2_loss_terms(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
                   const int32_t* len, int B, int T, int M, double* loss3, float* d_mels, float* d_post, float* d_gates,
                   float grad_scale, void* stream);
+/* Guided-attention loss (Tachibana et al. 2018) on the alignments (B,T,L) of a teacher-forced forward: value and gradient in ONE launch.
+ *   G[b][t][l] = 1 - exp(-(l/N_b - t/T_b)^2 / (2 sigma^2))      for t < T_b and l < N_b, else 0
+ *   loss       = alpha / B * sum_b ( sum_{t,l} G[b][t][l] * align[b][t][l] ) / (N_b * T_b)
+ *   dalign     = grad_scale * alpha / (B * N_b * T_b) * G[b][t][l]    (optional; written over the whole (B,T,L), zeros included)
+ * N_b = chars_len[b] clipped to [0, L], T_b = mel_len[b] clipped to [0, T] (device int32); an utterance with N_b * T_b == 0
+ * contributes nothing.  The mean is taken per utterance and then over the batch (equal shards averaged = the whole batch).  The
+ * loss is accumulated in double into ONE device double; sigma > 0, alpha >= 0 (customary: 0.4, 1.0). */
+int t2_guided_attn(const float* align, const int32_t* chars_len, const int32_t* mel_len, int B, int T, int L, float sigma,
+                   float alpha, double* loss, float* dalign, float grad_scale, void* stream);
 int t2_relu_mask_bwd(const float* g, const float* y, const float* mask, float* out, int64_t n, void* stream);
 int t2_condition_fwd(const float* enc, const float* spk_table, const int32_t* spk, const float* desc, float* memory, int B,
                      int L, int E, int Ef, void* stream);

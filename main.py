@@ -2,6 +2,7 @@
 """CLI with the reference's surface for the hot path (main.py:15-107,150-226 of mattm458/tacotron2):
 
     python main.py --config C --device N train --speech-dir S [--results-dir R] [--resume-ckpt K] [--finetune --finetune-steps n]
+                                                  [--guided-attention SIGMA,ALPHA]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
                                                   [--attention-window BACK,FWD]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
@@ -28,6 +29,21 @@ def parse_attention_window(ctx, param, value):
     if len(parts) != 2 or not all(re.fullmatch(r"[0-9]+", p) for p in parts):
         raise click.BadParameter(f"expected BACK,FWD (two integers >= 0, e.g. 1,3), got {value!r}")
     return int(parts[0]), int(parts[1])
+
+
+def parse_guided_attention(ctx, param, value):
+    """--guided-attention SIGMA,ALPHA -> (sigma, alpha): two numbers, sigma > 0 and alpha >= 0, anything else a usage error."""
+    if value is None:
+        return None
+    from tacotron2_amd.engine import check_guided_attention
+    parts = [p.strip() for p in value.split(",")]
+    try:
+        if len(parts) != 2:
+            raise ValueError
+        return check_guided_attention((float(parts[0]), float(parts[1])))
+    except ValueError:
+        raise click.BadParameter(f"expected SIGMA,ALPHA (two numbers, sigma > 0 and alpha >= 0, e.g. 0.4,1.0), got {value!r}") \
+            from None
 
 
 attention_window_option = click.option(
@@ -57,8 +73,12 @@ def main(ctx, config, device):
 @click.option("--finetune-steps", required=False, type=int, help="Steps to fine-tune. Required if --finetune is given.")
 @click.option("--max-steps", required=False, type=int, default=None, help="Override training.args.max_steps (smoke runs).")
 @click.option("--synthetic", is_flag=True, default=False, help="Train on synthetic LJSpeech-shaped batches (no dataset needed).")
+@click.option("--guided-attention", required=False, type=str, default=None, callback=parse_guided_attention, metavar="SIGMA,ALPHA",
+              help="Guided-attention loss: adds ALPHA times the mean of the attention weights under the off-diagonal mask "
+                   "1 - exp(-(l/N - t/T)^2 / (2 SIGMA^2)) to the training and validation loss, so that the alignment forms early "
+                   "(0.4,1.0 is the usual value). Wins over training.guided_attention of the config. Default: off.")
 def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_checkpoint=None, finetune=False,
-          finetune_steps=None, max_steps=None, synthetic=False):
+          finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None):
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for training!")
     if finetune and finetune_steps is None:
@@ -68,7 +88,7 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
     do_train(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
              extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, results_dir=results_dir,
              resume_ckpt=resume_ckpt, finetune=finetune, finetune_steps=finetune_steps, max_steps_override=max_steps,
-             synthetic=synthetic)
+             synthetic=synthetic, guided_attention=guided_attention)
 
 
 @main.command()

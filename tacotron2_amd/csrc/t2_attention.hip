@@ -709,6 +709,9 @@ extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) {
 //     softmax backward needs sigma = sum_l w[l]*(dw[l]+dwx[l]) = dctx.context_t + sum_l w[l]*dwx[l],
 //     which every workgroup recomputes locally - no cross-workgroup reduction.
 //     de[l] = w[l] * (dw[l] + dwx[l] - sigma)        (masked positions have w = 0 -> de = 0)
+//     An upstream gradient da on the weights as returned (T2AttnSeqBwd.dalign, optional) is one more term of the same softmax
+//     backward: de[l] = w[l] * (dw[l] + dwx[l] + da[l] - sigma), sigma += sum_l w[l]*da[l].  It is NOT part of G_t: the carry is
+//     the gradient that reaches w_t through the cumulative weights, da reaches w_t directly.
 //  attn_bwd_ds_mfma_kernel / attn_bwd_ds_tiled_kernel   grid (B, Ad/16): workgroup (b, j) owns 16 attention dims for all l.
 //     ds[l][a] = de[l] * v[a] * (1 - th^2);  dpmT += ds;  dq[a] = sum_l ds;  dv[a] += sum_l de[l]*th[l][a]
 //     dU[a][c][k] += sum_l ds[l][a] * in[c][l+k-15]                   (per-sample partial, summed after the loop)
@@ -720,6 +723,7 @@ struct AttnBwdK {
     const float* w; long ldw;
     const float* memory;
     const float* din_part; const float* G_in; float* G_out;
+    const float* dalign;       // upstream gradient of this frame's weights, row b at dalign + b*ldw (the layout of w), or null
     float* de;
     const float* th; const float* v; const float* U;
     const float* w_prev; long ldwp; const float* cum_prev; long ldcp;
@@ -768,6 +772,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
     const float gin0 = p.G_in ? p.G_in[(long)b * L + lc0] : 0.f;
     const float wl0 = p.w[(long)b * p.ldw + lc0];
     const float wme = p.w[(long)b * p.ldw + imin(l, L - 1)];
+    float da0 = 0.f, dame = 0.f;
+    if (p.dalign) {
+        da0 = p.dalign[(long)b * p.ldw + lc0];
+        dame = p.dalign[(long)b * p.ldw + imin(l, L - 1)];
+    }
     __builtin_amdgcn_sched_barrier(0);
     // ---- issue: this thread's share of its memory row (8 lanes per position, 16 B each, stride 128 B) ----
     const float* mp = p.memory + ((long)b * L + imin(l, L - 1)) * Ef;
@@ -823,6 +832,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
             dwx_s[ll] = dx;
             if (blockIdx.y == 0) p.G_out[(long)b * L + ll] = Gn;
             part = fmaf(wl, dx, part);
+            if (p.dalign) part = fmaf(wl, ll0 == 0 ? da0 : p.dalign[(long)b * p.ldw + lc], part);
         }
     }
     T2_STAMP(p, stamp, 17);
@@ -848,7 +858,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
         }
     }
     acc = t2_oct_sum(acc);
-    if (sub == 0 && l < L) p.de[(long)b * L + l] = wme * (acc + dwx_s[l] - sigma);
+    if (sub == 0 && l < L) {
+        float up = acc + dwx_s[l];
+        if (p.dalign) up += dame;
+        p.de[(long)b * L + l] = wme * (up - sigma);
+    }
     T2_STAMP(p, stamp, 19);
     T2_RING_END();
 }
@@ -1228,6 +1242,7 @@ extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) {
         k.din_part = last ? nullptr : a->din_part;
         k.G_in = last ? nullptr : a->G + (long)((t + 1) & 1) * B * L;
         k.G_out = a->G + (long)(t & 1) * B * L;
+        k.dalign = a->dalign ? a->dalign + (long)t * L : nullptr;
         k.de = a->de;
         k.th = a->th + (long)t * B * Ad * ((L + 3) & ~3); k.v = a->v; k.U = a->U;
         if (t > 0) { k.w_prev = a->align + (long)(t - 1) * L; k.ldwp = (long)T * L; }

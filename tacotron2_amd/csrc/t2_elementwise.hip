@@ -425,6 +425,41 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* mels, const floa
     }
 }
 
+// Guided-attention loss and its gradient w.r.t. the alignments (include/tacotron2_amd.h: t2_guided_attn).  One WAVE walks whole
+// (b, t) rows - four rows in flight per workgroup - so the lengths and the row's scale are wave-uniform and no thread divides by L.
+// The exponent's argument is formed in double from the exact integer l*T_b - t*N_b (its rounding would otherwise dominate the
+// error at small sigma); exp itself is fp32.
+__global__ __launch_bounds__(256) void guided_attn_kernel(const float* align, const int32_t* chars_len, const int32_t* mel_len,
+                                                          int B, int T, int L, double inv2s2, float alpha, double* loss,
+                                                          float* dalign, float gscale) {
+    __shared__ double red[4];
+    double acc = 0;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (long row = (long)blockIdx.x * 4 + w; row < (long)B * T; row += (long)gridDim.x * 4) {
+        const int b = (int)(row / T), t = (int)(row - (long)b * T);
+        const int Nb = min(max(chars_len[b], 0), L), Tb = min(max(mel_len[b], 0), T);
+        const bool live = t < Tb && Nb > 0;
+        const double invNT = live ? 1.0 / ((double)Nb * (double)Tb) : 0.0;
+        const double coef = (double)alpha / (double)B * invNT;
+        const float cg = (float)(coef * (double)gscale);
+        float rowsum = 0.f;
+        for (int l = lane; l < L; l += 64) {
+            float g = 0.f;
+            if (live && l < Nb) {
+                const double x = (double)((long)l * Tb - (long)t * Nb) * invNT;
+                g = -expm1f(-(float)(x * x * inv2s2));
+                rowsum = fmaf(g, align[row * L + l], rowsum);
+            }
+            if (dalign) dalign[row * L + l] = cg * g;
+        }
+        acc += coef * (double)rowsum;
+    }
+    acc = t2_wave_sum_d(acc);
+    if (lane == 0) red[w] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss, red[0] + red[1] + red[2] + red[3]);
+}
+
 // Arbitrary upstream gradients (autograd path) -> the two tensors backward_tf consumes.  Masked positions are constants
 // (masked_fill, model/tacotron2.py:343-345) so their gradient is dropped.
 __global__ void outgrad_pack_kernel(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,
@@ -784,6 +819,18 @@ extern "C" int t2_loss_terms(const float* mels, const float* post, const float* 
     (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
     hipLaunchKernelGGL(loss_kernel, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt, gate_tgt,
                        len, B, T, M, loss3, d_post, (float*)nullptr, grad_scale, d_mels, d_gates);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_guided_attn(const float* align, const int32_t* chars_len, const int32_t* mel_len, int B, int T, int L, float sigma,
+                              float alpha, double* loss, float* dalign, float grad_scale, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(align && chars_len && mel_len && loss, "t2_guided_attn: null");
+    T2_REQUIRE(B >= 1 && T >= 1 && L >= 1, "t2_guided_attn: need B, T, L >= 1");
+    T2_REQUIRE(sigma > 0.f && alpha >= 0.f, "t2_guided_attn: need sigma > 0 and alpha >= 0");
+    (void)hipMemsetAsync(loss, 0, sizeof(double), ST);
+    const long wgs = ((long)B * T + 3) / 4;
+    hipLaunchKernelGGL(guided_attn_kernel, dim3((unsigned)(wgs > 4096 ? 4096 : wgs)), dim3(256), 0, ST, align, chars_len, mel_len,
+                       B, T, L, 1.0 / (2.0 * (double)sigma * (double)sigma), alpha, loss, dalign, grad_scale);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_outgrad_pack(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,

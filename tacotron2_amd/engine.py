@@ -90,6 +90,23 @@ def check_attention_window(window):
     return int(back), int(fwd)
 
 
+def check_guided_attention(guided):
+    """None, or (sigma, alpha) of the guided-attention loss as two real numbers, sigma > 0 and alpha >= 0 -> a tuple of floats;
+    anything else raises ValueError."""
+    if guided is None:
+        return None
+    try:
+        sigma, alpha = guided
+    except (TypeError, ValueError):
+        raise ValueError(f"guided_attention must be (sigma, alpha), got {guided!r}") from None
+    for v in (sigma, alpha):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or abs(v) == float("inf"):
+            raise ValueError(f"guided_attention must be two finite numbers (sigma, alpha), got {guided!r}")
+    if sigma <= 0 or alpha < 0:
+        raise ValueError(f"guided_attention needs sigma > 0 and alpha >= 0, got {guided!r}")
+    return float(sigma), float(alpha)
+
+
 def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
     return t.data_ptr() + 4 * elem_off
 
@@ -210,6 +227,7 @@ class Engine:
                                         # its epilogue costs more than the 22 us statistics pass it saves (profiles/r05_ab_bn_epilogue_stats.txt)
         self.bptt_off_chain = True    # the decoder-LSTM BPTT launches (side stream, a chunk ahead) keep the default wave priority
         self.sync_bn_group = None     # torch.distributed group: BatchNorm statistics over all ranks' shards (Trainer(sync_bn=True))
+        self.guided_loss = None       # loss_and_grads(guided=...): the guided-attention term of the latest step (device float64[1])
         self.grad_tail_hook = None    # called on the side stream once the gradients from prenet.0.weight onwards are enqueued
         self.generation = 0           # bumped by every forward: activations live in the shared named workspaces,
                                       # so only the LATEST forward can be back-propagated (checked in backward_tf)
@@ -915,14 +933,27 @@ class Engine:
         gemm_fill(draw, wf, dx, R, Ci, 5 * Co, Co, 5 * Co, Ci)
         return dx
 
-    def backward_tf(self, ctx, d_post, dproj):
+    def backward_tf(self, ctx, d_post, dproj, d_align=None):
         """d_post (B,T,M): gradient w.r.t. mels_post (masked positions zero).  dproj [T][B][M+1]: gradient w.r.t. the
-        decoder projection from the mel / residual / gate terms.  Accumulates into ps.grad (caller zeroes it)."""
+        decoder projection from the mel / residual / gate terms.  d_align: optional gradient w.r.t. the alignments output, a
+        contiguous float32 (B,T,L) tensor on the engine's device (every frame counts, also those behind an utterance's mel length).
+        Accumulates into ps.grad (caller zeroes it)."""
         d, P, G, ps = self.d, self.ps.P, self.ps.G, self.ps
         if ctx.get("generation") != self.generation:
             raise RuntimeError("backward of a stale forward: the activation stashes of this forward were overwritten by a later "
                                "grad-enabled forward of the same model (one live teacher-forced graph per model; INTEGRATION.md)")
         B, L, T = ctx["B"], ctx["L"], ctx["T"]
+        if d_align is not None:
+            # the dw kernel indexes it by hand with the strides of the alignments: anything else must not reach it as a pointer
+            if not isinstance(d_align, torch.Tensor) or d_align.dtype != torch.float32:
+                raise ValueError("backward_tf: d_align must be a float32 tensor, got "
+                                 f"{d_align.dtype if isinstance(d_align, torch.Tensor) else type(d_align).__name__}")
+            if tuple(d_align.shape) != (B, T, L):
+                raise ValueError(f"backward_tf: d_align has shape {tuple(d_align.shape)}, the alignments {(B, T, L)}")
+            if not d_align.is_contiguous():
+                raise ValueError("backward_tf: d_align must be contiguous")
+            if d_align.device != ctx["align"].device:
+                raise ValueError(f"backward_tf: d_align is on {d_align.device}, the engine on {ctx['align'].device}")
         M, E, Pd, A, D, Ad = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
@@ -1026,7 +1057,7 @@ class Engine:
                   cum=ctx["cum"], th=ctx["th"], att_drop=masks.get("att_drop"),
                   dh_ext=dxdec, ld_dh=ldx, dctx_ext1=_ptr(dxdec, A), ld_dc1=ldx, dctx_ext2=_ptr(dxproj, D), ld_dc2=ldp,
                   dgates=Z, dctx_tot=dctx_tot, dq=None, dpmT=dpmT, dv_part=dv_part, dU_part=dU_part,
-                  dc=dc_att, G=Gc, de=de, din_part=din_part, dgates_t=Zt, clk=getattr(self, "clk_bwd", None),
+                  dc=dc_att, G=Gc, de=de, din_part=din_part, dgates_t=Zt, clk=getattr(self, "clk_bwd", None), dalign=d_align,
                   ws_bd=self.buf("attn.ws_bd", Ad // 16 * 16896))
         self.mark("bwd.dec.proj")
         main, side = torch.cuda.current_stream(), self.side_stream()
@@ -1274,16 +1305,29 @@ class Engine:
     # =============================================================================================
     # loss + one optimisation step
     # =============================================================================================
-    def loss_and_grads(self, outs, ctx, mel_tgt, gate_tgt, grad_scale=1.0):
-        """3-term loss of model/tts_model.py:197-201 and the full backward.  Returns loss3 (device, float64[3])."""
-        mels, post, gates, _ = outs
+    def loss_and_grads(self, outs, ctx, mel_tgt, gate_tgt, grad_scale=1.0, guided=None):
+        """3-term loss of model/tts_model.py:197-201 and the full backward.  Returns loss3 (device, float64[3]).
+        guided=(sigma, alpha): the guided-attention term on the alignments joins the loss (t2_guided_attn: one launch for its value
+        and its gradient, which goes into the attention backward); its value is `self.guided_loss` (device, float64[1]) - None when
+        the term is off - and loss3 stays the three terms."""
+        mels, post, gates, align = outs
         B, T, M = mels.shape
+        guided = check_guided_attention(guided)
+        d_align = self.guided_loss = None
+        if guided is not None:
+            L = ctx["L"]
+            if tuple(align.shape) != (B, T, L) or not align.is_contiguous() or align.dtype != torch.float32:
+                raise ValueError(f"loss_and_grads: the alignments must be the forward's contiguous float32 {(B, T, L)} output")
+            d_align = self.buf("guided.dalign", B, T, L)
+            self.guided_loss = self.buf("guided.loss", 1, dtype=torch.float64)
+            call("t2_guided_attn", align, ctx["len32"], ctx["mlen32"], B, T, L, guided[0], guided[1], self.guided_loss, d_align,
+                 float(grad_scale), _stream())
         loss3 = self.buf("loss3", 3, dtype=torch.float64)
         d_post = self.buf("d_post", B, T, M)
         dproj = self.buf("dproj", T, B, M + 1)
         call("t2_loss_fwd_bwd", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, loss3, d_post, dproj,
              float(grad_scale), _stream())
-        self.backward_tf(ctx, d_post, dproj)
+        self.backward_tf(ctx, d_post, dproj, d_align=d_align)
         return loss3
 
     def adam_step(self, step, lr, weight_decay, max_norm=1.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, ranges=None):

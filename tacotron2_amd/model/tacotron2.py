@@ -3,8 +3,9 @@ forward signature and 4-tuple return :155-166,347, state_dict keys SURVEY.md App
 
 All learnable tensors are views into ONE flat fp32 device buffer (tacotron2_amd.params.ParamStore); they are exposed as
 ordinary nn.Parameters under the reference's module paths, so state_dict()/load_state_dict()/optimizers work unchanged.
-forward(teacher_forcing=True) is differentiable: autograd receives the hand-written backward through one
-torch.autograd.Function.  forward(teacher_forcing=False, max_len_override=N) is the autoregressive path.
+forward(teacher_forcing=True) is differentiable in all four outputs (the alignments included: a loss on the attention
+weights trains the model): autograd receives the hand-written backward through one torch.autograd.Function.
+forward(teacher_forcing=False, max_len_override=N) is the autoregressive path.
 There is no CPU fallback: the module can be constructed and (de)serialised anywhere, but forward needs the GPU library.
 """
 from __future__ import annotations
@@ -59,21 +60,23 @@ class _TacotronFn(torch.autograd.Function):
                                     training=model.training, masks=masks, save_for_backward=batch["need_grad"],
                                     controls=batch.get("controls"))
         ctx.model, ctx.ectx = model, ectx
-        ctx.mark_non_differentiable(outs[3])
+        # an output the loss does not touch arrives in backward as None, not as a tensor of zeros: the alignments are
+        # differentiable, but a loss on the mels alone allocates no (B,T,L) gradient and runs the attention backward without one
+        ctx.set_materialize_grads(False)
         return outs
 
     @staticmethod
-    def backward(ctx, d_mels, d_post, d_gates, _d_align):
+    def backward(ctx, d_mels, d_post, d_gates, d_align):
         model, ectx = ctx.model, ctx.ectx
         eng: Engine = model._engine
         ps = model.store
         B, T, M = ectx["B"], ectx["T"], model.num_mels
-        f = lambda g: g.contiguous() if g is not None else None
+        f = lambda g: g.contiguous().float() if g is not None else None
         d_post_m = eng.buf("ag.d_post", B, T, M)
         dproj = eng.buf("ag.dproj", T, B, M + 1)
         call("t2_outgrad_pack", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, _stream())
         ps.grad.zero_()
-        eng.backward_tf(ectx, d_post_m, dproj)
+        eng.backward_tf(ectx, d_post_m, dproj, d_align=f(d_align))
         grads = tuple(ps.G[name] for name in model._param_names)
         return (None, None) + grads
 

@@ -10,6 +10,7 @@ import torch
 from torch import Tensor, nn
 
 from .._lib import call
+from ..engine import check_guided_attention
 from .tacotron2 import Tacotron2
 
 
@@ -57,6 +58,31 @@ class _LossTermsFn(torch.autograd.Function):
                 d_gate * g3[0] if d_gate is not None else None, None, None, None)
 
 
+class _GuidedAttnFn(torch.autograd.Function):
+    """Guided-attention loss on the alignments (t2_guided_attn, include/tacotron2_amd.h): value and - with autograd on - the dense
+    gradient from ONE launch; backward scales it by the upstream gradient of the term."""
+
+    @staticmethod
+    def forward(ctx, alignment, chars_len, mel_len, sigma, alpha):
+        if alignment.dim() != 3 or chars_len.numel() != alignment.shape[0] or mel_len.numel() != alignment.shape[0]:
+            raise ValueError(f"guided attention: alignments {tuple(alignment.shape)} must be (B, T, L) with B text and mel lengths, "
+                             f"got {chars_len.numel()} and {mel_len.numel()}")
+        for name, t in (("text lengths", chars_len), ("mel lengths", mel_len)):
+            if t.device != alignment.device:
+                raise ValueError(f"guided attention: the {name} are on {t.device}, the alignments on {alignment.device}")
+        B, T, L = alignment.shape
+        alignment = alignment.contiguous().float()
+        loss = torch.empty(1, dtype=torch.float64, device=alignment.device)
+        ctx.grad = torch.empty_like(alignment) if ctx.needs_input_grad[0] else None
+        call("t2_guided_attn", alignment, chars_len.to(torch.int32), mel_len.to(torch.int32), B, T, L, float(sigma), float(alpha),
+             loss, ctx.grad, 1.0, torch.cuda.current_stream().cuda_stream)
+        return loss.float()[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad * g if ctx.grad is not None else None, None, None, None, None)
+
+
 class TTSModel(nn.Module):
     def __init__(self, lr: float, weight_decay: float, num_chars: int, encoded_dim: int = 512, encoder_kernel_size: int = 5,
                  num_mels: int = 80, prenet_dim: int = 256, att_rnn_dim: int = 1024, att_dim: int = 128,
@@ -82,6 +108,9 @@ class TTSModel(nn.Module):
         self.max_len_override, self.description_embeddings = max_len_override, description_embeddings
         # (back, fwd) windowed attention of predict_step and the run drivers' decoding (run/test.py); None = the whole text
         self.attention_window: Optional[Tuple[int, int]] = None
+        # (sigma, alpha) of the guided-attention loss that training_step / validation_step add to the three terms; None = off.  Set by
+        # the driver (run/train.py), not a constructor argument: checkpoint hyper_parameters stay as the reference writes them
+        self.guided_attention: Optional[Tuple[float, float]] = None
         self.tacotron2 = Tacotron2(num_chars=num_chars, encoded_dim=encoded_dim, encoder_kernel_size=encoder_kernel_size,
                                    num_mels=num_mels, prenet_dim=prenet_dim, att_rnn_dim=att_rnn_dim, att_dim=att_dim,
                                    rnn_hidden_dim=rnn_hidden_dim, postnet_dim=postnet_dim, dropout=dropout,
@@ -119,13 +148,17 @@ class TTSModel(nn.Module):
 
     def _loss(self, batch):
         data, meta = batch[0], batch[1]
+        guided = check_guided_attention(self.guided_attention)
         mel, post, gate, alignment = self(chars_idx=data["chars_idx"], chars_idx_len=meta["chars_idx_len"],
                                           teacher_forcing=True, mel_spectrogram=data["mel_spectrogram"],
                                           mel_spectrogram_len=meta["mel_spectrogram_len"], **self._args(meta))
         # the three terms of model/tts_model.py:197-199 from the library's loss kernel (no ATen arithmetic on this path)
         l3 = _LossTermsFn.apply(mel, post, gate, data["mel_spectrogram"], data["gate"], meta["mel_spectrogram_len"])
         gate_loss, mel_loss, post_loss = l3[0], l3[1], l3[2]
-        return l3.sum(), (gate_loss, mel_loss, post_loss), (mel, post, gate, alignment)
+        loss = l3.sum()
+        if guided is not None:
+            loss = loss + _GuidedAttnFn.apply(alignment, meta["chars_idx_len"], meta["mel_spectrogram_len"], *guided)
+        return loss, (gate_loss, mel_loss, post_loss), (mel, post, gate, alignment)
 
     def training_step(self, batch, batch_idx=0):
         return self._loss(batch)[0]

@@ -32,3 +32,19 @@ def model_kwargs(cfg: dict) -> dict:
                 num_mels=pre.get("num_mels", 80), speaker_tokens=spk,
                 num_speakers=ext["speaker_tokens"].get("num_speakers", 1) if spk else 1,
                 scheduler_milestones=[int(x * max_steps) for x in md.get("scheduler_milestones", [])], **args)
+
+
+def guided_attention_setting(training_config: dict, override=None):
+    """(sigma, alpha) of the guided-attention loss, or None when it is off: `override` (the --guided-attention option) wins over
+    `"training": {"guided_attention": {"sigma": 0.4, "alpha": 1.0}}` (either key may be left out: 0.4 and 1.0).  A section of
+    another form, sigma <= 0 or alpha < 0 raises ValueError."""
+    from ..engine import check_guided_attention
+    if override is not None:
+        return check_guided_attention(override)
+    sec = training_config.get("guided_attention")
+    if sec is None or sec is False:
+        return None
+    if not isinstance(sec, dict) or set(sec) - {"sigma", "alpha"}:
+        raise ValueError('training.guided_attention must be an object with the keys "sigma" and "alpha" '
+                         f'(e.g. {{"sigma": 0.4, "alpha": 1.0}}), got {sec!r}')
+    return check_guided_attention((sec.get("sigma", 0.4), sec.get("alpha", 1.0)))

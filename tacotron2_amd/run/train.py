@@ -15,7 +15,7 @@ import torch.distributed as dist
 
 from ..model.tts_model import TTSModel
 from ..trainer import Trainer
-from .common import model_kwargs
+from .common import guided_attention_setting, model_kwargs
 
 
 def _to_dev(batch, dev):
@@ -33,7 +33,10 @@ def _to_dev(batch, dev):
 
 def do_train(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
              speech_dir: str, results_dir: Optional[str], resume_ckpt: Optional[str], finetune: bool = False,
-             finetune_steps: Optional[int] = None, max_steps_override: Optional[int] = None, synthetic: bool = False):
+             finetune_steps: Optional[int] = None, max_steps_override: Optional[int] = None, synthetic: bool = False,
+             guided_attention=None):
+    """guided_attention: (sigma, alpha) of the guided-attention loss on the alignments (Trainer(guided_attention=...)); None takes the
+    config's `training.guided_attention` if there is one (`main.py train --guided-attention` wins over it), else the term is off."""
     import pandas as pd
     from ..datasets.tts_dataset import DeviceBatchLoader, DevicePrefetcher, TTSDataLoader, TTSDataset
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
@@ -69,7 +72,9 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
     from ..engine import set_float32_matmul_precision
     set_float32_matmul_precision(training_config.get("float32_matmul_precision", "highest"))
     max_steps = max_steps_override or training_config["args"]["max_steps"]
+    guided = guided_attention_setting(training_config, guided_attention)
     model = TTSModel(device=dev, **kw)
+    model.guided_attention = guided          # (the validation loss includes the term)
     start_step = 0
     # training.sync_batchnorm (not a reference key; Lightning's Trainer(sync_batchnorm=...) name): BatchNorm batch statistics over
     # all ranks' shards, so that N x b utterances give the single-device result on the N*b batch.  Default: per shard.
@@ -77,7 +82,7 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
                  scheduler_milestones=kw["scheduler_milestones"], max_norm=1.0,
                  sync_bn=bool(training_config.get("sync_batchnorm", False)),
                  overlap_allreduce=bool(training_config.get("overlap_allreduce", False)),
-                 force_collectives=force_dp)
+                 force_collectives=force_dp, guided_attention=guided)
     if world > 1 and os.environ.get("T2_SHARE_GPU") == "1":
         # rehearsal of N ranks on ONE card: persistent launches of different processes cannot promise each other co-residency
         tr.engine.dec_chain = "steps"; tr.engine.enc_chain = "steps"
@@ -208,12 +213,15 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
         steps_done += 1
         frames += batch["mel_spectrogram_len"].sum()
         if step % log_every == 0 or step == max_steps - 1:
+            if guided is not None:                              # the fourth term rides along in the same host synchronisation
+                loss3 = torch.cat([loss3, tr.last_guided_loss])
             l = [float(x) for x in loss3.cpu()]                 # the step's only host synchronisation, every log_every steps
             healthy(f"step {step + 1}", l)
             if rank == 0:
                 dt = time.time() - t0
+                gtxt = f" training_guided_loss {l[3]:.5f}" if guided is not None else ""
                 print(f"step {step + 1}/{max_steps} training_gate_loss {l[0]:.5f} training_mel_loss {l[1]:.5f} "
-                      f"training_mel_post_loss {l[2]:.5f} training_loss {sum(l):.5f} lr {tr.lr_at(step):.2e} "
+                      f"training_mel_post_loss {l[2]:.5f}{gtxt} training_loss {sum(l):.5f} lr {tr.lr_at(step):.2e} "
                       f"{int(frames) * world / max(dt, 1e-9):.0f} mel-frames/s", flush=True)
         if val_loader is not None and (step + 1) % val_every == 0:
             vl = validate()                       # every rank runs it (keeps the ranks in step); rank 0 reports
