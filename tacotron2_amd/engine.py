@@ -13,7 +13,9 @@ the hardware:
 """
 from __future__ import annotations
 
+import contextlib
 import numbers
+import threading as _threading
 from typing import Dict, Optional
 
 import torch
@@ -30,7 +32,21 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-SHARE_CU = [0]     # set to [1] while enqueuing GEMMs that run next to a latency-bound chain on another stream
+_TLS = _threading.local()      # per thread: the share_cu request (below) and the pending zero list (zero_later)
+
+
+@contextlib.contextmanager
+def share_cu(n: int):
+    """T2Gemm.share_cu of the GEMMs enqueued by this thread inside the block: 1 = ONE workgroup per CU, for GEMMs that run next to
+    a latency-bound chain on another stream.  The previous value comes back on exit, also when the body raises."""
+    prev = getattr(_TLS, "share_cu", 0)
+    _TLS.share_cu = n
+    try:
+        yield
+    finally:
+        _TLS.share_cu = prev
+
+
 # 0: fp32 GEMMs on the bf16 matrix pipe by error-free 3-way operand splitting (csrc/t2_gemm.hip, fp32-accurate, 2.7x the MFMA
 # rate); 1: f32-input MFMA.  One process-wide switch for A/B measurements and the kernel tests.
 import os as _os
@@ -52,28 +68,20 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, alpha=1.0, bias=None, bi
     """C-ABI t2_gemm on raw pointers (ints) or tensors."""
     g = make("T2Gemm", A=A, B=B, C=C, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, a_kmajor=a_k, b_kmajor=b_k,
              alpha=alpha, bias=bias, bias2=bias2, mulmask=mulmask, ldmask=ldmask, relu=relu, accumulate=accumulate,
-             splitk=splitk, batch=batch, sA=sA, sB=sB, sC=sC, share_cu=SHARE_CU[0], native_fp32=GEMM_NATIVE_FP32[0], precision=GEMM_PRECISION[0],
-             a_tap_len=a_tap_len, a_tap_stride=a_tap_stride, stat_out=stat_out, stat_Lp=stat_Lp, stat_L=stat_L)
+             splitk=splitk, batch=batch, sA=sA, sB=sB, sC=sC, share_cu=getattr(_TLS, "share_cu", 0), native_fp32=GEMM_NATIVE_FP32[0],
+             precision=GEMM_PRECISION[0], a_tap_len=a_tap_len, a_tap_stride=a_tap_stride, stat_out=stat_out, stat_Lp=stat_Lp, stat_L=stat_L)
     call("t2_gemm", g, _stream())
-
-
-_PREZEROED: Dict[int, bool] = {}      # data_ptr of buffers a phase's prologue has already put on the zero list (one-shot marks)
 
 
 def fill_splits(M: int, N: int, K: int) -> bool:
     return ((M + 127) // 128) * ((N + 127) // 128) < 256 and K >= 1024
 
 
-def gemm_fill(A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, bias=None):
-    """Plain C = A.B (+ bias) for shapes that leave the chip under-filled (fewer than 256 output tiles of 128 x 128, long K): two
-    K slices accumulate into the zeroed C with atomics - encoder convolution 178 -> 123 us, BiLSTM dgrad 123 -> 94 us
-    (tools/bench_gemm_small.py).  C must be a tensor whose first M rows of ldc floats are exactly the output."""
-    if fill_splits(M, N, K) and torch.is_tensor(C):
-        if not _PREZEROED.pop(C.data_ptr(), False):      # (cleared ahead, with the phase's other regions: Engine.prezero)
-            zero_later(C.view(-1)[:M * ldc])
-        gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=a_k, b_k=b_k, bias=bias, accumulate=2, splitk=2)
-    else:
-        gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=a_k, b_k=b_k, bias=bias)
+def chunk_splits(frames: int, B: int, D: int) -> int:
+    """K slices of the hoisted decoder-LSTM input GEMM of a forward pipeline chunk: the short chunks at the end of the ramp leave
+    the chip under-filled (8 frames x 32 rows: 64 tiles of 128 x 128) and sit on the exposed tail of the forward."""
+    tiles = ((frames * B + 127) // 128) * ((4 * D + 127) // 128)
+    return max(1, min(4, 256 // max(tiles, 1)))
 
 
 def check_attention_window(window):
@@ -119,10 +127,6 @@ def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
 # library call of the process (a hook in _lib.call), i.e. before anything enqueued later can read or accumulate into it.  Code that
 # reads such a buffer with a torch operation and no library call in between must call flush_zeros() itself.
 # Per THREAD: a loader thread that calls into the library (log-mel) must not flush - or delay - the training thread's list.
-import threading as _threading
-_TLS = _threading.local()
-
-
 def _pending() -> Dict[int, list]:
     d = getattr(_TLS, "pending", None)
     if d is None:
@@ -200,7 +204,8 @@ class Engine:
         self.d = ps.dims
         self.dev = ps.device
         self._ws: Dict[str, torch.Tensor] = {}
-        self._prez: Dict[str, bool] = {}
+        self._cleared: Dict[tuple, tuple] = {}   # (data_ptr, bytes) -> (workspace name, view): regions put on the zero list ahead
+                                                 # of the code that needs them zero and not consumed yet (clear_ahead / need_zero)
         self._bn_clean: set = set()   # BatchNorm workspace slots cleared by begin_phase and not used since
         self._persist_next = 0
         self._side = None
@@ -209,13 +214,9 @@ class Engine:
         self.dec_chain = "persistent" # forward decoder-LSTM chain: "persistent" (one weight-stationary launch per chunk on the side
                                       # stream) or "steps" (one launch per frame there; also what runs when the persistent launch
                                       # cannot be co-resident or the batch has more than 64 rows)
-        self.persist_gemm_side = True    # the hoisted pre_dec GEMM of a chunk runs on the side stream too, in front of the chunk's
-                                         # persistent launch (70.0 against 71.3 ms per step on the main stream, profiles/r02_ab_fwd_dec_chain.txt)
         self._persist_sync = None
         self._persist_ok = {}            # (D, one row tile) -> residency verdict of the persistent launch
-        self.defer_wgrads = True      # weight-gradient GEMMs of postnet, projection and encoder leave the main stream (-1.4 ms per step)
         self.wgrad_group = 4          # pipeline chunks per weight-gradient GEMM call (profiles/r02_ab_wgrad_pipeline.txt)
-        self.chunk_att_wgrads = True  # attention-chain weight gradients per pipeline chunk, behind the chain, instead of all at its end
         self.ramp_chunks = True       # short chunks at the un-overlapped end of the forward / start of the backward pipeline
         self.share_cu = 1             # side-stream GEMMs next to the chains at ONE workgroup per CU: two 73 KB-LDS workgroups
                                       # per CU lock the attention kernels out (84.3 -> 83.2 ms)
@@ -300,7 +301,7 @@ class Engine:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(main)
             if spin:
-                side.wait_event(e0)
+                self._wait(side, e0)
                 call("t2_stream_probe_spin", _ptr(w, 4), spin, side.cuda_stream)
             call("t2_stream_probe_chain", w, n, main.cuda_stream)
             e1.record(main)
@@ -395,16 +396,65 @@ class Engine:
         if self.guard_bytes > 0:
             # guard mode: exactly n elements, so the after-band starts where the view ends (never a larger earlier tensor)
             if t is None or t.numel() != n or t.dtype != dtype:
-                assert not self._prez.get(name), \
+                assert all(nm != name for nm, _ in self._cleared.values()), \
                     f"workspace {name}: prezero() and the buf(zero=True) that follows it ask for different sizes"
                 t = self._ws[name] = self._guarded(name, n, dtype)
         elif t is None or t.numel() < n or t.dtype != dtype:
             t = torch.empty(max(n, 1), dtype=dtype, device=self.dev)
             self._ws[name] = t
         v = t[:n].view(*shape)
-        if zero and not self._prez.pop(name, False):
-            zero_later(v)       # cleared by the next t2_zero_regions launch, in front of the next library call
+        return self.need_zero(v) if zero else v
+
+    # ---- regions cleared ahead of their user --------------------------------------------------------
+    # A phase's prologue puts what the phase accumulates into on the zero list at once (one launch clears all of it) and leaves a
+    # mark; the code that needs the region zero consumes the mark instead of clearing again.  A mark is the region itself, holds
+    # its view (so the address cannot be handed out again while the mark is there), is good for ONE consumer and dies with the
+    # phase (begin_phase): whoever asks for any other region - another size, another allocation, another engine - gets it cleared.
+    def clear_ahead(self, v: torch.Tensor, name: str = "") -> torch.Tensor:
+        """Put the contiguous view `v` on the zero list NOW and remember it for the need_zero() of the code that uses it."""
+        assert v.is_contiguous()
+        self._cleared[(v.data_ptr(), v.numel() * v.element_size())] = (name, zero_later(v))
         return v
+
+    def need_zero(self, v: torch.Tensor) -> torch.Tensor:
+        """`v` must be zero here: a plain lookup if this very region was cleared ahead, otherwise it goes on the zero list (cleared
+        by the next t2_zero_regions launch, in front of the next library call)."""
+        if not (v.is_contiguous() and self._cleared.pop((v.data_ptr(), v.numel() * v.element_size()), None)):
+            zero_later(v)
+        return v
+
+    def prezero(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
+        """clear_ahead of the named workspace; the later `buf(name, ..., zero=True)` of the code that uses it is a plain lookup."""
+        return self.clear_ahead(self.buf(name, *shape, dtype=dtype), name)
+
+    def gemm_fill(self, A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, bias=None):
+        """Plain C = A.B (+ bias) for shapes that leave the chip under-filled (fewer than 256 output tiles of 128 x 128, long K): two
+        K slices accumulate into the zeroed C with atomics - encoder convolution 178 -> 123 us, BiLSTM dgrad 123 -> 94 us
+        (tools/bench_gemm_small.py).  C must be a tensor whose first M rows of ldc floats are exactly the output."""
+        if fill_splits(M, N, K) and torch.is_tensor(C):
+            self.need_zero(C.view(-1)[:M * ldc])
+            gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=a_k, b_k=b_k, bias=bias, accumulate=2, splitk=2)
+        else:
+            gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=a_k, b_k=b_k, bias=bias)
+
+    def fill_ahead(self, C, M, N, K, ldc) -> None:
+        """Prologue side of gemm_fill(., ., C, M, N, K, ., ., ldc): C is cleared ahead when that GEMM will run as K slices."""
+        if fill_splits(M, N, K):
+            self.clear_ahead(C.view(-1)[:M * ldc])
+
+    # ---- cross-stream edges: flush first ---------------------------------------------------------------
+    # The zero list is launched on the stream a region was recorded for, but only in front of the next library call: an edge taken
+    # in between would not order the clear for the other stream.  (The timing events of mark / span_begin / span_end order nothing.)
+    @staticmethod
+    def _record(stream):
+        flush_zeros()
+        return stream.record_event()
+
+    @staticmethod
+    def _wait(stream, other):
+        """`stream` waits for what is enqueued on `other` (a stream) or in front of it (an event)."""
+        flush_zeros()
+        (stream.wait_event if isinstance(other, torch.cuda.Event) else stream.wait_stream)(other)
 
     def _guarded(self, name: str, n: int, dtype) -> torch.Tensor:
         short = self._guard_short.get(name, 0)
@@ -429,14 +479,6 @@ class Engine:
         sizes = sorted(((t.numel() * t.element_size(), n) for n, t in self._ws.items()), reverse=True)
         return dict(total_bytes=sum(b for b, _ in sizes), buffers=len(sizes), largest={n: b for b, n in sizes[:top]})
 
-    def prezero(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        """Allocate the named workspace and put it on the zero list NOW (a phase's prologue: one launch clears everything the phase
-        accumulates into); the later `buf(name, ..., zero=True)` of the code that uses it is then a plain lookup."""
-        v = self.buf(name, *shape, dtype=dtype)
-        zero_later(v)
-        self._prez[name] = True
-        return v
-
     BN_SLOTS = {"enc.conv0": 0, "enc.conv1": 1, "enc.conv2": 2, "post.conv0": 3, "post.conv1": 4, "post.conv2": 5, "post.conv3": 6,
                 "post.conv4": 7}
 
@@ -458,7 +500,9 @@ class Engine:
 
     def begin_phase(self, backward: bool):
         """Start of a forward (teacher-forced or inference) / of a backward: the BatchNorm sums of the phase's 8 layers and - forward
-        - the arrival-counter ring of the persistent launches go on the zero list."""
+        - the arrival-counter ring of the persistent launches go on the zero list.  Marks that an earlier phase left behind
+        (clear_ahead without its need_zero: an exception in between) end here."""
+        self._cleared.clear()
         C = max(self.d["encoded_dim"], self.d["postnet_dim"], self.d["num_mels"])
         arena = self.buf("bn.sums", 16, 2 * C + 2, dtype=torch.float64)
         zero_later(arena[8:] if backward else arena[:8])
@@ -530,7 +574,7 @@ class Engine:
             tstats = self.buf(f"{tag}.tstats", (Mg + 127) // 128, 3, Co)
             gemm(x_pad, wp, raw, Mg, Co, 5 * Ci, Ci, 5 * Ci, Co, bias=bias, stat_out=tstats, stat_Lp=Lp, stat_L=L)
         else:
-            gemm_fill(x_pad, wp, raw, Mg, Co, 5 * Ci, Ci, 5 * Ci, Co, bias=bias)
+            self.gemm_fill(x_pad, wp, raw, Mg, Co, 5 * Ci, Ci, 5 * Ci, Co, bias=bias)
         mean = self.buf(f"{tag}.mean", Co)
         invstd = self.buf(f"{tag}.invstd", Co)
         sums = self.bn_sums(tag, backward=False)
@@ -567,10 +611,8 @@ class Engine:
         E, H = d["encoded_dim"], d["encoded_dim"] // 2
         Lp = L + 4
         x = self.buf("enc.x0", B, Lp, E)
-        if fill_splits(B * Lp - 4, E, 5 * E):      # (gemm_fill: the convolutions accumulate two K slices into a cleared output)
-            for li in range(3):
-                raw = self.buf(f"enc.conv{li}.raw", B * Lp, E)
-                zero_later(raw.view(-1)[:(B * Lp - 4) * E]); _PREZEROED[raw.data_ptr()] = True
+        for li in range(3):      # (gemm_fill: under-filled convolutions accumulate two K slices into a cleared output)
+            self.fill_ahead(self.buf(f"enc.conv{li}.raw", B * Lp, E), B * Lp - 4, E, 5 * E, E)
         call("t2_embedding_fwd", chars_idx, P["encoder.embedding.weight"], x, B, L, E, 2, _stream())
         enc_drop = masks.get("enc_drop") if masks else None
         for li, i in enumerate((0, 4, 8)):
@@ -658,6 +700,44 @@ class Engine:
         gemm(ctl, P["decoder.mel_out.weight#controls"], cmel1, B, M, C, C, C, M + 1)
         return ctl, cterm, cmel1
 
+    def condition(self, pf, enc, speaker_id, description_embeddings):
+        """Conditioning (model/tacotron2.py:201-229) of the encoder output `enc` (B, L, E), workspaces prefixed `pf`: returns
+        (memory, desc, spk32, pmT)."""
+        d, P = self.d, self.ps.P
+        B, L, E = enc.shape
+        Ef = E + (128 if d.get("description_embeddings") else 0)
+        Ad = d["att_dim"]
+        st = _stream()
+        memory = self.buf(pf + "memory", B, L, Ef)
+        desc = None
+        if d.get("description_embeddings"):
+            desc = self.buf(pf + "desc", B, 128)
+            Dd = d["description_embeddings_dim"]
+            gemm(description_embeddings, P["description_embeddings_linear.0.weight"], desc, B, 128, Dd, Dd, Dd, 128)
+            call("t2_tanh_bias", desc, P["description_embeddings_linear.0.bias"], B, 128, st)
+        spk32 = speaker_id.to(torch.int32) if d.get("speaker_tokens") else None
+        call("t2_condition_fwd", enc, P["speaker_embedding.weight"] if d.get("speaker_tokens") else None, spk32, desc,
+             memory, B, L, E, Ef, st)
+        pmT = self.buf(pf + "pmT", B, Ad, L)   # processed memory, transposed: one batched GEMM W_att x memory[b]^T
+        gemm(P["att_encoder.weight"], memory, pmT, Ad, L, Ef, Ef, Ef, L, batch=B, sA=0, sB=L * Ef, sC=Ad * L)
+        return memory, desc, spk32, pmT
+
+    def postnet_fwd(self, post_in, post, mlen32, B, T, post_drop, training, ctx):
+        """Postnet (model/postnet.py) + residual + output mask (model/tacotron2.py:331-345): post_in (B, T+4, M) padded layout ->
+        post (B, T, M)."""
+        d, P = self.d, self.ps.P
+        M, Pn = d["num_mels"], d["postnet_dim"]
+        chans = [M, Pn, Pn, Pn, Pn, M]
+        x = post_in
+        for li in range(5):
+            last = li == 4
+            x = self.conv_bn_fwd(f"post.conv{li}", x, P[f"postnet.postnet.{4 * li}.weight"], None,
+                                 f"postnet.postnet.{4 * li + 1}", B, T, chans[li], chans[li + 1], 0 if last else 2,
+                                 post_drop[li] if post_drop is not None else None, training, ctx,
+                                 y=post if last else None, Lp_y=T if last else None, pad_y=0 if last else 2,
+                                 res=post_in if last else None, Lp_res=T + 4, pad_res=2,
+                                 length=mlen32 if last else None, fill=0.0)
+
     def forward_tf(self, chars_idx, chars_len, mel, mel_len, speaker_id=None, description_embeddings=None,
                    training=True, masks: Optional[dict] = None, save_for_backward=True, controls=None):
         """Returns (mels, mels_post, gates, alignments), ctx.  masks: oracle-convention dict (see oracle.tacotron2_ref)
@@ -682,7 +762,7 @@ class Engine:
         # The prenet and the hoisted prenet part of the attention-RNN input projection depend only on the mel input: they run
         # on the side stream next to the encoder, whose BiLSTM recurrence is a chain of small latency-bound launches.
         main0, side0 = torch.cuda.current_stream(), self.side_stream()
-        side0.wait_stream(main0)
+        self._wait(side0, main0)
         with torch.cuda.stream(side0):
             mel_tm = self.buf("mel_tm", T + 1, B, M)
             call("t2_mel_to_tm", mel, mel_tm, B, T, M, _stream())
@@ -701,23 +781,11 @@ class Engine:
         enc = self.encoder_fwd(chars_idx, len32, training, masks, ctx)
         self.mark("fwd.enc.bilstm")
 
-        # conditioning (model/tacotron2.py:201-229)
-        memory = self.buf("memory", B, L, Ef)
-        desc = None
-        if d.get("description_embeddings"):
-            desc = self.buf("desc", B, 128)
-            Dd = d["description_embeddings_dim"]
-            gemm(description_embeddings, P["description_embeddings_linear.0.weight"], desc, B, 128, Dd, Dd, Dd, 128)
-            call("t2_tanh_bias", desc, P["description_embeddings_linear.0.bias"], B, 128, st)
-        spk32 = speaker_id.to(torch.int32) if d.get("speaker_tokens") else None
-        call("t2_condition_fwd", enc, P["speaker_embedding.weight"] if d.get("speaker_tokens") else None, spk32, desc,
-             memory, B, L, E, Ef, st)
+        memory, desc, spk32, pmT = self.condition("", enc, speaker_id, description_embeddings)
         ctx.update(enc=enc, memory=memory, desc=desc, spk32=spk32, desc_in=description_embeddings)
-        pmT = self.buf("pmT", B, Ad, L)   # processed memory, transposed: one batched GEMM W_att x memory[b]^T
-        gemm(P["att_encoder.weight"], memory, pmT, Ad, L, Ef, Ef, Ef, L, batch=B, sA=0, sB=L * Ef, sC=Ad * L)
 
         self.mark("fwd.condition")
-        main0.wait_stream(side0)      # prenet (model/tacotron2.py:255-258) and pre_att (side stream, above) are ready
+        self._wait(main0, side0)      # prenet (model/tacotron2.py:255-258) and pre_att (side stream, above) are ready
         self.mark("fwd.dec.pre_att_gemm")
         # attention chain
         U = self.buf("U", Ad, 2, KL)
@@ -767,7 +835,6 @@ class Engine:
         # chunk i-1 - its hoisted input-projection GEMM, then the recurrence - runs on the side stream.  (Round 1 co-scheduled the
         # decoder steps inside the attention-energies launches instead; that stretched every frame of the critical chain and was
         # removed in round 4: profiles/r02_ab_fwd_dec_chain.txt.)
-        CH = self.chunk
 
         def dec_chunk(c0, c1):
             stp = make("T2LstmStep", B=B, H=D, nseg=1, wpacked=wp_dec, pre=_ptr(pre_dec, c0 * B * 4 * D), ldpre=4 * D,
@@ -785,50 +852,45 @@ class Engine:
 
         ctl, cterm, cmel1 = self.controls_terms(controls, B)
 
+        def pre_dec_splits(c0, c1):
+            # K slices of a chunk's hoisted GEMM (chunk_splits: the short ones accumulate into the pre-filled block with atomics),
+            # and whether that block is a cleared one (with controls it holds their per-utterance term instead)
+            sk = chunk_splits(c1 - c0, B, D) if self.splitk_small_chunks else 1
+            return sk, sk > 1 and cterm is None
+
         def pre_dec_gemm(c0, c1):
             if cterm is not None:     # per-utterance controls term first, the projection accumulates on top
                 pre_dec[c0:c1].copy_(cterm.unsqueeze(0).expand(c1 - c0, B, 4 * D))
-            # the short chunks at the end of the ramp leave the chip under-filled (8 frames x 32 rows: 64 tiles of 128 x 128) and
-            # sit on the exposed tail of the forward: K slices accumulate into the pre-filled block with atomics
-            tiles = (((c1 - c0) * B + 127) // 128) * ((4 * D + 127) // 128)
-            sk = max(1, min(4, 256 // max(tiles, 1))) if self.splitk_small_chunks else 1
-            if sk > 1 and cterm is None and not _PREZEROED.pop(_ptr(pre_dec, c0 * B * 4 * D), False):
-                zero_later(pre_dec[c0:c1])
+            sk, cleared = pre_dec_splits(c0, c1)
+            if cleared:
+                self.need_zero(pre_dec[c0:c1])
             gemm(_ptr(xdec, (c0 + 1) * B * (A + Ef)), P["decoder.lstm.weight_ih"], _ptr(pre_dec, c0 * B * 4 * D), (c1 - c0) * B,
                  4 * D, A + Ef, A + Ef, A + Ef, 4 * D, bias=P["decoder.lstm.bias_ih"], bias2=P["decoder.lstm.bias_hh"],
                  accumulate=2 if sk > 1 else (1 if cterm is not None else 0), splitk=sk)
 
         main, side = torch.cuda.current_stream(), self.side_stream()
-        if cterm is None and self.splitk_small_chunks:
-            # the short chunks of the ramp run their hoisted GEMM split-K into a cleared block: cleared here, with everything else
-            c0_ = 0
-            for n_ in _chunk_sizes(T, self.chunk, ramp_at_end=self.ramp_chunks):
-                if max(1, min(4, 256 // max(((n_ * B + 127) // 128) * ((4 * D + 127) // 128), 1))) > 1:
-                    zero_later(pre_dec[c0_:c0_ + n_]); _PREZEROED[_ptr(pre_dec, c0_ * B * 4 * D)] = True
-                c0_ += n_
-            flush_zeros()              # (on the main stream, in front of the side stream's wait below)
-        side.wait_stream(main)
         # Pipeline chunks; the LAST ones shrink (CH/2, CH/4, CH/8, CH/8): what follows the attention chain's end on the side stream
         # (the decoder-LSTM frames of the final chunk) is exposed time, proportional to that chunk's length.
-        sizes = _chunk_sizes(T, CH, ramp_at_end=self.ramp_chunks)
         chunks, c0 = [], 0
-        for n in sizes:
+        for n in _chunk_sizes(T, self.chunk, ramp_at_end=self.ramp_chunks):
             chunks.append((c0, c0 + n)); c0 += n
+        for c0, c1 in chunks:      # blocks that a split-K GEMM accumulates into: cleared here, with everything else
+            if pre_dec_splits(c0, c1)[1]:
+                self.clear_ahead(pre_dec[c0:c1])
+        self._wait(side, main)
         persist = B <= 64 and self.dec_chain == "persistent" and D // 4 <= 256 and self.persist_resident(D, B)
         ctx["persist"] = persist
         sync = self.persist_sync() if persist else None
         for i, (c0, c1) in enumerate(chunks):
             seq.t_begin, seq.t_end = c0, c1
             call("t2_attn_seq_fwd", seq, st)
-            if persist and not self.persist_gemm_side:
-                pre_dec_gemm(c0, c1)
-            ev = main.record_event()
+            ev = self._record(main)
             with torch.cuda.stream(side):
-                side.wait_event(ev)
-                if not persist or self.persist_gemm_side:
-                    SHARE_CU[0] = self.share_cu if persist else 0
+                self._wait(side, ev)
+                # the hoisted pre_dec GEMM of the chunk runs here too, in front of the chunk's decoder-LSTM launch (70.0 against
+                # 71.3 ms per step with it on the main stream, profiles/r02_ab_fwd_dec_chain.txt)
+                with share_cu(self.share_cu if persist else 0):
                     pre_dec_gemm(c0, c1)
-                    SHARE_CU[0] = 0
                 stp, inc = dec_chunk(c0, c1)
                 if persist:
                     # The decoder-LSTM chain of a chunk as ONE persistent, weight-stationary launch (t2_lstm_seq_fwd_persist):
@@ -838,7 +900,7 @@ class Engine:
                 else:
                     call("t2_lstm_seq_fwd", stp, inc, 1, c1 - c0, side.cuda_stream)
         self.mark("fwd.dec.attn_chain")
-        main.wait_stream(side)
+        self._wait(main, side)
         self.mark("fwd.dec.lstm_chain_tail")
 
         # mel + stop projection over all frames: [mel_out.weight ; gate.weight] is one (M+1, D+Ef) matrix
@@ -861,20 +923,8 @@ class Engine:
         post_in = self.buf("post.x0", B, T + 4, M)
         call("t2_finalize_fwd", proj, M + 1, mlen32, mels, gates, post_in, B, T, M, st)
 
-        # postnet (model/postnet.py) + residual + output masks (model/tacotron2.py:331-345)
-        Pn = d["postnet_dim"]
-        chans = [M, Pn, Pn, Pn, Pn, M]
-        post_drop = masks.get("post_drop")
-        x = post_in
         post = self.out("post", B, T, M)
-        for li in range(5):
-            last = li == 4
-            x = self.conv_bn_fwd(f"post.conv{li}", x, P[f"postnet.postnet.{4 * li}.weight"], None,
-                                 f"postnet.postnet.{4 * li + 1}", B, T, chans[li], chans[li + 1], 0 if last else 2,
-                                 post_drop[li] if post_drop is not None else None, training, ctx,
-                                 y=post if last else None, Lp_y=T if last else None, pad_y=0 if last else 2,
-                                 res=post_in if last else None, Lp_res=T + 4, pad_res=2,
-                                 length=mlen32 if last else None, fill=0.0)
+        self.postnet_fwd(post_in, post, mlen32, B, T, masks.get("post_drop"), training, ctx)
         self.mark("fwd.postnet")
         ctx.update(controls=ctl, pmT=pmT, mel_tm=mel_tm, p1=p1, p2=p2, pd=pd, pre_att=pre_att, U=U, xdec=xdec, att_c=att_c, cum=cum,
                    xproj=xproj, gates_att=gates_att, th=th, align=align, pre_dec=pre_dec, dec_c=dec_c,
@@ -890,7 +940,9 @@ class Engine:
 
     def conv_bn_bwd(self, tag, ctx, dy, Lp_dy, pad_dy, w, gw, gbias, bn_prefix, B, L, Ci, Co, act, training, need_dx=True,
                     defer=None, wgrad_stream=None):
-        """Backward of conv_bn_fwd.  dy: gradient w.r.t. the layer output.  Returns dX in shifted rows (B*(L+4), Ci)."""
+        """Backward of conv_bn_fwd.  dy: gradient w.r.t. the layer output.  Returns dX in shifted rows (B*(L+4), Ci).  The weight
+        gradient is not on the critical path: it is appended to the list `defer` (the caller runs it later, on whatever stream is
+        current then), or runs at once on `wgrad_stream`, behind everything enqueued here so far."""
         P, G = self.ps.P, self.ps.G
         c = ctx[tag]
         Lp = L + 4
@@ -912,25 +964,23 @@ class Engine:
         R = B * Lp - 4
         if gbias is not None:
             call("t2_colsum", draw, Co, B * Lp, Co, gbias, st)
-        def wgrad():     # not on the critical path: with `defer` it is run later, on whatever stream is current then
+        def wgrad():
             dwp = self.buf(f"{tag}.dwp", Co, 5 * Ci, zero=True)
             self._wgrad(_ptr(draw, 2 * Co), Co, c["x_pad"], Ci, dwp, 5 * Ci, Co, 5 * Ci, R)
             call("t2_unpack_conv_wgrad", dwp, gw, Co, Ci, 5, _stream())
         if defer is not None:
             defer.append(wgrad)
-        elif wgrad_stream is not None:      # at once, but on another stream (behind everything enqueued here so far)
-            ev = torch.cuda.current_stream().record_event()
-            with torch.cuda.stream(wgrad_stream):
-                wgrad_stream.wait_event(ev)
-                wgrad()
         else:
-            wgrad()
+            ev = self._record(torch.cuda.current_stream())
+            with torch.cuda.stream(wgrad_stream):
+                self._wait(wgrad_stream, ev)
+                wgrad()
         if not need_dx:
             return None
         wf = self.buf(f"{tag}.wf", Ci, 5 * Co)
         call("t2_pack_conv_weight", w, wf, Co, Ci, 5, 1, st)
         dx = self.buf(f"{tag}.dx", B * Lp, Ci)
-        gemm_fill(draw, wf, dx, R, Ci, 5 * Co, Co, 5 * Co, Ci)
+        self.gemm_fill(draw, wf, dx, R, Ci, 5 * Co, Co, 5 * Co, Ci)
         return dx
 
     def backward_tf(self, ctx, d_post, dproj, d_align=None):
@@ -967,31 +1017,26 @@ class Engine:
         self.begin_phase(backward=True)
         # accumulators of the deferred weight-gradient GEMMs (run later, mostly on the side stream) and the split-K outputs of the
         # encoder's data-gradient GEMMs: cleared here, in the backward's first launch, not one launch each
-        pchans = [M, Pn, Pn, Pn, Pn, M]
+        chans = [M, Pn, Pn, Pn, Pn, M]
         for li in range(5):
-            self.prezero(f"post.conv{li}.dwp", pchans[li + 1], 5 * pchans[li])
+            self.prezero(f"post.conv{li}.dwp", chans[li + 1], 5 * chans[li])
         Lp_e = L + 4
         for li in range(3):
             self.prezero(f"enc.conv{li}.dwp", E, 5 * E)
-            if fill_splits(B * Lp_e - 4, E, 5 * E):
-                dxe = self.buf(f"enc.conv{li}.dx", B * Lp_e, E)
-                zero_later(dxe.view(-1)[:(B * Lp_e - 4) * E]); _PREZEROED[dxe.data_ptr()] = True
-        if fill_splits(B * Lp_e - 4, E, 8 * H):
-            dxe = self.buf("enc.dx3", B * Lp_e, E)
-            zero_later(dxe.view(-1)[:(B * Lp_e - 4) * E]); _PREZEROED[dxe.data_ptr()] = True
+            self.fill_ahead(self.buf(f"enc.conv{li}.dx", B * Lp_e, E), B * Lp_e - 4, E, 5 * E, E)
+        self.fill_ahead(self.buf("enc.dx3", B * Lp_e, E), B * Lp_e - 4, E, 8 * H, E)
 
         # ---- postnet --------------------------------------------------------------------------------
-        chans = [M, Pn, Pn, Pn, Pn, M]
         dy, Lp_dy = d_post, T
         # the five weight-gradient GEMMs of the postnet (1.5 ms) leave the critical path: they run on the side stream between the
-        # chunks of the backward frame loop, where the decoder-LSTM chain has slack
-        post_wgrads = [] if self.defer_wgrads else None
+        # chunks of the backward frame loop, where the decoder-LSTM chain has slack (with the projection's there and the encoder's
+        # on the side stream too: -1.4 ms per step, the round-2 A/B indexed in profiles/README.md)
+        post_wgrads = []
         for li in range(4, -1, -1):
             dy = self.conv_bn_bwd(f"post.conv{li}", ctx, dy, Lp_dy, 0, P[f"postnet.postnet.{4 * li}.weight"],
                                   G[f"postnet.postnet.{4 * li}.weight"], None, f"postnet.postnet.{4 * li + 1}", B, T,
                                   chans[li], chans[li + 1], 0 if li == 4 else 2, training, defer=post_wgrads)
             Lp_dy = T + 4
-        post_wgrads = post_wgrads or []
         call("t2_finalize_bwd", dy, dproj, B, T, M, st)
         self.mark("bwd.postnet")
 
@@ -1011,10 +1056,7 @@ class Engine:
                 s_proj = self.buf("ctl.dproj_sum", B, M + 1, zero=True)
                 call("t2_colsum", dproj, B * (M + 1), T, B * (M + 1), s_proj, _stream())
                 self._wgrad(s_proj, M + 1, ctl, C, G["decoder.mel_out.weight#controls"], C, M, C, B)
-        if self.defer_wgrads:
-            post_wgrads.append(proj_wgrads)
-        else:
-            proj_wgrads()
+        post_wgrads.append(proj_wgrads)
 
         # ---- both recurrences, back-propagation through time, as a two-stream pipeline over chunks of frames -----------
         # side stream: decoder-LSTM BPTT of chunk k (1 launch / frame) + the GEMM that turns its gate gradients into
@@ -1061,7 +1103,7 @@ class Engine:
                   ws_bd=self.buf("attn.ws_bd", Ad // 16 * 16896))
         self.mark("bwd.dec.proj")
         main, side = torch.cuda.current_stream(), self.side_stream()
-        side.wait_stream(main)
+        self._wait(side, main)
         CH = self.chunk_bwd
 
         def dec_bwd_chunk(hi, lo):
@@ -1078,33 +1120,11 @@ class Engine:
                        c_cur=-B * D, dt=0, dgt=-Bp * 4 * D)
             return s, inc
 
-        def dxdec_gemm(hi, lo, share_cu=0):
-            SHARE_CU[0] = share_cu
-            gemm(_ptr(dgd, lo * B * 4 * D), P["decoder.lstm.weight_ih"], _ptr(dxdec, lo * B * ldx), (hi - lo) * B, ldx, 4 * D,
-                 4 * D, ldx, ldx, a_k=1, b_k=0)
-            SHARE_CU[0] = 0
-
         def dec_wgrads_chunk(hi, lo):    # decoder-LSTM weight gradients over frames [lo, hi) (accumulating)
             n = (hi - lo) * B
             g0 = _ptr(dgd, lo * B * 4 * D)
             self._wgrad(g0, 4 * D, _ptr(xdec, (lo + 1) * B * ldx), ldx, G["decoder.lstm.weight_ih"], ldx, 4 * D, ldx, n)
             self._wgrad(g0, 4 * D, _ptr(xproj, lo * B * ldp), ldp, G["decoder.lstm.weight_hh"], D, 4 * D, D, n)
-
-        def dec_wgrads():   # decoder-LSTM weight gradients, on the side stream next to the attention chain's tail
-            with torch.cuda.stream(side):
-                if not self.chunk_att_wgrads:
-                    SHARE_CU[0] = self.share_cu
-                    dec_wgrads_chunk(T, 0)
-                    SHARE_CU[0] = 0
-                db = self.buf("db_dec", 4 * D, zero=True)                      # both biases see the same gate gradients
-                call("t2_colsum", dgd, 4 * D, R, 4 * D, db, side.cuda_stream)
-                for nm in ("decoder.lstm.bias_ih", "decoder.lstm.bias_hh"):    # t2_colsum over ONE row = accumulate
-                    call("t2_colsum", db, 4 * D, 1, 4 * D, G[nm], side.cuda_stream)
-                if ctl is not None:
-                    s_dgd = self.buf("ctl.dgd_sum", B, 4 * D, zero=True)
-                    call("t2_colsum", dgd, B * 4 * D, T, B * 4 * D, s_dgd, side.cuda_stream)
-                    self._wgrad(s_dgd, 4 * D, ctl, ctl.shape[1], G["decoder.lstm.weight_ih#controls"], ctl.shape[1], 4 * D,
-                                ctl.shape[1], B)
 
         # (time-descending) the FIRST chunks are short: the attention chain cannot start before the decoder-LSTM BPTT of its first
         # chunk and that chunk's GEMM are done on the side stream
@@ -1127,51 +1147,57 @@ class Engine:
             self._wgrad(z0, ldz, _ptr(xdec, lo * B * ldx), ldx, G["decoder.att_rnn.weight_hh"], A, 4 * A, A, n)
             self._wgrad(_ptr(Z, (lo + 1) * B * ldz + 4 * A), ldz, _ptr(xdec, (lo + 1) * B * ldx), ldx,
                         G["decoder.attention.query_layer.weight"], A, Ad, A, n)
-        # Weight gradients along the pipeline: frames are handed to the weight-gradient GEMMs in groups of `wgrad_group` chunks
-        # (a longer K per call keeps the split-K GEMMs efficient); ranges are contiguous and time-descending, so a group is one
-        # [lo, hi) range.  dec_*: gate gradients of the decoder-LSTM BPTT (this stream's own output: no wait);  att_*: of the
-        # attention chain (main stream: wait for the event recorded behind the group's last chunk).
+        # Weight gradients along the pipeline (not all at its end: profiles/r02_ab_wgrad_pipeline.txt): frames are handed to the
+        # weight-gradient GEMMs in groups of `wgrad_group` chunks (a longer K per call keeps the split-K GEMMs efficient); ranges are
+        # contiguous and time-descending, so a group is one [lo, hi) range.  dec_*: gate gradients of the decoder-LSTM BPTT (this
+        # stream's own output: no wait);  att_*: of the attention chain (main stream: wait for the event recorded behind the group's
+        # last chunk).
         WG = max(1, int(self.wgrad_group))
         dec_grp, att_done, att_grp = None, [], None        # [hi, lo, n]; [(hi, lo, event)]; [hi, lo, n, event]
         for ci_, (hi, lo) in enumerate(chunks):
-            with torch.cuda.stream(side):
+            with torch.cuda.stream(side), share_cu(self.share_cu):
                 s, inc = dec_bwd_chunk(hi, lo)
                 call("t2_lstm_seq_bwd", s, inc, 1, hi - lo, side.cuda_stream)
-                dxdec_gemm(hi, lo, self.share_cu)
-                ev = side.record_event()
+                gemm(_ptr(dgd, lo * B * 4 * D), P["decoder.lstm.weight_ih"], _ptr(dxdec, lo * B * ldx), (hi - lo) * B, ldx, 4 * D,
+                     4 * D, ldx, ldx, a_k=1, b_k=0)
+                ev = self._record(side)
                 # behind the event (the attention chain does not wait for any of this)
-                SHARE_CU[0] = self.share_cu
-                if self.chunk_att_wgrads:
-                    dec_grp = [hi, lo, 1] if dec_grp is None else [dec_grp[0], lo, dec_grp[2] + 1]
-                    if dec_grp[2] >= WG:
-                        dec_wgrads_chunk(dec_grp[0], dec_grp[1]); dec_grp = None
+                dec_grp = [hi, lo, 1] if dec_grp is None else [dec_grp[0], lo, dec_grp[2] + 1]
+                if dec_grp[2] >= WG:
+                    dec_wgrads_chunk(dec_grp[0], dec_grp[1]); dec_grp = None
                 if post_wgrads and ci_ >= 4:
                     post_wgrads.pop(0)()
-                if self.chunk_att_wgrads and len(att_done) >= 2:      # chunks the main stream finished two chunks ago
+                if len(att_done) >= 2:      # chunks the main stream finished two chunks ago
                     h2, l2, e2 = att_done.pop(0)
                     att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
                     if att_grp[2] >= WG:
-                        side.wait_event(att_grp[3])
+                        self._wait(side, att_grp[3])
                         att_wgrads(att_grp[0], att_grp[1]); att_grp = None
-                SHARE_CU[0] = 0
-            main.wait_event(ev)
+            self._wait(main, ev)
             sb.t_hi, sb.t_lo = hi, lo
             call("t2_attn_seq_bwd", sb, st)
-            if self.chunk_att_wgrads:
-                att_done.append((hi, lo, main.record_event()))
+            att_done.append((hi, lo, self._record(main)))
         with torch.cuda.stream(side):
             while post_wgrads:                      # (short sequences: fewer chunks than deferred GEMMs)
                 post_wgrads.pop(0)()
-            SHARE_CU[0] = self.share_cu
-            if dec_grp is not None:
-                dec_wgrads_chunk(dec_grp[0], dec_grp[1])
-            for h2, l2, e2 in att_done:
-                att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
-            if att_grp is not None:
-                side.wait_event(att_grp[3])
-                att_wgrads(att_grp[0], att_grp[1])
-            SHARE_CU[0] = 0
-        dec_wgrads()
+            with share_cu(self.share_cu):
+                if dec_grp is not None:
+                    dec_wgrads_chunk(dec_grp[0], dec_grp[1])
+                for h2, l2, e2 in att_done:
+                    att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
+                if att_grp is not None:
+                    self._wait(side, att_grp[3])
+                    att_wgrads(att_grp[0], att_grp[1])
+            # decoder-LSTM bias (and controls) gradients, next to the attention chain's tail
+            db = self.buf("db_dec", 4 * D, zero=True)                      # both biases see the same gate gradients
+            call("t2_colsum", dgd, 4 * D, R, 4 * D, db, side.cuda_stream)
+            for nm in ("decoder.lstm.bias_ih", "decoder.lstm.bias_hh"):    # t2_colsum over ONE row = accumulate
+                call("t2_colsum", db, 4 * D, 1, 4 * D, G[nm], side.cuda_stream)
+            if ctl is not None:
+                s_dgd = self.buf("ctl.dgd_sum", B, 4 * D, zero=True)
+                call("t2_colsum", dgd, B * 4 * D, T, B * 4 * D, s_dgd, side.cuda_stream)
+                self._wgrad(s_dgd, 4 * D, ctl, ctl.shape[1], G["decoder.lstm.weight_ih#controls"], ctl.shape[1], 4 * D,
+                            ctl.shape[1], B)
         self.mark("bwd.dec.chains")
 
         # gradient w.r.t. the encoder memory: context path (batched over samples) + processed-memory path.  It heads the
@@ -1184,11 +1210,9 @@ class Engine:
         # Independent branch on the side stream: weight gradients of the attention chain (large GEMMs over all frames) and the
         # prenet backward.  The main stream meanwhile walks the encoder BiLSTM backward recurrence, a chain of small
         # latency-bound launches that fits next to the GEMM workgroups.
-        side.wait_stream(main)
+        self._wait(side, main)
         with torch.cuda.stream(side):
             sst = side.cuda_stream
-            if not self.chunk_att_wgrads:
-                att_wgrads(T, 0)
             db = self.buf("db_att", 4 * A, zero=True)
             call("t2_colsum", dga, ldz, R, 4 * A, db, sst)
             for nm in ("decoder.att_rnn.bias_ih", "decoder.att_rnn.bias_hh"):
@@ -1281,25 +1305,21 @@ class Engine:
             self._wgrad(dpre, 8 * H, _ptr(x3, 2 * E), E, ps.cat_view("encoder.lstm.weight_ih_l0", 8 * H, E, grad=True), E, 8 * H, E, Rr)
             call("t2_colsum", dpre, 8 * H, B * Lp, 8 * H, ps.cat_view("encoder.lstm.bias_ih_l0", 8 * H, 0, grad=True), _stream())
             call("t2_colsum", dpre, 8 * H, B * Lp, 8 * H, ps.cat_view("encoder.lstm.bias_hh_l0", 8 * H, 0, grad=True), _stream())
-        enc_wgrad_stream = side if self.defer_wgrads else None
-        if enc_wgrad_stream is not None:     # the encoder's weight gradients leave the main stream too (it keeps the dgrad chain)
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                bilstm_wgrads()
-        else:
+        ev = self._record(main)              # the encoder's weight gradients leave the main stream too (it keeps the dgrad chain)
+        with torch.cuda.stream(side):
+            self._wait(side, ev)
             bilstm_wgrads()
         dx = self.buf("enc.dx3", B * Lp, E)
-        gemm_fill(dpre, ps.cat_view("encoder.lstm.weight_ih_l0", 8 * H, E), dx, Rr, E, 8 * H, 8 * H, E, E, a_k=1, b_k=0)
+        self.gemm_fill(dpre, ps.cat_view("encoder.lstm.weight_ih_l0", 8 * H, E), dx, Rr, E, 8 * H, 8 * H, E, E, a_k=1, b_k=0)
 
         self.mark("bwd.bilstm")
         # ---- encoder convolutions + embedding -----------------------------------------------------------------
         for li, i in reversed(list(enumerate((0, 4, 8)))):
             dx = self.conv_bn_bwd(f"enc.conv{li}", ctx, dx, Lp, 0, P[f"encoder.convolutions.{i}.weight"],
                                   G[f"encoder.convolutions.{i}.weight"], G[f"encoder.convolutions.{i}.bias"],
-                                  f"encoder.convolutions.{i + 1}", B, L, E, E, 1, training, wgrad_stream=enc_wgrad_stream)
+                                  f"encoder.convolutions.{i + 1}", B, L, E, E, 1, training, wgrad_stream=side)
         call("t2_embedding_bwd", ctx["chars_idx"], dx, G["encoder.embedding.weight"], B, L, E, Lp, 0, st)
-        torch.cuda.current_stream().wait_stream(self.side_stream())
+        self._wait(main, side)
         self.mark("bwd.encoder_convs")
 
     # =============================================================================================
@@ -1355,21 +1375,9 @@ class Engine:
         M, E, Pd, A, D, Ad = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
-        st = _stream()
         pf = f"inf{g}."
         len32 = chars_len.to(torch.int32)
-        memory = self.buf(pf + "memory", B, L, Ef)
-        desc = None
-        if d.get("description_embeddings"):
-            desc = self.buf(pf + "desc", B, 128)
-            Dd = d["description_embeddings_dim"]
-            gemm(description_embeddings, P["description_embeddings_linear.0.weight"], desc, B, 128, Dd, Dd, Dd, 128)
-            call("t2_tanh_bias", desc, P["description_embeddings_linear.0.bias"], B, 128, st)
-        spk32 = speaker_id.to(torch.int32) if d.get("speaker_tokens") else None
-        call("t2_condition_fwd", enc, P["speaker_embedding.weight"] if d.get("speaker_tokens") else None, spk32, desc,
-             memory, B, L, E, Ef, st)
-        pmT = self.buf(pf + "pmT", B, Ad, L)
-        gemm(P["att_encoder.weight"], memory, pmT, Ad, L, Ef, Ef, Ef, L, batch=B, sA=0, sB=L * Ef, sC=Ad * L)
+        memory, _, _, pmT = self.condition(pf, enc, speaker_id, description_embeddings)
         ldp = D + Ef
         ldo = (M + 1 + 3) // 4 * 4
         Bp = (B + 15) // 16 * 16
@@ -1498,8 +1506,7 @@ class Engine:
             buf = pins[k & 1]
             for gi, G in enumerate(groups):
                 buf[gi].copy_(G["state"], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
+            ev = self._record(torch.cuda.current_stream())
             if pend is not None:
                 pend[0].synchronize()
                 if bool((pend[1][:, 0] != 0).all()):
@@ -1525,17 +1532,7 @@ class Engine:
             Bg = G["B"]
             call("t2_finalize_fwd", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
                  post_in[b0:b0 + Bg], Bg, n, M, st)
-        Pn = d["postnet_dim"]
-        chans = [M, Pn, Pn, Pn, Pn, M]
-        x = post_in
         post = self.out("inf.post", B, n, M)
-        pctx: dict = {}
-        for li in range(5):
-            last = li == 4
-            x = self.conv_bn_fwd(f"post.conv{li}", x, P[f"postnet.postnet.{4 * li}.weight"], None,
-                                 f"postnet.postnet.{4 * li + 1}", B, n, chans[li], chans[li + 1], 0 if last else 2, None,
-                                 training, pctx, y=post if last else None, Lp_y=n if last else None,
-                                 pad_y=0 if last else 2, res=post_in if last else None, Lp_res=n + 4, pad_res=2,
-                                 length=mlen32 if last else None, fill=0.0)
+        self.postnet_fwd(post_in, post, mlen32, B, n, None, training, {})
         align = groups[0]["align"][:, :n] if len(groups) == 1 else torch.cat([G["align"][:, :n] for G in groups])
         return mels, post, gates, align.contiguous(), lengths.clone()

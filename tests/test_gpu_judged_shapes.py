@@ -35,7 +35,7 @@ def _bench_schedule(eng, T):
     persistent decoder-LSTM launches, weight gradients in groups of four chunks (five groups), deferred weight-gradient GEMMs."""
     from tacotron2_amd.engine import _chunk_sizes
     assert (eng.chunk, eng.chunk_bwd, eng.dec_chain, eng.wgrad_group) == (64, 64, "persistent", 4)
-    assert eng.ramp_chunks and eng.defer_wgrads and eng.chunk_att_wgrads and eng.bptt_off_chain and eng.splitk_small_chunks
+    assert eng.ramp_chunks and eng.bptt_off_chain and eng.splitk_small_chunks
     sizes = _chunk_sizes(T, eng.chunk)
     assert T == 872 and sizes == [64] * 12 + [40, 32, 16, 8, 8] and len(sizes) == 17
 

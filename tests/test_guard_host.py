@@ -114,6 +114,79 @@ def test_prezero_then_buf_of_another_size_asserts_in_guard_mode(no_zero_list):
         eng.buf("post.conv1.dwp", 4, 11, zero=True)
 
 
+# ---- marks of regions cleared ahead (Engine.clear_ahead / need_zero) ---------------------------------------------------------------
+def _region(t):
+    return t.data_ptr(), t.numel() * t.element_size()
+
+
+def test_buf_of_another_size_after_prezero_is_cleared_in_product_mode(no_zero_list):
+    eng = _engine(0)
+    eng.prezero("x", 4, 10)
+    no_zero_list.clear()
+    v = eng.buf("x", 4, 11, zero=True)             # a new, larger allocation: the mark is for another region
+    assert len(no_zero_list) == 1 and _region(no_zero_list[0]) == _region(v) and v.shape == (4, 11)
+
+
+def test_a_mark_does_not_outlive_begin_phase(no_zero_list):
+    eng = _engine(0)
+    eng.prezero("y", 4, 10)
+    eng.begin_phase(backward=True)                 # (the phase that set the mark was abandoned)
+    no_zero_list.clear()
+    v = eng.buf("y", 4, 10, zero=True)
+    assert len(no_zero_list) == 1 and _region(no_zero_list[0]) == _region(v)
+
+
+def test_a_fill_gemm_mark_stays_with_its_engine_and_its_phase(no_zero_list, monkeypatch):
+    gemms = []
+    monkeypatch.setattr(E, "gemm", lambda *a, **k: gemms.append(k))
+    eng, other = _engine(0), _engine(0)
+    C = torch.empty(128, 128)
+    assert E.fill_splits(128, 128, 1024)
+    eng.fill_ahead(C, 128, 128, 1024, 128)         # the encoder's prologue: clear now and remember
+    assert len(no_zero_list) == 1 and eng._cleared
+    for e in (eng, other):
+        e.begin_phase(backward=False)
+        no_zero_list.clear()
+        e.gemm_fill(None, None, C, 128, 128, 1024, 1024, 1024, 128)
+        assert len(no_zero_list) == 1 and _region(no_zero_list[0]) == _region(C)
+        assert gemms[-1]["accumulate"] == 2 and gemms[-1]["splitk"] == 2
+    # within one phase of one engine the consumer finds the mark, once
+    eng.fill_ahead(C, 128, 128, 1024, 128)
+    no_zero_list.clear()
+    eng.gemm_fill(None, None, C, 128, 128, 1024, 1024, 1024, 128)
+    assert no_zero_list == [] and not eng._cleared
+    eng.gemm_fill(None, None, C, 128, 128, 1024, 1024, 1024, 128)
+    assert len(no_zero_list) == 1
+
+
+def test_a_mark_is_consumed_once(no_zero_list):
+    eng = _engine(0)
+    eng.prezero("z", 4, 10)
+    no_zero_list.clear()
+    eng.buf("z", 4, 10, zero=True)
+    assert no_zero_list == []                      # the first user finds the region cleared ahead ...
+    v = eng.buf("z", 4, 10, zero=True)
+    assert len(no_zero_list) == 1 and _region(no_zero_list[0]) == _region(v)     # ... the second one in the phase clears it
+
+
+def test_share_cu_request_is_restored_when_the_body_raises(monkeypatch):
+    seen = []
+    monkeypatch.setattr(E, "make", lambda name, **kw: seen.append(kw["share_cu"]))
+    monkeypatch.setattr(E, "call", lambda *a: None)
+    monkeypatch.setattr(E, "_stream", lambda: 0)
+    g = lambda: E.gemm(None, None, None, 1, 1, 1, 1, 1, 1)
+    g()
+    with pytest.raises(RuntimeError, match="boom"):
+        with E.share_cu(1):
+            g()
+            with E.share_cu(0):
+                g()
+            g()
+            raise RuntimeError("boom")
+    g()
+    assert seen == [0, 1, 0, 1, 0]
+
+
 def test_guarded_outputs_are_fresh_and_checked():
     eng = _engine(512)
     a = eng.out("mels", 2, 3)
