@@ -245,7 +245,22 @@ int t2_lstm_seq_bwd(const T2LstmBwdStep* base, const T2LstmBwdStride* inc, int n
  * The location features still read w_prev / cum_prev over the full row (the window +- (Kl-1)/2 positions), so w_prev must be
  * the previous frame's full weights row (zero outside its window).  Energies, softmax and context touch only the window: the
  * work and bytes per frame follow its width, not L.  The cumulative weights are updated in place (cum_out == cum_prev
- * required), th_out must be NULL.  A window as wide as the text (win_back, win_fwd >= L) is the unconstrained step. */
+ * required), th_out must be NULL.  A window as wide as the text (win_back, win_fwd >= L) is the unconstrained step.
+ *
+ * Forward attention (autoregressive decoding only; Zhang et al. 2018, Mozilla TTS's `forward_attn` without a transition agent):
+ * with forward != 0 the step carries a probability over monotonic paths - attention stays where it is or advances one position
+ * per frame.  For utterance b with length len, frame t >= 0 and position n:
+ *     y_t(n)     = the softmax over the masked energies of frame t (model/attention.py:52-69); the energies come from the location
+ *                  features of [alpha_{t-1}, cum_{t-1}] exactly as without the option: the weights fed back (w_prev) are the forward
+ *                  weights alpha, and at frame 0 the location features see zeros
+ *     q_t(n)     = 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8,   alpha_{t-1}(-1) = 0
+ *     alpha_{-1} = one-hot at position 0 (w_prev == NULL): q_0(0) = q_0(1) = 0.5 + 1e-8, q_0(n) = 1e-8 elsewhere.  The 1e-8 floor
+ *                  keeps the sum positive when the softmax puts its mass where the prior is zero
+ *     alpha_t(n) = q_t(n) y_t(n) / sum_m q_t(m) y_t(m) for n < len, exactly 0.0 for n >= len
+ * Everything downstream uses alpha_t: the context sum_n alpha_t(n) memory(n), cum_t = cum_{t-1} + alpha_t, the returned
+ * alignments row (w_out) and the next frame's location features.  The softmax denominator cancels, so the kernel multiplies
+ * each exp term by q before its one block sum.  forward together with win_peak or with th_out is an argument error; w_out must
+ * not be w_prev (every workgroup of the context launch reads w_prev, one of them writes w_out). */
 typedef struct {
     int B, L, A, Ad, Ef, Kl;
     const float* att_h; int64_t ldh;
@@ -261,6 +276,7 @@ typedef struct {
                                                 clock (s_memtime) at phase boundaries: energies [0..3], context [8..13] */
     int win_back, win_fwd;                   /* attention window (with win_peak): see "Windowed attention" above */
     int32_t* win_peak;                       /* NULL = unconstrained (the whole text); else [2][B] int32 device words */
+    int forward;                             /* 0 = off; else forward attention: see "Forward attention" above */
 } T2AttnStep;
 int t2_attn_fold_location(const float* Wd, const float* Wc, float* U, int Ad, int F, int Kl, void* stream);
 int t2_attn_step_fwd(const T2AttnStep* s, void* stream);
@@ -474,6 +490,8 @@ typedef struct {
     int32_t* win_peak;               /* NULL = unconstrained attention (as before); else [2][B] int32, zero-filled by the caller
                                         before frame 0: the windowed attention step of every frame (T2AttnStep), with the
                                         cumulative weights kept in place in cum slot 0 (slot 1 unused) */
+    int forward;                     /* 0 = off; else forward attention in every frame (T2AttnStep.forward; frame 0 starts from the
+                                        one-hot prior).  Not together with win_peak */
 } T2Infer;
 int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream);
 /* proj[g] [nframes][Bg[g]][ld_proj] for g < ngroups (<= 64 groups of up to 64 utterances) -> lengths [sum Bg] int64,

@@ -4,11 +4,11 @@
     python main.py --config C --device N train --speech-dir S [--results-dir R] [--resume-ckpt K] [--finetune --finetune-steps n]
                                                   [--guided-attention SIGMA,ALPHA]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
-                                                  [--attention-window BACK,FWD]
+                                                  [--attention-window BACK,FWD | --forward-attention]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
-                                                  [--attention-window BACK,FWD]
+                                                  [--attention-window BACK,FWD | --forward-attention]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
-                                                  [--attention-window BACK,FWD]
+                                                  [--attention-window BACK,FWD | --forward-attention]
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
 
 Other reference sub-commands (preprocess, server) are data preparation / demo tooling outside the hot-path scope
@@ -51,6 +51,21 @@ attention_window_option = click.option(
     help="Windowed (monotonic) attention: each decoder frame attends only to the text positions from BACK before to FWD after "
          "the previous frame's attention peak (ESPnet's attention constraint; 1,3 is the usual value). Default: off, the whole "
          "text.")
+
+
+forward_attention_option = click.option(
+    "--forward-attention", is_flag=True, default=False,
+    help="Forward attention (Zhang et al. 2018; Mozilla TTS's use_forward_attn): each decoder frame's attention stays where it is or "
+         "advances one text position; no skipping ahead, no jumping back. The config's model.forward_attention sets the default; "
+         "the flag wins. Not together with --attention-window. Default: off.")
+
+
+def forward_attention_arg(forward_attention, attention_window):
+    """The drivers' forward_attention argument: True for the flag, None (= the config's model.forward_attention) without it; the
+    flag together with --attention-window is a usage error."""
+    if forward_attention and attention_window is not None:
+        raise click.UsageError("--forward-attention and --attention-window do not combine: use one of the two")
+    return True if forward_attention else None
 
 
 @click.group()
@@ -102,7 +117,10 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--controls", required=False, type=str, default=None, help="If controls are enabled, a comma-separated list of values to pass into the model. Defaults to all 0 values.")
 @click.option("--description", required=False, type=str, default=None, help="Path of a precomputed description embedding (.pt / .npy, pooler_output of bert-base-uncased); raw text needs the BERT weights (unavailable offline)")
 @attention_window_option
-def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window):
+@forward_attention_option
+def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
+        forward_attention):
+    forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for speech!")
     from tacotron2_amd.run.say import do_say
@@ -110,7 +128,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
     do_say(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
            extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, text=text, output=out,
            speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
-           description=description, attention_window=attention_window)
+           description=description, attention_window=attention_window, forward_attention=forward_attention)
 
 
 @main.command()
@@ -123,8 +141,11 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit", required=False, type=int, default=None, help="Only the first n utterances of the test manifest.")
 @attention_window_option
-def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window):
+@forward_attention_option
+def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window,
+         forward_attention):
     """Synthesise the test manifest (run/test.py of the reference): one wav per utterance + failures.csv."""
+    forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
     from tacotron2_amd.run.test import do_test
@@ -132,7 +153,7 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
     do_test(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
             extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
             hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit,
-            attention_window=attention_window)
+            attention_window=attention_window, forward_attention=forward_attention)
 
 
 @main.command()
@@ -145,14 +166,18 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit-overrides", required=False, type=int, default=None, help="Only the first n of the 51 control overrides.")
 @attention_window_option
+@forward_attention_option
 def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides,
-                     attention_window):
+                     attention_window, forward_attention):
     """The test manifest under 51 control-vector overrides (run/test_correlation.py of the reference)."""
+    forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
     from tacotron2_amd.run.test_correlation import do_test_correlation
     c = ctx.obj["config"]
     model_config = c["model"] if attention_window is None else dict(c["model"], attention_window=list(attention_window))
+    if forward_attention:      # load_test_model reads it from the model config, as it does the window
+        model_config = dict(model_config, forward_attention=True)
     do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=model_config,
                         extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
                         hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, samples_per_speaker=samples_per_speaker,

@@ -15,6 +15,8 @@
 //     softmax over l (block reductions, LDS-staged), then its 32-column slice of
 //     context[b][e] = sum_l w[l] * memory[b][l][e]  (128-byte coalesced rows), slice 0 also writes the new
 //     weights (the alignments row) and cumulative weights.
+//  attn_energy_win_kernel / attn_context_win_kernel: the same bodies over an attention window (inference);
+//  attn_context_fwd_kernel: the context body with the forward-attention prior folded into its softmax (inference).
 #include "t2_common.hpp"
 #include "t2_lstm_step.hpp"
 
@@ -401,7 +403,10 @@ __global__ __launch_bounds__(ENT, 4) void attn_energy_win_kernel(AttnK p) {
 // WIN: softmax and weighted sum over the window [lo, lo + W) only (every window position is < len); slice 0 writes the weights
 // and the cumulative weights of the window (cum in place: each position is read and written by the same thread) and the
 // frame's peak m_t = the lowest window position of the largest weight (torch.argmax) into win_peak[b].
-template <bool WIN>
+// FWD: forward attention (include/tacotron2_amd.h, "Forward attention"): the weights are alpha_t(l) = q(l) y(l) / sum_m q(m) y(m) with
+// y the softmax below and the prior q(l) = 0.5 w_prev[l] + 0.5 w_prev[l-1] + 1e-8 (w_prev == NULL: one-hot at position 0).  The
+// softmax denominator cancels, so every exp term is multiplied by q before the wave and block sums: still ONE workgroup exchange.
+template <bool WIN, bool FWD = false>
 __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, const int es0, float* sm) {
     const int tid = threadIdx.x;
     [[maybe_unused]] const bool stamp = b == 0 && es0 == 0 && tid == 0;
@@ -426,6 +431,17 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) ev0[jj] = p.e_part[((long)b * NA + imin(jj, NA - 1)) * Lt + lo + lc];
     }
+    // FWD: the previous frame's weights at position tid and tid - 1 ride with the energies (they are a frame old: ready); frame 0
+    // reads a dummy row and selects the one-hot prior afterwards, so the loads are unconditional
+    [[maybe_unused]] float* qv = part + 256;                                     // [WS] the prior q(l)
+    [[maybe_unused]] const float* wr = p.w_prev ? p.w_prev + (long)b * p.ldw : p.e_part + (long)b * NA * Lt;
+    [[maybe_unused]] const bool w1h = p.w_prev == nullptr;
+    [[maybe_unused]] float wq0 = 0.f, wq1 = 0.f;
+    if constexpr (FWD) {
+        const int lc = imin(tid, L - 1);
+        wq0 = wr[lc];
+        wq1 = wr[imax(lc - 1, 0)];
+    }
     __builtin_amdgcn_sched_barrier(0);   // keep these loads in front (the scheduler otherwise sinks them behind the rows below)
     // ---- issue: encoder-memory slice of the first 192 positions (independent of the softmax, consumed after it) ----
     const float* mp = p.memory + ((long)b * Lt + lo) * p.Ef + es0 + el;
@@ -448,10 +464,18 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) e += (j0 + jj) < NA ? ev[jj] : 0.f;
         }
+        if constexpr (FWD) {
+            if (l0 > 0) { wq0 = wr[lc]; wq1 = wr[lc - 1]; }
+        }
         if (l < L) {
             if (!WIN && l >= len) e = -INFINITY;
             ws[l] = e;
             mx = fmaxf(mx, e);
+            if constexpr (FWD) {
+                const float a0 = w1h ? (l == 0 ? 1.f : 0.f) : wq0;
+                const float a1 = l == 0 ? 0.f : (w1h ? (l == 1 ? 1.f : 0.f) : wq1);
+                qv[l] = 0.5f * a0 + 0.5f * a1 + 1e-8f;
+            }
         }
     }
     float cprev[2] = {0.f, 0.f};   // previous cumulative weights for the (<= 2) positions this thread writes
@@ -467,7 +491,8 @@ __device__ __forceinline__ void attn_context_body(const AttnK& p, const int b, c
     const float mws = mw == -INFINITY ? 0.f : mw;
     float sum = 0.f;
     for (int l = tid; l < L; l += 256) {
-        const float pe = expf(ws[l] - mws);
+        float pe = expf(ws[l] - mws);
+        if constexpr (FWD) pe *= qv[l];
         ws[l] = pe;
         sum += pe;
     }
@@ -556,6 +581,12 @@ __global__ __launch_bounds__(256, 1) void attn_context_win_kernel(AttnK p) {
     attn_context_body<true>(p, blockIdx.x, blockIdx.y * 32, sm);
 }
 
+__global__ __launch_bounds__(256, 1) void attn_context_fwd_kernel(AttnK p) {
+    T2_CHAIN_PRIO();
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    attn_context_body<false, true>(p, blockIdx.x, blockIdx.y * 32, sm);
+}
+
 // U[a][c][k] = sum_f Wd[a][f] * Wc[f][c][k]
 __global__ void fold_location_kernel(const float* Wd, const float* Wc, float* U, int Ad, int F, int CK) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -578,6 +609,11 @@ int check_attn(const T2AttnStep& s) {
         T2_REQUIRE(!s.th_out, "attention: the windowed step has no tanh stash (inference only)");
         T2_REQUIRE(s.cum_prev && s.cum_out == s.cum_prev && s.ldco == s.ldcum,
                    "attention: the windowed step updates the cumulative weights in place (cum_out == cum_prev)");
+    }
+    if (s.forward) {
+        T2_REQUIRE(!s.win_peak, "attention: forward attention does not compose with the attention window");
+        T2_REQUIRE(!s.th_out, "attention: the forward-attention step has no tanh stash (inference only)");
+        T2_REQUIRE(s.w_out != s.w_prev, "attention: the forward-attention step reads w_prev in every workgroup (w_out != w_prev)");
     }
     return T2_OK;
 }
@@ -610,6 +646,15 @@ int launch_attn(const T2AttnStep& s, hipStream_t st) {
                    "attention: the window is too wide for the LDS images of the attention kernels");
         hipLaunchKernelGGL(attn_energy_win_kernel, dim3(s.B, s.Ad / 16), dim3(ENT), sm_e, st, k);
         hipLaunchKernelGGL(attn_context_win_kernel, dim3(s.B, s.Ef / 32), dim3(256), sm_c, st, k);
+        T2_CHECK_LAUNCH();
+        return T2_OK;
+    }
+    if (s.forward) {   // the energies as ever (they read w_prev / cum_prev = the forward weights); the context kernel keeps q(l) in LDS
+        const size_t sm_f = sm_c + (size_t)wsn * sizeof(float);
+        T2_REQUIRE(t2_allow_lds(attn_energy_kernel, sm_e) && t2_allow_lds(attn_context_fwd_kernel, sm_f),
+                   "attention: the text is too long for the LDS images of the attention kernels");
+        hipLaunchKernelGGL(attn_energy_kernel, dim3(s.B, s.Ad / 16), dim3(ENT), sm_e, st, k);
+        hipLaunchKernelGGL(attn_context_fwd_kernel, dim3(s.B, s.Ef / 32), dim3(256), sm_f, st, k);
         T2_CHECK_LAUNCH();
         return T2_OK;
     }

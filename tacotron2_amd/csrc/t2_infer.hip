@@ -254,6 +254,7 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
     T2_REQUIRE(P % 16 == 0 && A % 16 == 0 && Ef % 16 == 0 && D % 16 == 0, "t2_decoder_infer: P, A, Ef, D must be multiples of 16");
     T2_REQUIRE(a->W_comb && a->W_pre2 && a->proj && a->xs, "t2_decoder_infer: null operand");
     T2_REQUIRE(!a->win_peak || (a->win_back >= 0 && a->win_fwd >= 0), "t2_decoder_infer: attention window bounds must be >= 0");
+    T2_REQUIRE(!(a->forward && a->win_peak), "t2_decoder_infer: forward attention does not compose with the attention window");
     const long ldp = D + Ef, ldo = a->ld_proj;
     const int Bp = (B + 15) / 16 * 16;
     const long cs = (long)Bp * 16;                               // chunk stride of the tiled state
@@ -322,6 +323,7 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
             q.cum_prev = q.cum_out = a->cum;
             q.win_back = a->win_back; q.win_fwd = a->win_fwd; q.win_peak = a->win_peak;
         }
+        q.forward = a->forward;   // frame 0 has w_prev == NULL: the one-hot prior
         q.ctx_out = a->xproj + D; q.ldctx = ldp;
         q.ctxt_out = xs_nxt; q.ctxt_col0 = P + A;
         T2_TRY(t2_attn_step_launch(&q, st));

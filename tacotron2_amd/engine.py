@@ -98,6 +98,15 @@ def check_attention_window(window):
     return int(back), int(fwd)
 
 
+def check_forward_attention(forward, window=None):
+    """True or False -> the same; anything else, or True together with an attention window, raises ValueError."""
+    if not isinstance(forward, bool):
+        raise ValueError(f"forward_attention must be True or False, got {forward!r}")
+    if forward and window is not None:
+        raise ValueError("forward_attention does not compose with attention_window: use one of the two")
+    return forward
+
+
 def check_guided_attention(guided):
     """None, or (sigma, alpha) of the guided-attention loss as two real numbers, sigma > 0 and alpha >= 0 -> a tuple of floats;
     anything else raises ValueError."""
@@ -1367,7 +1376,7 @@ class Engine:
     # autoregressive inference: forward(teacher_forcing=False, max_len_override=N)  (model/tacotron2.py:262-325)
     # =============================================================================================
     def _infer_group(self, g, enc, chars_len, Tcap, speaker_id, description_embeddings, training, prenet_masks, controls,
-                     attention_window=None):
+                     attention_window=None, forward_attention=False):
         """Conditioning and decode-loop operands of one group of <= 64 utterances (workspaces prefixed inf<g>.); `enc` is the
         group's slice of the encoder output, computed for the WHOLE batch by the caller."""
         d, P, ps = self.d, self.ps.P, self.ps
@@ -1410,7 +1419,7 @@ class Engine:
         if attention_window is not None:     # [2][B] peaks, row 0 zero-filled: m_{-1} = 0 (include/tacotron2_amd.h)
             win = dict(win_back=int(attention_window[0]), win_fwd=int(attention_window[1]),
                        win_peak=self.buf(pf + "win_peak", 2, B, dtype=torch.int32, zero=True))
-        a = make("T2Infer", B=B, L=L, A=A, D=D, Ef=Ef, Ad=Ad, P=Pd, M=M, Kl=KL, Tcap=Tcap, **win,
+        a = make("T2Infer", B=B, L=L, A=A, D=D, Ef=Ef, Ad=Ad, P=Pd, M=M, Kl=KL, Tcap=Tcap, **win, forward=int(forward_attention),
                  W_comb=self._w_comb, b_comb=self._b_comb, row_comb=row_comb, W_pre2=P["prenet.3.weight"],
                  W_comb_t=self._w_comb_t, W_pre2_t=self._w_pre2_t, p1_t=self.buf(pf + "p1_t", Pd // 16, Bp, 16, zero=True),
                  wp_att=self._wp_att_inf, b_att_ih=P["decoder.att_rnn.bias_ih"], b_att_hh=P["decoder.att_rnn.bias_hh"],
@@ -1421,7 +1430,7 @@ class Engine:
         return dict(a=a, B=B, proj=proj, align=align, state=state, pm=pm, philox=prenet_masks is None and pm is not None)
 
     def infer(self, chars_idx, chars_len, max_len, speaker_id=None, description_embeddings=None, training=False,
-              prenet_masks=None, seed=0, check_every=32, controls=None, attention_window=None):
+              prenet_masks=None, seed=0, check_every=32, controls=None, attention_window=None, forward_attention=False):
         """Returns (mels, mels_post, gates, alignments, lengths) exactly as the reference's non-teacher-forced forward: ONE loop
         over the whole batch that ends when every utterance has produced a negative stop logit (model/tacotron2.py:319-322).
         Batches above 64 utterances are decoded as groups of 64 in lock-step chunks of `check_every` frames; the break frame
@@ -1429,9 +1438,14 @@ class Engine:
         prenet_masks: optional [n][2][B][P] scale masks (parity tests); otherwise Philox masks (AlwaysDropout).
         attention_window: optional (back, fwd), integers >= 0 - frame t attends only to the positions
         max(0, m - back) .. min(len - 1, m + fwd) around the previous frame's attention peak m (0 before the first frame); the
-        other alignments are exactly 0 (include/tacotron2_amd.h, "Windowed attention").  None: the whole text, as before."""
-        d, P, ps = self.d, self.ps.P, self.ps
+        other alignments are exactly 0 (include/tacotron2_amd.h, "Windowed attention").  None: the whole text, as before.
+        forward_attention: True - every frame's weights are alpha_t(n) = q_t(n) y_t(n) / sum_m q_t(m) y_t(m) with y_t the softmax
+        and the prior q_t(n) = 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8, alpha_{-1} one-hot at position 0: attention stays
+        or advances one position per frame (include/tacotron2_amd.h, "Forward attention").  Context, cumulative weights, the
+        returned alignments and the next frame's location features all use alpha.  Not together with attention_window."""
         attention_window = check_attention_window(attention_window)
+        forward_attention = check_forward_attention(forward_attention, attention_window)
+        d, P, ps = self.d, self.ps.P, self.ps
         B, L = chars_idx.shape
         assert B <= 4096, "engine.infer handles up to 4096 utterances per call (64 groups of 64)"
         self.generation += 1          # the encoder / postnet workspaces are shared with forward_tf
@@ -1481,7 +1495,7 @@ class Engine:
                 speaker_id[sl] if speaker_id is not None else None,
                 description_embeddings[sl].contiguous() if description_embeddings is not None else None, training,
                 prenet_masks[:, :, sl].contiguous() if (prenet_masks is not None and B > 64) else prenet_masks,
-                controls[sl] if controls is not None else None, attention_window))
+                controls[sl] if controls is not None else None, attention_window, forward_attention))
         p = float(d["dropout"])
         t0 = 0
         self.mark("inf.encoder")

@@ -16,7 +16,7 @@ import torch
 from torch import Tensor, nn
 
 from .._lib import call
-from ..engine import Engine, _stream, check_attention_window
+from ..engine import Engine, _stream, check_attention_window, check_forward_attention
 from ..init import init_parameters
 from ..params import ParamStore
 
@@ -160,14 +160,20 @@ class Tacotron2(nn.Module):
                 mel_spectrogram: Optional[Tensor] = None, mel_spectrogram_len: Optional[Tensor] = None,
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
-                dropout_masks: Optional[dict] = None, attention_window: Optional[Tuple[int, int]] = None):
+                dropout_masks: Optional[dict] = None, attention_window: Optional[Tuple[int, int]] = None,
+                forward_attention: bool = False):
         """attention_window (autoregressive decoding only): (back, fwd) integers >= 0 - each frame attends only to the positions
         max(0, m - back) .. min(len - 1, m + fwd) around the previous frame's attention peak m (ESPnet's `use_att_constraint`);
-        None attends to the whole text, as the reference does."""
+        None attends to the whole text, as the reference does.
+        forward_attention (autoregressive decoding only, not together with attention_window): True decodes with forward
+        attention (Zhang et al. 2018; Mozilla TTS's `use_forward_attn` without a transition agent) - the weights of a frame are
+        the softmax times the prior 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8, renormalised (Engine.infer)."""
         if attention_window is not None:
             if teacher_forcing:
                 raise ValueError("attention_window applies to autoregressive decoding only (teacher_forcing=False)")
             attention_window = check_attention_window(attention_window)
+        if check_forward_attention(forward_attention, attention_window) and teacher_forcing:
+            raise ValueError("forward_attention applies to autoregressive decoding only (teacher_forcing=False)")
         if teacher_forcing:
             assert mel_spectrogram is not None, "Ground-truth Mel spectrogram is required for teacher forcing"
             assert mel_spectrogram_len is not None, "Ground-truth Mel spectrogram lengths are required for teacher forcing"
@@ -197,7 +203,7 @@ class Tacotron2(nn.Module):
                                    description_embeddings=description_embeddings.contiguous().float()
                                    if description_embeddings is not None else None,
                                    training=self.training, prenet_masks=pm, seed=self._seed + self._calls, controls=controls,
-                                   attention_window=attention_window)
+                                   attention_window=attention_window, forward_attention=forward_attention)
             self._calls += 1
         return o[:4]
 

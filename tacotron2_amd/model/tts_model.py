@@ -108,6 +108,8 @@ class TTSModel(nn.Module):
         self.max_len_override, self.description_embeddings = max_len_override, description_embeddings
         # (back, fwd) windowed attention of predict_step and the run drivers' decoding (run/test.py); None = the whole text
         self.attention_window: Optional[Tuple[int, int]] = None
+        # forward attention of predict_step and the run drivers' decoding (Tacotron2.forward); False = the plain softmax weights
+        self.forward_attention: bool = False
         # (sigma, alpha) of the guided-attention loss that training_step / validation_step add to the three terms; None = off.  Set by
         # the driver (run/train.py), not a constructor argument: checkpoint hyper_parameters stay as the reference writes them
         self.guided_attention: Optional[Tuple[float, float]] = None
@@ -130,11 +132,12 @@ class TTSModel(nn.Module):
                 mel_spectrogram: Optional[Tensor] = None, mel_spectrogram_len: Optional[Tensor] = None,
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
-                attention_window: Optional[Tuple[int, int]] = None):
+                attention_window: Optional[Tuple[int, int]] = None, forward_attention: bool = False):
         return self.tacotron2(chars_idx=chars_idx, chars_idx_len=chars_idx_len, teacher_forcing=teacher_forcing,
                               mel_spectrogram=mel_spectrogram, mel_spectrogram_len=mel_spectrogram_len,
                               speaker_id=speaker_id, controls=controls, max_len_override=max_len_override,
-                              description_embeddings=description_embeddings, attention_window=attention_window)
+                              description_embeddings=description_embeddings, attention_window=attention_window,
+                              forward_attention=forward_attention)
 
     def _args(self, meta):
         args = {}
@@ -176,6 +179,7 @@ class TTSModel(nn.Module):
         with torch.no_grad():
             return self(chars_idx=data["chars_idx"], chars_idx_len=meta["chars_idx_len"], teacher_forcing=False,
                         max_len_override=self.max_len_override or 5000, attention_window=self.attention_window,
+                        forward_attention=self.forward_attention,
                         **self._args(meta))
 
     # Lightning-style checkpoint exchange: {"state_dict": {"tacotron2.<name>": tensor}, "hyper_parameters": {...}}

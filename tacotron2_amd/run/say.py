@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
-from ..engine import check_attention_window
+from ..engine import check_attention_window, check_forward_attention
 from ..model.tts_model import TTSModel
 from .common import model_kwargs
 
@@ -41,7 +41,8 @@ def load_description(description: Optional[str], dim: int, n: int, dev) -> torch
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
-           description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None):
+           description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
+           forward_attention: Optional[bool] = None):
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
@@ -58,6 +59,9 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     if attention_window is None:       # the config's model.attention_window, if any (as load_test_model does)
         attention_window = model_config.get("attention_window")
     model.attention_window = check_attention_window(attention_window)
+    if forward_attention is None:      # likewise the config's model.forward_attention (a bool)
+        forward_attention = model_config.get("forward_attention", False)
+    model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
     kw = {}
     if model.speaker_tokens:
         kw["speaker_id"] = torch.full((len(texts),), int(speaker_id or 0), dtype=torch.int32, device=dev)
@@ -71,7 +75,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         kw["controls"] = torch.tensor([vals] * len(texts), dtype=torch.float32, device=dev)
     with torch.no_grad():
         _, post, gates, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                  attention_window=model.attention_window, **kw)
+                                  attention_window=model.attention_window, forward_attention=model.forward_attention, **kw)
     post = post.cpu().numpy()
     # run/say.py:155,161 keeps mel_spectrogram_post[:, :-1]: all emitted frames but the last.  The stop frame itself is already
     # masked (gate -1000 from `lengths` on), so an utterance that stopped keeps its `lengths` = n - 1 frames; one that ran into

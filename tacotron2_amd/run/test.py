@@ -23,16 +23,19 @@ import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
-from ..engine import check_attention_window
+from ..engine import check_attention_window, check_forward_attention
 from ..model.tts_model import TTSModel
 from .common import model_kwargs
 
 
 def load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed=None,
-                    attention_window=None):
+                    attention_window=None, forward_attention=None):
     """TTSModel.load_from_checkpoint as run/test.py:116-130 calls it (max_len_override 5000, no scheduler), in eval mode.
     attention_window: (back, fwd) of the windowed attention the model decodes with (TTSModel.attention_window); None takes the
-    config's `model.attention_window` if there is one (`main.py --attention-window` puts it there for test-correlation), else off."""
+    config's `model.attention_window` if there is one (`main.py --attention-window` puts it there for test-correlation), else off.
+    forward_attention: True decodes with forward attention (TTSModel.forward_attention); None takes the config's
+    `model.forward_attention` (a bool; `main.py --forward-attention` puts it there for test-correlation), else off.  Forward
+    attention together with a window is refused."""
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
     kw["scheduler_milestones"] = []
@@ -43,6 +46,9 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
     if attention_window is None:
         attention_window = model_config.get("attention_window")
     model.attention_window = check_attention_window(attention_window)
+    if forward_attention is None:
+        forward_attention = model_config.get("forward_attention", False)
+    model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
     return model
 
 
@@ -80,7 +86,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     zero_length: what is written for an utterance that never stopped (mel_length 0): "test" = run/test.py:176-193 (wav_length
     becomes -1 and is applied twice: the row minus its last two samples); "correlation" = run/test_correlation.py:196-209 (an
     empty file).  Both log the utterance.  Griffin-Lim (librosa raises on an empty spectrogram): logged, nothing written.
-    The decode uses the model's attention window (TTSModel.attention_window, set by load_test_model; None = off)."""
+    The decode uses the model's attention window (TTSModel.attention_window, set by load_test_model; None = off) or its forward
+    attention (TTSModel.forward_attention; False = off)."""
     from ..vocoder import write_wav
     dev = model.tacotron2.store.device
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
@@ -116,7 +123,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
             args["description_embeddings"] = torch.stack(rows).to(dev)
         with torch.no_grad():
             _, post, gate, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                     attention_window=model.attention_window, **args)
+                                     attention_window=model.attention_window,
+                                     forward_attention=getattr(model, "forward_attention", False), **args)
         mel_lengths = (gate[:, :, 0] < 0).to(torch.int64).argmax(dim=-1).cpu().tolist()
         for k, j in enumerate(sel):
             i += 1
@@ -143,7 +151,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
 def do_test(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
             speech_dir: Optional[str], checkpoint: str, hifi_gan_checkpoint: Optional[str] = None,
             results_dir: Optional[str] = None, batch_size: int = 8, max_len: int = 5000, limit: Optional[int] = None,
-            random_seed: Optional[int] = None, attention_window: Optional[Tuple[int, int]] = None) -> List[str]:
+            random_seed: Optional[int] = None, attention_window: Optional[Tuple[int, int]] = None,
+            forward_attention: Optional[bool] = None) -> List[str]:
     import pandas as pd
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
@@ -154,7 +163,7 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
     if limit is not None:
         df = df.iloc[:int(limit)].reset_index(drop=True)
     model = load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
-                            attention_window)
+                            attention_window, forward_attention)
     ctl_cfg = extensions_config.get("controls", {"active": False})
     feats = df[ctl_cfg["features"]].values.tolist() if model.controls else None
     if results_dir is None:
