@@ -354,6 +354,23 @@ typedef struct {
 } T2AttnSeqBwd;
 int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream);
 
+/* The same chain with the three accumulators nothing on it waits for (dpmT, dv_part, dU_part) taken off it.
+ *   t2_attn_seq_bwd_stash: frame t writes its energy gradients to de_stash + t * ld_stash ([B][L], ld_stash >= B * L; the
+ *   stash spans all T frames) instead of the reused workspace `de`, and the per-slice launch computes only what the next launch
+ *   needs (ds -> dq, the location-input gradient); dpmT, dv_part and dU_part are NOT touched.  de_stash = NULL: exactly
+ *   t2_attn_seq_bwd.
+ *   t2_attn_acc_bwd: one launch, grid (B, Ad/16), for the frames t_end-1 .. t_begin (the chain's order) that a stash call has
+ *   finished: rebuilds ds from the stashed de, the tanh stash and v, keeps its dpmT slice, dv and dU sums in registers over
+ *   the frames and adds them to dpmT / dv_part / dU_part once.  It may run on another stream behind the chain call's event;
+ *   calls for different frame ranges must not overlap each other (plain read-modify-write, no atomics).  It reads th, align,
+ *   cum, v, dpmT, dv_part, dU_part and the dims of `a`.  Sums are re-associated per call: results match t2_attn_seq_bwd to
+ *   rounding, not bit for bit; everything else the chain writes is bit-identical.
+ * Texts longer than one pass (L > 252) ignore the stash: t2_attn_seq_bwd_stash accumulates in the chain as t2_attn_seq_bwd
+ * does, and t2_attn_acc_bwd returns without a launch.
+ * (The stash travels as arguments: T2AttnSeqBwd keeps its layout.) */
+int t2_attn_seq_bwd_stash(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, void* stream);
+int t2_attn_acc_bwd(const T2AttnSeqBwd* a, const float* de_stash, int64_t ld_stash, int t_begin, int t_end, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Conv stacks (encoder model/encoder.py:31-46,57; postnet model/postnet.py:8-49).
  * Activations use the padded channel-last layout (B, Lp = L+4, C): data rows [2, L+2), zero rows elsewhere, so a

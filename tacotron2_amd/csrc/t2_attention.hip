@@ -757,10 +757,15 @@ extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) {
 //     An upstream gradient da on the weights as returned (T2AttnSeqBwd.dalign, optional) is one more term of the same softmax
 //     backward: de[l] = w[l] * (dw[l] + dwx[l] + da[l] - sigma), sigma += sum_l w[l]*da[l].  It is NOT part of G_t: the carry is
 //     the gradient that reaches w_t through the cumulative weights, da reaches w_t directly.
-//  attn_bwd_ds_mfma_kernel / attn_bwd_ds_tiled_kernel   grid (B, Ad/16): workgroup (b, j) owns 16 attention dims for all l.
+//  attn_bwd_ds_mfma_kernel / attn_bwd_ds_chain_kernel / attn_bwd_ds_tiled_kernel   grid (B, Ad/16): workgroup (b, j) owns 16
+//  attention dims for all l.
 //     ds[l][a] = de[l] * v[a] * (1 - th^2);  dpmT += ds;  dq[a] = sum_l ds;  dv[a] += sum_l de[l]*th[l][a]
 //     dU[a][c][k] += sum_l ds[l][a] * in[c][l+k-15]                   (per-sample partial, summed after the loop)
 //     d_in partial [c][l'] = sum_{a in slice,k} ds[l'+15-k][a] * U[a][c][k]  (summed over slices by the next frame)
+//     Only ds, dq and the d_in partials are waited for by the next launch of the frame.  With a de stash (t2_attn_seq_bwd_stash)
+//     the chain runs attn_bwd_ds_chain_kernel, which computes just those, and
+//  attn_bwd_acc_kernel  grid (B, Ad/16), off the chain: walks the frames of a chunk in the chain's order, rebuilds ds from the
+//     stashed de, and keeps its dpmT slice, dv and dU sums in registers until one read-modify-write per call.
 struct AttnBwdK {
     int B, L, Ad, Ef;
     const float* dctx; long lddctx;
@@ -775,6 +780,8 @@ struct AttnBwdK {
     float* dpmT; float* dq; long lddq; float* dv_part; float* dU_part; float* din_part_out;
     unsigned long long* clk;   // diagnostic stamps (T2AttnSeqBwd.clk) or null
     const unsigned* bd;        // fragment-ready bf16 planes of the d_in filter operand (attn_bwd_prep_kernel)
+    // attn_bwd_acc_kernel only: frames t_end-1 .. t_begin; de, th, cum_prev and w (NOT w_prev) then point at frame 0
+    int t_begin, t_end; long de_fs, th_fs, cum_fs, w_fs;
 };
 
 namespace {
@@ -968,11 +975,19 @@ __host__ __device__ inline DsDims ds_dims(int L) {
     return d;
 }
 
-template <bool TILED>
+// MODE: which share of the frame's work an instantiation does
+//   DS_FULL   everything, one frame per launch (no de stash, and every text longer than one pass)
+//   DS_CHAIN  what the chain waits for: ds -> dq, d_in partials.  No dpmT, dv, dU, no location-input planes
+//   DS_ACC    the rest, for the frames [t_begin, t_end) of one launch: dpmT, dv, dU summed in registers, added to memory once
+enum { DS_FULL = 0, DS_CHAIN = 1, DS_ACC = 2 };
+
+template <bool TILED, int MODE>
 __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* sm) {
+    constexpr bool ACC = MODE != DS_CHAIN, CHN = MODE != DS_ACC, WALK = MODE == DS_ACC;
+    static_assert(!TILED || MODE == DS_FULL, "position tiles accumulate in the chain");
     const int b = blockIdx.x, j = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63;
-    [[maybe_unused]] const bool stamp = b == 0 && j == 0 && tid == 0;
+    [[maybe_unused]] const bool stamp = !WALK && b == 0 && j == 0 && tid == 0;
     T2_STAMP(p, stamp, 24);
     T2_RING_BEGIN(p.clk, stamp, 4);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -983,14 +998,15 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
     const DsDims dm = ds_dims(TILED ? imin(Lg, DS_TI + 2 * DS_MARGIN) : Lg);
     const int S16 = dm.S16, LpI = dm.LpI;
     u32x4v* DX = reinterpret_cast<u32x4v*>(sm);              // [3][16][S16] items of 8 bf16
-    unsigned* PX = reinterpret_cast<unsigned*>(DX + 48 * S16);   // [3][2*LpI] neighbour pairs, in[c][l'] at index l' + 40
-    float* des = reinterpret_cast<float*>(PX + 6 * LpI);     // [4 + L4 + 4]: de[l] at index l + 1 (zero at 0, past L and outside the owned range)
-    float* redC = des + dm.L4 + 8;                           // [4][256]   phase C: second K half of each (c,k) tile
+    unsigned* PX = reinterpret_cast<unsigned*>(DX + 48 * S16);   // ACC: [3][2*LpI] neighbour pairs, in[c][l'] at index l' + 40
+    float* des = reinterpret_cast<float*>(PX + (ACC ? 6 * LpI : 0));   // [4 + L4 + 4]: de[l] at index l + 1 (zero at 0, past L and outside the owned range)
+    float* redC = des + dm.L4 + 8;                           // ACC: [4][256]   phase C: second K half of each (c,k) tile
     float* dinacc = redC + 4 * 256;                          // TILED: [2][Lg4] d_in of this slice over the whole text
     float* red = reinterpret_cast<float*>(DX);               // [8][MT][256] phase D: the waves' K shares (aliases DX after the MFMAs)
     const long rowoff = ((long)b * p.Ad + a) * Lg;
     const float va = p.v[a];
     const float* th_base = p.th + ((long)b * p.Ad + a) * Lg4;
+    float dpv[EMAXI][4];                                     // old dpmT values of this thread's positions; DS_ACC: their sums over the frames
     // phase C result ownership of waves 0..3: tile nt = w, lane holds dims 4q + r, column n -> (c, k)
     const int c_nt = w & 3, c_c = c_nt >> 1, c_k = 16 * (c_nt & 1) + n;
     float sq = 0.f, sv = 0.f;                                // dq, dv of this thread's positions (all tiles)
@@ -1001,7 +1017,20 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
     if (TILED) {
         for (int i = tid; i < 2 * Lg4; i += ENT) dinacc[i] = 0.f;
     }
-    for (int tile = 0; tile < ntile; ++tile) {
+    if (WALK) {
+#pragma unroll
+        for (int it = 0; it < EMAXI; ++it)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dpv[it][i] = 0.f;
+        for (int i = tid; i < 48 * S16; i += ENT) DX[i] = (u32x4v){0u, 0u, 0u, 0u};     // halo and tail: every frame rewrites the same items
+    }
+    // DS_ACC walks frames t_end - 1 .. t_begin here, the other modes the position tiles of their one frame
+    const int nwalk = WALK ? p.t_end - p.t_begin : ntile;
+    for (int tile = 0; tile < nwalk; ++tile) {
+        const int fr = WALK ? p.t_end - 1 - tile : 0;
+        const float* de_fr = WALK ? p.de + fr * p.de_fs : p.de;
+        const float* w_prev = WALK ? (fr > 0 ? p.w + (fr - 1) * p.w_fs : nullptr) : p.w_prev;
+        const float* cum_prev = WALK ? p.cum_prev + fr * p.cum_fs : p.cum_prev;
         // owned positions [a0, b0), window [v0, v1) in text coordinates; everything below runs in window coordinates l = 0 .. L-1
         const int a0 = TILED ? tile * DS_TI : 0, b0 = TILED ? imin(a0 + DS_TI, Lg) : Lg;
         const int v0 = TILED ? imax(a0 - DS_MARGIN, 0) : 0, v1 = TILED ? imin(b0 + DS_MARGIN, Lg) : Lg;
@@ -1013,11 +1042,21 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
         const int NGA = (L + 4) >> 2;                        // groups 0 .. NGA - 1 cover positions -1 .. L - 1 (<= 64 for L <= 252)
         // ---- issue: the energy gradients first (the only operand that depends on the previous launch), tanh stash / old dpmT,
         //      location inputs, old accumulator values, the d_in filter fragments ----
-        float dev[TILED ? 1 : 2];
+        float dev[TILED ? 1 : 2], dew[EMAXI][4];
+        if (!WALK) {
 #pragma unroll
-        for (int i = 0; i < (TILED ? 1 : 2); ++i) dev[i] = p.de[(long)b * Lg + v0 + imin(tid + ENT * i, L - 1)];
-        float thv[EMAXI][4], dpv[EMAXI][4];
-        const float* th_row = th_base + v0;                  // (v0 is a multiple of 8: 16-byte items stay aligned)
+            for (int i = 0; i < (TILED ? 1 : 2); ++i) dev[i] = de_fr[(long)b * Lg + v0 + imin(tid + ENT * i, L - 1)];
+        }
+        float thv[EMAXI][4];
+        const float* th_row = th_base + (WALK ? fr * p.th_fs : 0) + v0;      // (v0 is a multiple of 8: 16-byte items stay aligned)
+        if (WALK) {      // no other launch waits for this one: de straight into the registers of the thread that uses it
+#pragma unroll
+            for (int it = 0; it < EMAXI; ++it) {
+                const int g = imin(sub + 32 * it, NGA - 1);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dew[it][i] = de_fr[(long)b * Lg + imin(imax(4 * g - 1 + i, 0), L - 1)];
+            }
+        }
 #pragma unroll
         for (int it = 0; it < EMAXI; ++it) {
             const int g = imin(sub + 32 * it, NGA - 1);
@@ -1026,16 +1065,18 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
             thv[it][0] = th_row[imax(4 * g - 1, 0)];
             thv[it][1] = t4[0]; thv[it][2] = t4[1]; thv[it][3] = t4[2];
         }
+        if (MODE == DS_FULL) {
 #pragma unroll
-        for (int it = 0; it < EMAXI; ++it) {                 // old dpmT values of this thread's positions (previous frame's launch: L2)
-            const int g = imin(sub + 32 * it, NGA - 1);
+            for (int it = 0; it < EMAXI; ++it) {             // old dpmT values of this thread's positions (previous frame's launch: L2)
+                const int g = imin(sub + 32 * it, NGA - 1);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dpv[it][i] = p.dpmT[rowoff + v0 + imin(imax(4 * g - 1 + i, 0), L - 1)];
+                for (int i = 0; i < 4; ++i) dpv[it][i] = p.dpmT[rowoff + v0 + imin(imax(4 * g - 1 + i, 0), L - 1)];
+            }
+            if (tile == 0) dv_old = p.dv_part[(long)b * p.Ad + a];
         }
-        if (tile == 0) dv_old = p.dv_part[(long)b * p.Ad + a];
         StageRegs<ENT> sr;
-        stage_issue<ENT, true, false>(sr, p.w_prev, p.ldwp, p.cum_prev, p.ldcp, p.U, p.dpmT, b, j, Lg, LpI, tid, 40, v0);
-        if (tile == 0) {       // this wave's d_in filter fragments (k-steps w, w + 8, w + 16 < 20): from L2, independent of the chain
+        if (ACC) stage_issue<ENT, true, false>(sr, w_prev, p.ldwp, cum_prev, p.ldcp, p.U, p.dpmT, b, j, Lg, LpI, tid, 40, v0);
+        if (CHN && tile == 0) {       // this wave's d_in filter fragments (k-steps w, w + 8, w + 16 < 20): from L2, independent of the chain
             const u32x4v* bdp = reinterpret_cast<const u32x4v*>(p.bd) + (long)j * 20 * 3 * 64 + lane;
 #pragma unroll
             for (int ki = 0; ki < 3; ++ki) {
@@ -1044,15 +1085,21 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
                 for (int pl = 0; pl < 3; ++pl) bdv[ki][pl] = bdp[(ks * 3 + pl) * 64];
             }
         }
-        for (int i = tid; i < 48 * S16; i += ENT) DX[i] = (u32x4v){0u, 0u, 0u, 0u};     // halo and tail of the ds planes
-        stage_commit_split<ENT, false>(sr, PX, nullptr, p.w_prev, p.ldwp, p.cum_prev, p.ldcp, p.dpmT, b, Lg, LpI, tid, 40, v0);
-#pragma unroll
-        for (int i = 0; i < (TILED ? 1 : 2); ++i) {
-            const int l = tid + ENT * i;
-            if (l < dm.L4 + 7) des[l + 1] = (l >= ia && l < ib) ? dev[i] : 0.f;
+        if (WALK) {
+            __syncthreads();     // the previous frame's last fragment reads of both images (first frame: the zero fill above)
+        } else {
+            for (int i = tid; i < 48 * S16; i += ENT) DX[i] = (u32x4v){0u, 0u, 0u, 0u};     // halo and tail of the ds planes
         }
-        if (tid == 0) des[0] = 0.f;
-        __syncthreads();
+        if (ACC) stage_commit_split<ENT, false>(sr, PX, nullptr, w_prev, p.ldwp, cum_prev, p.ldcp, p.dpmT, b, Lg, LpI, tid, 40, v0);
+        if (!WALK) {
+#pragma unroll
+            for (int i = 0; i < (TILED ? 1 : 2); ++i) {
+                const int l = tid + ENT * i;
+                if (l < dm.L4 + 7) des[l + 1] = (l >= ia && l < ib) ? dev[i] : 0.f;
+            }
+            if (tid == 0) des[0] = 0.f;
+            __syncthreads();
+        }
         T2_STAMP(p, stamp, 25);
 
         // ---- phase A: ds -> its bf16 planes, dpmT accumulation; phase B sums in registers ----
@@ -1063,40 +1110,44 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
                 const int g = sub + 32 * it;
                 if (g >= NGA) continue;
                 f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
-                const f32x4 de4 = *reinterpret_cast<const f32x4*>(des + 4 * g);      // de[4g - 1 .. 4g + 2]
+                f32x4 de4;                                                           // de[4g - 1 .. 4g + 2]
+                if (WALK) de4 = (f32x4){dew[it][0], dew[it][1], dew[it][2], dew[it][3]};
+                else de4 = *reinterpret_cast<const f32x4*>(des + 4 * g);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int l = 4 * g - 1 + i;
                     if (l >= ia && l < ib) {
                         const float th = thv[it][i];
                         d4[i] = de4[i] * va * (1.f - th * th);
-                        sv += de4[i] * th;
-                        p.dpmT[rowoff + v0 + l] = dpv[it][i] + d4[i];
+                        if (ACC) sv += de4[i] * th;
+                        if (MODE == DS_FULL) p.dpmT[rowoff + v0 + l] = dpv[it][i] + d4[i];
+                        if (WALK) dpv[it][i] += d4[i];
                     }
                 }
-                sq += (d4[0] + d4[1]) + (d4[2] + d4[3]);
+                if (CHN) sq += (d4[0] + d4[1]) + (d4[2] + d4[3]);
                 const Split3 s3 = split3_attn(d4);     // packed (d0,d1), (d2,d3) of every plane: elements x = 24 + 4g .. 27 + 4g
                 const int o = al * S16 * 2 + 6 + g;    // 8-byte items: row base + (24 + 4 g) / 4
                 dx64[o] = s3.h; dx64[16 * S16 * 2 + o] = s3.m; dx64[32 * S16 * 2 + o] = s3.l;
             }
         }
-        if (!TILED) {       // one pass: the sums are complete - out before the MFMA phases (the cell-backward launch waits for dq)
-            sq = t2_half_sum_hi(sq); sv = t2_half_sum_hi(sv);   // totals of the dim's 32 lanes land in its upper 16 lanes
+        if (!TILED && CHN) {       // one pass: the sums are complete - out before the MFMA phases (the cell-backward launch waits for dq)
+            sq = t2_half_sum_hi(sq);                            // totals of the dim's 32 lanes land in its upper 16 lanes
+            if (MODE == DS_FULL) sv = t2_half_sum_hi(sv);
             if (sub == 31) {
                 p.dq[(long)b * p.lddq + a] = sq;
-                p.dv_part[(long)b * p.Ad + a] = dv_old + sv;
+                if (MODE == DS_FULL) p.dv_part[(long)b * p.Ad + a] = dv_old + sv;
             }
         }
         __syncthreads();
         T2_STAMP(p, stamp, 26);
-        if (tile == 0 && w < 4 && c_k < KL) {      // old accumulator values: consumed after the last tile's MFMA phases
+        if (MODE == DS_FULL && tile == 0 && w < 4 && c_k < KL) {      // old accumulator values: consumed after the last tile's MFMA phases
 #pragma unroll
             for (int r = 0; r < 4; ++r) dU_old[r] = p.dU_part[(((long)b * p.Ad + j * 16 + 4 * q + r) * 2 + c_c) * KL + c_k];
         }
 
         // ---- phase C: dU tile c_nt, k-steps (w >> 2), +2, +4, ...: A[a = n][x = 32 ks + 8 q + jj] (ds[l = x - 25]),
         //      B[x][(c,k)] = in[c][l + k - 15] = input index x + k ----
-        for (int ks = w >> 2; ks < KS + 1; ks += 2) {            // x runs to 25 + L - 1 < 32 (KS + 1)
+        for (int ks = w >> 2; ACC && ks < KS + 1; ks += 2) {     // x runs to 25 + L - 1 < 32 (KS + 1)
             const int it = n * S16 + 4 * ks + q;
             Split8 fa, fb;
             fa.h = __builtin_bit_cast(bf16x8, DX[it]); fa.m = __builtin_bit_cast(bf16x8, DX[16 * S16 + it]); fa.l = __builtin_bit_cast(bf16x8, DX[32 * S16 + it]);
@@ -1111,12 +1162,13 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
             cl1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa.h, fb.m, cl1, 0, 0, 0);
             ch0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa.h, fb.h, ch0, 0, 0, 0);
         }
-        if (!TILED && w >= 4) {      // one pass: the dU sums are complete - second K half of every (c,k) tile to its partner wave
+        if (MODE == DS_FULL && !TILED && w >= 4) {      // one pass: the dU sums are complete - second K half of every (c,k) tile to its partner wave
             const f32x4 cC1 = ch0 + ((cl0 + cl1) + cl2);
 #pragma unroll
             for (int r = 0; r < 4; ++r) redC[c_nt * 256 + (4 * q + r) * 16 + n] = cC1[r];
         }
         T2_STAMP(p, stamp, 28);
+        if (WALK) continue;
         // ---- phase D: d_in, this wave's K share (k-steps w, w + 8, w + 16) for the MT row tiles:
         //      A[m][(a, r = 8 rb + jj)] = ds[a][8 m + r - 17] = element x = 8 (m + rb + 1) + jj of dim a ----
         f32x4 cD[2];
@@ -1154,7 +1206,7 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
                 for (int r = 0; r < 4; ++r) red[((w * MT + mt) * 16 + 4 * q + r) * 16 + n] = cD[mt][r];
             }
         }
-        if (!TILED && w < 4 && c_k < KL) {      // dU: first K half (registers) + second (redC, visible since the barrier above)
+        if (MODE == DS_FULL && !TILED && w < 4 && c_k < KL) {      // dU: first K half (registers) + second (redC, visible since the barrier above)
             const f32x4 cC0 = ch0 + ((cl0 + cl1) + cl2);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -1183,7 +1235,26 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
             p.dv_part[(long)b * p.Ad + a] = dv_old + sv;
         }
     }
-    if (TILED) {
+    if (WALK) {      // the call's sums join the accumulators: one read-modify-write per (dim, position) and call
+        sv = t2_half_sum_hi(sv);
+        if (sub == 31) p.dv_part[(long)b * p.Ad + a] += sv;
+        const int NGA = (Lg + 4) >> 2;
+#pragma unroll
+        for (int it = 0; it < EMAXI; ++it) {
+            const int g = sub + 32 * it;
+            if (g >= NGA) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int l = 4 * g - 1 + i;
+                if (l >= 0 && l < Lg) p.dpmT[rowoff + l] += dpv[it][i];
+            }
+        }
+        if (w < 4 && c_k < KL) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dU_old[r] = p.dU_part[(((long)b * p.Ad + j * 16 + 4 * q + r) * 2 + c_c) * KL + c_k];
+        }
+    }
+    if (TILED || WALK) {
         const f32x4 cC = ch0 + ((cl0 + cl1) + cl2);
         if (w >= 4) {
 #pragma unroll
@@ -1210,27 +1281,42 @@ __device__ __forceinline__ void attn_bwd_ds_mfma_body(const AttnBwdK& p, float* 
 __global__ __launch_bounds__(ENT, 4) void attn_bwd_ds_mfma_kernel(AttnBwdK p) {
     T2_CHAIN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    attn_bwd_ds_mfma_body<false>(p, sm);
+    attn_bwd_ds_mfma_body<false, DS_FULL>(p, sm);
+}
+// one pass, with a de stash: the chain's share only
+__global__ __launch_bounds__(ENT, 4) void attn_bwd_ds_chain_kernel(AttnBwdK p) {
+    T2_CHAIN_PRIO();
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    attn_bwd_ds_mfma_body<false, DS_CHAIN>(p, sm);
+}
+// one pass, off the chain (default wave priority): the accumulators' share over the frames of a chunk
+__global__ __launch_bounds__(ENT, 4) void attn_bwd_acc_kernel(AttnBwdK p) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    attn_bwd_ds_mfma_body<false, DS_ACC>(p, sm);
 }
 // position tiles (L > 252)
 __global__ __launch_bounds__(ENT, 2) void attn_bwd_ds_tiled_kernel(AttnBwdK p) {
     T2_CHAIN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    attn_bwd_ds_mfma_body<true>(p, sm);
+    attn_bwd_ds_mfma_body<true, DS_FULL>(p, sm);
 }
 
 // dynamic LDS of the per-slice kernel (floats: ds planes | input planes | de | phase-C exchange [| d_in image of the whole text])
-size_t ds_mfma_lds(int L) {
+// DS_CHAIN has neither the input planes nor the phase-C exchange; its phase-D exchange ([8][MT][256], over the ds planes) then
+// reaches past everything else for texts of up to 32 positions
+size_t ds_mfma_lds(int L, int mode = DS_FULL) {
     const bool tiled = L > DS_ONE;
     const DsDims dd = ds_dims(tiled ? (L < DS_TI + 2 * DS_MARGIN ? L : DS_TI + 2 * DS_MARGIN) : L);
-    size_t f = (size_t)48 * dd.S16 * 4 + 6 * dd.LpI + dd.L4 + 8 + 4 * 256;
+    size_t f = (size_t)48 * dd.S16 * 4 + dd.L4 + 8;
+    if (mode != DS_CHAIN) f += 6 * dd.LpI + 4 * 256;
+    if (f < (size_t)8 * dd.MT * 256) f = (size_t)8 * dd.MT * 256;
     if (tiled) f += (size_t)2 * ((L + 3) & ~3);
     return f * sizeof(float);
 }
 
 }  // namespace
 
-extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) {
+static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(a != nullptr, "t2_attn_seq_bwd: null");
     T2_REQUIRE(a->Kl == KL && a->Ad % 16 == 0 && a->Ef % 32 == 0, "t2_attn_seq_bwd: unsupported dims");
@@ -1241,8 +1327,10 @@ extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) {
     const long ldx = A + Ef;
     const size_t sm_dw = (size_t)((Ef > 640 ? Ef : 640) + ((L + 3) & ~3) + 8) * sizeof(float);
     const bool tiled = L > DS_ONE;
-    const size_t sm_dsm = ds_mfma_lds(L);
-    T2_REQUIRE(t2_allow_lds(attn_bwd_dw_kernel, sm_dw) && (tiled ? t2_allow_lds(attn_bwd_ds_tiled_kernel, sm_dsm) : t2_allow_lds(attn_bwd_ds_mfma_kernel, sm_dsm)),
+    if (tiled) de_stash = nullptr;      // position tiles keep accumulating in the chain: nothing is left for t2_attn_acc_bwd
+    T2_REQUIRE(!de_stash || ld_stash >= (long)B * L, "t2_attn_seq_bwd_stash: ld_stash < B * L");
+    const size_t sm_dsm = ds_mfma_lds(L, de_stash ? DS_CHAIN : DS_FULL);
+    T2_REQUIRE(t2_allow_lds(attn_bwd_dw_kernel, sm_dw) && (tiled ? t2_allow_lds(attn_bwd_ds_tiled_kernel, sm_dsm) : de_stash ? t2_allow_lds(attn_bwd_ds_chain_kernel, sm_dsm) : t2_allow_lds(attn_bwd_ds_mfma_kernel, sm_dsm)),
                "t2_attn_seq_bwd: the text is too long for the LDS images of the attention backward kernels");
     hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(NA, 20), dim3(64), 0, st, a->U, reinterpret_cast<unsigned*>(a->ws_bd), Ad);
     T2_REQUIRE(a->wtp_ctx && a->wtp_h, "t2_attn_seq_bwd: packed weight streams (t2_lstm_pack_bwd) are required");
@@ -1288,7 +1376,7 @@ extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) {
         k.G_in = last ? nullptr : a->G + (long)((t + 1) & 1) * B * L;
         k.G_out = a->G + (long)(t & 1) * B * L;
         k.dalign = a->dalign ? a->dalign + (long)t * L : nullptr;
-        k.de = a->de;
+        k.de = de_stash ? de_stash + (long)t * ld_stash : a->de;
         k.th = a->th + (long)t * B * Ad * ((L + 3) & ~3); k.v = a->v; k.U = a->U;
         if (t > 0) { k.w_prev = a->align + (long)(t - 1) * L; k.ldwp = (long)T * L; }
         k.cum_prev = a->cum + (long)t * B * L; k.ldcp = L;
@@ -1298,6 +1386,7 @@ extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) {
         hipLaunchKernelGGL(attn_bwd_dw_kernel, dim3(B, t2_cdiv(L, 32)), dim3(256), sm_dw, st, k);
         k.bd = reinterpret_cast<const unsigned*>(a->ws_bd);
         if (tiled) hipLaunchKernelGGL(attn_bwd_ds_tiled_kernel, dim3(B, NA), dim3(ENT), sm_dsm, st, k);
+        else if (de_stash) hipLaunchKernelGGL(attn_bwd_ds_chain_kernel, dim3(B, NA), dim3(ENT), sm_dsm, st, k);
         else hipLaunchKernelGGL(attn_bwd_ds_mfma_kernel, dim3(B, NA), dim3(ENT), sm_dsm, st, k);
         // (4) attention-LSTM cell backward: dh = (dh_ext + dgates_{t+1}.W_hh) + dq_t.Wq  (short K = Ad product + pointwise)
         T2LstmBwdStep c;
@@ -1314,6 +1403,38 @@ extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) {
         if (a->dgates_t) c.dgt_out = a->dgates_t + (long)t * zts;
         T2_TRY(t2_lstm_step_bwd_launch(&c, 1, st, (unsigned long long*)a->clk));
     }
+    T2_CHECK_LAUNCH();
+    return T2_OK;
+}
+
+extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) { return attn_seq_bwd(a, nullptr, 0, stream); }
+
+extern "C" int t2_attn_seq_bwd_stash(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, void* stream) {
+    return attn_seq_bwd(a, de_stash, (long)ld_stash, stream);
+}
+
+extern "C" int t2_attn_acc_bwd(const T2AttnSeqBwd* a, const float* de_stash, int64_t ld_stash, int t_begin, int t_end, void* stream) {
+    (void)hipGetLastError();
+    T2_REQUIRE(a != nullptr && de_stash != nullptr, "t2_attn_acc_bwd: null");
+    T2_REQUIRE(a->Kl == KL && a->Ad % 16 == 0 && a->L >= 1, "t2_attn_acc_bwd: unsupported dims");
+    T2_REQUIRE(a->th && a->align && a->cum && a->v && a->dpmT && a->dv_part && a->dU_part, "t2_attn_acc_bwd: null operand");
+    T2_REQUIRE(t_begin >= 0 && t_end <= a->T && t_begin <= t_end, "t2_attn_acc_bwd: bad frame range");
+    const int B = a->B, L = a->L, Ad = a->Ad;
+    T2_REQUIRE(ld_stash >= (long)B * L, "t2_attn_acc_bwd: ld_stash < B * L");
+    if (L > DS_ONE || t_begin == t_end) return T2_OK;      // position tiles accumulated in the chain (t2_attn_seq_bwd_stash)
+    const size_t smem = ds_mfma_lds(L, DS_ACC);
+    T2_REQUIRE(t2_allow_lds(attn_bwd_acc_kernel, smem), "t2_attn_acc_bwd: LDS");
+    AttnBwdK k;
+    memset(&k, 0, sizeof(k));
+    k.B = B; k.L = L; k.Ad = Ad; k.Ef = a->Ef;
+    k.t_begin = t_begin; k.t_end = t_end;
+    k.de = const_cast<float*>(de_stash); k.de_fs = (long)ld_stash;
+    k.th = a->th; k.th_fs = (long)B * Ad * ((L + 3) & ~3);
+    k.v = a->v; k.U = a->U;
+    k.w = a->align; k.w_fs = L; k.ldwp = (long)a->T * L;
+    k.cum_prev = a->cum; k.cum_fs = (long)B * L; k.ldcp = L;
+    k.dpmT = a->dpmT; k.dv_part = a->dv_part; k.dU_part = a->dU_part;
+    hipLaunchKernelGGL(attn_bwd_acc_kernel, dim3(B, Ad / 16), dim3(ENT), smem, (hipStream_t)stream, k);
     T2_CHECK_LAUNCH();
     return T2_OK;
 }

@@ -1095,6 +1095,10 @@ class Engine:
         dc_att = self.buf("dc_att", B, A, zero=True)
         Gc = self.buf("Gcum", 2, B, L)
         de = self.buf("de", B, L)
+        # every frame's energy gradients stay (21 MB at B = 32, L = 188, T = 872): dpmT, dv and dU are rebuilt from them off the
+        # chain, one t2_attn_acc_bwd launch per chunk on the side stream.  Texts longer than one pass of the per-slice kernel
+        # (252 positions, include/tacotron2_amd.h) accumulate in the chain: no stash for them
+        de_stash = self.buf("de_stash", T, B, L) if L <= 252 else None
         din_part = self.buf("din_part", B, Ad // 16, 2, L)
         wtp_ctx = self.pack_bwd("att.ctx.t", _ptr(P["decoder.att_rnn.weight_ih"], Pd), Pd + Ef, 4 * A, Ef)
         wtp_h = self.pack_bwd("att.h.t", P["decoder.att_rnn.weight_hh"], A, 4 * A, A)
@@ -1163,6 +1167,12 @@ class Engine:
         # last chunk).
         WG = max(1, int(self.wgrad_group))
         dec_grp, att_done, att_grp = None, [], None        # [hi, lo, n]; [(hi, lo, event)]; [hi, lo, n, event]
+
+        def att_acc(hi, lo, ev):     # dpmT / dv / dU of the chain's frames [lo, hi): behind the chunk's event, default wave priority
+            if de_stash is None:
+                return
+            self._wait(side, ev)
+            call("t2_attn_acc_bwd", sb, de_stash, B * L, lo, hi, side.cuda_stream)
         for ci_, (hi, lo) in enumerate(chunks):
             with torch.cuda.stream(side), share_cu(self.share_cu):
                 s, inc = dec_bwd_chunk(hi, lo)
@@ -1178,20 +1188,27 @@ class Engine:
                     post_wgrads.pop(0)()
                 if len(att_done) >= 2:      # chunks the main stream finished two chunks ago
                     h2, l2, e2 = att_done.pop(0)
+                    att_acc(h2, l2, e2)
                     att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
                     if att_grp[2] >= WG:
                         self._wait(side, att_grp[3])
                         att_wgrads(att_grp[0], att_grp[1]); att_grp = None
             self._wait(main, ev)
             sb.t_hi, sb.t_lo = hi, lo
-            call("t2_attn_seq_bwd", sb, st)
+            call("t2_attn_seq_bwd_stash", sb, de_stash, B * L, st)
             att_done.append((hi, lo, self._record(main)))
         with torch.cuda.stream(side):
+            for h2, l2, e2 in att_done[:-1]:        # next to the chain's last chunk
+                att_acc(h2, l2, e2)
             while post_wgrads:                      # (short sequences: fewer chunks than deferred GEMMs)
                 post_wgrads.pop(0)()
             with share_cu(self.share_cu):
                 if dec_grp is not None:
                     dec_wgrads_chunk(dec_grp[0], dec_grp[1])
+                # the last chunk's accumulators wait for the chain's end, so they follow what does not; the main stream waits for
+                # them in front of the first reader of dpmT
+                att_acc(*att_done[-1])
+                acc_done = self._record(side)
                 for h2, l2, e2 in att_done:
                     att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
                 if att_grp is not None:
@@ -1214,6 +1231,7 @@ class Engine:
         dmem = self.buf("dmem", B, L, Ef)
         gemm(ctx["align"], dctx_tot, dmem, L, Ef, T, L, B * Ef, Ef, a_k=0, b_k=0, batch=B, sA=T * L, sB=Ef, sC=L * Ef)
         Watt = P["att_encoder.weight"]
+        self._wait(main, acc_done)                  # dpmT (and dv_part / dU_part, read behind the side stream's wait below) is complete
         gemm(dpmT, Watt, dmem, L, Ef, Ad, L, Ef, Ef, a_k=0, b_k=0, accumulate=1, batch=B, sA=Ad * L, sB=0, sC=L * Ef)
 
         # Independent branch on the side stream: weight gradients of the attention chain (large GEMMs over all frames) and the
