@@ -259,7 +259,7 @@ int t2_lstm_seq_bwd(const T2LstmBwdStep* base, const T2LstmBwdStride* inc, int n
  *     alpha_t(n) = q_t(n) y_t(n) / sum_m q_t(m) y_t(m) for n < len, exactly 0.0 for n >= len
  * Everything downstream uses alpha_t: the context sum_n alpha_t(n) memory(n), cum_t = cum_{t-1} + alpha_t, the returned
  * alignments row (w_out) and the next frame's location features.  The softmax denominator cancels, so the kernel multiplies
- * each exp term by q before its one block sum.  forward together with win_peak or with th_out is an argument error; w_out must
+ * each exp term by q before its one block sum.  forward together with win_peak or with th_out is an argument error (the teacher-forced chain, T2AttnSeq.forward, keeps the stash); w_out must
  * not be w_prev (every workgroup of the context launch reads w_prev, one of them writes w_out). */
 typedef struct {
     int B, L, A, Ad, Ef, Kl;
@@ -304,6 +304,9 @@ typedef struct {
     float* xdec_t;                   /* optional (with wpacked): x16-tiled copy of xdec, [T+1][(A+Ef)/16][Bp][16], slot 0
                                         zero-filled by the caller; the attention-LSTM step then reads its input from it */
     uint64_t* clk;                   /* diagnostic (T2AttnStep.clk), normally NULL */
+    int forward;                     /* 0 = off; else every frame is a forward-attention step (T2AttnStep.forward, "Forward attention"
+                                        above) that keeps its tanh stash: training under the monotonic prior.  Frame 0 has the one-hot
+                                        prior; a call with t_begin > 0 reads alpha_{t_begin-1} from `align` */
 } T2AttnSeq;
 int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream);
 
@@ -369,6 +372,21 @@ int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream);
  * does, and t2_attn_acc_bwd returns without a launch.
  * (The stash travels as arguments: T2AttnSeqBwd keeps its layout.) */
 int t2_attn_seq_bwd_stash(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, void* stream);
+/* The backward of a t2_attn_seq_fwd with T2AttnSeq.forward != 0 (forward attention under teacher forcing): t2_attn_seq_bwd_stash
+ * (de_stash = NULL: t2_attn_seq_bwd) with the prior's term in the softmax backward.  The weights are
+ * alpha_t = softmax(e_t + log q_t), so with g_t = dw + dwx + da + P_{t+1} (P_T = 0):
+ *     de_t[l] = alpha_t[l] (g_t[l] - sum_m alpha_t[m] g_t[m])
+ *     r_t[l]  = de_t[l] / q_t[l]                       (t >= 1; exactly 0 behind len)
+ *     P_t[n]  = 0.5 r_t[n] + 0.5 r_t[n+1],   r_t[L] = 0
+ * P_t is the gradient frame t hands to alpha_{t-1} through its prior (none from frame 0: its prior is a constant).  It reaches
+ * alpha_{t-1} directly, as dalign does: it is not part of the cumulative-weights carry G.  Same launches per frame (the first one is
+ * another instantiation of the same kernel); everything else - the per-slice launches, t2_attn_acc_bwd on the stash - is unchanged:
+ * they are functions of de, th, align and cum.
+ *   dprior: workspace [2][B][L].  Frame t writes r_t (every position < L) into slot t & 1 - the ABSOLUTE frame's parity - and
+ *   frame t-1 reads it, so (t_hi, t_lo) calls carry it from one call to the next as they carry G.  No zero-fill.
+ * dprior == NULL or a->align == NULL is T2_ERR_ARG before any launch.  (The workspace travels as an argument: T2AttnSeqBwd keeps
+ * its layout.) */
+int t2_attn_seq_bwd_forward(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, float* dprior, void* stream);
 int t2_attn_acc_bwd(const T2AttnSeqBwd* a, const float* de_stash, int64_t ld_stash, int t_begin, int t_end, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

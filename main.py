@@ -92,8 +92,12 @@ def main(ctx, config, device):
               help="Guided-attention loss: adds ALPHA times the mean of the attention weights under the off-diagonal mask "
                    "1 - exp(-(l/N - t/T)^2 / (2 SIGMA^2)) to the training and validation loss, so that the alignment forms early "
                    "(0.4,1.0 is the usual value). Wins over training.guided_attention of the config. Default: off.")
+@click.option("--forward-attention", is_flag=True, default=False,
+              help="Train under forward attention (Zhang et al. 2018): every teacher-forced frame's weights are the softmax times the "
+                   "prior 0.5 a[t-1][n] + 0.5 a[t-1][n-1], renormalised, forward and backward. Decode such a model with "
+                   "--forward-attention. Wins over training.forward_attention of the config. Default: off.")
 def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_checkpoint=None, finetune=False,
-          finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None):
+          finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None, forward_attention=False):
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for training!")
     if finetune and finetune_steps is None:
@@ -103,7 +107,7 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
     do_train(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
              extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, results_dir=results_dir,
              resume_ckpt=resume_ckpt, finetune=finetune, finetune_steps=finetune_steps, max_steps_override=max_steps,
-             synthetic=synthetic, guided_attention=guided_attention)
+             synthetic=synthetic, guided_attention=guided_attention, forward_attention=True if forward_attention else None)
 
 
 @main.command()

@@ -597,7 +597,8 @@ __global__ void fold_location_kernel(const float* Wd, const float* Wc, float* U,
     U[idx] = s;
 }
 
-int check_attn(const T2AttnStep& s) {
+// seq: the step is a frame of t2_attn_seq_fwd, where forward attention keeps the tanh stash (training)
+int check_attn(const T2AttnStep& s, const bool seq = false) {
     T2_REQUIRE(s.B >= 1 && s.L >= 1, "attention: need B >= 1 and L >= 1");
     T2_REQUIRE(s.Kl == KL, "attention: location kernel size must be 31 (model/decoder.py:36)");
     T2_REQUIRE(s.Ad % 16 == 0 && s.Ef % 32 == 0 && s.A % 4 == 0, "attention: need Ad%16==0, Ef%32==0, A%4==0");
@@ -612,7 +613,7 @@ int check_attn(const T2AttnStep& s) {
     }
     if (s.forward) {
         T2_REQUIRE(!s.win_peak, "attention: forward attention does not compose with the attention window");
-        T2_REQUIRE(!s.th_out, "attention: the forward-attention step has no tanh stash (inference only)");
+        T2_REQUIRE(seq || !s.th_out, "attention: the forward-attention step has no tanh stash (inference only)");
         T2_REQUIRE(s.w_out != s.w_prev, "attention: the forward-attention step reads w_prev in every workgroup (w_out != w_prev)");
     }
     return T2_OK;
@@ -738,7 +739,8 @@ extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) {
         if (a->xproj_ctx) { q.ctx_out2 = a->xproj_ctx + (long)t * B * a->ld_xproj; q.ldctx2 = a->ld_xproj; }
         if (a->xdec_t) { q.ctxt_out = a->xdec_t + (long)(t + 1) * xts; q.ctxt_col0 = A; }
         q.clk = a->clk;
-        if (t == tb) T2_TRY(check_attn(q));
+        q.forward = a->forward;
+        if (t == tb) T2_TRY(check_attn(q, true));
         T2_TRY(launch_attn(q, st));
     }
     return T2_OK;
@@ -782,10 +784,22 @@ struct AttnBwdK {
     const unsigned* bd;        // fragment-ready bf16 planes of the d_in filter operand (attn_bwd_prep_kernel)
     // attn_bwd_acc_kernel only: frames t_end-1 .. t_begin; de, th, cum_prev and w (NOT w_prev) then point at frame 0
     int t_begin, t_end; long de_fs, th_fs, cum_fs, w_fs;
+    // attn_bwd_dw_kernel<true> only (forward attention in training): r of frame t+1 ([B][L], null at the last frame) and this frame's r
+    // (null at frame 0: its prior is a constant)
+    const float* dprior_in; float* dprior_out;
 };
 
 namespace {
 
+// FA: forward attention under teacher forcing (include/tacotron2_amd.h, t2_attn_seq_bwd_forward).  The weights are
+// alpha_t = softmax(e_t + log q_t), q_t[l] = 0.5 alpha_{t-1}[l] + 0.5 alpha_{t-1}[l-1] + 1e-8, so the softmax backward keeps its form
+// with one more direct term on alpha_t - the gradient P_{t+1} that frame t+1 hands back through its prior:
+//     r_t[l] = de_t[l] / q_t[l],   P_t[n] = 0.5 r_t[n] + 0.5 r_t[n+1]  (r_t[L] = 0).
+// A workgroup owns 32 positions and P needs r[l+1], so the kernel writes r (dprior_out) and the next frame's launch forms P from the
+// two neighbours (dprior_in).  P joins sigma and the bracket of de; like dalign it is NOT part of the cumulative-weights carry G_out.
+// (The kernel itself is the template, not a body behind two wrappers: inlined through a wrapper, the instantiation without the option
+// comes out with the parent's instructions in another order; as a template its gfx950 stream is the parent's, line for line.)
+template <bool FA>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
     T2_CHAIN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -828,6 +842,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
     if (p.dalign) {
         da0 = p.dalign[(long)b * p.ldw + lc0];
         dame = p.dalign[(long)b * p.ldw + imin(l, L - 1)];
+    }
+    // FA: the two r rows of frame t+1 around position tid (P of the sigma loop) and the previous weights around the own position
+    // (the prior q_t that r_t is divided by); all a frame or a launch old
+    [[maybe_unused]] float pr0 = 0.f, pr1 = 0.f, wp0 = 0.f, wp1 = 0.f;
+    if constexpr (FA) {
+        if (p.dprior_in) {
+            pr0 = p.dprior_in[(long)b * L + lc0];
+            pr1 = p.dprior_in[(long)b * L + imin(lc0 + 1, L - 1)];
+        }
+        if (p.w_prev) {
+            const int lm = imin(l, L - 1);
+            wp0 = p.w_prev[(long)b * p.ldwp + lm];
+            wp1 = p.w_prev[(long)b * p.ldwp + imax(lm - 1, 0)];
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- issue: this thread's share of its memory row (8 lanes per position, 16 B each, stride 128 B) ----
@@ -878,9 +906,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
         }
         const float gin = ll0 == 0 ? gin0 : (p.G_in ? p.G_in[(long)b * L + lc] : 0.f);
         const float wl = ll0 == 0 ? wl0 : p.w[(long)b * p.ldw + lc];
+        if constexpr (FA) {
+            if (ll0 > 0 && p.dprior_in) {
+                pr0 = p.dprior_in[(long)b * L + lc];
+                pr1 = p.dprior_in[(long)b * L + imin(lc + 1, L - 1)];
+            }
+        }
         if (ll < L) {
             const float Gn = g1 + gin;
-            const float dx = g0 + Gn;
+            float dx = g0 + Gn;
+            if constexpr (FA) dx += 0.5f * pr0 + (ll + 1 < L ? 0.5f * pr1 : 0.f);   // + P_{t+1}[ll]: direct, not in the carry Gn
             dwx_s[ll] = dx;
             if (blockIdx.y == 0) p.G_out[(long)b * L + ll] = Gn;
             part = fmaf(wl, dx, part);
@@ -913,7 +948,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dw_kernel(AttnBwdK p) {
     if (sub == 0 && l < L) {
         float up = acc + dwx_s[l];
         if (p.dalign) up += dame;
-        p.de[(long)b * L + l] = wme * (up - sigma);
+        const float de = wme * (up - sigma);
+        p.de[(long)b * L + l] = de;
+        if constexpr (FA) {
+            // the prior exactly as attn_context_body<.., FWD> formed it; every position < L is written (0 behind len: w = 0 there)
+            if (p.dprior_out) p.dprior_out[(long)b * L + l] = de / (0.5f * wp0 + (l > 0 ? 0.5f * wp1 : 0.f) + 1e-8f);
+        }
     }
     T2_STAMP(p, stamp, 19);
     T2_RING_END();
@@ -1316,12 +1356,14 @@ size_t ds_mfma_lds(int L, int mode = DS_FULL) {
 
 }  // namespace
 
-static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, void* stream) {
+static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, void* stream, const bool forward = false,
+                        float* dprior = nullptr) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(a != nullptr, "t2_attn_seq_bwd: null");
     T2_REQUIRE(a->Kl == KL && a->Ad % 16 == 0 && a->Ef % 32 == 0, "t2_attn_seq_bwd: unsupported dims");
     T2_REQUIRE(a->L >= 1, "t2_attn_seq_bwd: need L >= 1");
     T2_REQUIRE(a->ws_bd && a->th, "t2_attn_seq_bwd: the filter workspace ws_bd and the forward's tanh stash th are required");
+    T2_REQUIRE(!forward || (dprior && a->align), "t2_attn_seq_bwd_forward: the workspace dprior and the alignments are required");
     hipStream_t st = (hipStream_t)stream;
     const int B = a->B, L = a->L, T = a->T, A = a->A, Ef = a->Ef, Ad = a->Ad, NA = Ad / 16;
     const long ldx = A + Ef;
@@ -1330,8 +1372,10 @@ static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, v
     if (tiled) de_stash = nullptr;      // position tiles keep accumulating in the chain: nothing is left for t2_attn_acc_bwd
     T2_REQUIRE(!de_stash || ld_stash >= (long)B * L, "t2_attn_seq_bwd_stash: ld_stash < B * L");
     const size_t sm_dsm = ds_mfma_lds(L, de_stash ? DS_CHAIN : DS_FULL);
-    T2_REQUIRE(t2_allow_lds(attn_bwd_dw_kernel, sm_dw) && (tiled ? t2_allow_lds(attn_bwd_ds_tiled_kernel, sm_dsm) : de_stash ? t2_allow_lds(attn_bwd_ds_chain_kernel, sm_dsm) : t2_allow_lds(attn_bwd_ds_mfma_kernel, sm_dsm)),
-               "t2_attn_seq_bwd: the text is too long for the LDS images of the attention backward kernels");
+    const bool lds_dw = forward ? t2_allow_lds(attn_bwd_dw_kernel<true>, sm_dw) : t2_allow_lds(attn_bwd_dw_kernel<false>, sm_dw);
+    const bool lds_ds = tiled ? t2_allow_lds(attn_bwd_ds_tiled_kernel, sm_dsm)
+                              : de_stash ? t2_allow_lds(attn_bwd_ds_chain_kernel, sm_dsm) : t2_allow_lds(attn_bwd_ds_mfma_kernel, sm_dsm);
+    T2_REQUIRE(lds_dw && lds_ds, "t2_attn_seq_bwd: the text is too long for the LDS images of the attention backward kernels");
     hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(NA, 20), dim3(64), 0, st, a->U, reinterpret_cast<unsigned*>(a->ws_bd), Ad);
     T2_REQUIRE(a->wtp_ctx && a->wtp_h, "t2_attn_seq_bwd: packed weight streams (t2_lstm_pack_bwd) are required");
     // Z[s][b] = [ dgates_s (4A) | dq_{s-1} (Ad) ], s = 0..T; slot T's dgates part is zero-filled by the caller, so the
@@ -1383,7 +1427,13 @@ static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, v
         k.dpmT = a->dpmT; k.dq = Z + (long)(t + 1) * B * ldz + 4 * A; k.lddq = ldz;
         k.dv_part = a->dv_part; k.dU_part = a->dU_part; k.din_part_out = a->din_part;
         k.clk = (unsigned long long*)a->clk;
-        hipLaunchKernelGGL(attn_bwd_dw_kernel, dim3(B, t2_cdiv(L, 32)), dim3(256), sm_dw, st, k);
+        if (forward) {   // r of frame t lives in slot t & 1 (the ABSOLUTE frame's parity: chunked calls carry it as they carry G)
+            k.dprior_in = last ? nullptr : dprior + (long)((t + 1) & 1) * B * L;
+            k.dprior_out = t > 0 ? dprior + (long)(t & 1) * B * L : nullptr;
+            hipLaunchKernelGGL(attn_bwd_dw_kernel<true>, dim3(B, t2_cdiv(L, 32)), dim3(256), sm_dw, st, k);
+        } else {
+            hipLaunchKernelGGL(attn_bwd_dw_kernel<false>, dim3(B, t2_cdiv(L, 32)), dim3(256), sm_dw, st, k);
+        }
         k.bd = reinterpret_cast<const unsigned*>(a->ws_bd);
         if (tiled) hipLaunchKernelGGL(attn_bwd_ds_tiled_kernel, dim3(B, NA), dim3(ENT), sm_dsm, st, k);
         else if (de_stash) hipLaunchKernelGGL(attn_bwd_ds_chain_kernel, dim3(B, NA), dim3(ENT), sm_dsm, st, k);
@@ -1411,6 +1461,10 @@ extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) { return att
 
 extern "C" int t2_attn_seq_bwd_stash(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, void* stream) {
     return attn_seq_bwd(a, de_stash, (long)ld_stash, stream);
+}
+
+extern "C" int t2_attn_seq_bwd_forward(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, float* dprior, void* stream) {
+    return attn_seq_bwd(a, de_stash, (long)ld_stash, stream, true, dprior);
 }
 
 extern "C" int t2_attn_acc_bwd(const T2AttnSeqBwd* a, const float* de_stash, int64_t ld_stash, int t_begin, int t_end, void* stream) {

@@ -748,9 +748,13 @@ class Engine:
                                  length=mlen32 if last else None, fill=0.0)
 
     def forward_tf(self, chars_idx, chars_len, mel, mel_len, speaker_id=None, description_embeddings=None,
-                   training=True, masks: Optional[dict] = None, save_for_backward=True, controls=None):
+                   training=True, masks: Optional[dict] = None, save_for_backward=True, controls=None, forward_attention=False):
         """Returns (mels, mels_post, gates, alignments), ctx.  masks: oracle-convention dict (see oracle.tacotron2_ref)
-        already on the device, with prenet/att/dec masks time-major; None entries = identity."""
+        already on the device, with prenet/att/dec masks time-major; None entries = identity.
+        forward_attention: True - every frame's weights are the forward-attention weights alpha_t (include/tacotron2_amd.h, "Forward
+        attention"; T2AttnSeq.forward): the model is trained under the monotonic prior it is later decoded with
+        (infer(forward_attention=True)).  The flag travels in ctx; backward_tf reads it there."""
+        forward_attention = check_forward_attention(forward_attention)
         d, P, ps = self.d, self.ps.P, self.ps
         masks = masks or {}
         B, L = chars_idx.shape
@@ -758,7 +762,7 @@ class Engine:
         E, Pd, A, D, Ad = d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
-        ctx: dict = dict(B=B, L=L, T=T)
+        ctx: dict = dict(B=B, L=L, T=T, forward_attention=forward_attention)
         self.generation += 1          # any forward (grad-enabled or not) rewrites the shared workspaces
         ctx["generation"] = self.generation
         st = _stream()
@@ -830,7 +834,8 @@ class Engine:
                    W_hh=P["decoder.att_rnn.weight_hh"], Wq=P["decoder.attention.query_layer.weight"], U=U,
                    v=P["decoder.attention.v.weight"], pre=pre_att, pmT=pmT, memory=memory, len=len32,
                    att_drop=masks.get("att_drop"), xdec=xdec, att_c=att_c, gates=gates_att, align=align, cum=cum, th=th,
-                   xproj_ctx=_ptr(xproj, B * (D + Ef) + D), ld_xproj=D + Ef, e_part=e_part, xdec_t=xdec_t)
+                   xproj_ctx=_ptr(xproj, B * (D + Ef) + D), ld_xproj=D + Ef, e_part=e_part, xdec_t=xdec_t,
+                   forward=int(forward_attention))
         # decoder-LSTM chain operands (prepared before the pipeline below)
         pre_dec = self.buf("pre_dec", T, B, 4 * D)
         dec_c = self.buf("dec_c", T + 1, B, D)
@@ -1104,6 +1109,10 @@ class Engine:
         wtp_h = self.pack_bwd("att.h.t", P["decoder.att_rnn.weight_hh"], A, 4 * A, A)
         wtp_q = self.pack_bwd("att.q.t", P["decoder.attention.query_layer.weight"], A, Ad, A)
         dh_rec = self.buf("dh_rec", B, A)
+        # forward attention: the ping-pong rows of r_t = de_t / q_t that frame t-1 turns into its prior gradient (t2_attn_seq_bwd_forward);
+        # written before they are read, no clearing.  Without the option the workspace does not exist
+        fwd_att = bool(ctx.get("forward_attention"))
+        dprior = self.buf("dprior", 2, B, L) if fwd_att else None
         sb = make("T2AttnSeqBwd", B=B, L=L, T=T, A=A, Ad=Ad, Ef=Ef, Kl=KL, wtp_ctx=wtp_ctx, wtp_h=wtp_h, wtp_q=wtp_q,
                   dh_rec=dh_rec,
                   W_ih_ctx=_ptr(P["decoder.att_rnn.weight_ih"], Pd), ld_wih=Pd + Ef, W_hh=P["decoder.att_rnn.weight_hh"],
@@ -1195,7 +1204,10 @@ class Engine:
                         att_wgrads(att_grp[0], att_grp[1]); att_grp = None
             self._wait(main, ev)
             sb.t_hi, sb.t_lo = hi, lo
-            call("t2_attn_seq_bwd_stash", sb, de_stash, B * L, st)
+            if fwd_att:
+                call("t2_attn_seq_bwd_forward", sb, de_stash, B * L, dprior, st)
+            else:
+                call("t2_attn_seq_bwd_stash", sb, de_stash, B * L, st)
             att_done.append((hi, lo, self._record(main)))
         with torch.cuda.stream(side):
             for h2, l2, e2 in att_done[:-1]:        # next to the chain's last chunk

@@ -58,7 +58,7 @@ class _TacotronFn(torch.autograd.Function):
                                     speaker_id=batch.get("speaker_id"),
                                     description_embeddings=batch.get("description_embeddings"),
                                     training=model.training, masks=masks, save_for_backward=batch["need_grad"],
-                                    controls=batch.get("controls"))
+                                    controls=batch.get("controls"), forward_attention=batch.get("forward_attention", False))
         ctx.model, ctx.ectx = model, ectx
         # an output the loss does not touch arrives in backward as None, not as a tensor of zeros: the alignments are
         # differentiable, but a loss on the mels alone allocates no (B,T,L) gradient and runs the attention backward without one
@@ -161,13 +161,19 @@ class Tacotron2(nn.Module):
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
                 dropout_masks: Optional[dict] = None, attention_window: Optional[Tuple[int, int]] = None,
-                forward_attention: bool = False):
+                forward_attention: bool = False, train_forward_attention: bool = False):
         """attention_window (autoregressive decoding only): (back, fwd) integers >= 0 - each frame attends only to the positions
         max(0, m - back) .. min(len - 1, m + fwd) around the previous frame's attention peak m (ESPnet's `use_att_constraint`);
         None attends to the whole text, as the reference does.
         forward_attention (autoregressive decoding only, not together with attention_window): True decodes with forward
         attention (Zhang et al. 2018; Mozilla TTS's `use_forward_attn` without a transition agent) - the weights of a frame are
-        the softmax times the prior 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8, renormalised (Engine.infer)."""
+        the softmax times the prior 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8, renormalised (Engine.infer).
+        train_forward_attention (teacher forcing only): True runs the teacher-forced attention chain under the same prior, forward
+        and backward (Engine.forward_tf(forward_attention=True)) - training-time forward attention; such a model is decoded with
+        forward_attention=True."""
+        if check_forward_attention(train_forward_attention) and not teacher_forcing:
+            raise ValueError("train_forward_attention applies to teacher forcing only (teacher_forcing=True); decode with "
+                             "forward_attention=True")
         if attention_window is not None:
             if teacher_forcing:
                 raise ValueError("attention_window applies to autoregressive decoding only (teacher_forcing=False)")
@@ -193,7 +199,7 @@ class Tacotron2(nn.Module):
                          speaker_id=speaker_id,
                          description_embeddings=description_embeddings.contiguous().float()
                          if description_embeddings is not None else None, masks=dropout_masks,
-                         controls=controls, need_grad=torch.is_grad_enabled())
+                         controls=controls, need_grad=torch.is_grad_enabled(), forward_attention=train_forward_attention)
             named = dict(self.named_parameters())
             params = [named[n] for n in self._param_names]      # store order = order of the returned gradients
             return _TacotronFn.apply(self, batch, *params)

@@ -113,6 +113,9 @@ class TTSModel(nn.Module):
         # (sigma, alpha) of the guided-attention loss that training_step / validation_step add to the three terms; None = off.  Set by
         # the driver (run/train.py), not a constructor argument: checkpoint hyper_parameters stay as the reference writes them
         self.guided_attention: Optional[Tuple[float, float]] = None
+        # forward attention under teacher forcing in training_step / validation_step (Tacotron2.forward(train_forward_attention=True)).
+        # Set by the driver like guided_attention: not a constructor argument, not in hparams
+        self.train_forward_attention: bool = False
         self.tacotron2 = Tacotron2(num_chars=num_chars, encoded_dim=encoded_dim, encoder_kernel_size=encoder_kernel_size,
                                    num_mels=num_mels, prenet_dim=prenet_dim, att_rnn_dim=att_rnn_dim, att_dim=att_dim,
                                    rnn_hidden_dim=rnn_hidden_dim, postnet_dim=postnet_dim, dropout=dropout,
@@ -132,12 +135,13 @@ class TTSModel(nn.Module):
                 mel_spectrogram: Optional[Tensor] = None, mel_spectrogram_len: Optional[Tensor] = None,
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
-                attention_window: Optional[Tuple[int, int]] = None, forward_attention: bool = False):
+                attention_window: Optional[Tuple[int, int]] = None, forward_attention: bool = False,
+                train_forward_attention: bool = False):
         return self.tacotron2(chars_idx=chars_idx, chars_idx_len=chars_idx_len, teacher_forcing=teacher_forcing,
                               mel_spectrogram=mel_spectrogram, mel_spectrogram_len=mel_spectrogram_len,
                               speaker_id=speaker_id, controls=controls, max_len_override=max_len_override,
                               description_embeddings=description_embeddings, attention_window=attention_window,
-                              forward_attention=forward_attention)
+                              forward_attention=forward_attention, train_forward_attention=train_forward_attention)
 
     def _args(self, meta):
         args = {}
@@ -154,7 +158,8 @@ class TTSModel(nn.Module):
         guided = check_guided_attention(self.guided_attention)
         mel, post, gate, alignment = self(chars_idx=data["chars_idx"], chars_idx_len=meta["chars_idx_len"],
                                           teacher_forcing=True, mel_spectrogram=data["mel_spectrogram"],
-                                          mel_spectrogram_len=meta["mel_spectrogram_len"], **self._args(meta))
+                                          mel_spectrogram_len=meta["mel_spectrogram_len"],
+                                          train_forward_attention=self.train_forward_attention, **self._args(meta))
         # the three terms of model/tts_model.py:197-199 from the library's loss kernel (no ATen arithmetic on this path)
         l3 = _LossTermsFn.apply(mel, post, gate, data["mel_spectrogram"], data["gate"], meta["mel_spectrogram_len"])
         gate_loss, mel_loss, post_loss = l3[0], l3[1], l3[2]

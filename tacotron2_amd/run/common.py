@@ -34,6 +34,16 @@ def model_kwargs(cfg: dict) -> dict:
                 scheduler_milestones=[int(x * max_steps) for x in md.get("scheduler_milestones", [])], **args)
 
 
+def train_forward_attention_setting(training_config: dict, override=None) -> bool:
+    """Forward attention under teacher forcing (training, validation, train-mel-export): `override` (True for the
+    `--forward-attention` flag of `main.py train`, None without it) wins over `"training": {"forward_attention": true}`; default off.
+    A value that is not a bool raises ValueError."""
+    from ..engine import check_forward_attention
+    if override is not None:
+        return check_forward_attention(override)
+    return check_forward_attention(training_config.get("forward_attention", False))
+
+
 def guided_attention_setting(training_config: dict, override=None):
     """(sigma, alpha) of the guided-attention loss, or None when it is off: `override` (the --guided-attention option) wins over
     `"training": {"guided_attention": {"sigma": 0.4, "alpha": 1.0}}` (either key may be left out: 0.4 and 1.0).  A section of

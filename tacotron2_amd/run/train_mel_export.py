@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ..model.tts_model import TTSModel
-from .common import model_kwargs
+from .common import model_kwargs, train_forward_attention_setting
 
 
 def do_train_mel_export(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
@@ -31,6 +31,8 @@ def do_train_mel_export(dataset_config: dict, training_config: dict, model_confi
     kw = model_kwargs(cfg)
     model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **kw)
     model.eval()
+    # a model trained under forward attention (training.forward_attention) is aligned by the recursion: its teacher-forced mels need it
+    fwd_att = train_forward_attention_setting(training_config)
     if results_dir is None:
         results_dir = f"results_{training_config['name']}_train_mel_export {datetime.datetime.now()}"
     os.makedirs(results_dir, exist_ok=True)
@@ -54,7 +56,8 @@ def do_train_mel_export(dataset_config: dict, training_config: dict, model_confi
             args = {k: b[k] for k in ("speaker_id", "controls", "description_embeddings") if k in b}
             with torch.no_grad():
                 _, post, _, _ = model(chars_idx=b["chars_idx"], chars_idx_len=b["chars_idx_len"], teacher_forcing=True,
-                                      mel_spectrogram=b["mel_spectrogram"], mel_spectrogram_len=b["mel_spectrogram_len"], **args)
+                                      mel_spectrogram=b["mel_spectrogram"], mel_spectrogram_len=b["mel_spectrogram_len"],
+                                      train_forward_attention=fwd_att, **args)
             post = post.cpu()
             model.tacotron2._engine.check_persistent_kernels()     # (the copy above synchronised) never export a poisoned forward
             for mel_out, n, fn in zip(post, b["mel_spectrogram_len"].cpu().tolist(), b["filename"]):
