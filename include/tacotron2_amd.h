@@ -465,6 +465,26 @@ int t2_loss_terms(const float* mels, const float* post, const float* gates, cons
  * loss is accumulated in double into ONE device double; sigma > 0, alpha >= 0 (customary: 0.4, 1.0). */
 int t2_guided_attn(const float* align, const int32_t* chars_len, const int32_t* mel_len, int B, int T, int L, float sigma,
                    float alpha, double* loss, float* dalign, float grad_scale, void* stream);
+/* Reduction factor r >= 2 (a decoder step emits r consecutive mel frames; S = ceil(T / r) steps for T frames): the grouped forms of
+ * the boundary kernels above.  A step's projection row is [r*M + 1] wide: column j*M + m is mel bin m of frame s*r + j, column r*M
+ * the step's ONE stop logit.  Frames at or beyond T of the last step are dropped (forward) / get a zero gradient (backward).
+ *   t2_mel_to_tm_r     (B,T,M) -> [S+1][B][M]: slot 0 = 0, slot s = frame r*s - 1, the LAST frame of the previous group (0 where r*s - 1 >= T:
+ *                      only slot S, which no step reads)
+ *   t2_finalize_fwd_r  proj [S][B][ld_proj] -> mels (B,T,M) masked 0, gates (B,T,1) = the step's logit repeated over its frames,
+ *                      masked -1000, post_in (B,T+4,M) padded layout (unmasked)
+ *   t2_finalize_bwd_r  dproj[s][b][j*M + m] += dpost_in[b][s*r + j][m]
+ *   t2_outgrad_pack_r / t2_loss_fwd_bwd_r  as t2_outgrad_pack / t2_loss_fwd_bwd (the same three sums, the same d_post) with dproj
+ *                      [S][B][r*M+1]; the gradient of a step's stop logit is the sum over its frames below T and below len[b],
+ *                      formed by one thread per (b, s) - no atomics.  d_post and dproj are required. */
+int t2_mel_to_tm_r(const float* mel, float* out, int B, int T, int M, int r, void* stream);
+int t2_finalize_fwd_r(const float* proj, int64_t ld_proj, const int32_t* len, float* mels, float* gates, float* post_in, int B,
+                      int T, int M, int r, void* stream);
+int t2_finalize_bwd_r(const float* dpost_in, float* dproj, int B, int T, int M, int r, void* stream);
+int t2_outgrad_pack_r(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len, float* d_post_out,
+                      float* dproj, int B, int T, int M, int r, void* stream);
+int t2_loss_fwd_bwd_r(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
+                      const int32_t* len, int B, int T, int M, int r, double* loss3, float* d_post, float* dproj,
+                      float grad_scale, void* stream);
 int t2_relu_mask_bwd(const float* g, const float* y, const float* mask, float* out, int64_t n, void* stream);
 int t2_condition_fwd(const float* enc, const float* spk_table, const int32_t* spk, const float* desc, float* memory, int B,
                      int L, int E, int Ef, void* stream);
@@ -533,6 +553,11 @@ int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream);
  * out2 = {frames emitted n, 0} */
 typedef struct { const float* proj[64]; int Bg[64]; int ngroups; int64_t ld_proj; int M, nframes; } T2StopScan;
 int t2_stop_scan(const T2StopScan* s, int64_t* lengths, int32_t* out2, void* stream);
+/* With a reduction factor r >= 2 the decode loop runs unchanged on steps: T2Infer.M = r * num_mels, the first prenet layer folded
+ * onto the LAST block of the projection (W_comb = [W_pre1 . W_mel[(r-1)M : rM] ; W_mel ; W_gate], b_comb and row_comb alike), Tcap
+ * and align in steps.  t2_stop_scan_r applies the count rule to the `nframes` stored STEPS (T2StopScan.M = r * num_mels):
+ * lengths [sum Bg] = min(r * counted steps, max_len) frames, out2 = {frames emitted = min(r * steps, max_len), steps emitted}. */
+int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):

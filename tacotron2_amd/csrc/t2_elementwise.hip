@@ -494,6 +494,151 @@ __global__ void finalize_bwd_kernel(const float* dpost_in, float* dproj, int B, 
     }
 }
 
+// ---- reduction factor r > 1: a decoder step emits r consecutive frames (include/tacotron2_amd.h, "Reduction factor") ------------
+// The grouped forms of the boundary kernels above.  A step's projection row is [S][B][r*M+1]: column j*M + m is mel bin m of frame
+// s*r + j, column r*M the step's one stop logit; S = ceil(T / r), frames at or beyond T of the last step do not exist.
+
+// Teacher pack: (B,T,M) -> [S+1][B][M]; slot 0 = 0, slot s = frame r*s - 1 (the LAST frame of the previous group), 0 where r*s - 1 >= T
+__global__ void mel_to_tm_r_kernel(const float* mel, float* out, int B, int T, int M, int r, int S) {
+    const long n = (long)(S + 1) * B * M;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int m = (int)(i % M);
+        const long row = i / M;
+        const int b = (int)(row % B), s = (int)(row / B);
+        const long t = (long)r * s - 1;         // (slot S of a T that is no multiple of r lies behind the target: zero, never consumed)
+        out[i] = (s == 0 || t >= T) ? 0.f : mel[((long)b * T + t) * M + m];
+    }
+}
+
+// proj [S][B][ldp] -> mels (B,T,M) masked 0, gates (B,T,1) = the step's logit for each of its frames, masked -1000, postnet input
+// (B,T+4,M) padded layout holding the unmasked mels
+__global__ void finalize_fwd_r_kernel(const float* proj, long ldp, const int32_t* len, float* mels, float* gates, float* post_in,
+                                      int B, int T, int M, int r) {
+    const int Tp = T + 4, M1 = M + 1;
+    const long n = (long)B * Tp * M1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int m = (int)(i % M1);
+        const long row = i / M1;
+        const int tp = (int)(row % Tp), b = (int)(row / Tp);
+        const int t = tp - 2;
+        const bool in = t >= 0 && t < T;
+        const int s = in ? t / r : 0, j = in ? t - s * r : 0;
+        const float v = in ? proj[((long)s * B + b) * ldp + (m < M ? j * M + m : r * M)] : 0.f;
+        if (m < M) {
+            if (post_in) post_in[((long)b * Tp + tp) * M + m] = v;
+            if (in) mels[((long)b * T + t) * M + m] = (t >= len[b]) ? 0.f : v;
+        } else if (in) {
+            gates[(long)b * T + t] = (t >= len[b]) ? -1000.f : v;
+        }
+    }
+}
+
+// Loss and its gradient, grouped: the three sums and d_post as loss_kernel; dproj [S][B][r*M+1] in the grouped layout (zero in the
+// columns of frames >= T).  The stop-logit gradient of a step is the sum over its frames below T and below len[b], formed by the
+// ONE thread that owns the (b, s) pair - no atomics.
+__global__ __launch_bounds__(256) void loss_r_kernel(const float* mels, const float* post, const float* gates, const float* mel_tgt,
+                                                     const float* gate_tgt, const int32_t* len, int B, int T, int M, int r, int S,
+                                                     double* loss3, float* d_post, float* dproj, float gscale) {
+    __shared__ double red[3][4];
+    const long nm = (long)B * T * M, ng = (long)B * T;
+    const long nv = (long)B * S * r * M, ns = (long)B * S;       // virtual frames S*r >= T; one gate entry per step
+    const long ldq = (long)r * M + 1;
+    const float sm = 1.f / (float)nm, sg = 1.f / (float)ng;
+    double a_g = 0, a_m = 0, a_p = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv + ns; i += (long)gridDim.x * blockDim.x) {
+        if (i < nv) {
+            const int m = (int)(i % M);
+            const long row = i / M;
+            const int tv = (int)(row % ((long)S * r)), b = (int)(row / ((long)S * r));
+            const int s = tv / r, j = tv - s * r;
+            float g = 0.f;
+            if (tv < T) {
+                const long k = ((long)b * T + tv) * M + m;
+                const bool masked = tv >= len[b];
+                const float tg = mel_tgt[k];
+                const float e1 = mels[k] - tg, e2 = post[k] - tg;
+                a_m += (double)e1 * e1; a_p += (double)e2 * e2;
+                const float g1 = masked ? 0.f : 2.f * e1 * sm * gscale;
+                const float g2 = masked ? 0.f : 2.f * e2 * sm * gscale;
+                d_post[k] = g2;
+                g = g1 + g2;
+            }
+            dproj[((long)s * B + b) * ldq + (long)j * M + m] = g;
+        } else {
+            const long q = i - nv;
+            const int s = (int)(q % S), b = (int)(q / S);
+            float gsum = 0.f;
+            for (int j = 0; j < r; ++j) {
+                const int t = s * r + j;
+                if (t >= T) break;
+                const float x = gates[(long)b * T + t], y = gate_tgt[(long)b * T + t];
+                a_g += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
+                if (t < len[b]) gsum += (t2_sigmoid(x) - y) * sg * gscale;
+            }
+            dproj[((long)s * B + b) * ldq + (long)r * M] = gsum;
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    a_g = t2_wave_sum_d(a_g); a_m = t2_wave_sum_d(a_m); a_p = t2_wave_sum_d(a_p);
+    if (lane == 0) { red[0][w] = a_g; red[1][w] = a_m; red[2][w] = a_p; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const double s = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        atomicAdd(&loss3[threadIdx.x], s / (threadIdx.x == 0 ? (double)ng : (double)nm));
+    }
+}
+
+// Upstream gradients (autograd path), grouped: d_post_out (B,T,M) and dproj [S][B][r*M+1]; the step's stop-logit gradient is the sum
+// of d_gates over its unmasked frames below T, by the thread that owns (b, s)
+__global__ void outgrad_pack_r_kernel(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,
+                                      float* d_post_out, float* dproj, int B, int T, int M, int r, int S) {
+    const long nv = (long)B * S * r * M, ns = (long)B * S;
+    const long ldq = (long)r * M + 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv + ns; i += (long)gridDim.x * blockDim.x) {
+        if (i < nv) {
+            const int m = (int)(i % M);
+            const long row = i / M;
+            const int tv = (int)(row % ((long)S * r)), b = (int)(row / ((long)S * r));
+            const int s = tv / r, j = tv - s * r;
+            float g = 0.f;
+            if (tv < T) {
+                const long k = ((long)b * T + tv) * M + m;
+                const bool masked = tv >= len[b];
+                const float g1 = (masked || !d_mels) ? 0.f : d_mels[k];
+                const float g2 = (masked || !d_post) ? 0.f : d_post[k];
+                d_post_out[k] = g2;
+                g = g1 + g2;
+            }
+            dproj[((long)s * B + b) * ldq + (long)j * M + m] = g;
+        } else {
+            const long q = i - nv;
+            const int s = (int)(q % S), b = (int)(q / S);
+            float gsum = 0.f;
+            if (d_gates)
+                for (int j = 0; j < r; ++j) {
+                    const int t = s * r + j;
+                    if (t >= T || t >= len[b]) break;
+                    gsum += d_gates[(long)b * T + t];
+                }
+            dproj[((long)s * B + b) * ldq + (long)r * M] = gsum;
+        }
+    }
+}
+
+// Gradient of the grouped finalize + postnet residual: dproj[s][b][j*M + m] += dpost_in[b][s*r + j][m]  (frames below T only)
+__global__ void finalize_bwd_r_kernel(const float* dpost_in, float* dproj, int B, int T, int M, int r) {
+    const int Tp = T + 4;
+    const long n = (long)B * T * M;
+    const long ldq = (long)r * M + 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int m = (int)(i % M);
+        const long row = i / M;
+        const int t = (int)(row % T), b = (int)(row / T);
+        const int s = t / r, j = t - s * r;
+        dproj[((long)s * B + b) * ldq + (long)j * M + m] += dpost_in[((long)b * Tp + t) * M + m];
+    }
+}
+
 // out = relu'(y) * mask * g   (prenet layers: y is the stored post-dropout output; y > 0 <=> pre-activation > 0 and kept)
 __global__ void relu_mask_bwd_kernel(const float* g, const float* y, const float* mask, float* out, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
@@ -845,6 +990,56 @@ extern "C" int t2_finalize_bwd(const float* dpost_in, float* dproj, int B, int T
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(dpost_in && dproj, "t2_finalize_bwd: null");
     hipLaunchKernelGGL(finalize_bwd_kernel, dim3(ew_grid((long)B * T * M)), dim3(256), 0, ST, dpost_in, dproj, B, T, M);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+// grouped boundary kernels (reduction factor r >= 2; r = 1 is the entry points above)
+#define T2_REQUIRE_GROUPED(name) \
+    T2_REQUIRE(B >= 1 && T >= 1 && M >= 1 && r >= 2 && (long)((T + r - 1) / r) * r < (1L << 31), name ": need B, T, M >= 1 and r >= 2")
+extern "C" int t2_mel_to_tm_r(const float* mel, float* out, int B, int T, int M, int r, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(mel && out, "t2_mel_to_tm_r: null");
+    T2_REQUIRE_GROUPED("t2_mel_to_tm_r");
+    const int S = (T + r - 1) / r;
+    hipLaunchKernelGGL(mel_to_tm_r_kernel, dim3(ew_grid((long)(S + 1) * B * M)), dim3(256), 0, ST, mel, out, B, T, M, r, S);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_finalize_fwd_r(const float* proj, int64_t ld_proj, const int32_t* len, float* mels, float* gates, float* post_in,
+                                 int B, int T, int M, int r, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(proj && len && mels && gates, "t2_finalize_fwd_r: null");
+    T2_REQUIRE_GROUPED("t2_finalize_fwd_r");
+    T2_REQUIRE(ld_proj >= (int64_t)r * M + 1, "t2_finalize_fwd_r: ld_proj < r * M + 1");
+    hipLaunchKernelGGL(finalize_fwd_r_kernel, dim3(ew_grid((long)B * (T + 4) * (M + 1))), dim3(256), 0, ST, proj, (long)ld_proj, len, mels,
+                       gates, post_in, B, T, M, r);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_loss_fwd_bwd_r(const float* mels, const float* post, const float* gates, const float* mel_tgt,
+                                 const float* gate_tgt, const int32_t* len, int B, int T, int M, int r, double* loss3, float* d_post,
+                                 float* dproj, float grad_scale, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(mels && post && gates && mel_tgt && gate_tgt && len && loss3 && d_post && dproj, "t2_loss_fwd_bwd_r: null");
+    T2_REQUIRE_GROUPED("t2_loss_fwd_bwd_r");
+    const int S = (T + r - 1) / r;
+    (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
+    hipLaunchKernelGGL(loss_r_kernel, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt,
+                       gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, grad_scale);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_outgrad_pack_r(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,
+                                 float* d_post_out, float* dproj, int B, int T, int M, int r, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(len && d_post_out && dproj, "t2_outgrad_pack_r: null");
+    T2_REQUIRE_GROUPED("t2_outgrad_pack_r");
+    const int S = (T + r - 1) / r;
+    hipLaunchKernelGGL(outgrad_pack_r_kernel, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, d_mels, d_post, d_gates,
+                       len, d_post_out, dproj, B, T, M, r, S);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_finalize_bwd_r(const float* dpost_in, float* dproj, int B, int T, int M, int r, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(dpost_in && dproj, "t2_finalize_bwd_r: null");
+    T2_REQUIRE_GROUPED("t2_finalize_bwd_r");
+    hipLaunchKernelGGL(finalize_bwd_r_kernel, dim3(ew_grid((long)B * T * M)), dim3(256), 0, ST, dpost_in, dproj, B, T, M, r);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_relu_mask_bwd(const float* g, const float* y, const float* mask, float* out, int64_t n, void* stream) {

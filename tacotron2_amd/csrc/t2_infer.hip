@@ -211,7 +211,58 @@ __global__ void stop_scan_kernel(StopScan p) {
     if (threadIdx.x == 0) { p.out2[0] = n; p.out2[1] = 0; }
 }
 
+// The same scan with a reduction factor r: `nframes` rows of proj are decoder STEPS of r frames each, column M (= r * num_mels)
+// the step's one stop logit.  The count rule runs on steps; lengths[b] = min(r * counted steps, max_len) frames,
+// out2 = {frames emitted = min(r * (n* + 1), max_len), steps emitted n* + 1}.
+// (A kernel of its own, the two passes written out again: sharing them through __device__ helpers changes the register allocation -
+// the instruction stream - of stop_scan_kernel, which the paths without the option keep.)
+__global__ void stop_scan_r_kernel(StopScan p, int r, int max_len) {
+    __shared__ int nstar;
+    if (threadIdx.x == 0) nstar = 0;
+    __syncthreads();
+    int Btot = 0;
+    for (int g = 0; g < p.ng; ++g) Btot += p.Bg[g];
+    for (int bb = threadIdx.x; bb < Btot; bb += blockDim.x) {
+        int g = 0, b = bb;
+        while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
+        int first = p.nframes - 1;     // never stops: the loop runs to the cap
+        for (int t = 0; t < p.nframes; ++t)
+            if (p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] < 0.f) { first = t; break; }
+        atomicMax(&nstar, first);
+    }
+    __syncthreads();
+    const int n = nstar + 1;
+    for (int bb = threadIdx.x; bb < Btot; bb += blockDim.x) {
+        int g = 0, b = bb;
+        while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
+        long cnt = 0;
+        for (int t = 0; t < n; ++t) cnt += p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] >= 0.f ? 1 : 0;
+        cnt *= r;
+        p.lengths[bb] = cnt < (long)max_len ? cnt : (long)max_len;
+    }
+    if (threadIdx.x == 0) {
+        const long fr = (long)n * r;
+        p.out2[0] = (int)(fr < (long)max_len ? fr : (long)max_len); p.out2[1] = n;
+    }
+}
+
 }  // namespace
+
+extern "C" int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(s && lengths && out2 && s->ngroups >= 1 && s->ngroups <= 64 && s->nframes >= 1, "t2_stop_scan_r: bad arguments");
+    T2_REQUIRE(r >= 2 && max_len >= 1 && (long)s->nframes * r < (1L << 31), "t2_stop_scan_r: need r >= 2 and max_len >= 1");
+    StopScan p;
+    memset(&p, 0, sizeof(p));
+    for (int g = 0; g < s->ngroups; ++g) {
+        T2_REQUIRE(s->proj[g] && s->Bg[g] >= 1, "t2_stop_scan_r: bad group");
+        p.proj[g] = s->proj[g]; p.Bg[g] = s->Bg[g];
+    }
+    p.ng = s->ngroups; p.ldp = s->ld_proj; p.M = s->M; p.nframes = s->nframes; p.lengths = lengths; p.out2 = out2;
+    hipLaunchKernelGGL(stop_scan_r_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p, r, max_len);
+    T2_CHECK_LAUNCH();
+    return T2_OK;
+}
 
 extern "C" int t2_linear_rows(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const float* mask,
                               int64_t ldmask, int relu, float* out, int64_t ldo, int B, int N, int K, void* stream) {

@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from . import guard as _guard
 from ._lib import call, make
-from .params import ParamStore
+from .params import ParamStore, reduction_factor
 
 KL, KPAD = 31, 15
 
@@ -211,6 +211,7 @@ class Engine:
     def __init__(self, ps: ParamStore):
         self.ps = ps
         self.d = ps.dims
+        self.r = reduction_factor(ps.dims)   # mel frames per decoder step (missing key: 1); the chains walk ceil(T / r) steps
         self.dev = ps.device
         self._ws: Dict[str, torch.Tensor] = {}
         self._cleared: Dict[tuple, tuple] = {}   # (data_ptr, bytes) -> (workspace name, view): regions put on the zero list ahead
@@ -377,6 +378,7 @@ class Engine:
         E, Pd, A, D, M, Pn = d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["num_mels"], d["postnet_dim"]
         st = _stream()
         sid = [step * 64]
+        Tf, T = T, (T + self.r - 1) // self.r      # decoder-side masks are per step; the postnet's per frame
 
         def gen(name, n, rate):
             m = self.buf("mask." + name, n)
@@ -391,7 +393,7 @@ class Engine:
             if p > 0.0:
                 masks["enc_drop"] = [gen(f"enc{i}", B * L * E, p).view(B, L, E) for i in range(3)]
                 chans = [Pn, Pn, Pn, Pn, M]
-                masks["post_drop"] = [gen(f"post{i}", B * T * c, p).view(B, T, c) for i, c in enumerate(chans)]
+                masks["post_drop"] = [gen(f"post{i}", B * Tf * c, p).view(B, Tf, c) for i, c in enumerate(chans)]
             masks["att_drop"] = gen("att", T * B * A, 0.1).view(T, B, A)
             masks["dec_drop"] = gen("dec", T * B * D, 0.1).view(T, B, D)
         return masks
@@ -692,7 +694,7 @@ class Engine:
     def controls_terms(self, controls, B):
         """Prosody controls (model/tacotron2.py:279-286, model/decoder.py:94-109): the same (B, controls_dim) vector is
         appended to the decoder-LSTM input and to the mel projection input at every frame, so its contribution is one
-        per-utterance term for each: cterm (B, 4D) and cmel1 (B, M+1) (stop column zero)."""
+        per-utterance term for each: cterm (B, 4D) and cmel1 (B, r*M+1) (stop column zero)."""
         d, P = self.d, self.ps.P
         C = d.get("controls_dim", 0) if d.get("controls") else 0
         assert (controls is not None) == bool(C), \
@@ -700,7 +702,7 @@ class Engine:
             "Controls are disabled, but a control vector was passed to the model!"
         if not C:
             return None, None, None
-        M, D = d["num_mels"], d["rnn_hidden_dim"]
+        M, D = self.r * d["num_mels"], d["rnn_hidden_dim"]
         ctl = controls.to(self.dev, torch.float32).contiguous()
         assert tuple(ctl.shape) == (B, C), f"controls must be (B, {C})"
         cterm = self.buf("ctl.dec", B, 4 * D)
@@ -753,16 +755,22 @@ class Engine:
         already on the device, with prenet/att/dec masks time-major; None entries = identity.
         forward_attention: True - every frame's weights are the forward-attention weights alpha_t (include/tacotron2_amd.h, "Forward
         attention"; T2AttnSeq.forward): the model is trained under the monotonic prior it is later decoded with
-        (infer(forward_attention=True)).  The flag travels in ctx; backward_tf reads it there."""
+        (infer(forward_attention=True)).  The flag travels in ctx; backward_tf reads it there.
+        With a reduction factor r > 1 (dims["reduction_factor"]) the chains run S = ceil(T / r) decoder steps: mels, mels_post and gates
+        keep the (B, T, .) frames (a step's stop logit repeated over its r frames), alignments is (B, S, L), and the decoder-side masks
+        are per step - prenet_drop [S+1][B][P], att_drop / dec_drop S rows (post_drop stays per frame).  ctx carries T, S and r."""
         forward_attention = check_forward_attention(forward_attention)
         d, P, ps = self.d, self.ps.P, self.ps
         masks = masks or {}
         B, L = chars_idx.shape
-        T, M = mel.shape[1], d["num_mels"]
+        Tf, M = mel.shape[1], d["num_mels"]
+        # reduction factor: T = S decoder steps of r frames each; Tf frames only at the boundary (teacher pack, finalize, postnet)
+        r = self.r
+        T, Mr = (Tf + r - 1) // r, r * M
         E, Pd, A, D, Ad = d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
-        ctx: dict = dict(B=B, L=L, T=T, forward_attention=forward_attention)
+        ctx: dict = dict(B=B, L=L, T=Tf, S=T, r=r, forward_attention=forward_attention)
         self.generation += 1          # any forward (grad-enabled or not) rewrites the shared workspaces
         ctx["generation"] = self.generation
         st = _stream()
@@ -778,7 +786,10 @@ class Engine:
         self._wait(side0, main0)
         with torch.cuda.stream(side0):
             mel_tm = self.buf("mel_tm", T + 1, B, M)
-            call("t2_mel_to_tm", mel, mel_tm, B, T, M, _stream())
+            if r == 1:
+                call("t2_mel_to_tm", mel, mel_tm, B, T, M, _stream())
+            else:             # slot s = frame r*s - 1: the last frame of the previous group (ESPnet's ys[:, r-1::r])
+                call("t2_mel_to_tm_r", mel, mel_tm, B, Tf, M, r, _stream())
             pd = masks.get("prenet_drop")
             p1 = self.buf("p1", T + 1, B, Pd)
             p2 = self.buf("p2", T + 1, B, Pd)
@@ -917,28 +928,31 @@ class Engine:
         self._wait(main, side)
         self.mark("fwd.dec.lstm_chain_tail")
 
-        # mel + stop projection over all frames: [mel_out.weight ; gate.weight] is one (M+1, D+Ef) matrix
-        wproj = ps.cat_view("decoder.mel_out.weight", M + 1, D + Ef)
-        bproj = ps.cat_view("decoder.mel_out.bias", M + 1, 0)
-        proj = self.buf("proj", T, B, M + 1)
+        # mel + stop projection over all steps: [mel_out.weight ; gate.weight] is one (r*M+1, D+Ef) matrix
+        wproj = ps.cat_view("decoder.mel_out.weight", Mr + 1, D + Ef)
+        bproj = ps.cat_view("decoder.mel_out.bias", Mr + 1, 0)
+        proj = self.buf("proj", T, B, Mr + 1)
         if cmel1 is not None:
-            proj.copy_(cmel1.unsqueeze(0).expand(T, B, M + 1))
-        gemm(_ptr(xproj, B * ldp), wproj, proj, R, M + 1, ldp, ldp, ldp, M + 1, bias=bproj,
+            proj.copy_(cmel1.unsqueeze(0).expand(T, B, Mr + 1))
+        gemm(_ptr(xproj, B * ldp), wproj, proj, R, Mr + 1, ldp, ldp, ldp, Mr + 1, bias=bproj,
              accumulate=1 if cmel1 is not None else 0)
         if persist:
             # A persistent launch that gave up on an inter-workgroup wait (sticky device flag) must not pass unnoticed: with the
             # flag set the projection - and with it every output, the loss and every gradient of this step - becomes NaN, and
             # t2_adam_step skips a step with a non-finite gradient norm.  No host synchronisation here; the host raises where it
             # reads the loss anyway (check_persistent_kernels).
-            call("t2_guard_poison", self._persist_sync.data_ptr() + 4 * 256, proj, R * (M + 1), st)
+            call("t2_guard_poison", self._persist_sync.data_ptr() + 4 * 256, proj, R * (Mr + 1), st)
         self.mark("fwd.dec.proj_gemm")
-        mels = self.out("mels", B, T, M)
-        gates = self.out("gates", B, T, 1)
-        post_in = self.buf("post.x0", B, T + 4, M)
-        call("t2_finalize_fwd", proj, M + 1, mlen32, mels, gates, post_in, B, T, M, st)
+        mels = self.out("mels", B, Tf, M)
+        gates = self.out("gates", B, Tf, 1)
+        post_in = self.buf("post.x0", B, Tf + 4, M)
+        if r == 1:
+            call("t2_finalize_fwd", proj, M + 1, mlen32, mels, gates, post_in, B, T, M, st)
+        else:
+            call("t2_finalize_fwd_r", proj, Mr + 1, mlen32, mels, gates, post_in, B, Tf, M, r, st)
 
-        post = self.out("post", B, T, M)
-        self.postnet_fwd(post_in, post, mlen32, B, T, masks.get("post_drop"), training, ctx)
+        post = self.out("post", B, Tf, M)
+        self.postnet_fwd(post_in, post, mlen32, B, Tf, masks.get("post_drop"), training, ctx)
         self.mark("fwd.postnet")
         ctx.update(controls=ctl, pmT=pmT, mel_tm=mel_tm, p1=p1, p2=p2, pd=pd, pre_att=pre_att, U=U, xdec=xdec, att_c=att_c, cum=cum,
                    xproj=xproj, gates_att=gates_att, th=th, align=align, pre_dec=pre_dec, dec_c=dec_c,
@@ -1001,12 +1015,15 @@ class Engine:
         """d_post (B,T,M): gradient w.r.t. mels_post (masked positions zero).  dproj [T][B][M+1]: gradient w.r.t. the
         decoder projection from the mel / residual / gate terms.  d_align: optional gradient w.r.t. the alignments output, a
         contiguous float32 (B,T,L) tensor on the engine's device (every frame counts, also those behind an utterance's mel length).
+        With a reduction factor r > 1 dproj is [S][B][r*M+1] and d_align (B,S,L), S = ceil(T / r) decoder steps.
         Accumulates into ps.grad (caller zeroes it)."""
         d, P, G, ps = self.d, self.ps.P, self.ps.G, self.ps
         if ctx.get("generation") != self.generation:
             raise RuntimeError("backward of a stale forward: the activation stashes of this forward were overwritten by a later "
                                "grad-enabled forward of the same model (one live teacher-forced graph per model; INTEGRATION.md)")
-        B, L, T = ctx["B"], ctx["L"], ctx["T"]
+        B, L, Tf = ctx["B"], ctx["L"], ctx["T"]
+        r = ctx.get("r", 1)
+        T = ctx.get("S", Tf)          # decoder steps: what the chains walk; Tf frames at the postnet / finalize boundary only
         if d_align is not None:
             # the dw kernel indexes it by hand with the strides of the alignments: anything else must not reach it as a pointer
             if not isinstance(d_align, torch.Tensor) or d_align.dtype != torch.float32:
@@ -1019,6 +1036,7 @@ class Engine:
             if d_align.device != ctx["align"].device:
                 raise ValueError(f"backward_tf: d_align is on {d_align.device}, the engine on {ctx['align'].device}")
         M, E, Pd, A, D, Ad = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
+        Mr = r * M
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
         H = E // 2
@@ -1041,35 +1059,38 @@ class Engine:
         self.fill_ahead(self.buf("enc.dx3", B * Lp_e, E), B * Lp_e - 4, E, 8 * H, E)
 
         # ---- postnet --------------------------------------------------------------------------------
-        dy, Lp_dy = d_post, T
+        dy, Lp_dy = d_post, Tf
         # the five weight-gradient GEMMs of the postnet (1.5 ms) leave the critical path: they run on the side stream between the
         # chunks of the backward frame loop, where the decoder-LSTM chain has slack (with the projection's there and the encoder's
         # on the side stream too: -1.4 ms per step, the round-2 A/B indexed in profiles/README.md)
         post_wgrads = []
         for li in range(4, -1, -1):
             dy = self.conv_bn_bwd(f"post.conv{li}", ctx, dy, Lp_dy, 0, P[f"postnet.postnet.{4 * li}.weight"],
-                                  G[f"postnet.postnet.{4 * li}.weight"], None, f"postnet.postnet.{4 * li + 1}", B, T,
+                                  G[f"postnet.postnet.{4 * li}.weight"], None, f"postnet.postnet.{4 * li + 1}", B, Tf,
                                   chans[li], chans[li + 1], 0 if li == 4 else 2, training, defer=post_wgrads)
-            Lp_dy = T + 4
-        call("t2_finalize_bwd", dy, dproj, B, T, M, st)
+            Lp_dy = Tf + 4
+        if r == 1:
+            call("t2_finalize_bwd", dy, dproj, B, T, M, st)
+        else:
+            call("t2_finalize_bwd_r", dy, dproj, B, Tf, M, r, st)
         self.mark("bwd.postnet")
 
         # ---- mel/stop projection ----------------------------------------------------------------------
         xproj, xdec = ctx["xproj"], ctx["xdec"]
-        wproj = ps.cat_view("decoder.mel_out.weight", M + 1, ldp)
+        wproj = ps.cat_view("decoder.mel_out.weight", Mr + 1, ldp)
         dxproj = self.buf("dxproj", T, B, ldp)
-        gemm(dproj, wproj, dxproj, R, ldp, M + 1, M + 1, ldp, ldp, a_k=1, b_k=0)
+        gemm(dproj, wproj, dxproj, R, ldp, Mr + 1, Mr + 1, ldp, ldp, a_k=1, b_k=0)
         ctl = ctx.get("controls")
 
         def proj_wgrads():       # weight / bias gradients of the projection: off the critical path (deferred with the postnet's)
-            self._wgrad(dproj, M + 1, _ptr(xproj, B * ldp), ldp, ps.cat_view("decoder.mel_out.weight", M + 1, ldp, grad=True),
-                        ldp, M + 1, ldp, R)
-            call("t2_colsum", dproj, M + 1, R, M + 1, ps.cat_view("decoder.mel_out.bias", M + 1, 0, grad=True), _stream())
-            if ctl is not None:       # controls columns: sum the gradient over frames per utterance, then (M, B) x (B, C)
+            self._wgrad(dproj, Mr + 1, _ptr(xproj, B * ldp), ldp, ps.cat_view("decoder.mel_out.weight", Mr + 1, ldp, grad=True),
+                        ldp, Mr + 1, ldp, R)
+            call("t2_colsum", dproj, Mr + 1, R, Mr + 1, ps.cat_view("decoder.mel_out.bias", Mr + 1, 0, grad=True), _stream())
+            if ctl is not None:       # controls columns: sum the gradient over steps per utterance, then (r*M, B) x (B, C)
                 C = ctl.shape[1]
-                s_proj = self.buf("ctl.dproj_sum", B, M + 1, zero=True)
-                call("t2_colsum", dproj, B * (M + 1), T, B * (M + 1), s_proj, _stream())
-                self._wgrad(s_proj, M + 1, ctl, C, G["decoder.mel_out.weight#controls"], C, M, C, B)
+                s_proj = self.buf("ctl.dproj_sum", B, Mr + 1, zero=True)
+                call("t2_colsum", dproj, B * (Mr + 1), T, B * (Mr + 1), s_proj, _stream())
+                self._wgrad(s_proj, Mr + 1, ctl, C, G["decoder.mel_out.weight#controls"], C, Mr, C, B)
         post_wgrads.append(proj_wgrads)
 
         # ---- both recurrences, back-propagation through time, as a two-stream pipeline over chunks of frames -----------
@@ -1371,21 +1392,29 @@ class Engine:
         the term is off - and loss3 stays the three terms."""
         mels, post, gates, align = outs
         B, T, M = mels.shape
+        r = ctx.get("r", 1)
+        S = ctx.get("S", T)
         guided = check_guided_attention(guided)
         d_align = self.guided_loss = None
         if guided is not None:
             L = ctx["L"]
-            if tuple(align.shape) != (B, T, L) or not align.is_contiguous() or align.dtype != torch.float32:
-                raise ValueError(f"loss_and_grads: the alignments must be the forward's contiguous float32 {(B, T, L)} output")
-            d_align = self.buf("guided.dalign", B, T, L)
+            if tuple(align.shape) != (B, S, L) or not align.is_contiguous() or align.dtype != torch.float32:
+                raise ValueError(f"loss_and_grads: the alignments must be the forward's contiguous float32 {(B, S, L)} output")
+            d_align = self.buf("guided.dalign", B, S, L)
             self.guided_loss = self.buf("guided.loss", 1, dtype=torch.float64)
-            call("t2_guided_attn", align, ctx["len32"], ctx["mlen32"], B, T, L, guided[0], guided[1], self.guided_loss, d_align,
+            # the alignments have one row per decoder step: the mask's T is S and its T_b the utterance's steps, ceil(mel_len / r)
+            slen32 = ctx["mlen32"] if r == 1 else torch.div(ctx["mlen32"] + (r - 1), r, rounding_mode="floor").to(torch.int32)
+            call("t2_guided_attn", align, ctx["len32"], slen32, B, S, L, guided[0], guided[1], self.guided_loss, d_align,
                  float(grad_scale), _stream())
         loss3 = self.buf("loss3", 3, dtype=torch.float64)
         d_post = self.buf("d_post", B, T, M)
-        dproj = self.buf("dproj", T, B, M + 1)
-        call("t2_loss_fwd_bwd", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, loss3, d_post, dproj,
-             float(grad_scale), _stream())
+        dproj = self.buf("dproj", S, B, r * M + 1)
+        if r == 1:
+            call("t2_loss_fwd_bwd", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, loss3, d_post, dproj,
+                 float(grad_scale), _stream())
+        else:
+            call("t2_loss_fwd_bwd_r", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, r, loss3, d_post, dproj,
+                 float(grad_scale), _stream())
         self.backward_tf(ctx, d_post, dproj, d_align=d_align)
         return loss3
 
@@ -1411,7 +1440,8 @@ class Engine:
         group's slice of the encoder output, computed for the WHOLE batch by the caller."""
         d, P, ps = self.d, self.ps.P, self.ps
         B, L = enc.shape[0], enc.shape[1]
-        M, E, Pd, A, D, Ad = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
+        M0, E, Pd, A, D, Ad = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["att_dim"]
+        M = self.r * M0              # the decode loop sees r*M projection columns per step; Tcap counts steps
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
         pf = f"inf{g}."
@@ -1436,7 +1466,8 @@ class Engine:
         row_comb = None
         if cmel1 is not None:        # per-utterance controls term of the folded linear: [W_pre1 . cmel_b ; cmel_b ; 0]
             row_comb = self.buf(pf + "row_comb", B, Pd + M + 1)
-            gemm(cmel1, P["prenet.0.weight"], row_comb, B, Pd, M, M + 1, M, Pd + M + 1)
+            # (the prenet sees the step's LAST frame: columns (r-1)*M0 .. r*M0 - 1 of the controls term)
+            gemm(_ptr(cmel1, M - M0), P["prenet.0.weight"], row_comb, B, Pd, M0, M + 1, M0, Pd + M + 1)
             row_comb[:, Pd:].copy_(cmel1)
             cterm = cterm.clone()    # (controls_terms reuses one workspace per engine)
         if prenet_masks is not None:
@@ -1472,7 +1503,10 @@ class Engine:
         forward_attention: True - every frame's weights are alpha_t(n) = q_t(n) y_t(n) / sum_m q_t(m) y_t(m) with y_t the softmax
         and the prior q_t(n) = 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8, alpha_{-1} one-hot at position 0: attention stays
         or advances one position per frame (include/tacotron2_amd.h, "Forward attention").  Context, cumulative weights, the
-        returned alignments and the next frame's location features all use alpha.  Not together with attention_window."""
+        returned alignments and the next frame's location features all use alpha.  Not together with attention_window.
+        With a reduction factor r > 1 `max_len` stays in frames: the loop runs at most ceil(max_len / r) decoder steps (one row of
+        prenet_masks and of the alignments per step), the count rule applies to steps, lengths = min(r * counted steps, max_len), and
+        the outputs have n = min(r * steps run, max_len) frames; window and forward attention act per step."""
         attention_window = check_attention_window(attention_window)
         forward_attention = check_forward_attention(forward_attention, attention_window)
         d, P, ps = self.d, self.ps.P, self.ps
@@ -1480,13 +1514,17 @@ class Engine:
         assert B <= 4096, "engine.infer handles up to 4096 utterances per call (64 groups of 64)"
         self.generation += 1          # the encoder / postnet workspaces are shared with forward_tf
         self.begin_phase(backward=False)
-        M, E, Pd, A, D = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"]
+        M0, E, Pd, A, D = d["num_mels"], d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"]
+        r = self.r
+        M = r * M0                   # projection columns of one decoder step
         Ef = E + (128 if d.get("description_embeddings") else 0)
         F = d.get("loc_filters", 32)
         st = _stream()
-        Tcap = int(max_len)
+        max_len = int(max_len)
+        Tcap = (max_len + r - 1) // r                        # decoder steps: at most ceil(max_len / r)
         if prenet_masks is not None:
-            Tcap = min(Tcap, int(prenet_masks.shape[0]))     # only as many frames as masks were supplied
+            Tcap = min(Tcap, int(prenet_masks.shape[0]))     # only as many steps as masks were supplied
+            max_len = min(max_len, Tcap * r)
         ldp = D + Ef
         # ---- per-call operands shared by all groups ----
         self._U_inf = self.buf("U", d["att_dim"], 2, KL)
@@ -1498,13 +1536,14 @@ class Engine:
                                                      (_ptr(Wih_a, Pd), Pd + Ef, Ef)], A)
         self._wp_dec_inf = self.pack_fwd("inf.dec", [(Wih_d, A + Ef, A), (_ptr(Wih_d, A), A + Ef, Ef),
                                                      (P["decoder.lstm.weight_hh"], D, D)], D)
-        # first prenet layer folded onto the mel projection: W_comb = [W_pre1 . W_mel ; W_mel ; W_gate] (include/tacotron2_amd.h)
+        # first prenet layer folded onto the mel projection: W_comb = [W_pre1 . W_mel ; W_mel ; W_gate] (include/tacotron2_amd.h);
+        # with a reduction factor onto its LAST block, rows (r-1)*M0 .. r*M0 - 1: the next step's prenet sees the last predicted frame
         wproj = ps.cat_view("decoder.mel_out.weight", M + 1, ldp)
         bproj = ps.cat_view("decoder.mel_out.bias", M + 1, 0)
         self._w_comb = self.buf("inf.w_comb", Pd + M + 1, ldp)
         self._b_comb = self.buf("inf.b_comb", Pd + M + 1)
-        gemm(P["prenet.0.weight"], wproj, self._w_comb, Pd, ldp, M, M, ldp, ldp, a_k=1, b_k=0)
-        gemm(P["prenet.0.weight"], bproj, self._b_comb, Pd, 1, M, M, 1, 1, a_k=1, b_k=0)
+        gemm(P["prenet.0.weight"], _ptr(wproj, (M - M0) * ldp), self._w_comb, Pd, ldp, M0, M0, ldp, ldp, a_k=1, b_k=0)
+        gemm(P["prenet.0.weight"], _ptr(bproj, M - M0), self._b_comb, Pd, 1, M0, M0, 1, 1, a_k=1, b_k=0)
         self._w_comb[Pd:].copy_(wproj); self._b_comb[Pd:].copy_(bproj)
         # x16-tiled copies of the two small linears' weights (data movement only): [K/16][rows padded to 16][16], the combined
         # linear's K chunks in the order [ctx | dec_h] of the tiled state
@@ -1564,19 +1603,28 @@ class Engine:
         ldo = (M + 1 + 3) // 4 * 4
         scan = make("T2StopScan", proj=[G["proj"] for G in groups] + [0] * (64 - len(groups)),
                     Bg=[G["B"] for G in groups] + [0] * (64 - len(groups)), ngroups=len(groups), ld_proj=ldo, M=M, nframes=t0)
-        call("t2_stop_scan", scan, lengths, nfr, st)
-        n = max(int(nfr.cpu()[0]), 1)
+        if r == 1:
+            call("t2_stop_scan", scan, lengths, nfr, st)
+        else:      # the count rule on steps; lengths and the emitted count n in frames, cut at max_len (nfr[1]: steps)
+            call("t2_stop_scan_r", scan, r, max_len, lengths, nfr, st)
+        nfr_h = nfr.cpu()
+        n = max(int(nfr_h[0]), 1)
+        ns = n if r == 1 else max(int(nfr_h[1]), 1)
         self.check_persistent_kernels()      # (the encoder recurrence is a persistent launch; the host has just synchronised anyway)
         # outputs: mask by the counted lengths, postnet on the unmasked mels (model/tacotron2.py:327-345)
         mlen32 = lengths.to(torch.int32)
-        mels = self.out("inf.mels", B, n, M)
+        mels = self.out("inf.mels", B, n, M0)
         gates = self.out("inf.gates", B, n, 1)
-        post_in = self.buf("post.x0", B, n + 4, M)
+        post_in = self.buf("post.x0", B, n + 4, M0)
         for G, b0 in zip(groups, range(0, B, 64)):
             Bg = G["B"]
-            call("t2_finalize_fwd", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
-                 post_in[b0:b0 + Bg], Bg, n, M, st)
-        post = self.out("inf.post", B, n, M)
+            if r == 1:
+                call("t2_finalize_fwd", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
+                     post_in[b0:b0 + Bg], Bg, n, M, st)
+            else:
+                call("t2_finalize_fwd_r", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
+                     post_in[b0:b0 + Bg], Bg, n, M0, r, st)
+        post = self.out("inf.post", B, n, M0)
         self.postnet_fwd(post_in, post, mlen32, B, n, None, training, {})
-        align = groups[0]["align"][:, :n] if len(groups) == 1 else torch.cat([G["align"][:, :n] for G in groups])
+        align = groups[0]["align"][:, :ns] if len(groups) == 1 else torch.cat([G["align"][:, :ns] for G in groups])
         return mels, post, gates, align.contiguous(), lengths.clone()

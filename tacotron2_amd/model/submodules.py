@@ -63,6 +63,9 @@ class Decoder(_Sub):
                 att_weights_cum, rnn_hidden: Tuple[Tensor, Tensor], encoded, att_encoded, encoded_mask,
                 speech_features: Optional[Tensor] = None, extra_att_in: Optional[Tensor] = None,
                 extra_decoder_in: Optional[Tensor] = None):
+        """One decoder step.  With Tacotron2(reduction_factor=r) the first result is the step's (B, r * num_mels) block - columns
+        j * num_mels .. (j + 1) * num_mels - 1 are its j-th frame - and the second its one stop logit (B, 1); the next step's
+        prenet input is the LAST frame, columns (r - 1) * num_mels onwards."""
         assert speech_features is None and extra_att_in is None, \
             "speech_features / extra_att_in are never passed by the reference's Tacotron2 (model/tacotron2.py:288-301)"
         root = self._root()
@@ -72,7 +75,7 @@ class Decoder(_Sub):
         A, D = root.att_rnn_dim, root.rnn_hidden_dim
         Pd = prev_mel_prenet.shape[1]
         Ef = encoded.shape[2]
-        M = root.num_mels
+        M = root.num_mels * root.reduction_factor      # a step's projection: r frames of num_mels bins (row j*num_mels + m), then the gate row
         training = root.training
         with torch.no_grad():
             st = _stream()

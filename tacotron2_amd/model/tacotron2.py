@@ -18,7 +18,7 @@ from torch import Tensor, nn
 from .._lib import call
 from ..engine import Engine, _stream, check_attention_window, check_forward_attention
 from ..init import init_parameters
-from ..params import ParamStore
+from ..params import ParamStore, check_reduction_factor
 
 
 class _Node(nn.Module):
@@ -72,9 +72,13 @@ class _TacotronFn(torch.autograd.Function):
         ps = model.store
         B, T, M = ectx["B"], ectx["T"], model.num_mels
         f = lambda g: g.contiguous().float() if g is not None else None
+        r, S = ectx.get("r", 1), ectx.get("S", T)
         d_post_m = eng.buf("ag.d_post", B, T, M)
-        dproj = eng.buf("ag.dproj", T, B, M + 1)
-        call("t2_outgrad_pack", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, _stream())
+        dproj = eng.buf("ag.dproj", S, B, r * M + 1)
+        if r == 1:
+            call("t2_outgrad_pack", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, _stream())
+        else:      # grouped layout [S][B][r*M+1]; a step's stop-logit gradient is the sum over its frames
+            call("t2_outgrad_pack_r", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, r, _stream())
         ps.grad.zero_()
         eng.backward_tf(ectx, d_post_m, dproj, d_align=f(d_align))
         grads = tuple(ps.G[name] for name in model._param_names)
@@ -86,8 +90,13 @@ class Tacotron2(nn.Module):
                  att_rnn_dim: int, att_dim: int, rnn_hidden_dim: int, postnet_dim: int, dropout: float,
                  speaker_tokens: bool = False, speaker_tokens_dim: Optional[int] = 128, num_speakers: int = 1,
                  controls: bool = False, controls_dim: int = 0, description_embeddings: bool = False,
-                 description_embeddings_dim: int = 0, device=None, seed: int = 0):
+                 description_embeddings_dim: int = 0, device=None, seed: int = 0, reduction_factor: int = 1):
+        """reduction_factor r >= 1: every decoder step emits r consecutive mel frames (`decoder.mel_out` has r * num_mels rows), so
+        the recurrences run ceil(T / r) times for T frames.  mels, mels_post and gates keep frame resolution (a step's stop logit
+        is repeated over its frames); `alignments` has one row per step, (B, ceil(T / r), L).  1: the reference's model."""
         super().__init__()
+        reduction_factor = check_reduction_factor(reduction_factor)
+        self.reduction_factor = reduction_factor
         assert not speaker_tokens or num_speakers is not None, "If speaker tokens are enabled, you must give a num_speakers!"
         assert encoder_kernel_size == 5, "the conv-as-GEMM kernels are specialised for the reference's k=5"
         self.embedding_dim = self.char_embedding_dim = encoded_dim
@@ -102,6 +111,8 @@ class Tacotron2(nn.Module):
                          description_embeddings=description_embeddings,
                          description_embeddings_dim=description_embeddings_dim,
                          controls=bool(controls), controls_dim=int(controls_dim) if controls else 0)
+        if reduction_factor != 1:     # (a missing key means 1: the dims of an r = 1 model are what they always were)
+            self.dims["reduction_factor"] = reduction_factor
         if device is None:
             device = "cuda:0" if torch.cuda.is_available() else "cpu"
         self._seed, self._calls = seed, 0

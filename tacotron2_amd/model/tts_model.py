@@ -11,6 +11,7 @@ from torch import Tensor, nn
 
 from .._lib import call
 from ..engine import check_guided_attention
+from ..params import check_reduction_factor
 from .tacotron2 import Tacotron2
 
 
@@ -90,8 +91,9 @@ class TTSModel(nn.Module):
                  scheduler_milestones: List[int] = (), speaker_tokens: bool = False, num_speakers: int = 1,
                  controls: bool = False, controls_dim: int = 0, max_len_override: Optional[int] = None,
                  description_embeddings: bool = False, description_embeddings_dim: int = 0,
-                 char_embedding_dim: Optional[int] = None, device=None):
+                 char_embedding_dim: Optional[int] = None, device=None, reduction_factor: int = 1):
         super().__init__()
+        reduction_factor = check_reduction_factor(reduction_factor)    # mel frames per decoder step (Tacotron2)
         if char_embedding_dim is not None:     # stale configs name encoded_dim `char_embedding_dim`
             encoded_dim = char_embedding_dim
         self.hparams = dict(lr=lr, weight_decay=weight_decay, num_chars=num_chars, encoded_dim=encoded_dim,
@@ -101,7 +103,7 @@ class TTSModel(nn.Module):
                             speaker_tokens=speaker_tokens, num_speakers=num_speakers, controls=controls,
                             controls_dim=controls_dim, max_len_override=max_len_override,
                             description_embeddings=description_embeddings,
-                            description_embeddings_dim=description_embeddings_dim)
+                            description_embeddings_dim=description_embeddings_dim, reduction_factor=reduction_factor)
         self.lr, self.weight_decay = lr, weight_decay
         self.scheduler_milestones = list(scheduler_milestones)
         self.speaker_tokens, self.controls = speaker_tokens, controls
@@ -121,7 +123,8 @@ class TTSModel(nn.Module):
                                    rnn_hidden_dim=rnn_hidden_dim, postnet_dim=postnet_dim, dropout=dropout,
                                    speaker_tokens=speaker_tokens, num_speakers=num_speakers, controls=controls,
                                    controls_dim=controls_dim, description_embeddings=description_embeddings,
-                                   description_embeddings_dim=description_embeddings_dim, device=device)
+                                   description_embeddings_dim=description_embeddings_dim, device=device,
+                                   reduction_factor=reduction_factor)
 
     def configure_optimizers(self):
         optimizer = torch.optim.Adam(self.tacotron2.parameters(), lr=self.lr, weight_decay=self.weight_decay)
@@ -165,7 +168,10 @@ class TTSModel(nn.Module):
         gate_loss, mel_loss, post_loss = l3[0], l3[1], l3[2]
         loss = l3.sum()
         if guided is not None:
-            loss = loss + _GuidedAttnFn.apply(alignment, meta["chars_idx_len"], meta["mel_spectrogram_len"], *guided)
+            r = self.tacotron2.reduction_factor      # the alignments have one row per decoder step: ceil(mel_len / r) of them count
+            steps = meta["mel_spectrogram_len"] if r == 1 else \
+                torch.div(meta["mel_spectrogram_len"] + (r - 1), r, rounding_mode="floor")
+            loss = loss + _GuidedAttnFn.apply(alignment, meta["chars_idx_len"], steps, *guided)
         return loss, (gate_loss, mel_loss, post_loss), (mel, post, gate, alignment)
 
     def training_step(self, batch, batch_idx=0):
@@ -175,9 +181,9 @@ class TTSModel(nn.Module):
         with torch.no_grad():
             loss, _, (mel, post, gate, alignment) = self._loss(batch)
         data, meta = batch[0], batch[1]
-        ml, cl = meta["mel_spectrogram_len"], meta["chars_idx_len"]
+        ml, cl, r = meta["mel_spectrogram_len"], meta["chars_idx_len"], self.tacotron2.reduction_factor
         return {"mel_spectrogram_pred": post[0, :ml[0]], "mel_spectrogram": data["mel_spectrogram"][0, :ml[0]],
-                "alignment": alignment[0, :ml[0], :cl[0]], "gate": data["gate"][0], "gate_pred": gate[0], "loss": loss}
+                "alignment": alignment[0, :(ml[0] + r - 1) // r, :cl[0]], "gate": data["gate"][0], "gate_pred": gate[0], "loss": loss}
 
     def predict_step(self, batch, batch_idx=0, dataloader_idx=0):
         data, meta = batch[0], batch[1]
@@ -202,7 +208,7 @@ class TTSModel(nn.Module):
     def load_from_checkpoint(cls, path: str, map_location=None, device=None, **overrides):
         ck = torch.load(path, map_location="cpu", weights_only=True)
         hp = dict(ck.get("hyper_parameters", {}))
-        hp.update({k: v for k, v in overrides.items() if k in hp or k in ("lr", "weight_decay", "num_chars")})
+        hp.update({k: v for k, v in overrides.items() if k in hp or k in ("lr", "weight_decay", "num_chars", "reduction_factor")})
         hp = {k: v for k, v in hp.items() if k in cls.__init__.__code__.co_varnames}
         model = cls(device=device, **hp)
         model.load_checkpoint_dict(ck)

@@ -9,6 +9,7 @@ in ONE contiguous fp32 device buffer, each tensor 16-byte aligned, so that
 """
 from __future__ import annotations
 
+import numbers
 from collections import OrderedDict
 from typing import Dict, Optional
 
@@ -17,8 +18,22 @@ import torch
 from . import guard as _guard
 
 
+def check_reduction_factor(r) -> int:
+    """The reduction factor (mel frames per decoder step) as an int >= 1; anything else - a bool, a float, a string, 0 - raises
+    ValueError."""
+    if isinstance(r, bool) or not isinstance(r, numbers.Integral) or r < 1:
+        raise ValueError(f"reduction_factor must be an integer >= 1, got {r!r}")
+    return int(r)
+
+
+def reduction_factor(d: dict) -> int:
+    """`reduction_factor` of a dims dict; a missing key means 1."""
+    return check_reduction_factor(d.get("reduction_factor", 1))
+
+
 def param_manifest(d: dict) -> "OrderedDict[str, tuple]":
     """name -> shape in flat-buffer order (learnable parameters only)."""
+    r = reduction_factor(d)
     E, k = d["encoded_dim"], d["encoder_kernel_size"]
     Ef = E + (128 if d.get("description_embeddings") else 0)
     P, A, D = d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"]
@@ -60,10 +75,10 @@ def param_manifest(d: dict) -> "OrderedDict[str, tuple]":
     s["decoder.lstm.weight_hh"] = (4 * D, D)
     s["decoder.lstm.bias_ih"] = (4 * D,)
     s["decoder.lstm.bias_hh"] = (4 * D,)
-    # adjacent: (M+1, D+Ef) projection and (M+1,) bias
-    s["decoder.mel_out.weight"] = (M, D + Ef)
+    # adjacent: (r*M+1, D+Ef) projection and (r*M+1,) bias; with a reduction factor r row j*M + m is mel bin m of a step's j-th frame
+    s["decoder.mel_out.weight"] = (r * M, D + Ef)
     s["decoder.gate.weight"] = (1, D + Ef)
-    s["decoder.mel_out.bias"] = (M,)
+    s["decoder.mel_out.bias"] = (r * M,)
     s["decoder.gate.bias"] = (1,)
     chans = [M, Pn, Pn, Pn, Pn, M]
     for li in range(5):
@@ -76,7 +91,7 @@ def param_manifest(d: dict) -> "OrderedDict[str, tuple]":
     C = d.get("controls_dim", 0) if d.get("controls") else 0
     if C:
         s["decoder.lstm.weight_ih#controls"] = (4 * D, C)
-        s["decoder.mel_out.weight#controls"] = (M, C)
+        s["decoder.mel_out.weight#controls"] = (r * M, C)
     return s
 
 
@@ -200,6 +215,11 @@ class ParamStore:
             key = prefix + name
             if key in sd:
                 t = torch.as_tensor(sd[key]).to(torch.float32)
+                if name in ("decoder.mel_out.weight", "decoder.mel_out.bias") and t.shape[0] != self.shapes[name][0]:
+                    M, r = self.dims["num_mels"], reduction_factor(self.dims)
+                    theirs = t.shape[0] // M if t.shape[0] % M == 0 else f"{t.shape[0]}/{M}"
+                    raise ValueError(f"{key} has {t.shape[0]} rows: the checkpoint was written with reduction_factor = {theirs}, this "
+                                     f"model is configured with reduction_factor = {r} ({r} x {M} = {r * M} rows)")
                 if ctrl and name in CONTROL_SPLITS:       # reference layout: [main columns | controls columns]
                     k0 = self.shapes[name][1]
                     self.P[name + "#controls"].copy_(t[:, k0:])
