@@ -560,6 +560,43 @@ int t2_stop_scan(const T2StopScan* s, int64_t* lengths, int32_t* out2, void* str
 int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-character durations from alignments (no reference counterpart; the teacher export that duration-based models such as
+ * FastSpeech train on, and character timestamps at decode time): how many mel frames each input character lasts, from the
+ * (B, S, L) alignments of a teacher-forced forward or of a decode.  One launch, one 256-thread workgroup per utterance
+ * (csrc/t2_align.hip); no cross-workgroup synchronisation, no atomics to global memory.
+ *   N_b = clip(chars_len[b], 0, L) characters, F_b = clip(frames_len[b], 0, r*S) mel frames, S_b = ceil(F_b / r) decoder steps.
+ *   Frames per step: step s < S_b - 1 carries r frames, the last step F_b - r*(S_b - 1).  Every step is assigned ONE position
+ *   pos[s] < N_b; dur[b][n] = the sum of the frames of the steps assigned to n, so sum_n dur[b][n] == F_b always; dur[b][n] = 0
+ *   for N_b <= n < L.
+ *   mode 0 (argmax): pos[s] = the LOWEST n < N_b with the largest align[b][s][n].
+ *   mode 1 (monotonic; the monotonic alignment search of Glow-TTS, Kim et al. 2020): the best path that starts on the first
+ *     character, ends on the last and stays or advances by one per step.  With la[s][n] = log((double)fmaxf(a, 1e-8f)):
+ *       Q[0][0] = la[0][0], Q[0][n > 0] = -inf;   Q[s][n] = la[s][n] + max(Q[s-1][n], Q[s-1][n-1])
+ *     the predecessor of (s, n) is n-1 only when Q[s-1][n-1] > Q[s-1][n] STRICTLY (a tie stays at n); pos is the backtrack
+ *     from (S_b - 1, N_b - 1), so every character gets at least one step.  The recurrence runs in fp64: over a few thousand
+ *     steps Q reaches ~4e4, where an fp32 ulp (4e-3) is the size of real decision margins.
+ *     Infeasible utterance (S_b < N_b: fewer steps than characters): its positions are those of mode 0.
+ *   N_b == 0 or S_b == 0: dur[b] and stats[b] are zero.
+ *   stats[b][0..3], each accumulated in double and stored as float:
+ *     [0] focus rate = mean_s max_{n < N_b} align[b][s][n]        [1] mean_s la[s][pos[s]]
+ *     [2] feasible = (S_b >= N_b) ? 1 : 0 (either mode)           [3] share of the steps with pos[s] == the argmax position (mode 0: 1)
+ *   Nothing at n >= N_b or s >= S_b is read.  back: mode 1 workspace of B*S*L bytes (bit 0 = predecessor is n-1, bit 1 = the
+ *   step's argmax), rewritten by every call; may be NULL in mode 0.
+ *   L > T2_ALIGN_MAX_L (two fp64 rows of Q in LDS: 64 KB at the cap), r < 1, a mode other than 0 / 1, a NULL back in mode 1 or
+ *   leading dimensions smaller than the shapes are T2_ERR_ARG before any launch. */
+#define T2_ALIGN_MAX_L 4096
+typedef struct {
+    const float* align; int64_t ld_b, ld_s;   /* align[b*ld_b + s*ld_s + n], n contiguous */
+    int B, S, L, r, mode;                     /* r >= 1 frames per step; mode 0 = argmax, 1 = monotonic */
+    const int32_t* chars_len;                 /* [B] device; N_b = clip(., 0, L) */
+    const int32_t* frames_len;                /* [B] device; F_b = clip(., 0, r*S); S_b = ceil(F_b / r) */
+    int32_t* dur; int64_t ld_dur;             /* [B][ld_dur >= L]: frames per character, 0 for n >= N_b */
+    float* stats;                             /* [B][4] */
+    uint8_t* back;                            /* mode 1 workspace [B][S][L]; may be NULL in mode 0 */
+} T2AlignDur;
+int t2_align_durations(const T2AlignDur* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

@@ -4,12 +4,13 @@
     python main.py --config C --device N train --speech-dir S [--results-dir R] [--resume-ckpt K] [--finetune --finetune-steps n]
                                                   [--guided-attention SIGMA,ALPHA]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
-                                                  [--attention-window BACK,FWD | --forward-attention]
+                                                  [--attention-window BACK,FWD | --forward-attention] [--durations-out PATH]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention]
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
+    python main.py --config C --device N duration-export --speech-dir S --checkpoint K [--results-dir R] [--mode monotonic|argmax]
 
 Other reference sub-commands (preprocess, server) are data preparation / demo tooling outside the hot-path scope
 (SURVEY.md section 2).  Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N
@@ -122,8 +123,11 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--description", required=False, type=str, default=None, help="Path of a precomputed description embedding (.pt / .npy, pooler_output of bert-base-uncased); raw text needs the BERT weights (unavailable offline)")
 @attention_window_option
 @forward_attention_option
+@click.option("--durations-out", required=False, type=str, default=None, metavar="PATH",
+              help="Write character timestamps as JSON: per text the encoded symbols, the mel frames each one lasts (the best "
+                   "monotonic path through the decode's own alignments), start_s / end_s, focus_rate and feasible. Default: off.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
-        forward_attention):
+        forward_attention, durations_out=None):
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for speech!")
@@ -132,7 +136,8 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
     do_say(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
            extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, text=text, output=out,
            speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
-           description=description, attention_window=attention_window, forward_attention=forward_attention)
+           description=description, attention_window=attention_window, forward_attention=forward_attention,
+           durations_out=durations_out)
 
 
 @main.command()
@@ -202,6 +207,25 @@ def train_mel_export(ctx, speech_dir, checkpoint, results_dir=None):
     do_train_mel_export(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
                         extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
                         results_dir=results_dir)
+
+
+@main.command()
+@click.pass_context
+@click.option("--speech-dir", required=True, type=str, help="A directory containing audio files from the dataset.")
+@click.option("--checkpoint", required=True, type=str, help="A trained Tacotron model checkpoint")
+@click.option("--results-dir", required=False, type=str, default=None, help="The directory to save results. Defaults to the model configuration name with a timestamp.")
+@click.option("--mode", required=False, type=click.Choice(["monotonic", "argmax"]), default="monotonic",
+              help="monotonic: the best monotonic path through the alignment (first character to last, stay or advance by one per "
+                   "decoder step); argmax: each decoder step's attention peak. Default: monotonic.")
+def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monotonic"):
+    """Per-character durations (mel frames) of the train + val manifests from teacher-forced alignments, plus durations.csv."""
+    if ctx.obj["config"] is None:
+        raise Exception("Configuration required!")
+    from tacotron2_amd.run.duration_export import do_duration_export
+    c = ctx.obj["config"]
+    do_duration_export(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
+                       extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
+                       results_dir=results_dir, mode=mode)
 
 
 if __name__ == "__main__":

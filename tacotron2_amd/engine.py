@@ -1628,3 +1628,50 @@ class Engine:
         self.postnet_fwd(post_in, post, mlen32, B, n, None, training, {})
         align = groups[0]["align"][:, :ns] if len(groups) == 1 else torch.cat([G["align"][:, :ns] for G in groups])
         return mels, post, gates, align.contiguous(), lengths.clone()
+
+    # =============================================================================================
+    # per-character durations from alignments (include/tacotron2_amd.h: t2_align_durations)
+    # =============================================================================================
+    ALIGN_MAX_L = 4096          # T2_ALIGN_MAX_L: two fp64 rows of the search in LDS
+    DURATION_MODES = {"argmax": 0, "monotonic": 1}
+
+    def durations(self, align, chars_len, frames_len, mode="monotonic"):
+        """How many mel frames each input character lasts: (dur, stats) = int32 (B, L), float32 (B, 4) from float32 alignments
+        (B, S, L) - the output of forward_tf, or a strided view such as infer's `align[:, :ns]` (the last dimension contiguous) -
+        the text lengths and the utterances' FRAME counts (mel lengths, or infer's `lengths`; S_b = ceil(frames / r) steps with
+        the engine's reduction factor r).  mode "monotonic": the best monotonic path (first character to last, stay or advance by
+        one per step, fp64 recurrence); "argmax": each step's peak.  dur[b] sums to the utterance's frames and is 0 behind its
+        text; stats[b] = (focus rate, mean log-weight on the path, feasible, agreement with the argmax).  An utterance with fewer
+        steps than characters has no monotonic path: it gets the argmax counts and feasible = 0."""
+        if mode not in self.DURATION_MODES:
+            raise ValueError(f"durations: mode must be one of {sorted(self.DURATION_MODES)}, got {mode!r}")
+        if not torch.is_tensor(align) or align.dim() != 3 or align.dtype != torch.float32:
+            raise ValueError("durations: the alignments must be a float32 (B, S, L) tensor")
+        B, S, L = align.shape
+        if B < 1 or S < 1 or L < 1:
+            raise ValueError(f"durations: empty alignments {tuple(align.shape)}")
+        if L > self.ALIGN_MAX_L:
+            raise ValueError(f"durations: L = {L} is above the limit of {self.ALIGN_MAX_L} text positions")
+        if align.stride(2) != 1 and L > 1:
+            raise ValueError("durations: the last dimension of the alignments must be contiguous")
+        dev = self.ps.flat.device          # (the parameters' device with its index: self.dev may be a bare "cuda")
+        for name, t in (("align", align), ("chars_len", chars_len), ("frames_len", frames_len)):
+            if not torch.is_tensor(t) or t.device != dev:
+                raise ValueError(f"durations: {name} must be a tensor on the engine's device {dev}")
+        for name, t in (("chars_len", chars_len), ("frames_len", frames_len)):
+            if t.dim() != 1 or t.shape[0] != B or t.is_floating_point() or t.dtype == torch.bool:
+                raise ValueError(f"durations: {name} must be {B} integers")
+        ld_s = align.stride(1) if S > 1 else L
+        ld_b = align.stride(0) if B > 1 else S * ld_s
+        if ld_s < L or (B > 1 and ld_b < (S - 1) * ld_s + L):
+            raise ValueError(f"durations: overlapping alignment rows (strides {tuple(align.stride())})")
+        m = self.DURATION_MODES[mode]
+        clen32 = chars_len.to(torch.int32).contiguous()
+        flen32 = frames_len.to(torch.int32).contiguous()
+        dur = self.buf("dur.dur", B, L, dtype=torch.int32)
+        stats = self.buf("dur.stats", B, 4)
+        back = self.buf("dur.back", B, S, L, dtype=torch.uint8) if m == 1 else None
+        a = make("T2AlignDur", align=align, ld_b=ld_b, ld_s=ld_s, B=B, S=S, L=L, r=self.r, mode=m, chars_len=clen32,
+                 frames_len=flen32, dur=dur, ld_dur=L, stats=stats, back=back)
+        call("t2_align_durations", a, _stream())
+        return dur.clone(), stats.clone()      # (the workspaces belong to the next call)

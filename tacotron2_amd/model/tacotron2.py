@@ -224,6 +224,28 @@ class Tacotron2(nn.Module):
             self._calls += 1
         return o[:4]
 
+    def durations(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
+                  mode: str = "monotonic", **kw):
+        """Per-character durations of a batch from its teacher-forced alignments: an EVAL-mode forward(teacher_forcing=True, ...)
+        with the same arguments (speaker_id, controls, description_embeddings, max_len_override, dropout_masks,
+        train_forward_attention), no gradients, then Engine.durations on its alignments.  Returns (durations, stats, alignments):
+        int32 (B, L) mel frames per character (each row sums to the utterance's mel length, 0 behind its text), float32 (B, 4) =
+        (focus rate, mean log-weight on the path, feasible, agreement with the argmax) and the (B, S, L) alignments.  mode:
+        "monotonic" (the best monotonic path, Glow-TTS's alignment search) or "argmax".  The module's train/eval state is kept."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                align = self.forward(chars_idx, chars_idx_len, True, mel_spectrogram=mel_spectrogram,
+                                     mel_spectrogram_len=mel_spectrogram_len, **kw)[3]
+                T = mel_spectrogram.shape[1] if kw.get("max_len_override") is None else min(int(kw["max_len_override"]),
+                                                                                            mel_spectrogram.shape[1])
+                frames = mel_spectrogram_len.to(align.device).clamp(max=T)
+                dur, stats = self._engine.durations(align, chars_idx_len.to(align.device), frames, mode=mode)
+        finally:
+            self.train(was_training)
+        return dur, stats, align
+
     def inference(self, chars_idx, chars_idx_len, max_len: int = 5000, **kw):
         """Alias of forward(teacher_forcing=False, max_len_override=max_len) (north_star's "inference() surface")."""
         return self.forward(chars_idx, chars_idx_len, False, max_len_override=max_len, **kw)

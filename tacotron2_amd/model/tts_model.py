@@ -146,6 +146,16 @@ class TTSModel(nn.Module):
                               description_embeddings=description_embeddings, attention_window=attention_window,
                               forward_attention=forward_attention, train_forward_attention=train_forward_attention)
 
+    def durations(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
+                  mode: str = "monotonic", speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
+                  max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
+                  train_forward_attention: bool = False):
+        """(durations, stats, alignments) of an eval-mode teacher-forced forward: Tacotron2.durations."""
+        return self.tacotron2.durations(chars_idx, chars_idx_len, mel_spectrogram, mel_spectrogram_len, mode=mode,
+                                        speaker_id=speaker_id, controls=controls, max_len_override=max_len_override,
+                                        description_embeddings=description_embeddings,
+                                        train_forward_attention=train_forward_attention)
+
     def _args(self, meta):
         args = {}
         if self.speaker_tokens:

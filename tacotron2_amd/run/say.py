@@ -38,11 +38,36 @@ def load_description(description: Optional[str], dim: int, n: int, dev) -> torch
     return v.to(dev).unsqueeze(0).repeat(n, 1).contiguous()
 
 
+def write_durations(path: str, model, enc: TextEncoder, texts: List[str], align: torch.Tensor, lens: torch.Tensor,
+                    frames: List[int], sample_rate: int, hop: int = 256) -> list:
+    """`say --durations-out`: the monotonic path through the decode's alignments (one row per decoder step; r frames per step with
+    a reduction factor) over each text's written frames -> per-symbol frame counts and times, as a JSON list."""
+    import json
+    flen = torch.tensor(frames, dtype=torch.int32, device=align.device)
+    dur, stats = model.tacotron2._engine.durations(align, lens, flen, mode="monotonic")
+    dur, stats = dur.cpu().numpy(), stats.cpu().numpy()
+    out = []
+    for b, t in enumerate(texts):
+        sym = list(enc.clean(t))
+        fr = [int(x) for x in dur[b, :len(sym)]]
+        ends = np.cumsum(fr)
+        out.append(dict(symbols=sym, frames=fr, start_s=[float((e - f) * hop / sample_rate) for e, f in zip(ends, fr)],
+                        end_s=[float(e * hop / sample_rate) for e in ends], focus_rate=float(stats[b, 0]),
+                        feasible=bool(stats[b, 2] != 0)))
+    with open(path, "w") as f:
+        json.dump(out, f)
+    return out
+
+
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
            description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
-           forward_attention: Optional[bool] = None):
+           forward_attention: Optional[bool] = None, durations_out: Optional[str] = None):
+    """durations_out: a path - character timestamps of the decode are written there as a JSON list with one object per text:
+    `symbols` (the encoded sequence, end token included), `frames` per symbol (the monotonic path through the decode's own
+    alignments, Engine.durations; they sum to the frames of the mel that is written), `start_s` / `end_s` per symbol (hop of 256
+    samples at the dataset's sample rate), `focus_rate` and `feasible`.  None: nothing of this runs."""
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
@@ -74,8 +99,8 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         assert len(vals) == n_ctl, f"--controls needs {n_ctl} comma-separated values"
         kw["controls"] = torch.tensor([vals] * len(texts), dtype=torch.float32, device=dev)
     with torch.no_grad():
-        _, post, gates, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                  attention_window=model.attention_window, forward_attention=model.forward_attention, **kw)
+        _, post, gates, align = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
+                                      attention_window=model.attention_window, forward_attention=model.forward_attention, **kw)
     post = post.cpu().numpy()
     # run/say.py:155,161 keeps mel_spectrogram_post[:, :-1]: all emitted frames but the last.  The stop frame itself is already
     # masked (gate -1000 from `lengths` on), so an utterance that stopped keeps its `lengths` = n - 1 frames; one that ran into
@@ -83,6 +108,8 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     valid = (gates.cpu().numpy()[:, :, 0] != -1000.0).sum(1)
     n_emitted = post.shape[1]
     mels = [post[b, :max(min(int(valid[b]), n_emitted - 1), 1)] for b in range(len(texts))]
+    if durations_out is not None:
+        write_durations(durations_out, model, enc, texts, align, lens, [len(m) for m in mels], int(pre.get("sample_rate", 22050)))
     if hifi_gan_checkpoint is not None:
         # run/say.py:66-86,153-159: generator(mel_post[:, :-1].swapaxes(1, 2)) -> waveform, written as audio whatever the name
         from ..hifigan import Generator
