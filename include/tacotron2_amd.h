@@ -465,8 +465,10 @@ int t2_loss_terms(const float* mels, const float* post, const float* gates, cons
  * loss is accumulated in double into ONE device double; sigma > 0, alpha >= 0 (customary: 0.4, 1.0). */
 int t2_guided_attn(const float* align, const int32_t* chars_len, const int32_t* mel_len, int B, int T, int L, float sigma,
                    float alpha, double* loss, float* dalign, float grad_scale, void* stream);
-/* Reduction factor r >= 2 (a decoder step emits r consecutive mel frames; S = ceil(T / r) steps for T frames): the grouped forms of
- * the boundary kernels above.  A step's projection row is [r*M + 1] wide: column j*M + m is mel bin m of frame s*r + j, column r*M
+/* Reduction factor r >= 1 (a decoder step emits r consecutive mel frames; S = ceil(T / r) steps for T frames): the boundary kernels
+ * above with a run-time r.  Each operation has ONE kernel body; the entry points without the suffix run it with r = 1 as a constant,
+ * and so do these when r == 1 - their results are then those of the entry point above, bit for bit.  r <= 0 is refused (rc = 1), and so
+ * is B, T or M < 1, at r == 1 too (the entry points without the suffix do not check that).  A step's projection row is [r*M + 1] wide: column j*M + m is mel bin m of frame s*r + j, column r*M
  * the step's ONE stop logit.  Frames at or beyond T of the last step are dropped (forward) / get a zero gradient (backward).
  *   t2_mel_to_tm_r     (B,T,M) -> [S+1][B][M]: slot 0 = 0, slot s = frame r*s - 1, the LAST frame of the previous group (0 where r*s - 1 >= T:
  *                      only slot S, which no step reads)
@@ -553,10 +555,11 @@ int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream);
  * out2 = {frames emitted n, 0} */
 typedef struct { const float* proj[64]; int Bg[64]; int ngroups; int64_t ld_proj; int M, nframes; } T2StopScan;
 int t2_stop_scan(const T2StopScan* s, int64_t* lengths, int32_t* out2, void* stream);
-/* With a reduction factor r >= 2 the decode loop runs unchanged on steps: T2Infer.M = r * num_mels, the first prenet layer folded
+/* With a reduction factor r the decode loop runs unchanged on steps: T2Infer.M = r * num_mels, the first prenet layer folded
  * onto the LAST block of the projection (W_comb = [W_pre1 . W_mel[(r-1)M : rM] ; W_mel ; W_gate], b_comb and row_comb alike), Tcap
- * and align in steps.  t2_stop_scan_r applies the count rule to the `nframes` stored STEPS (T2StopScan.M = r * num_mels):
- * lengths [sum Bg] = min(r * counted steps, max_len) frames, out2 = {frames emitted = min(r * steps, max_len), steps emitted}. */
+ * and align in steps.  t2_stop_scan_r (r >= 1, max_len >= 1) applies the count rule to the `nframes` stored STEPS (T2StopScan.M =
+ * r * num_mels): lengths [sum Bg] = min(r * counted steps, max_len) frames, out2 = {frames emitted = min(r * steps, max_len), steps
+ * emitted}.  At r = 1 that is t2_stop_scan's result cut at max_len, with the steps in out2[1]. */
 int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -333,14 +333,24 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const float* x, long ld, l
     }
 }
 
-// (B,T,M) batch-major -> [T+1][B][M] time-major with a zero frame at slot 0 (F.pad(mel,(0,0,1,0)), model/tacotron2.py:255)
-__global__ void mel_to_tm_kernel(const float* mel, float* out, int B, int T, int M) {
-    const long n = (long)(T + 1) * B * M;
+// ---- the frame / step boundary (include/tacotron2_amd.h, "Reduction factor") ----------------------------------------------------
+// A decoder step emits r consecutive frames: S = ceil(T / r) steps, a step's projection row [r*M+1] wide - column j*M + m is mel bin
+// m of frame s*r + j, column r*M the step's one stop logit; frames at or beyond T of the last step do not exist.  Each of the kernels
+// at this boundary has ONE body: GROUPED = true takes r and S at run time, GROUPED = false is r = 1 (S = T, s = t, j = 0) as a
+// constant, so the divisions by r, the j*M offsets and the loops over a step's frames fold away.
+
+// Teacher pack (F.pad(mel,(0,0,1,0)), model/tacotron2.py:255): (B,T,M) batch-major -> [S+1][B][M] time-major; slot 0 = 0, slot s =
+// frame r*s - 1 (the LAST frame of the previous group), 0 where r*s - 1 >= T
+template <bool GROUPED>
+__global__ void mel_to_tm_kernel(const float* mel, float* out, int B, int T, int M, int r_, int S_) {
+    const int r = GROUPED ? r_ : 1, S = GROUPED ? S_ : T;
+    const long n = (long)(S + 1) * B * M;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int m = (int)(i % M);
         const long row = i / M;
         const int b = (int)(row % B), s = (int)(row / B);
-        out[i] = s == 0 ? 0.f : mel[((long)b * T + (s - 1)) * M + m];
+        const long t = (long)r * s - 1;         // (slot S of a T that is no multiple of r lies behind the target: zero, never consumed)
+        out[i] = (s == 0 || (GROUPED && t >= T)) ? 0.f : mel[((long)b * T + t) * M + m];      // (r = 1: t = s - 1 < T always)
     }
 }
 
@@ -356,10 +366,12 @@ __global__ void swap01_kernel(const float* in, float* out, int D0, int D1, int C
     }
 }
 
-// proj [T][B][M+1] (time-major, col M = stop logit) -> mels (B,T,M) masked 0, gates (B,T,1) masked -1000,
-// postnet input (B,T+4,M) padded layout holding the UNMASKED mels (model/tacotron2.py:327-345)
+// proj [S][B][ldp] (time-major, col r*M = stop logit) -> mels (B,T,M) masked 0, gates (B,T,1) = the step's logit for each of its
+// frames, masked -1000, postnet input (B,T+4,M) padded layout holding the UNMASKED mels (model/tacotron2.py:327-345)
+template <bool GROUPED>
 __global__ void finalize_fwd_kernel(const float* proj, long ldp, const int32_t* len, float* mels, float* gates, float* post_in,
-                                    int B, int T, int M) {
+                                    int B, int T, int M, int r_) {
+    const int r = GROUPED ? r_ : 1;
     const int Tp = T + 4, M1 = M + 1;
     const long n = (long)B * Tp * M1;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -368,7 +380,8 @@ __global__ void finalize_fwd_kernel(const float* proj, long ldp, const int32_t* 
         const int tp = (int)(row % Tp), b = (int)(row / Tp);
         const int t = tp - 2;
         const bool in = t >= 0 && t < T;
-        const float v = in ? proj[((long)t * B + b) * ldp + m] : 0.f;
+        const int s = in ? t / r : 0, j = in ? t - s * r : 0;
+        const float v = in ? proj[((long)s * B + b) * ldp + (m < M ? j * M + m : r * M)] : 0.f;
         if (m < M) {
             if (post_in) post_in[((long)b * Tp + tp) * M + m] = v;
             if (in) mels[((long)b * T + t) * M + m] = (t >= len[b]) ? 0.f : v;
@@ -381,38 +394,55 @@ __global__ void finalize_fwd_kernel(const float* proj, long ldp, const int32_t* 
 // Loss (model/tts_model.py:197-201) and its gradient in one pass.
 //   loss = mean BCEWithLogits(gates, gate_tgt) + mean (mels - tgt)^2 + mean (post - tgt)^2   (padding included)
 // Gradients are w.r.t. the UNDERLYING (pre-masking) tensors: masked positions are constants -> zero gradient.
-//   d_post (B,T,M) dense;  dproj [T][B][M+1] time-major gets d_mels + d_post in cols < M and d_gate in col M.
+//   d_post, d_mels (B,T,M) and d_gates (B,T) dense;  dproj [S][B][r*M+1] time-major gets d_mels + d_post in the mel columns (zero in
+//   the columns of frames >= T) and the stop-logit gradient in column r*M: the sum over the step's frames below T and below len[b],
+//   formed by the ONE thread that owns the (b, s) pair - no atomics.  Each of the four is optional.
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void loss_kernel(const float* mels, const float* post, const float* gates, const float* mel_tgt,
-                                                   const float* gate_tgt, const int32_t* len, int B, int T, int M,
-                                                   double* loss3, float* d_post, float* dproj, float gscale,
-                                                   float* d_mels = nullptr, float* d_gates = nullptr) {
+                                                   const float* gate_tgt, const int32_t* len, int B, int T, int M, int r_, int S_,
+                                                   double* loss3, float* d_post, float* dproj, float gscale, float* d_mels,
+                                                   float* d_gates) {
     __shared__ double red[3][4];
+    const int r = GROUPED ? r_ : 1, S = GROUPED ? S_ : T;
     const long nm = (long)B * T * M, ng = (long)B * T;
+    const long nv = (long)B * S * r * M, ns = (long)B * S;       // virtual frames S*r >= T; one gate entry per step
+    const long ldq = (long)r * M + 1;
     const float sm = 1.f / (float)nm, sg = 1.f / (float)ng;
     double a_g = 0, a_m = 0, a_p = 0;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nm + ng; i += (long)gridDim.x * blockDim.x) {
-        if (i < nm) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv + ns; i += (long)gridDim.x * blockDim.x) {
+        if (i < nv) {
             const int m = (int)(i % M);
             const long row = i / M;
-            const int t = (int)(row % T), b = (int)(row / T);
-            const bool masked = t >= len[b];
-            const float tg = mel_tgt[i];
-            const float e1 = mels[i] - tg, e2 = post[i] - tg;
-            a_m += (double)e1 * e1; a_p += (double)e2 * e2;
-            const float g1 = masked ? 0.f : 2.f * e1 * sm * gscale;
-            const float g2 = masked ? 0.f : 2.f * e2 * sm * gscale;
-            if (d_post) d_post[i] = g2;
-            if (d_mels) d_mels[i] = g1;
-            if (dproj) dproj[((long)t * B + b) * (M + 1) + m] = g1 + g2;
+            const int tv = (int)(row % ((long)S * r)), b = (int)(row / ((long)S * r));
+            const int s = tv / r, j = tv - s * r;
+            float g = 0.f;
+            if (tv < T) {
+                const long k = ((long)b * T + tv) * M + m;
+                const bool masked = tv >= len[b];
+                const float tg = mel_tgt[k];
+                const float e1 = mels[k] - tg, e2 = post[k] - tg;
+                a_m += (double)e1 * e1; a_p += (double)e2 * e2;
+                const float g1 = masked ? 0.f : 2.f * e1 * sm * gscale;
+                const float g2 = masked ? 0.f : 2.f * e2 * sm * gscale;
+                if (d_post) d_post[k] = g2;
+                if (d_mels) d_mels[k] = g1;
+                g = g1 + g2;
+            }
+            if (dproj) dproj[((long)s * B + b) * ldq + (long)j * M + m] = g;
         } else {
-            const long r = i - nm;
-            const int t = (int)(r % T), b = (int)(r / T);
-            const bool masked = t >= len[b];
-            const float x = gates[r], y = gate_tgt[r];
-            a_g += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
-            const float g = masked ? 0.f : (t2_sigmoid(x) - y) * sg * gscale;
-            if (dproj) dproj[((long)t * B + b) * (M + 1) + M] = g;
-            if (d_gates) d_gates[r] = g;
+            const long q = i - nv;
+            const int s = (int)(q % S), b = (int)(q / S);
+            float gsum = 0.f;
+            for (int j = 0; j < r; ++j) {
+                const int t = s * r + j;
+                if (t >= T) break;
+                const float x = gates[(long)b * T + t], y = gate_tgt[(long)b * T + t];
+                a_g += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
+                const float g = t >= len[b] ? 0.f : (t2_sigmoid(x) - y) * sg * gscale;
+                if (d_gates) d_gates[(long)b * T + t] = g;
+                gsum = GROUPED ? gsum + g : g;       // (r = 1: the value itself, a signed zero included)
+            }
+            if (dproj) dproj[((long)s * B + b) * ldq + (long)r * M] = gsum;
         }
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -460,138 +490,13 @@ __global__ __launch_bounds__(256) void guided_attn_kernel(const float* align, co
     if (threadIdx.x == 0) atomicAdd(loss, red[0] + red[1] + red[2] + red[3]);
 }
 
-// Arbitrary upstream gradients (autograd path) -> the two tensors backward_tf consumes.  Masked positions are constants
-// (masked_fill, model/tacotron2.py:343-345) so their gradient is dropped.
+// Arbitrary upstream gradients (autograd path) -> the two tensors backward_tf consumes: d_post_out (B,T,M) and dproj [S][B][r*M+1].
+// Masked positions are constants (masked_fill, model/tacotron2.py:343-345) so their gradient is dropped; the step's stop-logit
+// gradient is the sum of d_gates over its unmasked frames below T, by the thread that owns (b, s)
+template <bool GROUPED>
 __global__ void outgrad_pack_kernel(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,
-                                    float* d_post_out, float* dproj, int B, int T, int M) {
-    const long n = (long)B * T * (M + 1);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int m = (int)(i % (M + 1));
-        const long row = i / (M + 1);
-        const int t = (int)(row % T), b = (int)(row / T);
-        const bool masked = t >= len[b];
-        if (m < M) {
-            const long j = row * M + m;
-            const float g1 = (masked || !d_mels) ? 0.f : d_mels[j];
-            const float g2 = (masked || !d_post) ? 0.f : d_post[j];
-            d_post_out[j] = g2;
-            dproj[((long)t * B + b) * (M + 1) + m] = g1 + g2;
-        } else {
-            dproj[((long)t * B + b) * (M + 1) + M] = (masked || !d_gates) ? 0.f : d_gates[row];
-        }
-    }
-}
-
-// Gradient of finalize + postnet residual: dproj[t][b][m] += dpost_in[b][t][m]  (dpost_in in shifted rows b*Tp + t)
-__global__ void finalize_bwd_kernel(const float* dpost_in, float* dproj, int B, int T, int M) {
-    const int Tp = T + 4;
-    const long n = (long)B * T * M;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int m = (int)(i % M);
-        const long row = i / M;
-        const int t = (int)(row % T), b = (int)(row / T);
-        dproj[((long)t * B + b) * (M + 1) + m] += dpost_in[((long)b * Tp + t) * M + m];
-    }
-}
-
-// ---- reduction factor r > 1: a decoder step emits r consecutive frames (include/tacotron2_amd.h, "Reduction factor") ------------
-// The grouped forms of the boundary kernels above.  A step's projection row is [S][B][r*M+1]: column j*M + m is mel bin m of frame
-// s*r + j, column r*M the step's one stop logit; S = ceil(T / r), frames at or beyond T of the last step do not exist.
-
-// Teacher pack: (B,T,M) -> [S+1][B][M]; slot 0 = 0, slot s = frame r*s - 1 (the LAST frame of the previous group), 0 where r*s - 1 >= T
-__global__ void mel_to_tm_r_kernel(const float* mel, float* out, int B, int T, int M, int r, int S) {
-    const long n = (long)(S + 1) * B * M;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int m = (int)(i % M);
-        const long row = i / M;
-        const int b = (int)(row % B), s = (int)(row / B);
-        const long t = (long)r * s - 1;         // (slot S of a T that is no multiple of r lies behind the target: zero, never consumed)
-        out[i] = (s == 0 || t >= T) ? 0.f : mel[((long)b * T + t) * M + m];
-    }
-}
-
-// proj [S][B][ldp] -> mels (B,T,M) masked 0, gates (B,T,1) = the step's logit for each of its frames, masked -1000, postnet input
-// (B,T+4,M) padded layout holding the unmasked mels
-__global__ void finalize_fwd_r_kernel(const float* proj, long ldp, const int32_t* len, float* mels, float* gates, float* post_in,
-                                      int B, int T, int M, int r) {
-    const int Tp = T + 4, M1 = M + 1;
-    const long n = (long)B * Tp * M1;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int m = (int)(i % M1);
-        const long row = i / M1;
-        const int tp = (int)(row % Tp), b = (int)(row / Tp);
-        const int t = tp - 2;
-        const bool in = t >= 0 && t < T;
-        const int s = in ? t / r : 0, j = in ? t - s * r : 0;
-        const float v = in ? proj[((long)s * B + b) * ldp + (m < M ? j * M + m : r * M)] : 0.f;
-        if (m < M) {
-            if (post_in) post_in[((long)b * Tp + tp) * M + m] = v;
-            if (in) mels[((long)b * T + t) * M + m] = (t >= len[b]) ? 0.f : v;
-        } else if (in) {
-            gates[(long)b * T + t] = (t >= len[b]) ? -1000.f : v;
-        }
-    }
-}
-
-// Loss and its gradient, grouped: the three sums and d_post as loss_kernel; dproj [S][B][r*M+1] in the grouped layout (zero in the
-// columns of frames >= T).  The stop-logit gradient of a step is the sum over its frames below T and below len[b], formed by the
-// ONE thread that owns the (b, s) pair - no atomics.
-__global__ __launch_bounds__(256) void loss_r_kernel(const float* mels, const float* post, const float* gates, const float* mel_tgt,
-                                                     const float* gate_tgt, const int32_t* len, int B, int T, int M, int r, int S,
-                                                     double* loss3, float* d_post, float* dproj, float gscale) {
-    __shared__ double red[3][4];
-    const long nm = (long)B * T * M, ng = (long)B * T;
-    const long nv = (long)B * S * r * M, ns = (long)B * S;       // virtual frames S*r >= T; one gate entry per step
-    const long ldq = (long)r * M + 1;
-    const float sm = 1.f / (float)nm, sg = 1.f / (float)ng;
-    double a_g = 0, a_m = 0, a_p = 0;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv + ns; i += (long)gridDim.x * blockDim.x) {
-        if (i < nv) {
-            const int m = (int)(i % M);
-            const long row = i / M;
-            const int tv = (int)(row % ((long)S * r)), b = (int)(row / ((long)S * r));
-            const int s = tv / r, j = tv - s * r;
-            float g = 0.f;
-            if (tv < T) {
-                const long k = ((long)b * T + tv) * M + m;
-                const bool masked = tv >= len[b];
-                const float tg = mel_tgt[k];
-                const float e1 = mels[k] - tg, e2 = post[k] - tg;
-                a_m += (double)e1 * e1; a_p += (double)e2 * e2;
-                const float g1 = masked ? 0.f : 2.f * e1 * sm * gscale;
-                const float g2 = masked ? 0.f : 2.f * e2 * sm * gscale;
-                d_post[k] = g2;
-                g = g1 + g2;
-            }
-            dproj[((long)s * B + b) * ldq + (long)j * M + m] = g;
-        } else {
-            const long q = i - nv;
-            const int s = (int)(q % S), b = (int)(q / S);
-            float gsum = 0.f;
-            for (int j = 0; j < r; ++j) {
-                const int t = s * r + j;
-                if (t >= T) break;
-                const float x = gates[(long)b * T + t], y = gate_tgt[(long)b * T + t];
-                a_g += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
-                if (t < len[b]) gsum += (t2_sigmoid(x) - y) * sg * gscale;
-            }
-            dproj[((long)s * B + b) * ldq + (long)r * M] = gsum;
-        }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    a_g = t2_wave_sum_d(a_g); a_m = t2_wave_sum_d(a_m); a_p = t2_wave_sum_d(a_p);
-    if (lane == 0) { red[0][w] = a_g; red[1][w] = a_m; red[2][w] = a_p; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const double s = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-        atomicAdd(&loss3[threadIdx.x], s / (threadIdx.x == 0 ? (double)ng : (double)nm));
-    }
-}
-
-// Upstream gradients (autograd path), grouped: d_post_out (B,T,M) and dproj [S][B][r*M+1]; the step's stop-logit gradient is the sum
-// of d_gates over its unmasked frames below T, by the thread that owns (b, s)
-__global__ void outgrad_pack_r_kernel(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,
-                                      float* d_post_out, float* dproj, int B, int T, int M, int r, int S) {
+                                    float* d_post_out, float* dproj, int B, int T, int M, int r_, int S_) {
+    const int r = GROUPED ? r_ : 1, S = GROUPED ? S_ : T;
     const long nv = (long)B * S * r * M, ns = (long)B * S;
     const long ldq = (long)r * M + 1;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv + ns; i += (long)gridDim.x * blockDim.x) {
@@ -618,15 +523,18 @@ __global__ void outgrad_pack_r_kernel(const float* d_mels, const float* d_post, 
                 for (int j = 0; j < r; ++j) {
                     const int t = s * r + j;
                     if (t >= T || t >= len[b]) break;
-                    gsum += d_gates[(long)b * T + t];
+                    gsum = GROUPED ? gsum + d_gates[(long)b * T + t] : d_gates[(long)b * T + t];
                 }
             dproj[((long)s * B + b) * ldq + (long)r * M] = gsum;
         }
     }
 }
 
-// Gradient of the grouped finalize + postnet residual: dproj[s][b][j*M + m] += dpost_in[b][s*r + j][m]  (frames below T only)
-__global__ void finalize_bwd_r_kernel(const float* dpost_in, float* dproj, int B, int T, int M, int r) {
+// Gradient of finalize + postnet residual: dproj[s][b][j*M + m] += dpost_in[b][s*r + j][m]  (dpost_in in shifted rows b*Tp + t;
+// frames below T only)
+template <bool GROUPED>
+__global__ void finalize_bwd_kernel(const float* dpost_in, float* dproj, int B, int T, int M, int r_) {
+    const int r = GROUPED ? r_ : 1;
     const int Tp = T + 4;
     const long n = (long)B * T * M;
     const long ldq = (long)r * M + 1;
@@ -929,7 +837,7 @@ extern "C" int t2_colsum(const float* x, int64_t ld, int64_t R, int C, float* ou
 extern "C" int t2_mel_to_tm(const float* mel, float* out, int B, int T, int M, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(mel && out, "t2_mel_to_tm: null");
-    hipLaunchKernelGGL(mel_to_tm_kernel, dim3(ew_grid((long)(T + 1) * B * M)), dim3(256), 0, ST, mel, out, B, T, M);
+    hipLaunchKernelGGL(mel_to_tm_kernel<false>, dim3(ew_grid((long)(T + 1) * B * M)), dim3(256), 0, ST, mel, out, B, T, M, 1, T);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_swap01(const float* in, float* out, int D0, int D1, int C, int accumulate, void* stream) {
@@ -942,8 +850,8 @@ extern "C" int t2_finalize_fwd(const float* proj, int64_t ld_proj, const int32_t
                                int B, int T, int M, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(proj && len && mels && gates, "t2_finalize_fwd: null");
-    hipLaunchKernelGGL(finalize_fwd_kernel, dim3(ew_grid((long)B * (T + 4) * (M + 1))), dim3(256), 0, ST, proj, (long)ld_proj, len, mels, gates,
-                       post_in, B, T, M);
+    hipLaunchKernelGGL(finalize_fwd_kernel<false>, dim3(ew_grid((long)B * (T + 4) * (M + 1))), dim3(256), 0, ST, proj, (long)ld_proj, len,
+                       mels, gates, post_in, B, T, M, 1);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_loss_fwd_bwd(const float* mels, const float* post, const float* gates, const float* mel_tgt,
@@ -952,8 +860,8 @@ extern "C" int t2_loss_fwd_bwd(const float* mels, const float* post, const float
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(mels && post && gates && mel_tgt && gate_tgt && len && loss3, "t2_loss_fwd_bwd: null");
     (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
-    hipLaunchKernelGGL(loss_kernel, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt, gate_tgt,
-                       len, B, T, M, loss3, d_post, dproj, grad_scale);
+    hipLaunchKernelGGL(loss_kernel<false>, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt, gate_tgt,
+                       len, B, T, M, 1, T, loss3, d_post, dproj, grad_scale, (float*)nullptr, (float*)nullptr);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_loss_terms(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
@@ -962,8 +870,8 @@ extern "C" int t2_loss_terms(const float* mels, const float* post, const float* 
     (void)hipGetLastError();
     T2_REQUIRE(mels && post && gates && mel_tgt && gate_tgt && len && loss3, "t2_loss_terms: null");
     (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
-    hipLaunchKernelGGL(loss_kernel, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt, gate_tgt,
-                       len, B, T, M, loss3, d_post, (float*)nullptr, grad_scale, d_mels, d_gates);
+    hipLaunchKernelGGL(loss_kernel<false>, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt, gate_tgt,
+                       len, B, T, M, 1, T, loss3, d_post, (float*)nullptr, grad_scale, d_mels, d_gates);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_guided_attn(const float* align, const int32_t* chars_len, const int32_t* mel_len, int B, int T, int L, float sigma,
@@ -982,25 +890,26 @@ extern "C" int t2_outgrad_pack(const float* d_mels, const float* d_post, const f
                                float* d_post_out, float* dproj, int B, int T, int M, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(len && d_post_out && dproj, "t2_outgrad_pack: null");
-    hipLaunchKernelGGL(outgrad_pack_kernel, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, d_mels, d_post, d_gates, len,
-                       d_post_out, dproj, B, T, M);
+    hipLaunchKernelGGL(outgrad_pack_kernel<false>, dim3(ew_grid((long)B * T * (M + 1))), dim3(256), 0, ST, d_mels, d_post, d_gates, len,
+                       d_post_out, dproj, B, T, M, 1, T);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_finalize_bwd(const float* dpost_in, float* dproj, int B, int T, int M, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(dpost_in && dproj, "t2_finalize_bwd: null");
-    hipLaunchKernelGGL(finalize_bwd_kernel, dim3(ew_grid((long)B * T * M)), dim3(256), 0, ST, dpost_in, dproj, B, T, M);
+    hipLaunchKernelGGL(finalize_bwd_kernel<false>, dim3(ew_grid((long)B * T * M)), dim3(256), 0, ST, dpost_in, dproj, B, T, M, 1);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
-// grouped boundary kernels (reduction factor r >= 2; r = 1 is the entry points above)
+// the same kernels with a reduction factor r >= 1: r = 1 is the entry point above (the constant-r instantiation), after this entry's checks
 #define T2_REQUIRE_GROUPED(name) \
-    T2_REQUIRE(B >= 1 && T >= 1 && M >= 1 && r >= 2 && (long)((T + r - 1) / r) * r < (1L << 31), name ": need B, T, M >= 1 and r >= 2")
+    T2_REQUIRE(B >= 1 && T >= 1 && M >= 1 && r >= 1 && (long)((T + r - 1) / r) * r < (1L << 31), name ": need B, T, M >= 1 and r >= 1")
 extern "C" int t2_mel_to_tm_r(const float* mel, float* out, int B, int T, int M, int r, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(mel && out, "t2_mel_to_tm_r: null");
     T2_REQUIRE_GROUPED("t2_mel_to_tm_r");
+    if (r == 1) return t2_mel_to_tm(mel, out, B, T, M, stream);
     const int S = (T + r - 1) / r;
-    hipLaunchKernelGGL(mel_to_tm_r_kernel, dim3(ew_grid((long)(S + 1) * B * M)), dim3(256), 0, ST, mel, out, B, T, M, r, S);
+    hipLaunchKernelGGL(mel_to_tm_kernel<true>, dim3(ew_grid((long)(S + 1) * B * M)), dim3(256), 0, ST, mel, out, B, T, M, r, S);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_finalize_fwd_r(const float* proj, int64_t ld_proj, const int32_t* len, float* mels, float* gates, float* post_in,
@@ -1009,7 +918,8 @@ extern "C" int t2_finalize_fwd_r(const float* proj, int64_t ld_proj, const int32
     T2_REQUIRE(proj && len && mels && gates, "t2_finalize_fwd_r: null");
     T2_REQUIRE_GROUPED("t2_finalize_fwd_r");
     T2_REQUIRE(ld_proj >= (int64_t)r * M + 1, "t2_finalize_fwd_r: ld_proj < r * M + 1");
-    hipLaunchKernelGGL(finalize_fwd_r_kernel, dim3(ew_grid((long)B * (T + 4) * (M + 1))), dim3(256), 0, ST, proj, (long)ld_proj, len, mels,
+    if (r == 1) return t2_finalize_fwd(proj, ld_proj, len, mels, gates, post_in, B, T, M, stream);
+    hipLaunchKernelGGL(finalize_fwd_kernel<true>, dim3(ew_grid((long)B * (T + 4) * (M + 1))), dim3(256), 0, ST, proj, (long)ld_proj, len, mels,
                        gates, post_in, B, T, M, r);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
@@ -1019,10 +929,11 @@ extern "C" int t2_loss_fwd_bwd_r(const float* mels, const float* post, const flo
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(mels && post && gates && mel_tgt && gate_tgt && len && loss3 && d_post && dproj, "t2_loss_fwd_bwd_r: null");
     T2_REQUIRE_GROUPED("t2_loss_fwd_bwd_r");
+    if (r == 1) return t2_loss_fwd_bwd(mels, post, gates, mel_tgt, gate_tgt, len, B, T, M, loss3, d_post, dproj, grad_scale, stream);
     const int S = (T + r - 1) / r;
     (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
-    hipLaunchKernelGGL(loss_r_kernel, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt,
-                       gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, grad_scale);
+    hipLaunchKernelGGL(loss_kernel<true>, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt,
+                       gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, grad_scale, (float*)nullptr, (float*)nullptr);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_outgrad_pack_r(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,
@@ -1030,8 +941,9 @@ extern "C" int t2_outgrad_pack_r(const float* d_mels, const float* d_post, const
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(len && d_post_out && dproj, "t2_outgrad_pack_r: null");
     T2_REQUIRE_GROUPED("t2_outgrad_pack_r");
+    if (r == 1) return t2_outgrad_pack(d_mels, d_post, d_gates, len, d_post_out, dproj, B, T, M, stream);
     const int S = (T + r - 1) / r;
-    hipLaunchKernelGGL(outgrad_pack_r_kernel, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, d_mels, d_post, d_gates,
+    hipLaunchKernelGGL(outgrad_pack_kernel<true>, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, d_mels, d_post, d_gates,
                        len, d_post_out, dproj, B, T, M, r, S);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
@@ -1039,7 +951,8 @@ extern "C" int t2_finalize_bwd_r(const float* dpost_in, float* dproj, int B, int
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(dpost_in && dproj, "t2_finalize_bwd_r: null");
     T2_REQUIRE_GROUPED("t2_finalize_bwd_r");
-    hipLaunchKernelGGL(finalize_bwd_r_kernel, dim3(ew_grid((long)B * T * M)), dim3(256), 0, ST, dpost_in, dproj, B, T, M, r);
+    if (r == 1) return t2_finalize_bwd(dpost_in, dproj, B, T, M, stream);
+    hipLaunchKernelGGL(finalize_bwd_kernel<true>, dim3(ew_grid((long)B * T * M)), dim3(256), 0, ST, dpost_in, dproj, B, T, M, r);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_relu_mask_bwd(const float* g, const float* y, const float* mask, float* out, int64_t n, void* stream) {

@@ -182,10 +182,14 @@ __global__ void stop_kernel(const float* proj, long ldp, int M, int B, int t, in
 }
 
 // Exact break frame and lengths from the stored stop logits of ALL utterances (several groups: proj_g [n][B_g][ldp]):
-// first[b] = first frame with logit < 0; the loop breaks after frame n* = max_b first[b] (or runs to `nframes` if some
-// utterance never stops); lengths[b] = #{t <= n* : logit[t][b] >= 0}; out2 = {frames emitted, 0}.  One workgroup.
+// first[b] = first row with logit < 0; the loop breaks after row n* = max_b first[b] (or runs to `nframes` if some
+// utterance never stops); counted[b] = #{t <= n* : logit[t][b] >= 0}.  One workgroup.
+//   GROUPED = false: a row is a frame; lengths[b] = counted[b], out2 = {frames emitted n* + 1, 0}.
+//   GROUPED = true : a row is a decoder STEP of r >= 1 frames, column M (= r * num_mels) the step's one stop logit; the count rule
+//                    runs on steps, lengths[b] = min(r * counted[b], max_len) frames, out2 = {min(r * (n* + 1), max_len), n* + 1}.
 struct StopScan { const float* proj[64]; int Bg[64]; int ng; long ldp; int M; int nframes; int64_t* lengths; int32_t* out2; };
-__global__ void stop_scan_kernel(StopScan p) {
+template <bool GROUPED>
+__global__ void stop_scan_kernel(StopScan p, int r, int max_len) {
     __shared__ int nstar;
     if (threadIdx.x == 0) nstar = 0;
     __syncthreads();
@@ -206,43 +210,13 @@ __global__ void stop_scan_kernel(StopScan p) {
         while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
         long cnt = 0;
         for (int t = 0; t < n; ++t) cnt += p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] >= 0.f ? 1 : 0;
+        if (GROUPED) { cnt *= r; cnt = cnt < (long)max_len ? cnt : (long)max_len; }
         p.lengths[bb] = cnt;
-    }
-    if (threadIdx.x == 0) { p.out2[0] = n; p.out2[1] = 0; }
-}
-
-// The same scan with a reduction factor r: `nframes` rows of proj are decoder STEPS of r frames each, column M (= r * num_mels)
-// the step's one stop logit.  The count rule runs on steps; lengths[b] = min(r * counted steps, max_len) frames,
-// out2 = {frames emitted = min(r * (n* + 1), max_len), steps emitted n* + 1}.
-// (A kernel of its own, the two passes written out again: sharing them through __device__ helpers changes the register allocation -
-// the instruction stream - of stop_scan_kernel, which the paths without the option keep.)
-__global__ void stop_scan_r_kernel(StopScan p, int r, int max_len) {
-    __shared__ int nstar;
-    if (threadIdx.x == 0) nstar = 0;
-    __syncthreads();
-    int Btot = 0;
-    for (int g = 0; g < p.ng; ++g) Btot += p.Bg[g];
-    for (int bb = threadIdx.x; bb < Btot; bb += blockDim.x) {
-        int g = 0, b = bb;
-        while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
-        int first = p.nframes - 1;     // never stops: the loop runs to the cap
-        for (int t = 0; t < p.nframes; ++t)
-            if (p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] < 0.f) { first = t; break; }
-        atomicMax(&nstar, first);
-    }
-    __syncthreads();
-    const int n = nstar + 1;
-    for (int bb = threadIdx.x; bb < Btot; bb += blockDim.x) {
-        int g = 0, b = bb;
-        while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
-        long cnt = 0;
-        for (int t = 0; t < n; ++t) cnt += p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] >= 0.f ? 1 : 0;
-        cnt *= r;
-        p.lengths[bb] = cnt < (long)max_len ? cnt : (long)max_len;
     }
     if (threadIdx.x == 0) {
         const long fr = (long)n * r;
-        p.out2[0] = (int)(fr < (long)max_len ? fr : (long)max_len); p.out2[1] = n;
+        p.out2[0] = GROUPED ? (int)(fr < (long)max_len ? fr : (long)max_len) : n;
+        p.out2[1] = GROUPED ? n : 0;
     }
 }
 
@@ -251,7 +225,7 @@ __global__ void stop_scan_r_kernel(StopScan p, int r, int max_len) {
 extern "C" int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(s && lengths && out2 && s->ngroups >= 1 && s->ngroups <= 64 && s->nframes >= 1, "t2_stop_scan_r: bad arguments");
-    T2_REQUIRE(r >= 2 && max_len >= 1 && (long)s->nframes * r < (1L << 31), "t2_stop_scan_r: need r >= 2 and max_len >= 1");
+    T2_REQUIRE(r >= 1 && max_len >= 1 && (long)s->nframes * r < (1L << 31), "t2_stop_scan_r: need r >= 1 and max_len >= 1");
     StopScan p;
     memset(&p, 0, sizeof(p));
     for (int g = 0; g < s->ngroups; ++g) {
@@ -259,7 +233,7 @@ extern "C" int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* 
         p.proj[g] = s->proj[g]; p.Bg[g] = s->Bg[g];
     }
     p.ng = s->ngroups; p.ldp = s->ld_proj; p.M = s->M; p.nframes = s->nframes; p.lengths = lengths; p.out2 = out2;
-    hipLaunchKernelGGL(stop_scan_r_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p, r, max_len);
+    hipLaunchKernelGGL(stop_scan_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, r, max_len);
     T2_CHECK_LAUNCH();
     return T2_OK;
 }
@@ -291,7 +265,7 @@ extern "C" int t2_stop_scan(const T2StopScan* s, int64_t* lengths, int32_t* out2
         p.proj[g] = s->proj[g]; p.Bg[g] = s->Bg[g];
     }
     p.ng = s->ngroups; p.ldp = s->ld_proj; p.M = s->M; p.nframes = s->nframes; p.lengths = lengths; p.out2 = out2;
-    hipLaunchKernelGGL(stop_scan_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(stop_scan_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, 1, 0);
     T2_CHECK_LAUNCH();
     return T2_OK;
 }

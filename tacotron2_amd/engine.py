@@ -786,10 +786,8 @@ class Engine:
         self._wait(side0, main0)
         with torch.cuda.stream(side0):
             mel_tm = self.buf("mel_tm", T + 1, B, M)
-            if r == 1:
-                call("t2_mel_to_tm", mel, mel_tm, B, T, M, _stream())
-            else:             # slot s = frame r*s - 1: the last frame of the previous group (ESPnet's ys[:, r-1::r])
-                call("t2_mel_to_tm_r", mel, mel_tm, B, Tf, M, r, _stream())
+            # slot s = frame r*s - 1: the last frame of the previous group (ESPnet's ys[:, r-1::r])
+            call("t2_mel_to_tm_r", mel, mel_tm, B, Tf, M, r, _stream())
             pd = masks.get("prenet_drop")
             p1 = self.buf("p1", T + 1, B, Pd)
             p2 = self.buf("p2", T + 1, B, Pd)
@@ -946,10 +944,7 @@ class Engine:
         mels = self.out("mels", B, Tf, M)
         gates = self.out("gates", B, Tf, 1)
         post_in = self.buf("post.x0", B, Tf + 4, M)
-        if r == 1:
-            call("t2_finalize_fwd", proj, M + 1, mlen32, mels, gates, post_in, B, T, M, st)
-        else:
-            call("t2_finalize_fwd_r", proj, Mr + 1, mlen32, mels, gates, post_in, B, Tf, M, r, st)
+        call("t2_finalize_fwd_r", proj, Mr + 1, mlen32, mels, gates, post_in, B, Tf, M, r, st)
 
         post = self.out("post", B, Tf, M)
         self.postnet_fwd(post_in, post, mlen32, B, Tf, masks.get("post_drop"), training, ctx)
@@ -1022,8 +1017,8 @@ class Engine:
             raise RuntimeError("backward of a stale forward: the activation stashes of this forward were overwritten by a later "
                                "grad-enabled forward of the same model (one live teacher-forced graph per model; INTEGRATION.md)")
         B, L, Tf = ctx["B"], ctx["L"], ctx["T"]
-        r = ctx.get("r", 1)
-        T = ctx.get("S", Tf)          # decoder steps: what the chains walk; Tf frames at the postnet / finalize boundary only
+        r = ctx["r"]
+        T = ctx["S"]                  # decoder steps: what the chains walk; Tf frames at the postnet / finalize boundary only
         if d_align is not None:
             # the dw kernel indexes it by hand with the strides of the alignments: anything else must not reach it as a pointer
             if not isinstance(d_align, torch.Tensor) or d_align.dtype != torch.float32:
@@ -1069,10 +1064,7 @@ class Engine:
                                   G[f"postnet.postnet.{4 * li}.weight"], None, f"postnet.postnet.{4 * li + 1}", B, Tf,
                                   chans[li], chans[li + 1], 0 if li == 4 else 2, training, defer=post_wgrads)
             Lp_dy = Tf + 4
-        if r == 1:
-            call("t2_finalize_bwd", dy, dproj, B, T, M, st)
-        else:
-            call("t2_finalize_bwd_r", dy, dproj, B, Tf, M, r, st)
+        call("t2_finalize_bwd_r", dy, dproj, B, Tf, M, r, st)
         self.mark("bwd.postnet")
 
         # ---- mel/stop projection ----------------------------------------------------------------------
@@ -1392,8 +1384,7 @@ class Engine:
         the term is off - and loss3 stays the three terms."""
         mels, post, gates, align = outs
         B, T, M = mels.shape
-        r = ctx.get("r", 1)
-        S = ctx.get("S", T)
+        r, S = ctx["r"], ctx["S"]
         guided = check_guided_attention(guided)
         d_align = self.guided_loss = None
         if guided is not None:
@@ -1409,12 +1400,8 @@ class Engine:
         loss3 = self.buf("loss3", 3, dtype=torch.float64)
         d_post = self.buf("d_post", B, T, M)
         dproj = self.buf("dproj", S, B, r * M + 1)
-        if r == 1:
-            call("t2_loss_fwd_bwd", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, loss3, d_post, dproj,
-                 float(grad_scale), _stream())
-        else:
-            call("t2_loss_fwd_bwd_r", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, r, loss3, d_post, dproj,
-                 float(grad_scale), _stream())
+        call("t2_loss_fwd_bwd_r", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, r, loss3, d_post, dproj,
+             float(grad_scale), _stream())
         self.backward_tf(ctx, d_post, dproj, d_align=d_align)
         return loss3
 
@@ -1603,13 +1590,11 @@ class Engine:
         ldo = (M + 1 + 3) // 4 * 4
         scan = make("T2StopScan", proj=[G["proj"] for G in groups] + [0] * (64 - len(groups)),
                     Bg=[G["B"] for G in groups] + [0] * (64 - len(groups)), ngroups=len(groups), ld_proj=ldo, M=M, nframes=t0)
-        if r == 1:
-            call("t2_stop_scan", scan, lengths, nfr, st)
-        else:      # the count rule on steps; lengths and the emitted count n in frames, cut at max_len (nfr[1]: steps)
-            call("t2_stop_scan_r", scan, r, max_len, lengths, nfr, st)
+        # the count rule on steps; lengths and the emitted count n in frames, cut at max_len (nfr[1]: steps)
+        call("t2_stop_scan_r", scan, r, max_len, lengths, nfr, st)
         nfr_h = nfr.cpu()
         n = max(int(nfr_h[0]), 1)
-        ns = n if r == 1 else max(int(nfr_h[1]), 1)
+        ns = max(int(nfr_h[1]), 1)
         self.check_persistent_kernels()      # (the encoder recurrence is a persistent launch; the host has just synchronised anyway)
         # outputs: mask by the counted lengths, postnet on the unmasked mels (model/tacotron2.py:327-345)
         mlen32 = lengths.to(torch.int32)
@@ -1618,12 +1603,8 @@ class Engine:
         post_in = self.buf("post.x0", B, n + 4, M0)
         for G, b0 in zip(groups, range(0, B, 64)):
             Bg = G["B"]
-            if r == 1:
-                call("t2_finalize_fwd", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
-                     post_in[b0:b0 + Bg], Bg, n, M, st)
-            else:
-                call("t2_finalize_fwd_r", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
-                     post_in[b0:b0 + Bg], Bg, n, M0, r, st)
+            call("t2_finalize_fwd_r", G["proj"], ldo, mlen32[b0:b0 + Bg], mels[b0:b0 + Bg], gates[b0:b0 + Bg],
+                 post_in[b0:b0 + Bg], Bg, n, M0, r, st)
         post = self.out("inf.post", B, n, M0)
         self.postnet_fwd(post_in, post, mlen32, B, n, None, training, {})
         align = groups[0]["align"][:, :ns] if len(groups) == 1 else torch.cat([G["align"][:, :ns] for G in groups])

@@ -72,13 +72,11 @@ class _TacotronFn(torch.autograd.Function):
         ps = model.store
         B, T, M = ectx["B"], ectx["T"], model.num_mels
         f = lambda g: g.contiguous().float() if g is not None else None
-        r, S = ectx.get("r", 1), ectx.get("S", T)
+        r, S = ectx["r"], ectx["S"]
         d_post_m = eng.buf("ag.d_post", B, T, M)
         dproj = eng.buf("ag.dproj", S, B, r * M + 1)
-        if r == 1:
-            call("t2_outgrad_pack", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, _stream())
-        else:      # grouped layout [S][B][r*M+1]; a step's stop-logit gradient is the sum over its frames
-            call("t2_outgrad_pack_r", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, r, _stream())
+        # grouped layout [S][B][r*M+1]; a step's stop-logit gradient is the sum over its frames
+        call("t2_outgrad_pack_r", f(d_mels), f(d_post), f(d_gates), ectx["mlen32"], d_post_m, dproj, B, T, M, r, _stream())
         ps.grad.zero_()
         eng.backward_tf(ectx, d_post_m, dproj, d_align=f(d_align))
         grads = tuple(ps.G[name] for name in model._param_names)

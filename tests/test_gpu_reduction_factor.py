@@ -1,6 +1,7 @@
 """Reduction factor (r mel frames per decoder step) on the GPU: the grouped boundary kernels through the C ABI against a few lines
-of torch, the engine's training step and decode loop against the float64 restatement (tests/reduction_ref.py), guard bands, the
-composition with forward and guided attention, r = 1 against an engine without the key, and the module / trainer / CLI surface."""
+of torch (at r = 1 also bit for bit against the entry points without the suffix), the engine's training step and decode loop
+against the float64 restatement (tests/reduction_ref.py), guard bands, the composition with forward and guided attention, r = 1
+against an engine without the key, and the module / trainer / CLI surface."""
 import functools
 import json
 import os
@@ -34,7 +35,7 @@ def _st():
 # ---------------------------------------------------------------------------------------------------------------------------
 # boundary kernels through the C ABI
 # ---------------------------------------------------------------------------------------------------------------------------
-KERNEL_CASES = [(5, 2), (7, 3), (8, 2), (1, 2)]
+KERNEL_CASES = [(5, 2), (7, 3), (8, 2), (1, 2), (5, 1), (1, 1)]
 B_K, M_K = 3, 80
 
 
@@ -47,9 +48,9 @@ def _behind_nan(t, dev):
 
 
 def _kernel_lens(T, r):
-    """0, a length in the middle of a group (or 1 when T = 1), and T."""
+    """0, a length in the middle of a group (or 1 when T = 1; r = 1 has no middle), and T."""
     mid = min(T, r + 1) if r + 1 < T else max(T - 1, 1)
-    assert T == 1 or mid % r != 0
+    assert T == 1 or r == 1 or mid % r != 0
     return torch.tensor([0, mid, T], dtype=torch.int32)
 
 
@@ -69,6 +70,10 @@ def test_teacher_pack_and_finalize_move_the_right_elements(T, r):
         if src is not None:
             want[s] = mel[:, src]
     assert torch.equal(out.cpu(), want)
+    if r == 1:       # the entry point without the suffix on the same inputs: the same bits (here and below)
+        out1 = torch.full((T + 1, B, M), 7.0, device=dev)
+        _lib.call("t2_mel_to_tm", _behind_nan(mel, dev), out1, B, T, M, _st())
+        assert torch.equal(out1, out)
     # finalize forward
     ld = r * M + 1
     proj = torch.randn(S, B, ld, generator=g)
@@ -82,6 +87,10 @@ def test_teacher_pack_and_finalize_move_the_right_elements(T, r):
     assert torch.equal(gates.cpu()[:, :, 0], lg.masked_fill(mm, -1000.0))
     assert torch.equal(post_in.cpu()[:, 2:T + 2], fr) and float(post_in.cpu()[:, :2].abs().max()) == 0.0 \
         and float(post_in.cpu()[:, T + 2:].abs().max()) == 0.0
+    if r == 1:
+        mels1, gates1, post_in1 = torch.full_like(mels, 7.0), torch.full_like(gates, 7.0), torch.full_like(post_in, 7.0)
+        _lib.call("t2_finalize_fwd", _behind_nan(proj, dev), ld, _behind_nan(lens, dev), mels1, gates1, post_in1, B, T, M, _st())
+        assert torch.equal(mels1, mels) and torch.equal(gates1, gates) and torch.equal(post_in1, post_in)
     # finalize backward: its transpose, accumulating; the columns of frames >= T and the gate column stay
     dpost = torch.randn(B, T + 4, M, generator=g)
     base = torch.randn(S, B, ld, generator=g)
@@ -91,6 +100,10 @@ def test_teacher_pack_and_finalize_move_the_right_elements(T, r):
     for t in range(T):
         want[t // r, :, (t % r) * M:(t % r + 1) * M] += dpost[:, t]          # (shifted rows b*Tp + t: row t of the padded layout)
     assert torch.equal(dproj.cpu(), want)
+    if r == 1:
+        dproj1 = base.clone().to(dev)
+        _lib.call("t2_finalize_bwd", _behind_nan(dpost, dev), dproj1, B, T, M, _st())
+        assert torch.equal(dproj1, dproj)
 
 
 @pytest.mark.parametrize("T,r", KERNEL_CASES)
@@ -115,6 +128,11 @@ def test_outgrad_pack_sums_the_stop_logit_gradient_over_the_group(T, r):
             if s * r + j < T:
                 want[s, :, r * M] += (dg * live)[:, s * r + j, 0]
     assert torch.equal(d_post_out.cpu(), want_post) and torch.equal(dproj.cpu(), want)
+    if r == 1:       # the entry point without the suffix on the same inputs: the same bits
+        d_post_out1, dproj1 = torch.full_like(d_post_out, 7.0), torch.full_like(dproj, 7.0)
+        _lib.call("t2_outgrad_pack", _behind_nan(dm, dev), _behind_nan(dp, dev), _behind_nan(dg, dev), _behind_nan(lens, dev),
+                  d_post_out1, dproj1, B, T, M, _st())
+        assert torch.equal(d_post_out1, d_post_out) and torch.equal(dproj1, dproj)
     # the optional operands
     _lib.call("t2_outgrad_pack_r", None, _behind_nan(dp, dev), None, _behind_nan(lens, dev), d_post_out, dproj, B, T, M, r, _st())
     assert float(dproj.cpu()[:, :, r * M].abs().max()) == 0.0
@@ -162,21 +180,45 @@ def test_grouped_loss_kernel_matches_torch(T, r):
         for s in range(S):
             if s * r >= int(lens[b]):
                 assert float(gcol[s, b]) == 0.0
-    # the r = 1 kernel on the same frames agrees on the three sums (one logit per frame there)
+    # the r = 1 entry point on the same frames agrees on the three sums (one logit per frame there; double atomics: 1e-12), and at
+    # r = 1, where it has the same inputs, on every bit of d_post and dproj
     loss1 = torch.empty(3, dtype=torch.float64, device=dev)
+    d_post1 = torch.full((B, T, M), 7.0, device=dev); dproj1 = torch.full((T, B, M + 1), 7.0, device=dev)
     _lib.call("t2_loss_fwd_bwd", mels.to(dev), post.to(dev), gates.to(dev), tgt.to(dev), gtgt.to(dev), lens.to(dev), B, T, M, loss1,
-              torch.empty(B, T, M, device=dev), torch.empty(T, B, M + 1, device=dev), 1.0, _st())
+              d_post1, dproj1, 1.0, _st())
     assert torch.allclose(loss1.cpu(), l3, rtol=1e-12, atol=0)
+    if r == 1:
+        assert torch.equal(d_post1, d_post) and torch.equal(dproj1, dproj)
 
 
 def test_grouped_entries_reject_r_below_2():
+    """The contract of the six `_r` entries, which was r >= 2 (hence the name) and is r >= 1.  r = 0 and r = -1 are refused with rc = 1 before anything is launched (every
+    output keeps its fill); r = 1 is accepted."""
     from tacotron2_amd import _lib
     dev = _dev()
-    x = torch.zeros(64, device=dev)
-    with pytest.raises(_lib.T2Error, match="rc=1"):
-        _lib.call("t2_mel_to_tm_r", x, x, 1, 4, 4, 1, _st())
-    with pytest.raises(_lib.T2Error, match="rc=1"):
-        _lib.call("t2_finalize_bwd_r", x, x, 1, 4, 4, 0, _st())
+    B, T, M = 1, 4, 4
+    x = torch.zeros(256, device=dev)
+    lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+    outs = [torch.full((256,), 7.0, device=dev) for _ in range(3)]
+    loss3 = torch.full((3,), 7.0, dtype=torch.float64, device=dev)
+    lengths = torch.full((B,), -7, dtype=torch.int64, device=dev)
+    out2 = torch.full((2,), -7, dtype=torch.int32, device=dev)
+    scan = _lib.make("T2StopScan", proj=[x] + [0] * 63, Bg=[B] + [0] * 63, ngroups=1, ld_proj=M + 1, M=M, nframes=T)
+    for r in (0, -1):
+        for name, args in (("t2_mel_to_tm_r", (x, outs[0], B, T, M, r)),
+                           ("t2_finalize_fwd_r", (x, M + 1, lens, outs[0], outs[1], outs[2], B, T, M, r)),
+                           ("t2_finalize_bwd_r", (x, outs[0], B, T, M, r)),
+                           ("t2_outgrad_pack_r", (x, x, x, lens, outs[0], outs[1], B, T, M, r)),
+                           ("t2_loss_fwd_bwd_r", (x, x, x, x, x, lens, B, T, M, r, loss3, outs[0], outs[1], 1.0)),
+                           ("t2_stop_scan_r", (scan, r, 100, lengths, out2))):
+            with pytest.raises(_lib.T2Error, match="rc=1"):
+                _lib.call(name, *args, _st())
+    torch.cuda.synchronize()
+    assert all(bool((o == 7.0).all()) for o in outs) and bool((loss3 == 7.0).all())
+    assert bool((lengths == -7).all()) and bool((out2 == -7).all())
+    _lib.call("t2_mel_to_tm_r", x, outs[0], B, T, M, 1, _st())
+    torch.cuda.synchronize()
+    assert float(outs[0][:(T + 1) * B * M].abs().max()) == 0.0 and bool((outs[0][(T + 1) * B * M:] == 7.0).all())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -469,13 +511,16 @@ def test_stop_scan_r_with_hand_set_logits():
     """Two groups (2 + 3 utterances), 5 stored steps, r = 3, M' = 6, ld_proj = 8, max_len = 13 (no multiple of r), logits set by hand:
     first negative steps (1, 3, never, 0, 2) -> the loop ends after step n* = 4 (someone never stops): 5 steps, min(15, 13) = 13
     frames; counted steps with logit >= 0 among the first 5: (3, 4, 5, 2, 3) -> lengths min(3 x, 13) = (9, 12, 13, 6, 9).  Then without
-    the utterance that never stops: n* = 3, 4 steps, 12 frames, counted among the first 4: (3, 3, 2, 2) -> (9, 9, 6, 6)."""
+    the utterance that never stops: n* = 3, 4 steps, 12 frames, counted among the first 4: (3, 3, 2, 2) -> (9, 9, 6, 6).
+    r = 1 (M' = 2, ld_proj = 4) with the same signs: a step is a frame, so lengths are the counts and out2 = {steps, steps} - what
+    t2_stop_scan gives on the same logits but for its out2[1] = 0 - and a max_len of 3 cuts lengths and the frames emitted, not the steps."""
     from tacotron2_amd import _lib
     dev = _dev()
-    r, Mr, ld, N = 3, 6, 8, 5
+    N = 5
     sign = {0: [1, -1, 1, 1, -1], 1: [1, 1, 1, -1, 1], 2: [1, 1, 1, 1, 1], 3: [-1, 1, -1, 1, -1], 4: [1, 1, -1, -1, 1]}
 
-    def run(utts, groups, max_len):
+    def run(utts, groups, max_len, r=3, plain=False):
+        Mr, ld = 2 * r, 2 * r + 2
         projs, k = [], 0
         for Bg in groups:
             p = torch.full((N, Bg, ld), float("nan"))
@@ -487,7 +532,10 @@ def test_stop_scan_r_with_hand_set_logits():
                          ngroups=len(groups), ld_proj=ld, M=Mr, nframes=N)
         lengths = torch.full((len(utts),), -7, dtype=torch.int64, device=dev)
         out2 = torch.full((2,), -7, dtype=torch.int32, device=dev)
-        _lib.call("t2_stop_scan_r", scan, r, max_len, lengths, out2, _st())
+        if plain:
+            _lib.call("t2_stop_scan", scan, lengths, out2, _st())
+        else:
+            _lib.call("t2_stop_scan_r", scan, r, max_len, lengths, out2, _st())
         torch.cuda.synchronize()
         return lengths.cpu().tolist(), out2.cpu().tolist()
     assert run([0, 1, 2, 3, 4], (2, 3), 13) == ([9, 12, 13, 6, 9], [13, 5])
@@ -496,6 +544,11 @@ def test_stop_scan_r_with_hand_set_logits():
     assert run([2], (1,), 14) == ([14], [14, 5])                             # never stops: the stored steps, cut at the cap
     with pytest.raises(_lib.T2Error, match="rc=1"):
         run([2], (1,), 0)
+    # r = 1 against the entry point without the suffix, both group splits, a cap that does not bind
+    for utts, groups, want, steps in (([0, 1, 2, 3, 4], (2, 3), [3, 4, 5, 2, 3], 5), ([0, 1, 3, 4], (2, 2), [3, 3, 2, 2], 4)):
+        got_r, got = run(utts, groups, 100, r=1), run(utts, groups, None, r=1, plain=True)
+        assert got_r == (want, [steps, steps]) and got == (want, [steps, 0])
+    assert run([0, 1, 2, 3, 4], (2, 3), 3, r=1) == ([3, 3, 3, 2, 3], [3, 5])  # a cap that binds: lengths and frames cut, steps not
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
