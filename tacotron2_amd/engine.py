@@ -16,7 +16,7 @@ from __future__ import annotations
 import contextlib
 import numbers
 import threading as _threading
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -203,6 +203,82 @@ def _chunk_sizes(T: int, CH: int, ramp_at_end: bool = True):
     body = T - CH
     sizes = [min(CH, body - c0) for c0 in range(0, body, CH)]
     return sizes + tail
+
+
+def chunk_ranges(T: int, CH: int, ramp: bool = True, descending: bool = False):
+    """The pipeline chunks of _chunk_sizes as frame ranges: (c0, c1) in time order, or (hi, lo) from the last frame down.  There
+    the ramp's short chunks come first: the backward's attention chain cannot start before the decoder-LSTM BPTT of its first chunk
+    and that chunk's GEMM are done on the side stream."""
+    edges = [0]
+    for n in _chunk_sizes(T, CH, ramp_at_end=ramp):
+        edges.append(edges[-1] + n)
+    asc = list(zip(edges[:-1], edges[1:]))
+    return [(c1, c0) for c0, c1 in reversed(asc)] if descending else asc
+
+
+def forward_schedule(T: int, CH: int, B: int, D: int, ramp: bool = True, splitk_small: bool = True, controls: bool = False):
+    """The forward frame loop's chunks, [(c0, c1, sk, cleared)] in time order.  sk: K slices of the chunk's hoisted decoder-LSTM
+    input GEMM (chunk_splits: the short ones accumulate into the pre-filled block with atomics); cleared: that block is a cleared
+    one (with controls it holds their per-utterance term instead)."""
+    out = []
+    for c0, c1 in chunk_ranges(T, CH, ramp):
+        sk = chunk_splits(c1 - c0, B, D) if splitk_small else 1
+        out.append((c0, c1, sk, sk > 1 and not controls))
+    return out
+
+
+class SideOp(NamedTuple):
+    """One side-stream operation of the backward frame loop (backward_schedule) over the frames [lo, hi)."""
+    kind: str           # "dec_wgrads" | "deferred" | "att_acc" | "att_wgrads" | "acc_done"
+    share: bool         # its GEMMs are issued inside share_cu(Engine.share_cu); False for what launches no GEMM
+    hi: int = 0
+    lo: int = 0
+    k: int = -1         # att_*: the chunk whose main-stream event the operation waits for
+
+
+class BackwardSchedule(NamedTuple):
+    chunks: tuple       # ((hi, lo, (SideOp, ...)), ...) time-descending: the operations issued behind the chunk's side-stream event
+    tail: tuple         # (SideOp, ...) issued on the side stream behind the loop
+
+
+def backward_schedule(T: int, CH: int, WG: int, n_deferred: int, stash: bool, ramp: bool = True) -> BackwardSchedule:
+    """What the side stream does behind each chunk of the backward frame loop, and behind the loop.  Frames go to the
+    weight-gradient GEMMs in groups of WG chunks (a group is one contiguous [lo, hi) range): the decoder LSTM's with the chunk that
+    completes a group, the attention chain's two chunks late, behind the main-stream event of the group's newest chunk k.  With a
+    stash every chunk's dpmT / dv / dU launch ("att_acc") goes the same way, two chunks late.  From the fifth chunk on, one
+    deferred postnet / projection weight gradient is popped per chunk.  The tail drains the rest: the last group of the attention
+    chain takes every chunk not yet handed over (up to WG + 1 of them), and "acc_done" marks the event that the first reader of
+    dpmT waits for.  The deferred GEMMs drained in the tail run outside share_cu, every other GEMM inside it: kept as it was
+    measured, not judged here."""
+    ranges = chunk_ranges(T, CH, ramp, descending=True)
+    n, left = len(ranges), n_deferred
+    dec_hi = att_hi = T               # upper ends of the decoder / attention groups being collected
+
+    def att(kind, k, hi=None):
+        return SideOp(kind, kind == "att_wgrads", ranges[k][0] if hi is None else hi, ranges[k][1], k)
+    chunks = []
+    for ci, (hi, lo) in enumerate(ranges):
+        ops = []
+        if (ci + 1) % WG == 0:
+            ops.append(SideOp("dec_wgrads", True, dec_hi, lo)); dec_hi = lo
+        if left and ci >= 4:
+            ops.append(SideOp("deferred", True)); left -= 1
+        k = ci - 2                    # the chunk the main stream finished two chunks ago
+        if k >= 0:
+            if stash:
+                ops.append(att("att_acc", k))
+            if (k + 1) % WG == 0:
+                ops.append(att("att_wgrads", k, hi=att_hi)); att_hi = ranges[k][1]
+        chunks.append((hi, lo, tuple(ops)))
+    tail = [att("att_acc", n - 2)] if stash and n >= 2 else []                 # next to the chain's last chunk
+    tail += [SideOp("deferred", False)] * left                                 # (short sequences: fewer chunks than deferred GEMMs)
+    if dec_hi > 0:
+        tail.append(SideOp("dec_wgrads", True, dec_hi, 0))
+    # the last chunk's accumulators wait for the chain's end, so they follow what does not
+    if stash:
+        tail.append(att("att_acc", n - 1))
+    tail += [SideOp("acc_done", False), att("att_wgrads", n - 1, hi=att_hi)]
+    return BackwardSchedule(tuple(chunks), tuple(tail))
 
 
 class Engine:
@@ -875,16 +951,9 @@ class Engine:
 
         ctl, cterm, cmel1 = self.controls_terms(controls, B)
 
-        def pre_dec_splits(c0, c1):
-            # K slices of a chunk's hoisted GEMM (chunk_splits: the short ones accumulate into the pre-filled block with atomics),
-            # and whether that block is a cleared one (with controls it holds their per-utterance term instead)
-            sk = chunk_splits(c1 - c0, B, D) if self.splitk_small_chunks else 1
-            return sk, sk > 1 and cterm is None
-
-        def pre_dec_gemm(c0, c1):
+        def pre_dec_gemm(c0, c1, sk, cleared):
             if cterm is not None:     # per-utterance controls term first, the projection accumulates on top
                 pre_dec[c0:c1].copy_(cterm.unsqueeze(0).expand(c1 - c0, B, 4 * D))
-            sk, cleared = pre_dec_splits(c0, c1)
             if cleared:
                 self.need_zero(pre_dec[c0:c1])
             gemm(_ptr(xdec, (c0 + 1) * B * (A + Ef)), P["decoder.lstm.weight_ih"], _ptr(pre_dec, c0 * B * 4 * D), (c1 - c0) * B,
@@ -894,17 +963,15 @@ class Engine:
         main, side = torch.cuda.current_stream(), self.side_stream()
         # Pipeline chunks; the LAST ones shrink (CH/2, CH/4, CH/8, CH/8): what follows the attention chain's end on the side stream
         # (the decoder-LSTM frames of the final chunk) is exposed time, proportional to that chunk's length.
-        chunks, c0 = [], 0
-        for n in _chunk_sizes(T, self.chunk, ramp_at_end=self.ramp_chunks):
-            chunks.append((c0, c0 + n)); c0 += n
-        for c0, c1 in chunks:      # blocks that a split-K GEMM accumulates into: cleared here, with everything else
-            if pre_dec_splits(c0, c1)[1]:
+        sched = forward_schedule(T, self.chunk, B, D, self.ramp_chunks, self.splitk_small_chunks, cterm is not None)
+        for c0, c1, sk, cleared in sched:      # blocks that a split-K GEMM accumulates into: cleared here, with everything else
+            if cleared:
                 self.clear_ahead(pre_dec[c0:c1])
         self._wait(side, main)
         persist = B <= 64 and self.dec_chain == "persistent" and D // 4 <= 256 and self.persist_resident(D, B)
         ctx["persist"] = persist
         sync = self.persist_sync() if persist else None
-        for i, (c0, c1) in enumerate(chunks):
+        for c0, c1, sk, cleared in sched:
             seq.t_begin, seq.t_end = c0, c1
             call("t2_attn_seq_fwd", seq, st)
             ev = self._record(main)
@@ -913,7 +980,7 @@ class Engine:
                 # the hoisted pre_dec GEMM of the chunk runs here too, in front of the chunk's decoder-LSTM launch (70.0 against
                 # 71.3 ms per step with it on the main stream, profiles/r02_ab_fwd_dec_chain.txt)
                 with share_cu(self.share_cu if persist else 0):
-                    pre_dec_gemm(c0, c1)
+                    pre_dec_gemm(c0, c1, sk, cleared)
                 stp, inc = dec_chunk(c0, c1)
                 if persist:
                     # The decoder-LSTM chain of a chunk as ONE persistent, weight-stationary launch (t2_lstm_seq_fwd_persist):
@@ -1139,7 +1206,6 @@ class Engine:
         self.mark("bwd.dec.proj")
         main, side = torch.cuda.current_stream(), self.side_stream()
         self._wait(side, main)
-        CH = self.chunk_bwd
 
         def dec_bwd_chunk(hi, lo):
             s = make("T2LstmBwdStep", B=B, H=D, N4=4 * D, dg_next=_ptr(dgd, hi * B * 4 * D), lddg=4 * D,
@@ -1161,11 +1227,6 @@ class Engine:
             self._wgrad(g0, 4 * D, _ptr(xdec, (lo + 1) * B * ldx), ldx, G["decoder.lstm.weight_ih"], ldx, 4 * D, ldx, n)
             self._wgrad(g0, 4 * D, _ptr(xproj, lo * B * ldp), ldp, G["decoder.lstm.weight_hh"], D, 4 * D, D, n)
 
-        # (time-descending) the FIRST chunks are short: the attention chain cannot start before the decoder-LSTM BPTT of its first
-        # chunk and that chunk's GEMM are done on the side stream
-        chunks, hi = [], T
-        for n in reversed(_chunk_sizes(T, CH, ramp_at_end=self.ramp_chunks)):
-            chunks.append((hi, hi - n)); hi -= n
         # Two-stream pipeline: decoder chain of chunk k+1 on the side stream next to the attention chain of chunk k.  Hosting the
         # decoder BPTT steps inside attention launches instead measured slower every way (inside the ds launch: round 1,
         # profiles/r01_sweep_bwd_chunk_co.txt; as a second operand block of the cell-backward launch: 75.3 against 71.9 ms
@@ -1186,59 +1247,44 @@ class Engine:
         # weight-gradient GEMMs in groups of `wgrad_group` chunks (a longer K per call keeps the split-K GEMMs efficient); ranges are
         # contiguous and time-descending, so a group is one [lo, hi) range.  dec_*: gate gradients of the decoder-LSTM BPTT (this
         # stream's own output: no wait);  att_*: of the attention chain (main stream: wait for the event recorded behind the group's
-        # last chunk).
-        WG = max(1, int(self.wgrad_group))
-        dec_grp, att_done, att_grp = None, [], None        # [hi, lo, n]; [(hi, lo, event)]; [hi, lo, n, event]
+        # last chunk).  Which operation goes behind which chunk, and what is left for the tail, is backward_schedule's.
+        sched = backward_schedule(T, self.chunk_bwd, max(1, int(self.wgrad_group)), len(post_wgrads), de_stash is not None,
+                                  self.ramp_chunks)
+        done = []                    # main-stream events behind the chunks' attention steps
 
-        def att_acc(hi, lo, ev):     # dpmT / dv / dU of the chain's frames [lo, hi): behind the chunk's event, default wave priority
-            if de_stash is None:
-                return
-            self._wait(side, ev)
+        def att_acc(hi, lo):         # dpmT / dv / dU of the chain's frames [lo, hi): default wave priority
             call("t2_attn_acc_bwd", sb, de_stash, B * L, lo, hi, side.cuda_stream)
-        for ci_, (hi, lo) in enumerate(chunks):
+        run = dict(dec_wgrads=dec_wgrads_chunk, att_acc=att_acc, att_wgrads=att_wgrads, deferred=lambda hi, lo: post_wgrads.pop(0)())
+
+        def side_op(op):
+            if op.k >= 0:                      # att_*: behind the main-stream event of chunk k
+                self._wait(side, done[op.k])
+            run[op.kind](op.hi, op.lo)
+        for hi, lo, ops in sched.chunks:
             with torch.cuda.stream(side), share_cu(self.share_cu):
                 s, inc = dec_bwd_chunk(hi, lo)
                 call("t2_lstm_seq_bwd", s, inc, 1, hi - lo, side.cuda_stream)
                 gemm(_ptr(dgd, lo * B * 4 * D), P["decoder.lstm.weight_ih"], _ptr(dxdec, lo * B * ldx), (hi - lo) * B, ldx, 4 * D,
                      4 * D, ldx, ldx, a_k=1, b_k=0)
                 ev = self._record(side)
-                # behind the event (the attention chain does not wait for any of this)
-                dec_grp = [hi, lo, 1] if dec_grp is None else [dec_grp[0], lo, dec_grp[2] + 1]
-                if dec_grp[2] >= WG:
-                    dec_wgrads_chunk(dec_grp[0], dec_grp[1]); dec_grp = None
-                if post_wgrads and ci_ >= 4:
-                    post_wgrads.pop(0)()
-                if len(att_done) >= 2:      # chunks the main stream finished two chunks ago
-                    h2, l2, e2 = att_done.pop(0)
-                    att_acc(h2, l2, e2)
-                    att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
-                    if att_grp[2] >= WG:
-                        self._wait(side, att_grp[3])
-                        att_wgrads(att_grp[0], att_grp[1]); att_grp = None
+                for op in ops:       # behind the event (the attention chain does not wait for any of this); all inside share_cu
+                    side_op(op)
             self._wait(main, ev)
             sb.t_hi, sb.t_lo = hi, lo
             if fwd_att:
                 call("t2_attn_seq_bwd_forward", sb, de_stash, B * L, dprior, st)
             else:
                 call("t2_attn_seq_bwd_stash", sb, de_stash, B * L, st)
-            att_done.append((hi, lo, self._record(main)))
+            done.append(self._record(main))
         with torch.cuda.stream(side):
-            for h2, l2, e2 in att_done[:-1]:        # next to the chain's last chunk
-                att_acc(h2, l2, e2)
-            while post_wgrads:                      # (short sequences: fewer chunks than deferred GEMMs)
-                post_wgrads.pop(0)()
-            with share_cu(self.share_cu):
-                if dec_grp is not None:
-                    dec_wgrads_chunk(dec_grp[0], dec_grp[1])
-                # the last chunk's accumulators wait for the chain's end, so they follow what does not; the main stream waits for
-                # them in front of the first reader of dpmT
-                att_acc(*att_done[-1])
-                acc_done = self._record(side)
-                for h2, l2, e2 in att_done:
-                    att_grp = [h2, l2, 1, e2] if att_grp is None else [att_grp[0], l2, att_grp[2] + 1, e2]
-                if att_grp is not None:
-                    self._wait(side, att_grp[3])
-                    att_wgrads(att_grp[0], att_grp[1])
+            # (the deferred GEMMs drained here run outside share_cu where the loop's run inside it: the schedule keeps that as it was
+            # measured and does not judge it)
+            for op in sched.tail:
+                if op.kind == "acc_done":      # the main stream waits for this event in front of the first reader of dpmT
+                    acc_done = self._record(side)
+                    continue
+                with share_cu(self.share_cu) if op.share else contextlib.nullcontext():
+                    side_op(op)
             # decoder-LSTM bias (and controls) gradients, next to the attention chain's tail
             db = self.buf("db_dec", 4 * D, zero=True)                      # both biases see the same gate gradients
             call("t2_colsum", dgd, 4 * D, R, 4 * D, db, side.cuda_stream)
