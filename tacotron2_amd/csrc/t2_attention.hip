@@ -18,12 +18,6 @@
 //  attn_energy_win_kernel / attn_context_win_kernel: the same bodies over an attention window (inference);
 //  attn_context_fwd_kernel: the context body with the forward-attention prior folded into its softmax (inference).
 #include "t2_common.hpp"
-#include "t2_lstm_step.hpp"
-
-int t2_lstm_step_fwd_launch(const T2LstmStep* steps, int n, hipStream_t st);
-int t2_lstm_step_bwd_launch(const T2LstmBwdStep* steps, int n, hipStream_t st, unsigned long long* clk = nullptr);
-void t2_lstm_fwd_advance(T2LstmStep& c, const T2LstmStride& inc);
-void t2_lstm_bwd_advance(T2LstmBwdStep& c, const T2LstmBwdStride& inc);
 
 namespace {
 

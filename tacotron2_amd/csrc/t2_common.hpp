@@ -43,6 +43,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void t2_set_error(const char* msg, const char* file, int line);
 
+// Internal entries of t2_lstm.hip that the attention sequences (t2_attention.hip) call between their own launches: one cell step
+// forward / backward on a stream (clk: the diagnostic build's stamp buffer), and the per-step advance of an operand block.
+int t2_lstm_step_fwd_launch(const T2LstmStep* steps, int n, hipStream_t st);
+int t2_lstm_step_bwd_launch(const T2LstmBwdStep* steps, int n, hipStream_t st, unsigned long long* clk = nullptr);
+void t2_lstm_fwd_advance(T2LstmStep& c, const T2LstmStride& inc);
+void t2_lstm_bwd_advance(T2LstmBwdStep& c, const T2LstmBwdStride& inc);
+
 // First statement of every kernel of the latency-bound frame chains (cell steps, attention kernels, decode linears): their
 // waves win instruction-issue arbitration against the GEMM waves of the other stream that share the SIMD (default priority 0).
 // 70.35 -> 69.47 ms per training step in one session (profiles/r02_ab_wave_priority.txt); no effect without a second stream.

@@ -13,8 +13,19 @@
 //   dx[b][u] = sum_n dgates_next[b][n] * W[n][u]  (K = 4H over 4 waves, two accumulator chains), one
 //   16 x 16 (batch x unit) tile per workgroup, then (epilogue) the cell's pointwise backward for step t,
 //   producing dgates_t - the A operand of the next launch and the row block of the wgrad GEMMs.
+//
+// Every step kernel ends in the same cell epilogue (fwd_epi_load / fwd_cell / fwd_epi_store; the persistent kernel shares the
+// pointwise cell and keeps its per-step loads and stores), every backward kernel in bwd_epi_load / bwd_epi_apply, and the
+// three packed kernels run the same software pipeline (pipe_groups).
 #include "t2_common.hpp"
 #include "t2_lstm_step.hpp"
+
+// Diagnostic builds only (tacotron2_amd/build.py --variant): T2_CELL_MFMA_KEEP < 4 issues only that many of the four fp32 MFMA
+// k-substeps of every 16-deep chunk in the packed step kernels - WRONG RESULTS, same loads and epilogue - to bound what a faster
+// matrix path could buy these kernels (tools/ablate_cell_mfma.py).  The product build keeps all four.
+#ifndef T2_CELL_MFMA_KEEP
+#define T2_CELL_MFMA_KEEP 4
+#endif
 
 // Diagnostic build only (-DT2_STAMPS; t2_debug_clock): when enabled, workgroup 0 of the forward fast kernel stamps the shader clock
 // (s_memtime, words 0 and 6) and the 100 MHz reference (s_memrealtime, words 1 and 7) at entry and exit; nothing else
@@ -24,7 +35,188 @@ __device__ int g_t2_clk_enable;
 
 namespace {
 
+template <typename T>
+inline void adv(T*& p, int64_t inc) { if (p) p += inc; }
 
+// ---------------------------------------------------------------------------------------------------------
+// The forward cell epilogue, shared by the forward kernels: operand load, pointwise cell, stores.
+// ---------------------------------------------------------------------------------------------------------
+struct FwdEpi {      // (as initialised: what absent operands read as)
+    float pre[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f}, b2[4] = {0.f, 0.f, 0.f, 0.f}, cp = 0.f, drop = 1.f;
+    int len = 0x7fffffff;
+};
+struct FwdCell { float h, c, gi, gf, gg, go; };
+
+// (a piece of its own for the persistent kernel, which has no registers to keep the biases in across its steps)
+__device__ __forceinline__ void fwd_epi_load_bias(FwdEpi& e, const LstmK& p, int H, int u) {
+    if (p.bias1) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) e.b1[g] = p.bias1[g * H + u];
+    }
+    if (p.bias2) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) e.b2[g] = p.bias2[g * H + u];
+    }
+}
+
+// Operands of the thread that owns (row b, unit u).  The row is clamped, so every thread may issue the loads: the packed
+// kernels do so BEFORE the GEMM (hoisted: consumed after it, they never add a memory round trip).  Absent operands read as
+// 0 (pre, biases, c_prev), 1 (drop) and INT_MAX (len).
+__device__ __forceinline__ FwdEpi fwd_epi_load(const LstmK& p, int b, int u) {
+    FwdEpi e;
+    const int H = p.H;
+    const long bc = b < p.B ? b : p.B - 1;
+    if (p.pre) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) e.pre[g] = p.pre[bc * p.ldpre + g * H + u];
+    }
+    fwd_epi_load_bias(e, p, H, u);
+    if (p.c_prev) e.cp = p.c_prev[bc * p.ldc_prev + u];
+    if (p.drop) e.drop = p.drop[bc * p.lddrop + u];
+    if (p.len) e.len = p.len[bc];
+    return e;
+}
+
+// The pointwise cell of one (row, unit) at step t.  red points at this thread's word of wave 0's partial tile in LDS (C/D
+// layout 16x16: col = lane&15, row = (lane>>4)*4 + reg); gate g is 4 words on, wave ww's share wstride words on.  Fixed order
+// of the sums: (((waves 0..3) + pre) + bias1) + bias2.  Rows past their length (t >= len) give exact zeros.
+// FUSED_C: c = fma(gf, c_prev, gi * gg) - what the compiler had made of the packed kernel's c = gf * c_prev + gi * gg, and of no
+// other kernel's.  Each keeps its rounding, now spelled out, so that every kernel's results stay what they were bit for bit.
+template <bool FUSED_C>
+__device__ __forceinline__ FwdCell fwd_cell(const FwdEpi& e, const float* red, int wstride, int t) {
+    float gsum[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float s = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) s += red[ww * wstride + g * 4];
+        gsum[g] = s + e.pre[g] + e.b1[g] + e.b2[g];
+    }
+    FwdCell o;
+    o.gi = t2_sigmoid(gsum[0]); o.gf = t2_sigmoid(gsum[1]); o.gg = t2_tanh(gsum[2]); o.go = t2_sigmoid(gsum[3]);
+    if (FUSED_C) {
+        o.c = __builtin_fmaf(o.gf, e.cp, o.gi * o.gg);
+    } else {
+#pragma clang fp contract(off)
+        o.c = o.gf * e.cp + o.gi * o.gg;
+    }
+    o.h = o.go * t2_tanh(o.c) * e.drop;
+    if (!(t < e.len)) { o.h = 0.f; o.c = 0.f; o.gi = o.gf = o.gg = o.go = 0.f; }
+    return o;
+}
+
+__device__ __forceinline__ void fwd_epi_store(const LstmK& p, int b, int u, const FwdCell& o) {
+    p.h_out[(long)b * p.ldh + u] = o.h;
+    if (p.h_out2) p.h_out2[(long)b * p.ldh2 + u] = o.h;
+    if (p.ht_out) { const int col = p.ht_col0 + u; p.ht_out[(long)(col >> 4) * p.xt_cs + b * 16 + (col & 15)] = o.h; }
+    if (p.c_out) p.c_out[(long)b * p.ldc_out + u] = o.c;
+    // gate-interleaved stash [b][u][4] = (i, f, g, o): one 16-byte store per thread, 64 contiguous bytes per 4 units
+    if (p.gates_out) *reinterpret_cast<f32x4*>(p.gates_out + (long)b * p.ldg + 4 * u) = (f32x4){o.gi, o.gf, o.gg, o.go};
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The backward pointwise cell, shared by every backward kernel: thread tid owns (row b0 + tid/16, column u0 + tid%16).
+// ---------------------------------------------------------------------------------------------------------
+struct BwdEpi { float ext, drop, gi, gf, gg, go, cp, cc, dc; int len; };
+
+// (row and column clamped: every thread may issue the loads, the packed kernels do so before the GEMM)
+__device__ __forceinline__ BwdEpi bwd_epi_load(const BwdK& p, int tid, int u0, int b0) {
+    BwdEpi e;
+    const int bl = tid >> 4, ul = tid & 15;
+    const long b = (b0 + bl) < p.B ? (b0 + bl) : p.B - 1;
+    const int u = (u0 + ul) < p.ncols ? (u0 + ul) : p.ncols - 1;
+    e.ext = 0.f; e.drop = 1.f; e.gi = e.gf = e.gg = e.go = 0.f; e.cp = 0.f; e.cc = 0.f; e.dc = 0.f; e.len = 0x7fffffff;
+    if (p.ext1) e.ext = p.ext1[b * p.ldx1 + u];
+    if (p.ext2) e.ext += p.ext2[b * p.ldx2 + u];
+    if (p.epi == 1) {
+        if (p.drop) e.drop = p.drop[b * p.lddrop + u];
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(p.gates + b * p.ldgs + 4 * u);   // gate-interleaved stash [b][u][4]
+        e.gi = g4[0]; e.gf = g4[1]; e.gg = g4[2]; e.go = g4[3];
+        if (p.c_prev) e.cp = p.c_prev[b * p.ldcp + u];
+        e.cc = p.c_cur[b * p.ldcc + u];
+        e.dc = p.dc[b * p.lddc + u];
+        if (p.len) e.len = p.len[b];
+    }
+    return e;
+}
+
+// dx = (ext1 + ext2) + the K shares of waves 0..NW-1 from LDS, in that order; then the plain store or the cell backward
+template <int NW>
+__device__ __forceinline__ void bwd_epi_apply(const BwdK& p, const BwdEpi& e, const float* red, int tid, int u0, int b0) {
+    const int bl = tid >> 4, ul = tid & 15;
+    const int b = b0 + bl, u = u0 + ul;
+    if (b < p.B && u < p.ncols) {
+        float dx = e.ext;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) dx += red[(ww * 16 + bl) * 16 + ul];
+        if (p.epi == 0) {
+            p.dx_out[(long)b * p.lddx + u] = dx;
+        } else {
+            const int H = p.H;
+            const bool active = p.t < e.len;
+            const float dh = dx * e.drop;
+            const float tc = t2_tanh(e.cc);
+            const float dcv = e.dc + dh * e.go * (1.f - tc * tc);
+            float d_o = dh * tc * e.go * (1.f - e.go);
+            float d_i = dcv * e.gg * e.gi * (1.f - e.gi);
+            float d_f = dcv * e.cp * e.gf * (1.f - e.gf);
+            float d_g = dcv * e.gi * (1.f - e.gg * e.gg);
+            float dcp = dcv * e.gf;
+            if (!active) { d_i = d_f = d_g = d_o = 0.f; dcp = 0.f; }
+            p.dc[(long)b * p.lddc + u] = dcp;
+            float* dgo = p.dg_out + (long)b * p.ldgo + u;
+            dgo[0] = d_i; dgo[H] = d_f; dgo[2 * H] = d_g; dgo[3 * H] = d_o;
+            if (p.dg_out2) {
+                float* dg2o = p.dg_out2 + (long)b * p.ldgo2 + u;
+                dg2o[0] = d_i; dg2o[H] = d_f; dg2o[2 * H] = d_g; dg2o[3 * H] = d_o;
+            }
+            if (p.dgt_out) {   // H % 16 == 0 (checked on the host): the four gate columns share (u & 15)
+                float* dt_ = p.dgt_out + (long)(u >> 4) * p.dgt_cs + b * 16 + (u & 15);
+                const long gs = (long)(H >> 4) * p.dgt_cs;
+                dt_[0] = d_i; dt_[gs] = d_f; dt_[2 * gs] = d_g; dt_[3 * gs] = d_o;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The main loop of the packed kernels: G groups of U chunks per wave, double-buffered, software-pipelined at chunk
+// granularity.  The loads of chunk j of group g+1 are issued right before the MFMAs of chunk j of group g, so the
+// vector-memory pipe and the MFMA pipe are busy at the same time (a wave that issues a whole group of loads and then a whole
+// group of MFMAs alternates between the two: 6.2 -> 5.3 us per step at K = 1536, tools/ubench_cell.hip).  One group of loads
+// stays in flight; sched_barrier pins the order, and the loads are unconditional so the compiler's counted vmcnt waits stay
+// exact.  load_chunk(g, j, Chunk&) requests chunk j of group g, mma_chunk(const Chunk&) consumes one, group0_done() is the
+// diagnostic builds' stamp: group 0 consumed, group 1 requested (only launches of more than two groups get there).
+// ---------------------------------------------------------------------------------------------------------
+template <int U, typename Chunk, typename Load, typename Mma, typename Stamp>
+__device__ __forceinline__ void pipe_groups(const int G, const Load& load_chunk, const Mma& mma_chunk, const Stamp& group0_done) {
+    Chunk bufA[U], bufB[U];
+    auto pipe_group = [&](int gl, Chunk (&L)[U], const Chunk (&M)[U]) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            load_chunk(gl, j, L[j]);
+            __builtin_amdgcn_sched_barrier(0);
+            mma_chunk(M[j]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < U; ++j) load_chunk(0, j, bufA[j]);
+    int g = 0;
+    for (; g + 2 < G; g += 2) {
+        pipe_group(g + 1, bufB, bufA);
+        if (g == 0) group0_done();
+        pipe_group(g + 2, bufA, bufB);
+    }
+    if (g + 1 < G) {
+        pipe_group(g + 1, bufB, bufA);
+#pragma unroll
+        for (int j = 0; j < U; ++j) mma_chunk(bufB[j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < U; ++j) mma_chunk(bufA[j]);
+    }
+}
 
 template <int MT>
 __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmK2 pp) {
@@ -104,53 +296,77 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmK2 pp) {
             c += 4 * U;
         }
     }
-    // C/D layout 16x16: col = lane&15, row = (lane>>4)*4 + reg
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int g = 0; g < 4; ++g) red[((w * MT + m) * 16 + (q * 4 + g)) * 16 + r] = acc[m][g];
     __syncthreads();
-
-    if (tid < MT * 64) {
-        const int b = tid >> 2, uu = tid & 3;
-        if (b < p.B) {
-            const int u = u0 + uu;
-            float gsum[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float s = 0.f;
-#pragma unroll
-                for (int ww = 0; ww < 4; ++ww) s += red[((ww * MT + (b >> 4)) * 16 + (b & 15)) * 16 + g * 4 + uu];
-                const int n = g * H + u;
-                if (p.pre) s += p.pre[(long)b * p.ldpre + n];
-                if (p.bias1) s += p.bias1[n];
-                if (p.bias2) s += p.bias2[n];
-                gsum[g] = s;
-            }
-            const bool active = (p.len == nullptr) || (p.t < p.len[b]);
-            float gi = t2_sigmoid(gsum[0]), gf = t2_sigmoid(gsum[1]), gg = t2_tanh(gsum[2]), go = t2_sigmoid(gsum[3]);
-            const float cp = p.c_prev ? p.c_prev[(long)b * p.ldc_prev + u] : 0.f;
-            float cn = gf * cp + gi * gg;
-            float hn = go * t2_tanh(cn);
-            if (p.drop) hn *= p.drop[(long)b * p.lddrop + u];
-            if (!active) { hn = 0.f; cn = 0.f; gi = gf = gg = go = 0.f; }
-            p.h_out[(long)b * p.ldh + u] = hn;
-            if (p.h_out2) p.h_out2[(long)b * p.ldh2 + u] = hn;
-            if (p.c_out) p.c_out[(long)b * p.ldc_out + u] = cn;
-            if (p.gates_out) {
-                // gate-interleaved stash [b][u][4] = (i, f, g, o): one 16-byte store per thread, 64 contiguous bytes per 4 units
-                *reinterpret_cast<f32x4*>(p.gates_out + (long)b * p.ldg + 4 * u) = (f32x4){gi, gf, gg, go};
-            }
-        }
-    }
+    const int b = tid >> 2, u = u0 + (tid & 3);      // tile b>>4, its row b&15: word b*16 of a wave's share
+    if (tid < MT * 64 && b < p.B) fwd_epi_store(p, b, u, fwd_cell<false>(fwd_epi_load(p, b, u), red + b * 16 + (tid & 3), MT * 256, p.t));
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Fast path: packed, zero-padded weight stream + ONE contiguous activation segment.  Branch-free main loop:
-// every wave runs NTpad/16 groups of 4 chunks; chunk c of group g is 16g + 4j + w.  Chunks past the real K multiply the
-// all-zero padding chunks of the weight stream with (clamped, finite) activations, so no guard, select or wait sits
-// between a load and the next load: two groups (2 x 12 x 1 KB per wave) are in flight while one is in the MFMAs.
+// Fast path: packed, zero-padded weight stream + ONE contiguous activation segment (256 threads: 4 waves split K).
+// Branch-free main loop: every wave runs NTpad/16 groups of 4 chunks; chunk c of group g is 16g + 4j + w.  Chunks past the
+// real K multiply the all-zero padding chunks of the weight stream with (clamped, finite) activations, so no guard, select
+// or wait sits between a load and the next load: two groups (2 x 12 x 1 KB per wave) are in flight while one is in the MFMAs.
 // ---------------------------------------------------------------------------------------------------------
+template <int MT, int U>
+__device__ __forceinline__ void t2_lstm_fwd_fast_body(const LstmK& p, const int bx, float* red /* [4*MT*256] */,
+                                                      unsigned long long* clk = nullptr /* diagnostic stamps [2..4] */) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, q = lane >> 4;
+    const int u0 = bx * 4;
+    const int NT = p.seg[0].K >> 4, NTpad = (NT + 15) & ~15, G = NTpad / (4 * U);   // host guarantees NTpad % (4U) == 0
+    const float* wb = p.wpacked + (long)bx * NTpad * 256 + lane * 4;
+    // x16-tiled input: chunk c, tile m is one contiguous 1 KB block (8 full cache lines per wave-load); row-major
+    // input: 16 rows x 64 B per wave-load (16 half lines - 3-4x slower through the vector memory pipe)
+    const float* xb[MT];
+    const long xcs = p.xt ? p.xt_cs : 16;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int row = m * 16 + r;
+        // (tiled rows exist up to round_up(B, 16) of the WHOLE batch: a last row block of 33..48 rows has no fourth tile - its lanes
+        //  re-read the last existing row, and their products land in rows the epilogue drops)
+        xb[m] = p.xt ? p.xt + (long)(row < p.xt_rows ? row : p.xt_rows - 1) * 16 + 4 * q
+                     : p.seg[0].x + (long)(row < p.B ? row : 0) * p.seg[0].ldx + 4 * q;
+    }
+    f32x4 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int eb = tid >> 2, eu = u0 + (tid & 3);
+    const FwdEpi epi = fwd_epi_load(p, eb, eu);      // hoisted: in flight during the GEMM
+    struct Chunk { f32x4 bw, ax[MT]; };
+    auto load_chunk = [&](int g, int j, Chunk& k) {
+        const int c = 4 * U * g + 4 * j + w;
+        const int cx = c < NT ? c : NT - 1;     // padding chunks: any finite activations x the zero weight chunk
+#ifdef T2_NT_WEIGHTS_MT1     // diagnostic build (A/B, profiles/r05_ab_decode_nt_weights.txt): once-read weight stream of the <= 16-row step
+        if (MT == 1) k.bw = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wb + (long)c * 256));
+        else
+#endif
+        k.bw = *reinterpret_cast<const f32x4*>(wb + (long)c * 256);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) k.ax[m] = *reinterpret_cast<const f32x4*>(xb[m] + xcs * cx);
+    };
+    auto mma_chunk = [&](const Chunk& k) {
+#pragma unroll
+        for (int s = 0; s < T2_CELL_MFMA_KEEP; ++s)
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(k.ax[m][s], k.bw[s], acc[m], 0, 0, 0);
+    };
+    pipe_groups<U, Chunk>(G, load_chunk, mma_chunk, [&] { if (clk) clk[2] = __builtin_amdgcn_s_memtime(); });
+    if (clk) clk[3] = __builtin_amdgcn_s_memtime();
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) red[((w * MT + m) * 16 + (q * 4 + g)) * 16 + r] = acc[m][g];
+    __syncthreads();
+    if (clk) clk[4] = __builtin_amdgcn_s_memtime();
+    if (tid < MT * 64 && eb < p.B) fwd_epi_store(p, eb, eu, fwd_cell<true>(epi, red + eb * 16 + (tid & 3), MT * 256, p.t));
+}
+
 template <int MT, int U>
 __global__ __launch_bounds__(256, 1) void lstm_step_fwd_fast_kernel(LstmK2 pp) {
     T2_CHAIN_PRIO();
@@ -182,7 +398,6 @@ __global__ __launch_bounds__(256, 1) void lstm_step_fwd_sq_kernel(LstmK2 pp) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
     const int bx = blockIdx.x, b0 = blockIdx.y * 32, u0 = bx * 8;
-    const int H = p.H;
     const int NT = p.seg[0].K >> 4, NTpad = (NT + 15) & ~15, G = NTpad / (4 * U);
     const float* wb[2];
 #pragma unroll
@@ -199,72 +414,28 @@ __global__ __launch_bounds__(256, 1) void lstm_step_fwd_sq_kernel(LstmK2 pp) {
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) acc[m][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // epilogue operands of this thread's (row, unit): hoisted, in flight during the GEMM
     const int bl = tid >> 3, uu8 = tid & 7, eb = b0 + bl, eu = u0 + uu8;
-    const long ebc = eb < p.B ? eb : p.B - 1;
-    float e_pre[4] = {0.f, 0.f, 0.f, 0.f}, e_b1[4] = {0.f, 0.f, 0.f, 0.f}, e_b2[4] = {0.f, 0.f, 0.f, 0.f};
-    float e_cp = 0.f, e_drop = 1.f;
-    int e_len = 0x7fffffff;
-    if (p.pre) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) e_pre[g] = p.pre[ebc * p.ldpre + g * H + eu];
-    }
-    if (p.bias1) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) e_b1[g] = p.bias1[g * H + eu];
-    }
-    if (p.bias2) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) e_b2[g] = p.bias2[g * H + eu];
-    }
-    if (p.c_prev) e_cp = p.c_prev[ebc * p.ldc_prev + eu];
-    if (p.drop) e_drop = p.drop[ebc * p.lddrop + eu];
-    if (p.len) e_len = p.len[ebc];
-    auto load_chunk = [&](int g, int j, f32x4 (&bw)[2], f32x4 (&ax)[2]) {
+    const FwdEpi epi = fwd_epi_load(p, eb, eu);      // hoisted: in flight during the GEMM
+    struct Chunk { f32x4 bw[2], ax[2]; };
+    auto load_chunk = [&](int g, int j, Chunk& k) {
         const int c = 4 * U * g + 4 * j + w;
         const int cx = c < NT ? c : NT - 1;     // padding chunks: any finite activations x the zero weight chunk
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) bw[ct] = *reinterpret_cast<const f32x4*>(wb[ct] + (long)c * 256);
+        for (int ct = 0; ct < 2; ++ct) k.bw[ct] = *reinterpret_cast<const f32x4*>(wb[ct] + (long)c * 256);
 #pragma unroll
-        for (int m = 0; m < 2; ++m) ax[m] = *reinterpret_cast<const f32x4*>(xb[m] + xcs * cx);
+        for (int m = 0; m < 2; ++m) k.ax[m] = *reinterpret_cast<const f32x4*>(xb[m] + xcs * cx);
     };
-    auto mma_chunk = [&](const f32x4 (&bw)[2], const f32x4 (&ax)[2]) {
+    auto mma_chunk = [&](const Chunk& k) {
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
-                    acc[m][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(ax[m][s], bw[ct][s], acc[m][ct], 0, 0, 0);
+                    acc[m][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(k.ax[m][s], k.bw[ct][s], acc[m][ct], 0, 0, 0);
     };
-    auto pipe_group = [&](int gl, f32x4 (&bwL)[U][2], f32x4 (&axL)[U][2], const f32x4 (&bwM)[U][2], const f32x4 (&axM)[U][2]) {
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            load_chunk(gl, j, bwL[j], axL[j]);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_chunk(bwM[j], axM[j]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    {
-        f32x4 bwA[U][2], bwB[U][2], axA[U][2], axB[U][2];
-#pragma unroll
-        for (int j = 0; j < U; ++j) load_chunk(0, j, bwA[j], axA[j]);
-        int g = 0;
-        for (; g + 2 < G; g += 2) {
-            pipe_group(g + 1, bwB, axB, bwA, axA);
-            pipe_group(g + 2, bwA, axA, bwB, axB);
-        }
-        if (g + 1 < G) {
-            pipe_group(g + 1, bwB, axB, bwA, axA);
-#pragma unroll
-            for (int j = 0; j < U; ++j) mma_chunk(bwB[j], axB[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < U; ++j) mma_chunk(bwA[j], axA[j]);
-        }
-    }
-    // C layout 16x16: col = lane&15 (gate column of the tile), row = (lane>>4)*4 + reg (batch row of the tile)
+    pipe_groups<U, Chunk>(G, load_chunk, mma_chunk, [] {});
+    // partial tile (row tile m, column tile ct) of wave w: 256 words at ((w*2 + m)*2 + ct) * 256
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -274,27 +445,7 @@ __global__ __launch_bounds__(256, 1) void lstm_step_fwd_sq_kernel(LstmK2 pp) {
     __syncthreads();
     if (eb < p.B) {
         const int m = bl >> 4, rl = bl & 15, ct = uu8 >> 2, uu = uu8 & 3;
-        float gsum[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float s = 0.f;
-#pragma unroll
-            for (int ww = 0; ww < 4; ++ww) s += red[(((ww * 2 + m) * 2 + ct) * 16 + rl) * 16 + g * 4 + uu];
-            gsum[g] = s + (p.pre ? e_pre[g] : 0.f) + (p.bias1 ? e_b1[g] : 0.f) + (p.bias2 ? e_b2[g] : 0.f);
-        }
-        if (!p.c_prev) e_cp = 0.f;
-        if (!p.drop) e_drop = 1.f;
-        if (!p.len) e_len = 0x7fffffff;
-        const bool active = p.t < e_len;
-        float gi = t2_sigmoid(gsum[0]), gf = t2_sigmoid(gsum[1]), gg = t2_tanh(gsum[2]), go = t2_sigmoid(gsum[3]);
-        float cn = gf * e_cp + gi * gg;
-        float hn = go * t2_tanh(cn) * e_drop;
-        if (!active) { hn = 0.f; cn = 0.f; gi = gf = gg = go = 0.f; }
-        p.h_out[(long)eb * p.ldh + eu] = hn;
-        if (p.h_out2) p.h_out2[(long)eb * p.ldh2 + eu] = hn;
-        if (p.ht_out) { const int col = p.ht_col0 + eu; p.ht_out[(long)(col >> 4) * p.xt_cs + eb * 16 + (col & 15)] = hn; }
-        if (p.c_out) p.c_out[(long)eb * p.ldc_out + eu] = cn;
-        if (p.gates_out) *reinterpret_cast<f32x4*>(p.gates_out + (long)eb * p.ldg + 4 * eu) = (f32x4){gi, gf, gg, go};
+        fwd_epi_store(p, eb, eu, fwd_cell<false>(epi, red + ((m * 2 + ct) * 16 + rl) * 16 + uu, 4 * 256, p.t));
     }
 }
 
@@ -463,19 +614,13 @@ __global__ __launch_bounds__(256, 1) void lstm_seq_persist_fwd_kernel(PersistK2 
             for (int g = 0; g < 4; ++g) red[((w * MT + m) * 16 + (q * 4 + g)) * 16 + r] = acc[m][g];
         __syncthreads();
         if (tid < MT * 64 && eb < p.B) {
-            float gsum[4];
+            FwdEpi e;                           // this step's operands, the biases loaded here: no registers to keep them in
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float sacc = 0.f;
-#pragma unroll
-                for (int ww = 0; ww < 4; ++ww) sacc += red[((ww * MT + (eb >> 4)) * 16 + (eb & 15)) * 16 + g * 4 + euu];
-                gsum[g] = sacc + e_pre[g] + (p.bias1 ? p.bias1[g * H + eu] : 0.f) + (p.bias2 ? p.bias2[g * H + eu] : 0.f);
-            }
-            const bool active = (p.t + s * pp.i_dt) < e_len;
-            float gi = t2_sigmoid(gsum[0]), gf = t2_sigmoid(gsum[1]), gg = t2_tanh(gsum[2]), go = t2_sigmoid(gsum[3]);
-            float cn = gf * c_reg + gi * gg;
-            float hn = go * t2_tanh(cn) * e_drop;
-            if (!active) { hn = 0.f; cn = 0.f; gi = gf = gg = go = 0.f; }
+            for (int g = 0; g < 4; ++g) e.pre[g] = e_pre[g];
+            e.cp = c_reg; e.drop = e_drop; e.len = e_len;
+            fwd_epi_load_bias(e, p, H, eu);
+            const FwdCell o = fwd_cell<false>(e, red + eb * 16 + euu, MT * 256, p.t + s * pp.i_dt);
+            const float hn = o.h, cn = o.c, gi = o.gi, gf = o.gf, gg = o.gg, go = o.go;
             c_reg = cn;
             (p.h_out + (long)s * pp.i_h_out)[(long)eb * p.ldh + eu] = hn;
             if (p.h_out2) (p.h_out2 + (long)s * pp.i_h_out2)[(long)eb * p.ldh2 + eu] = hn;
@@ -496,46 +641,6 @@ __global__ __launch_bounds__(256, 1) void lstm_seq_persist_fwd_kernel(PersistK2 
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
-
-
-__device__ __forceinline__ void bwd_epilogue(const BwdK& p, const float* red, int tid, int u0, int b0) {
-    {
-        const int bl = tid >> 4, ul = tid & 15;
-        const int b = b0 + bl, u = u0 + ul;
-        if (b < p.B && u < p.ncols) {
-            float dx = red[(0 * 16 + bl) * 16 + ul] + red[(1 * 16 + bl) * 16 + ul] + red[(2 * 16 + bl) * 16 + ul] +
-                       red[(3 * 16 + bl) * 16 + ul];
-            if (p.ext1) dx += p.ext1[(long)b * p.ldx1 + u];
-            if (p.ext2) dx += p.ext2[(long)b * p.ldx2 + u];
-            if (p.epi == 0) {
-                p.dx_out[(long)b * p.lddx + u] = dx;
-            } else {
-                const int H = p.H;
-                const bool active = (p.len == nullptr) || (p.t < p.len[b]);
-                float dh = dx;
-                if (p.drop) dh *= p.drop[(long)b * p.lddrop + u];
-                const f32x4 g4 = *reinterpret_cast<const f32x4*>(p.gates + (long)b * p.ldgs + 4 * u);
-                const float gi = g4[0], gf = g4[1], gg = g4[2], go = g4[3];
-                const float cp = p.c_prev ? p.c_prev[(long)b * p.ldcp + u] : 0.f;
-                const float tc = t2_tanh(p.c_cur[(long)b * p.ldcc + u]);
-                float dcv = p.dc[(long)b * p.lddc + u] + dh * go * (1.f - tc * tc);
-                float d_o = dh * tc * go * (1.f - go);
-                float d_i = dcv * gg * gi * (1.f - gi);
-                float d_f = dcv * cp * gf * (1.f - gf);
-                float d_g = dcv * gi * (1.f - gg * gg);
-                float dcp = dcv * gf;
-                if (!active) { d_i = d_f = d_g = d_o = 0.f; dcp = 0.f; }
-                p.dc[(long)b * p.lddc + u] = dcp;
-                float* dgo = p.dg_out + (long)b * p.ldgo + u;
-                dgo[0] = d_i; dgo[H] = d_f; dgo[2 * H] = d_g; dgo[3 * H] = d_o;
-                if (p.dg_out2) {
-                    float* dg2o = p.dg_out2 + (long)b * p.ldgo2 + u;
-                    dg2o[0] = d_i; dg2o[H] = d_f; dg2o[2 * H] = d_g; dg2o[3 * H] = d_o;
-                }
-            }
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(BwdK2 pp) {
     const BwdK& p = pp.s[blockIdx.z];
@@ -606,11 +711,52 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(BwdK2 pp) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) red[(w * 16 + (q * 4 + g)) * 16 + r] = acc0[g] + acc1[g];
     __syncthreads();
-    bwd_epilogue(p, red, tid, u0, b0);
+    bwd_epi_apply<4>(p, bwd_epi_load(p, tid, u0, b0), red, tid, u0, b0);
 }
 
 // Fast path of the backward step: ONE contiguous gradient row block dg[b][0:K) (K = N4 + N2) against the packed,
 // zero-padded transposed weight stream; same branch-free double-buffered structure as the forward fast path.
+// One 16 x 16 (batch x unit) tile of dx = dgates . W + epilogue; NW waves split K (NW*U must divide 32).
+template <int NW, int U>
+__device__ __forceinline__ void t2_lstm_bwd_fast_body(const BwdK& p, const int bx, const int by, float* red /* [NW*256] */) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, q = lane >> 4;
+    const int u0 = bx * 16, b0 = by * 16;
+    if (u0 >= p.ncols) return;   // descriptors of one launch may have different widths (whole workgroup exits)
+    // kinds: 0 = products (plain store), 1 = cell backward behind a short product (K < 4H), 2 = BPTT step (K = 4H + cell backward)
+    T2_RING_BEGIN(p.clk, bx == 0 && by == 0 && blockIdx.z == 0 && tid == 0, p.epi == 0 ? 0 : (p.N4 < 4 * p.H ? 1 : 2));
+    const int NCH = (p.N4 + p.N2) >> 4, NCHpad = (NCH + 31) & ~31, G = NCHpad / (NW * U);
+    const float* wb = p.wtpacked + (long)bx * NCHpad * 256 + lane * 4;
+    // x16-tiled gradients: one contiguous 1 KB block per (chunk, row tile) instead of 16 rows x 64 B
+    const float* ab = p.dgt ? p.dgt + (long)(b0 + r) * 16 + 4 * q
+                            : p.dg_next + (long)((b0 + r) < p.B ? (b0 + r) : 0) * p.lddg + 4 * q;
+    const long acs = p.dgt ? p.dgt_cs : 16;
+    const BwdEpi epi = bwd_epi_load(p, tid & 255, u0, b0);   // hoisted: in flight during the GEMM
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    struct Chunk { f32x4 a, b; };
+    auto load_chunk = [&](int g, int j, Chunk& k) {
+        const int c = NW * U * g + NW * j + w;
+        const int cx = c < NCH ? c : NCH - 1;   // padding chunks: finite gradients x the zero weight chunk
+        k.b = *reinterpret_cast<const f32x4*>(wb + (long)c * 256);
+        k.a = *reinterpret_cast<const f32x4*>(ab + acs * cx);
+    };
+    auto mma_chunk = [&](const Chunk& k) {
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(k.a[0], k.b[0], acc0, 0, 0, 0);
+        if (T2_CELL_MFMA_KEEP > 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(k.a[1], k.b[1], acc1, 0, 0, 0);
+        if (T2_CELL_MFMA_KEEP > 2) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(k.a[2], k.b[2], acc0, 0, 0, 0);
+        if (T2_CELL_MFMA_KEEP > 3) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(k.a[3], k.b[3], acc1, 0, 0, 0);
+    };
+    pipe_groups<U, Chunk>(G, load_chunk, mma_chunk, [&] { T2_RING(4); });   // (4: the first operands of this launch have arrived)
+    T2_RING(5);                              // main loop done
+#pragma unroll
+    for (int g = 0; g < 4; ++g) red[(w * 16 + (q * 4 + g)) * 16 + r] = acc0[g] + acc1[g];
+    __syncthreads();
+    T2_RING(6);                              // K shares of the waves in LDS
+    if (tid < 256) bwd_epi_apply<NW>(p, epi, red, tid, u0, b0);
+    T2_RING_END();
+}
+
 __global__ __launch_bounds__(256, 1) void lstm_step_bwd_fast_kernel(BwdK2 pp) {
     if (!pp.s[blockIdx.z].off_chain) T2_CHAIN_PRIO();
     __shared__ float red[4 * 256];
@@ -693,9 +839,6 @@ __global__ void lstm_pack_bwd_kernel(const float* W, long ldw, int N4, const flo
         *reinterpret_cast<f32x4*>(out + idx * 4) = v;
     }
 }
-
-template <typename T>
-inline void adv(T*& p, int64_t inc) { if (p) p += inc; }
 
 }  // namespace
 

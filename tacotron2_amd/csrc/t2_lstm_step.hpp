@@ -1,14 +1,7 @@
-// Kernel-side operand block of one LSTM cell step, its host conversion, and the device body of a step that is
-// CO-SCHEDULED inside another kernel's launch (shared by t2_lstm.hip and t2_attention.hip; no RDC needed).
+// Kernel-side operand blocks of one LSTM cell step (forward and backward) and their host-side checks and conversions from the
+// C ABI structs; the kernels that read them are in t2_lstm.hip.
 #pragma once
 #include "t2_common.hpp"
-
-// Diagnostic builds only (tacotron2_amd/build.py --variant): T2_CELL_MFMA_KEEP < 4 issues only that many of the four fp32 MFMA
-// k-substeps of every 16-deep chunk in the packed step kernels - WRONG RESULTS, same loads and epilogue - to bound what a faster
-// matrix path could buy these kernels (tools/ablate_cell_mfma.py).  The product build keeps all four.
-#ifndef T2_CELL_MFMA_KEEP
-#define T2_CELL_MFMA_KEEP 4
-#endif
 
 struct Seg { const float* x; long ldx; const float* w; long ldw; int K; };
 struct LstmK {
@@ -68,156 +61,7 @@ inline void t2_lstm_to_k(const T2LstmStep& s, LstmK& k, int b0, int bn) {
     k.ht_out = s.ht_out ? s.ht_out + (long)b0 * 16 : nullptr; k.ht_col0 = s.ht_col0;
 }
 
-
-// ------------------------------------------------------------------------------------------------------------------
-// Device body of one LSTM cell step on the packed path (256 threads: 4 waves split K; see t2_lstm.hip for the layout).
-// It is a function, not a kernel, so that a step can also be CO-SCHEDULED inside another kernel's launch
-// (t2_attention.hip: workgroups of the attention-context kernel and workgroups of an independent cell step share one
-// launch).  Why: every dependent launch costs ~2.7 us + a memory round trip, kernels of two streams do not overlap at
-// this size, and two cells in one launch take the sum of their times (same per-CU miss queue and MFMA pipe) - but a
-// cell step next to a latency-bound attention kernel uses otherwise idle pipes (tools/ubench_cell.hip).
-template <int MT, int U>
-__device__ __forceinline__ void t2_lstm_fwd_fast_body(const LstmK& p, const int bx, float* red /* [4*MT*256] */,
-                                                      unsigned long long* clk = nullptr /* diagnostic stamps [2..4] */) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const int u0 = bx * 4;
-    const int H = p.H;
-    const int NT = p.seg[0].K >> 4, NTpad = (NT + 15) & ~15, G = NTpad / (4 * U);   // host guarantees NTpad % (4U) == 0
-    const float* wb = p.wpacked + (long)bx * NTpad * 256 + lane * 4;
-    // x16-tiled input: chunk c, tile m is one contiguous 1 KB block (8 full cache lines per wave-load); row-major
-    // input: 16 rows x 64 B per wave-load (16 half lines - 3-4x slower through the vector memory pipe)
-    const float* xb[MT];
-    const long xcs = p.xt ? p.xt_cs : 16;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const int row = m * 16 + r;
-        // (tiled rows exist up to round_up(B, 16) of the WHOLE batch: a last row block of 33..48 rows has no fourth tile - its lanes
-        //  re-read the last existing row, and their products land in rows the epilogue drops)
-        xb[m] = p.xt ? p.xt + (long)(row < p.xt_rows ? row : p.xt_rows - 1) * 16 + 4 * q
-                     : p.seg[0].x + (long)(row < p.B ? row : 0) * p.seg[0].ldx + 4 * q;
-    }
-    f32x4 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // Epilogue operands (hoisted: issued now, consumed after the GEMM, so they never add a memory round trip)
-    const int eb = tid >> 2, euu = tid & 3, eu = u0 + euu;
-    const long ebc = eb < p.B ? eb : p.B - 1;
-    float e_pre[4] = {0.f, 0.f, 0.f, 0.f}, e_b1[4] = {0.f, 0.f, 0.f, 0.f}, e_b2[4] = {0.f, 0.f, 0.f, 0.f};
-    float e_cp = 0.f, e_drop = 1.f;
-    int e_len = 0x7fffffff;
-    auto load_epilogue_operands = [&]() {
-        if (p.pre) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) e_pre[g] = p.pre[ebc * p.ldpre + g * H + eu];
-        }
-        if (p.bias1) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) e_b1[g] = p.bias1[g * H + eu];
-        }
-        if (p.bias2) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) e_b2[g] = p.bias2[g * H + eu];
-        }
-        if (p.c_prev) e_cp = p.c_prev[ebc * p.ldc_prev + eu];
-        if (p.drop) e_drop = p.drop[ebc * p.lddrop + eu];
-        if (p.len) e_len = p.len[ebc];
-    };
-    load_epilogue_operands();
-    auto load_chunk = [&](int g, int j, f32x4& bw, f32x4 (&ax)[MT]) {
-        const int c = 4 * U * g + 4 * j + w;
-        const int cx = c < NT ? c : NT - 1;     // padding chunks: any finite activations x the zero weight chunk
-#ifdef T2_NT_WEIGHTS_MT1     // diagnostic build (A/B, profiles/r05_ab_decode_nt_weights.txt): once-read weight stream of the <= 16-row step
-        if (MT == 1) bw = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wb + (long)c * 256));
-        else
-#endif
-        bw = *reinterpret_cast<const f32x4*>(wb + (long)c * 256);
-#pragma unroll
-        for (int m = 0; m < MT; ++m) ax[m] = *reinterpret_cast<const f32x4*>(xb[m] + xcs * cx);
-    };
-    auto mma_chunk = [&](const f32x4& bw, const f32x4 (&ax)[MT]) {
-#pragma unroll
-        for (int s = 0; s < T2_CELL_MFMA_KEEP; ++s)
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(ax[m][s], bw[s], acc[m], 0, 0, 0);
-    };
-    // Software pipeline at chunk granularity: the loads of chunk j of group g+1 are issued right before the MFMAs of
-    // chunk j of group g, so the vector-memory pipe and the MFMA pipe are busy at the same time (a wave that issues a
-    // whole group of loads and then a whole group of MFMAs alternates between the two: 6.2 -> 5.3 us per step at
-    // K = 1536, tools/ubench_cell.hip).  ~U*(1+MT) loads stay in flight; sched_barrier pins the order, the loads are
-    // unconditional so the compiler's counted vmcnt waits stay exact.
-    auto pipe_group = [&](int gl, f32x4 (&bwL)[U], f32x4 (&axL)[U][MT], const f32x4 (&bwM)[U], const f32x4 (&axM)[U][MT]) {
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            load_chunk(gl, j, bwL[j], axL[j]);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_chunk(bwM[j], axM[j]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    {
-        f32x4 bwA[U], bwB[U], axA[U][MT], axB[U][MT];
-#pragma unroll
-        for (int j = 0; j < U; ++j) load_chunk(0, j, bwA[j], axA[j]);
-        int g = 0;
-        for (; g + 2 < G; g += 2) {
-            pipe_group(g + 1, bwB, axB, bwA, axA);
-            if (clk && g == 0) clk[2] = __builtin_amdgcn_s_memtime();     // group 0 consumed, group 1 requested
-            pipe_group(g + 2, bwA, axA, bwB, axB);
-        }
-        if (g + 1 < G) {
-            pipe_group(g + 1, bwB, axB, bwA, axA);
-#pragma unroll
-            for (int j = 0; j < U; ++j) mma_chunk(bwB[j], axB[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < U; ++j) mma_chunk(bwA[j], axA[j]);
-        }
-    }
-    if (clk) clk[3] = __builtin_amdgcn_s_memtime();
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) red[((w * MT + m) * 16 + (q * 4 + g)) * 16 + r] = acc[m][g];
-    __syncthreads();
-    if (clk) clk[4] = __builtin_amdgcn_s_memtime();
-    if (tid < MT * 64) {
-        const int b = eb, uu = euu;
-        if (b < p.B) {
-            const int u = eu;
-            float gsum[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float s = 0.f;
-#pragma unroll
-                for (int ww = 0; ww < 4; ++ww) s += red[((ww * MT + (b >> 4)) * 16 + (b & 15)) * 16 + g * 4 + uu];
-                gsum[g] = s + (p.pre ? e_pre[g] : 0.f) + (p.bias1 ? e_b1[g] : 0.f) + (p.bias2 ? e_b2[g] : 0.f);
-            }
-            if (!p.c_prev) e_cp = 0.f;
-            if (!p.drop) e_drop = 1.f;
-            if (!p.len) e_len = 0x7fffffff;
-            const bool active = p.t < e_len;
-            float gi = t2_sigmoid(gsum[0]), gf = t2_sigmoid(gsum[1]), gg = t2_tanh(gsum[2]), go = t2_sigmoid(gsum[3]);
-            float cn = gf * e_cp + gi * gg;
-            float hn = go * t2_tanh(cn) * e_drop;
-            if (!active) { hn = 0.f; cn = 0.f; gi = gf = gg = go = 0.f; }
-            p.h_out[(long)b * p.ldh + u] = hn;
-            if (p.h_out2) p.h_out2[(long)b * p.ldh2 + u] = hn;
-            if (p.ht_out) { const int col = p.ht_col0 + u; p.ht_out[(long)(col >> 4) * p.xt_cs + b * 16 + (col & 15)] = hn; }
-            if (p.c_out) p.c_out[(long)b * p.ldc_out + u] = cn;
-            if (p.gates_out) {
-                // gate-interleaved stash [b][u][4] = (i, f, g, o): one 16-byte store per thread, 64 contiguous bytes per 4 units
-                *reinterpret_cast<f32x4*>(p.gates_out + (long)b * p.ldg + 4 * u) = (f32x4){gi, gf, gg, go};
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Backward step on the packed path (see t2_lstm.hip); shared so that a BPTT step can be co-scheduled inside the attention
-// backward launch (t2_attention.hip).
+// Backward step: dx = dgates . W over one or two K segments, then a plain store (epi 0) or the cell's pointwise backward (epi 1).
 struct BwdK {
     int B, H, N4;                       // N4 = reduction length (4H of the producing cell)
     const float* dg_next; long lddg;    // [b][N4] or null (no recurrent contribution)
@@ -270,135 +114,4 @@ inline int t2_lstm_check_bwd(const T2LstmBwdStep& s) {
         T2_REQUIRE(s.dx_out != nullptr, "lstm bwd step: dx_out required");
     }
     return T2_OK;
-}
-
-
-struct BwdEpi { float ext, drop, gi, gf, gg, go, cp, cc, dc; int len; };
-
-__device__ __forceinline__ BwdEpi bwd_epi_load(const BwdK& p, int tid, int u0, int b0) {
-    BwdEpi e;
-    const int bl = tid >> 4, ul = tid & 15;
-    const long b = (b0 + bl) < p.B ? (b0 + bl) : p.B - 1;
-    const int u = (u0 + ul) < p.ncols ? (u0 + ul) : p.ncols - 1;
-    e.ext = 0.f; e.drop = 1.f; e.gi = e.gf = e.gg = e.go = 0.f; e.cp = 0.f; e.cc = 0.f; e.dc = 0.f; e.len = 0x7fffffff;
-    if (p.ext1) e.ext = p.ext1[b * p.ldx1 + u];
-    if (p.ext2) e.ext += p.ext2[b * p.ldx2 + u];
-    if (p.epi == 1) {
-        if (p.drop) e.drop = p.drop[b * p.lddrop + u];
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(p.gates + b * p.ldgs + 4 * u);   // gate-interleaved stash [b][u][4]
-        e.gi = g4[0]; e.gf = g4[1]; e.gg = g4[2]; e.go = g4[3];
-        if (p.c_prev) e.cp = p.c_prev[b * p.ldcp + u];
-        e.cc = p.c_cur[b * p.ldcc + u];
-        e.dc = p.dc[b * p.lddc + u];
-        if (p.len) e.len = p.len[b];
-    }
-    return e;
-}
-
-template <int NW>
-__device__ __forceinline__ void bwd_epi_apply(const BwdK& p, const BwdEpi& e, const float* red, int tid, int u0, int b0) {
-    const int bl = tid >> 4, ul = tid & 15;
-    const int b = b0 + bl, u = u0 + ul;
-    if (b < p.B && u < p.ncols) {
-        float dx = e.ext;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) dx += red[(ww * 16 + bl) * 16 + ul];
-        if (p.epi == 0) {
-            p.dx_out[(long)b * p.lddx + u] = dx;
-        } else {
-            const int H = p.H;
-            const bool active = p.t < e.len;
-            const float dh = dx * e.drop;
-            const float tc = t2_tanh(e.cc);
-            const float dcv = e.dc + dh * e.go * (1.f - tc * tc);
-            float d_o = dh * tc * e.go * (1.f - e.go);
-            float d_i = dcv * e.gg * e.gi * (1.f - e.gi);
-            float d_f = dcv * e.cp * e.gf * (1.f - e.gf);
-            float d_g = dcv * e.gi * (1.f - e.gg * e.gg);
-            float dcp = dcv * e.gf;
-            if (!active) { d_i = d_f = d_g = d_o = 0.f; dcp = 0.f; }
-            p.dc[(long)b * p.lddc + u] = dcp;
-            float* dgo = p.dg_out + (long)b * p.ldgo + u;
-            dgo[0] = d_i; dgo[H] = d_f; dgo[2 * H] = d_g; dgo[3 * H] = d_o;
-            if (p.dg_out2) {
-                float* dg2o = p.dg_out2 + (long)b * p.ldgo2 + u;
-                dg2o[0] = d_i; dg2o[H] = d_f; dg2o[2 * H] = d_g; dg2o[3 * H] = d_o;
-            }
-            if (p.dgt_out) {   // H % 16 == 0 (checked on the host): the four gate columns share (u & 15)
-                float* dt_ = p.dgt_out + (long)(u >> 4) * p.dgt_cs + b * 16 + (u & 15);
-                const long gs = (long)(H >> 4) * p.dgt_cs;
-                dt_[0] = d_i; dt_[gs] = d_f; dt_[2 * gs] = d_g; dt_[3 * gs] = d_o;
-            }
-        }
-    }
-}
-
-// One 16 x 16 (batch x unit) tile of dx = dgates . W on the packed path + epilogue; NW waves split K (NW*U must divide 32).
-template <int NW, int U>
-__device__ __forceinline__ void t2_lstm_bwd_fast_body(const BwdK& p, const int bx, const int by, float* red /* [NW*256] */) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const int u0 = bx * 16, b0 = by * 16;
-    if (u0 >= p.ncols) return;   // descriptors of one launch may have different widths (whole workgroup exits)
-    // kinds: 0 = products (plain store), 1 = cell backward behind a short product (K < 4H), 2 = BPTT step (K = 4H + cell backward)
-    T2_RING_BEGIN(p.clk, bx == 0 && by == 0 && blockIdx.z == 0 && tid == 0, p.epi == 0 ? 0 : (p.N4 < 4 * p.H ? 1 : 2));
-    const int NCH = (p.N4 + p.N2) >> 4, NCHpad = (NCH + 31) & ~31, G = NCHpad / (NW * U);
-    const float* wb = p.wtpacked + (long)bx * NCHpad * 256 + lane * 4;
-    // x16-tiled gradients: one contiguous 1 KB block per (chunk, row tile) instead of 16 rows x 64 B
-    const float* ab = p.dgt ? p.dgt + (long)(b0 + r) * 16 + 4 * q
-                            : p.dg_next + (long)((b0 + r) < p.B ? (b0 + r) : 0) * p.lddg + 4 * q;
-    const long acs = p.dgt ? p.dgt_cs : 16;
-    const BwdEpi epi = bwd_epi_load(p, tid & 255, u0, b0);   // hoisted: in flight during the GEMM
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    auto load_chunk = [&](int g, int j, f32x4& a, f32x4& b) {
-        const int c = NW * U * g + NW * j + w;
-        const int cx = c < NCH ? c : NCH - 1;   // padding chunks: finite gradients x the zero weight chunk
-        b = *reinterpret_cast<const f32x4*>(wb + (long)c * 256);
-        a = *reinterpret_cast<const f32x4*>(ab + acs * cx);
-    };
-    auto mma_chunk = [&](const f32x4& a, const f32x4& b) {
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], acc0, 0, 0, 0);
-        if (T2_CELL_MFMA_KEEP > 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], acc1, 0, 0, 0);
-        if (T2_CELL_MFMA_KEEP > 2) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], acc0, 0, 0, 0);
-        if (T2_CELL_MFMA_KEEP > 3) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], acc1, 0, 0, 0);
-    };
-    // chunk-granular software pipeline (see the forward kernel)
-    auto pipe_group = [&](int gl, f32x4 (&aL)[U], f32x4 (&bL)[U], const f32x4 (&aM)[U], const f32x4 (&bM)[U]) {
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            load_chunk(gl, j, aL[j], bL[j]);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_chunk(aM[j], bM[j]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    {
-        f32x4 aA[U], bA[U], aB[U], bB[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) load_chunk(0, j, aA[j], bA[j]);
-        int g = 0;
-        for (; g + 2 < G; g += 2) {
-            pipe_group(g + 1, aB, bB, aA, bA);
-#ifdef T2_STAMPS
-            if (g == 0) T2_RING(4);          // group 0 consumed: the first operands of this launch have arrived
-#endif
-            pipe_group(g + 2, aA, bA, aB, bB);
-        }
-        if (g + 1 < G) {
-            pipe_group(g + 1, aB, bB, aA, bA);
-#pragma unroll
-            for (int j = 0; j < U; ++j) mma_chunk(aB[j], bB[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < U; ++j) mma_chunk(aA[j], bA[j]);
-        }
-    }
-    T2_RING(5);                              // main loop done
-#pragma unroll
-    for (int g = 0; g < 4; ++g) red[(w * 16 + (q * 4 + g)) * 16 + r] = acc0[g] + acc1[g];
-    __syncthreads();
-    T2_RING(6);                              // K shares of the waves in LDS
-    if (tid < 256) bwd_epi_apply<NW>(p, epi, red, tid, u0, b0);
-    T2_RING_END();
 }

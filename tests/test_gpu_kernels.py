@@ -197,22 +197,30 @@ def test_split_gemm_is_as_accurate_as_f32_mfma(dev, layout):
 
 @pytest.mark.parametrize("B,H,Ks", [(3, 32, (16, 32)), (32, 1024, (512, 1024)), (64, 256, (256,)), (17, 64, (16, 32, 64))])
 def test_lstm_step_fwd(dev, B, H, Ks):
+    """The generic (segment-walking) kernel with every epilogue operand: two biases, dropout mask, lengths (rows past theirs
+    give exact zeros in h, c and the four stashed gates) and the second h copy with its own leading dimension."""
     from tacotron2_amd import _lib
     g = torch.Generator().manual_seed(B + H)
     xs = [torch.randn(B, K, generator=g) for K in Ks]
     Ws = [torch.randn(4 * H, K, generator=g) / (K ** 0.5) for K in Ks]
     pre = torch.randn(B, 4 * H, generator=g); b1 = torch.randn(4 * H, generator=g)
     c0 = torch.randn(B, H, generator=g); drop = (torch.rand(B, H, generator=g) > 0.1).float() / 0.9
-    gates = pre.double() + b1.double()
+    b2 = torch.randn(4 * H, generator=g)
+    lens = torch.tensor([3 if i % 4 == 1 else 9 for i in range(B)], dtype=torch.int32)
+    t = 5
+    act = (t < lens)[:, None]
+    assert bool(act.any()) and not bool(act.all())
+    gates = pre.double() + b1.double() + b2.double()
     for x, W in zip(xs, Ws):
         gates = gates + x.double() @ W.double().t()
     h_ref, c_ref = R.lstm_cell(gates, c0.double())
-    h_ref = h_ref * drop.double()
+    h_ref = h_ref * drop.double() * act; c_ref = c_ref * act
     xd = [x.to(dev) for x in xs]; Wd = [W.to(dev) for W in Ws]
     h = torch.empty(B, H, device=dev); c = torch.empty(B, H, device=dev); gs = torch.empty(B, 4 * H, device=dev)
-    st = _lib.make("T2LstmStep", B=B, H=H, nseg=len(Ks), pre=pre.to(dev), ldpre=4 * H, bias1=b1.to(dev),
-                   c_prev=c0.to(dev), ldc_prev=H, drop=drop.to(dev), lddrop=H, h_out=h, ldh=H, c_out=c, ldc_out=H,
-                   gates_out=gs, ldg=4 * H)
+    h2 = torch.full((B, H + 8), -7.0, device=dev)
+    st = _lib.make("T2LstmStep", B=B, H=H, nseg=len(Ks), pre=pre.to(dev), ldpre=4 * H, bias1=b1.to(dev), bias2=b2.to(dev),
+                   c_prev=c0.to(dev), ldc_prev=H, drop=drop.to(dev), lddrop=H, h_out=h, ldh=H, h_out2=h2, ldh2=H + 8,
+                   c_out=c, ldc_out=H, gates_out=gs, ldg=4 * H, len=lens.to(dev), t=t)
     keep = [st.pre, st.bias1]
     for i, (x, W) in enumerate(zip(xd, Wd)):
         st.seg[i].x = x.data_ptr(); st.seg[i].ldx = x.shape[1]; st.seg[i].w = W.data_ptr(); st.seg[i].ldw = W.shape[1]
@@ -220,8 +228,12 @@ def test_lstm_step_fwd(dev, B, H, Ks):
     _lib.call("t2_lstm_step_fwd", st, 1, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert _rel(h, h_ref) < 5e-6 and _rel(c, c_ref) < 5e-6
-    i_ref = 1 / (1 + torch.exp(-gates[:, :H]))
+    i_ref = 1 / (1 + torch.exp(-gates[:, :H])) * act
     assert _rel(gs.view(B, H, 4)[:, :, 0], i_ref) < 5e-6      # gate-interleaved stash [b][u][4] = (i, f, g, o)
+    off = ~act[:, 0]
+    assert float(h.cpu()[off].abs().max()) == 0.0 and float(c.cpu()[off].abs().max()) == 0.0
+    assert float(gs.cpu()[off].abs().max()) == 0.0            # all four gates of the rows past their length
+    assert torch.equal(h2[:, :H], h) and float((h2[:, H:] + 7.0).abs().max()) == 0.0
 
 
 def _tile16(x, Bp):
@@ -237,10 +249,13 @@ def _untile16(xt, B):
     return xt[:, :B].permute(1, 0, 2).reshape(B, nch * 16)
 
 
-@pytest.mark.parametrize("B,H,Ks,col0", [(32, 1024, (1024, 512), 0), (5, 64, (48,), 16), (64, 128, (128, 64), 0), (19, 32, (32,), 32)])
+@pytest.mark.parametrize("B,H,Ks,col0", [(32, 1024, (1024, 512), 0), (5, 64, (48,), 16), (64, 128, (128, 64), 0), (19, 32, (32,), 32),
+                                          (35, 64, (64,), 0)])
 def test_lstm_step_fwd_packed_tiled(dev, B, H, Ks, col0):
     """Packed weight stream + x16-tiled activations in / tiled h out (the product path of the frame loop) against float64;
-    the tiled input holds NaN in the rows >= B, which must not leak into any output row."""
+    the tiled input holds NaN in the rows >= B, which must not leak into any output row.  Every epilogue operand and output is
+    in: dropout mask, lengths, gate stash, second h copy.  (64, 128) takes the square-tile kernel, and so does (35, 64), whose
+    last row block (rows 32..34) has no fourth tile."""
     from tacotron2_amd import _lib
     g = torch.Generator().manual_seed(B * 7 + H)
     K = sum(Ks)
@@ -248,12 +263,15 @@ def test_lstm_step_fwd_packed_tiled(dev, B, H, Ks, col0):
     Ws = [torch.randn(4 * H, k, generator=g) / (K ** 0.5) for k in Ks]
     pre = torch.randn(B, 4 * H, generator=g); b1 = torch.randn(4 * H, generator=g); b2 = torch.randn(4 * H, generator=g)
     c0 = torch.randn(B, H, generator=g)
+    drop = (torch.rand(B, H, generator=g) > 0.1).float() / 0.9
     lens = torch.tensor([3 if i % 4 == 1 else 9 for i in range(B)], dtype=torch.int32)
     t = 5
     gates = pre.double() + b1.double() + b2.double() + x.double() @ torch.cat(Ws, 1).double().t()
     h_ref, c_ref = R.lstm_cell(gates, c0.double())
     act = (t < lens)[:, None]
-    h_ref = h_ref * act; c_ref = c_ref * act
+    h_ref = h_ref * drop.double() * act; c_ref = c_ref * act
+    gi, gf, gg, go = [gates[:, i * H:(i + 1) * H] for i in range(4)]
+    gs_ref = torch.stack([torch.sigmoid(gi), torch.sigmoid(gf), torch.tanh(gg), torch.sigmoid(go)], 2) * act[:, :, None]
     st_ = torch.cuda.current_stream().cuda_stream
     Wd = [W.to(dev) for W in Ws]
     segs = (_lib.S["T2Seg"] * len(Ks))()
@@ -269,27 +287,69 @@ def test_lstm_step_fwd_packed_tiled(dev, B, H, Ks, col0):
     Ht = (col0 + H + 15) // 16 * 16
     ht = torch.full((Ht // 16, Bp, 16), -7.0, device=dev)
     h = torch.empty(B, H, device=dev); c = torch.empty(B, H, device=dev); xd = x.to(dev)
-    keep = [pre.to(dev), b1.to(dev), b2.to(dev), c0.to(dev), lens.to(dev)]
+    gs = torch.empty(B, 4 * H, device=dev); hc = torch.full((B, H + 8), -7.0, device=dev)
+    keep = [pre.to(dev), b1.to(dev), b2.to(dev), c0.to(dev), lens.to(dev), drop.to(dev)]
     st = _lib.make("T2LstmStep", B=B, H=H, nseg=1, wpacked=wp, pre=keep[0], ldpre=4 * H, bias1=keep[1], bias2=keep[2],
-                   c_prev=keep[3], ldc_prev=H, h_out=h, ldh=H, c_out=c, ldc_out=H, len=keep[4], t=t, xt=xt, ht_out=ht,
-                   ht_col0=col0)
+                   c_prev=keep[3], ldc_prev=H, drop=keep[5], lddrop=H, h_out=h, ldh=H, h_out2=hc, ldh2=H + 8, c_out=c, ldc_out=H,
+                   gates_out=gs, ldg=4 * H, len=keep[4], t=t, xt=xt, ht_out=ht, ht_col0=col0)
     st.seg[0].x = xd.data_ptr(); st.seg[0].ldx = K; st.seg[0].K = K
     _lib.call("t2_lstm_step_fwd", st, 1, st_)
     torch.cuda.synchronize()
     assert _rel(h, h_ref) < 5e-6 and _rel(c, c_ref) < 5e-6
+    assert _rel(gs.view(B, H, 4), gs_ref) < 5e-6               # gate-interleaved stash [b][u][4] = (i, f, g, o)
+    assert torch.equal(hc[:, :H], h) and float((hc[:, H:] + 7.0).abs().max()) == 0.0
     got_t = _untile16(ht.cpu(), B)
     assert torch.equal(got_t[:, col0:col0 + H], h.cpu())       # the tiled copy holds the same values
     if col0:
         assert float((got_t[:, :col0] + 7.0).abs().max()) == 0.0   # other columns untouched
     # row-major activations through the same packed kernel give the same result (different load pattern only)
-    h2 = torch.empty(B, H, device=dev)
-    st.xt = None; st.ht_out = None; st.h_out = h2.data_ptr()
+    h2 = torch.empty(B, H, device=dev); c2 = torch.empty(B, H, device=dev); gs2 = torch.empty(B, 4 * H, device=dev)
+    st.xt = None; st.ht_out = None; st.h_out = h2.data_ptr(); st.c_out = c2.data_ptr(); st.gates_out = gs2.data_ptr()
     _lib.call("t2_lstm_step_fwd", st, 1, st_)
     torch.cuda.synchronize()
+    assert _rel(h2, h_ref) < 5e-6 and _rel(c2, c_ref) < 5e-6 and _rel(gs2.view(B, H, 4), gs_ref) < 5e-6
+    assert torch.equal(hc[:, :H], h2)
     if B <= 32:
         assert torch.equal(h2, h)
     else:      # 33..64 rows: the tiled input takes the 32 x 32-tile kernel, row-major input the 64 x 16 one - same sums, two kernels
         assert _rel(h2, h.double().cpu()) < 1e-6
+
+
+def test_lstm_step_fwd_two_cells_mixed_paths_write_the_tiled_copy(dev):
+    """Two cells in one launch, one packed with a tiled h copy and one with plain weights: the launch takes the generic kernel
+    for both, and the first cell's tiled copy is written all the same (it shares the stores of the packed kernels)."""
+    from tacotron2_amd import _lib
+    B, H, K, col0 = 19, 32, 32, 16
+    g = torch.Generator().manual_seed(77)
+    st_ = torch.cuda.current_stream().cuda_stream
+    Bp = (B + 15) // 16 * 16
+    steps = (_lib.S["T2LstmStep"] * 2)()
+    keep, hs, refs = [], [], []
+    ht = torch.full(((col0 + H) // 16, Bp, 16), -7.0, device=dev)
+    for i in range(2):
+        x = torch.randn(B, K, generator=g); W = torch.randn(4 * H, K, generator=g) / (K ** 0.5)
+        pre = torch.randn(B, 4 * H, generator=g); c0 = torch.randn(B, H, generator=g)
+        h_ref, _ = R.lstm_cell(pre.double() + x.double() @ W.double().t(), c0.double())
+        xd, Wd, pd, cd = x.to(dev), W.to(dev), pre.to(dev), c0.to(dev)
+        h = torch.empty(B, H, device=dev)
+        wp = None
+        if i == 0:
+            seg = (_lib.S["T2Seg"] * 1)()
+            seg[0].w = Wd.data_ptr(); seg[0].ldw = K; seg[0].K = K
+            wp = torch.empty(H // 4 * 16 * 256, device=dev)
+            _lib.call("t2_lstm_pack_fwd", seg, 1, H, wp, st_)
+        st = _lib.make("T2LstmStep", B=B, H=H, nseg=1, wpacked=wp, pre=pd, ldpre=4 * H, c_prev=cd, ldc_prev=H, h_out=h, ldh=H,
+                       xt=_tile16(x, Bp).to(dev) if i == 0 else None, ht_out=ht if i == 0 else None, ht_col0=col0)
+        st.seg[0].x = xd.data_ptr(); st.seg[0].ldx = K; st.seg[0].w = Wd.data_ptr(); st.seg[0].ldw = K; st.seg[0].K = K
+        keep += [xd, Wd, pd, cd, wp, st]
+        steps[i] = st
+        hs.append(h); refs.append(h_ref)
+    _lib.call("t2_lstm_step_fwd", steps, 2, st_)
+    torch.cuda.synchronize()
+    for h, h_ref in zip(hs, refs):
+        assert _rel(h, h_ref) < 5e-6
+    got_t = _untile16(ht.cpu(), B)
+    assert torch.equal(got_t[:, col0:col0 + H], hs[0].cpu()) and float((got_t[:, :col0] + 7.0).abs().max()) == 0.0
 
 
 @pytest.mark.parametrize("B,H,S", [(32, 1024, 9), (5, 64, 6), (17, 128, 4), (64, 1024, 5), (35, 128, 4)])
@@ -349,10 +409,21 @@ def test_lstm_seq_fwd_persistent_matches_step_launches(dev, B, H, S):
         assert _rel(_untile16(outs["persistent"][3][s + 1].cpu(), B), hs_ref[s]) < 2e-5
 
 
-@pytest.mark.parametrize("B,H,N4", [(32, 1024, 4096), (7, 48, 192), (33, 64, 256)])
+def _cell_bwd_ref(dh, gates, cp, cc, dc0, H):
+    """float64 pointwise cell backward: gates [B, 4H] gate-major (i, f, g, o) activations -> (dgates [B, 4H], dc_prev)."""
+    gi, gf, gg, go = [gates[:, i * H:(i + 1) * H].double() for i in range(4)]
+    tc = torch.tanh(cc.double())
+    dcv = dc0.double() + dh * go * (1 - tc * tc)
+    return torch.cat([dcv * gg * gi * (1 - gi), dcv * cp.double() * gf * (1 - gf), dcv * gi * (1 - gg * gg), dh * tc * go * (1 - go)], 1), dcv * gf
+
+
+@pytest.mark.parametrize("B,H,N4", [(32, 1024, 4096), (7, 48, 192), (33, 64, 256), (17, 528, 64)])
 def test_lstm_step_bwd_packed_tiled(dev, B, H, N4):
     """dx = dgates . W + pointwise cell backward on the packed path with x16-tiled gradients in and out, against the same
-    step with row-major operands (bit-identical) and float64."""
+    step with row-major operands (bit-identical) and float64; with a dropout mask, lengths (rows past theirs give exact zeros
+    in the four gate gradients and in dc) and the second gradient copy.  (7, 48) and (33, 64) run the 8-wave kernel; (17, 528)
+    is 33 x 2 = 66 workgroups, above the 64-workgroup switch: the 4-wave kernel, as (32, 1024).  Then the plain-store
+    products (epi = 0) of two descriptors of different widths in one call."""
     from tacotron2_amd import _lib
     g = torch.Generator().manual_seed(B + N4)
     W = torch.randn(N4, H, generator=g) / (N4 ** 0.5)
@@ -360,6 +431,11 @@ def test_lstm_step_bwd_packed_tiled(dev, B, H, N4):
     ext = torch.randn(B, H, generator=g)
     gates = torch.rand(B, 4 * H, generator=g) * 0.8 + 0.1
     cp = torch.randn(B, H, generator=g); cc = torch.randn(B, H, generator=g); dc0 = torch.randn(B, H, generator=g)
+    drop = (torch.rand(B, H, generator=g) > 0.1).float() / 0.9
+    lens = torch.tensor([3 if i % 4 == 1 else 9 for i in range(B)], dtype=torch.int32)
+    t = 5
+    act = (t < lens)[:, None]
+    assert bool(act.any()) and not bool(act.all())
     st_ = torch.cuda.current_stream().cuda_stream
     Wd = W.to(dev)
     nchpad = (N4 // 16 + 31) // 32 * 32
@@ -371,22 +447,97 @@ def test_lstm_step_bwd_packed_tiled(dev, B, H, N4):
     for tiled in (False, True):
         dc = dc0.clone().to(dev)
         dgo = torch.empty(B, 4 * H, device=dev)
+        dgo2 = torch.full((B, 2 * 4 * H), -7.0, device=dev)
         dgo_t = torch.zeros(4 * H // 16, Bp, 16, device=dev) if tiled else None
-        keep = [dg.to(dev), ext.to(dev), gates.view(B, 4, H).transpose(1, 2).contiguous().view(B, 4 * H).to(dev), cp.to(dev), cc.to(dev)]
+        keep = [dg.to(dev), ext.to(dev), gates.view(B, 4, H).transpose(1, 2).contiguous().view(B, 4 * H).to(dev), cp.to(dev), cc.to(dev),
+                drop.to(dev), lens.to(dev)]
         s = _lib.make("T2LstmBwdStep", B=B, H=H, N4=N4, dg_next=keep[0], lddg=N4, W=Wd, ldw=H, wtpacked=wtp, ncols=H, epi=1,
-                      ext1=keep[1], ldx1=H, gates=keep[2], ldgs=4 * H, c_prev=keep[3], ldcp=H, c_cur=keep[4], ldcc=H,
-                      dc=dc, lddc=H, dg_out=dgo, ldgo=4 * H, dgt_next=dgt if tiled else None, dgt_out=dgo_t)
+                      ext1=keep[1], ldx1=H, drop=keep[5], lddrop=H, gates=keep[2], ldgs=4 * H, c_prev=keep[3], ldcp=H,
+                      c_cur=keep[4], ldcc=H, dc=dc, lddc=H, dg_out=dgo, ldgo=4 * H, dg_out2=dgo2, ldgo2=2 * 4 * H,
+                      len=keep[6], t=t, dgt_next=dgt if tiled else None, dgt_out=dgo_t)
         _lib.call("t2_lstm_step_bwd", s, 1, st_)
         torch.cuda.synchronize()
+        assert torch.equal(dgo2[:, :4 * H], dgo) and float((dgo2[:, 4 * H:] + 7.0).abs().max()) == 0.0
         res.append((dgo.cpu(), dc.cpu(), None if dgo_t is None else _untile16(dgo_t.cpu(), B)))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert torch.equal(res[1][2], res[1][0])
-    dh = dg.double() @ W.double() + ext.double()
-    gi, gf, gg, go = [gates[:, i * H:(i + 1) * H].double() for i in range(4)]
-    tc = torch.tanh(cc.double())
-    dcv = dc0.double() + dh * go * (1 - tc * tc)
-    ref = torch.cat([dcv * gg * gi * (1 - gi), dcv * cp.double() * gf * (1 - gf), dcv * gi * (1 - gg * gg), dh * tc * go * (1 - go)], 1)
-    assert _rel(res[1][0], ref) < 5e-6 and _rel(res[1][1], dcv * gf) < 5e-6
+    dh = (dg.double() @ W.double() + ext.double()) * drop.double()
+    ref, dcp_ref = _cell_bwd_ref(dh, gates, cp, cc, dc0, H)
+    assert _rel(res[1][0], ref * act) < 5e-6 and _rel(res[1][1], dcp_ref * act) < 5e-6
+    off = ~act[:, 0]
+    assert float(res[1][0][off].abs().max()) == 0.0 and float(res[1][1][off].abs().max()) == 0.0
+    # epi = 0: two descriptors of different widths in ONE call (the workgroups past the narrower one's columns exit), each
+    # with both external addends
+    widths = (40, 64)
+    steps = (_lib.S["T2LstmBwdStep"] * 2)()
+    keep2, outs = [dg.to(dev)], []
+    for i, nc in enumerate(widths):
+        Wn = torch.randn(N4, nc, generator=g) / (N4 ** 0.5)
+        e1 = torch.randn(B, nc, generator=g); e2 = torch.randn(B, nc, generator=g)
+        Wnd, e1d, e2d = Wn.to(dev), e1.to(dev), e2.to(dev)
+        wtn = torch.empty((nc + 15) // 16 * nchpad * 256, device=dev)
+        _lib.call("t2_lstm_pack_bwd", Wnd, nc, N4, None, 0, 0, nc, wtn, st_)
+        dx = torch.full((B, nc + 8), -7.0, device=dev)
+        steps[i] = _lib.make("T2LstmBwdStep", B=B, H=H, N4=N4, dg_next=keep2[0], lddg=N4, W=Wnd, ldw=nc, wtpacked=wtn, ncols=nc,
+                             epi=0, ext1=e1d, ldx1=nc, ext2=e2d, ldx2=nc, dx_out=dx, lddx=nc + 8)
+        keep2 += [Wnd, wtn, e1d, e2d]          # (the array holds a copy of the struct, not its operand tensors)
+        outs.append((dx, dg.double() @ Wn.double() + e1.double() + e2.double()))
+    _lib.call("t2_lstm_step_bwd", steps, 2, st_)
+    torch.cuda.synchronize()
+    for (dx, dx_ref), nc in zip(outs, widths):
+        assert _rel(dx[:, :nc], dx_ref) < 5e-6 and float((dx[:, nc:] + 7.0).abs().max()) == 0.0
+
+
+def test_lstm_step_bwd_generic_matches_packed(dev):
+    """The generic (unpacked-weights) backward kernel and the packed one share the pointwise cell: the same inputs through
+    both - two external addends (summed before the K shares of the waves in both), dropout mask, lengths, second gradient
+    copy - against float64 at the bound of the packed test, with and without the recurrent product, and as plain products."""
+    from tacotron2_amd import _lib
+    B, H, N4 = 19, 48, 192
+    g = torch.Generator().manual_seed(B + N4 + 1)
+    W = torch.randn(N4, H, generator=g) / (N4 ** 0.5)
+    dg = torch.randn(B, N4, generator=g)
+    e1 = torch.randn(B, H, generator=g); e2 = torch.randn(B, H, generator=g)
+    gates = torch.rand(B, 4 * H, generator=g) * 0.8 + 0.1
+    cp = torch.randn(B, H, generator=g); cc = torch.randn(B, H, generator=g); dc0 = torch.randn(B, H, generator=g)
+    drop = (torch.rand(B, H, generator=g) > 0.1).float() / 0.9
+    lens = torch.tensor([3 if i % 4 == 1 else 9 for i in range(B)], dtype=torch.int32)
+    t = 5
+    act = (t < lens)[:, None]
+    st_ = torch.cuda.current_stream().cuda_stream
+    Wd = W.to(dev)
+    wtp = torch.empty((H + 15) // 16 * ((N4 // 16 + 31) // 32 * 32) * 256, device=dev)
+    _lib.call("t2_lstm_pack_bwd", Wd, H, N4, None, 0, 0, H, wtp, st_)
+    keep = [dg.to(dev), e1.to(dev), e2.to(dev), gates.view(B, 4, H).transpose(1, 2).contiguous().view(B, 4 * H).to(dev), cp.to(dev),
+            cc.to(dev), drop.to(dev), lens.to(dev)]
+
+    def run(packed, epi, recurrent=True):
+        dc = dc0.clone().to(dev)
+        dgo = torch.empty(B, 4 * H, device=dev); dgo2 = torch.full((B, 2 * 4 * H), -7.0, device=dev); dx = torch.empty(B, H, device=dev)
+        s = _lib.make("T2LstmBwdStep", B=B, H=H, N4=N4, dg_next=keep[0] if recurrent else None, lddg=N4, W=Wd, ldw=H,
+                      wtpacked=wtp if packed else None, ncols=H, epi=epi, ext1=keep[1], ldx1=H, ext2=keep[2], ldx2=H,
+                      dx_out=dx, lddx=H, drop=keep[6], lddrop=H, gates=keep[3], ldgs=4 * H, c_prev=keep[4], ldcp=H,
+                      c_cur=keep[5], ldcc=H, dc=dc, lddc=H, dg_out=dgo, ldgo=4 * H, dg_out2=dgo2, ldgo2=2 * 4 * H, len=keep[7], t=t)
+        _lib.call("t2_lstm_step_bwd", s, 1, st_)
+        torch.cuda.synchronize()
+        if epi == 0:
+            return dx.cpu()
+        assert torch.equal(dgo2[:, :4 * H], dgo) and float((dgo2[:, 4 * H:] + 7.0).abs().max()) == 0.0
+        return dgo.cpu(), dc.cpu()
+
+    ext = e1.double() + e2.double()
+    dx_ref = dg.double() @ W.double() + ext
+    off = ~act[:, 0]
+    for packed in (False, True):
+        assert _rel(run(packed, 0), dx_ref) < 5e-6
+        dgo, dc = run(packed, 1)
+        ref, dcp_ref = _cell_bwd_ref(dx_ref * drop.double(), gates, cp, cc, dc0, H)
+        assert _rel(dgo, ref * act) < 5e-6 and _rel(dc, dcp_ref * act) < 5e-6
+        assert float(dgo[off].abs().max()) == 0.0 and float(dc[off].abs().max()) == 0.0
+    # no recurrent product (the last step of a sequence): only the generic kernel takes a step without dg_next
+    dgo, dc = run(False, 1, recurrent=False)
+    ref, dcp_ref = _cell_bwd_ref(ext * drop.double(), gates, cp, cc, dc0, H)
+    assert _rel(dgo, ref * act) < 5e-6 and _rel(dc, dcp_ref * act) < 5e-6
 
 
 def test_lstm_step_bwd_matches_autograd(dev):
