@@ -490,8 +490,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_bf16(GemmK p) {
     // (Chan's update).  No atomics: every (tile, column) has one writer.
     if (p.stat_out) {
         __syncthreads();                                         // (the staging buffers are free: every wave is past its last read)
-        float* sh = reinterpret_cast<float*>(smem);              // [128] shift, then [2 sums][2 wm][128]
-        float* red = sh + 128;
+        float* sh = reinterpret_cast<float*>(smem);              // [128] shift, then [2 sums][2 wm][128] doubles
+        double* red = reinterpret_cast<double*>(sh + 128);
         const int Lp = p.stat_Lp, Lv = p.stat_L;
         auto valid = [&](int row) { return row < p.M && (row % Lp) < Lv; };
         int rv = 0;                                              // first valid row of the tile (junk runs are Lp - L rows long)
@@ -536,13 +536,17 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_bf16(GemmK p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const float sft = sh[wn * 64 + j * 32 + li];
-            float a = 0.f, q = 0.f;
+            // The tile's sums are accumulated in double and rounded to float once, at the store: the merge forms
+            // sum d^2 - (sum d)^2 / n, which amplifies their error by 1 + k^2 when the tile's first valid row lies k standard deviations
+            // off the column mean; with float partial sums a layer of two or three tiles missed 3e-6 in 1/std (3.35e-6 measured
+            // at 225 rows, tests/test_gpu_conv_path_kernels.py), with these the same case gives 8.2e-7
+            double a = 0.0, q = 0.0;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float dv = ((vmask >> (i * 16 + r)) & 1u) ? value(i, j, r) - sft : 0.f;
-                    a += dv; q = fmaf(dv, dv, q);
+                    const double dv = ((vmask >> (i * 16 + r)) & 1u) ? (double)(value(i, j, r) - sft) : 0.0;
+                    a += dv; q = fma(dv, dv, q);
                 }
             a += __shfl_xor(a, 32); q += __shfl_xor(q, 32);       // the two lane halves hold the other rows of the column
             if (lh == 0) { red[(0 * 2 + wm) * 128 + wn * 64 + j * 32 + li] = a; red[(1 * 2 + wm) * 128 + wn * 64 + j * 32 + li] = q; }
@@ -551,8 +555,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_bf16(GemmK p) {
         if (tid < 128 && n0 + tid < p.N) {
             float* o = p.stat_out + (long)tm * 3 * p.N + n0 + tid;
             o[0] = sh[tid];
-            o[p.N] = red[(0 * 2 + 0) * 128 + tid] + red[(0 * 2 + 1) * 128 + tid];
-            o[2 * (long)p.N] = red[(1 * 2 + 0) * 128 + tid] + red[(1 * 2 + 1) * 128 + tid];
+            o[p.N] = (float)(red[(0 * 2 + 0) * 128 + tid] + red[(0 * 2 + 1) * 128 + tid]);
+            o[2 * (long)p.N] = (float)(red[(1 * 2 + 0) * 128 + tid] + red[(1 * 2 + 1) * 128 + tid]);
         }
     }
 }
