@@ -114,6 +114,15 @@ typedef struct {
      * ht_out: tiled copy of h written at columns [ht_col0, ht_col0 + H) of a tiled matrix with the same Bp. */
     const float* xt;
     float* ht_out; int ht_col0;
+    /* Zoneout (Krueger et al. 2017; ESPnet's ZoneOutCell), optional: with c~ and h~ the cell's results as above (h~ post-dropout),
+     *   c' = zone_c * c_prev + (1 - zone_c) * c~ ;   h' = zone_h * h_prev + (1 - zone_h) * h~
+     * are what every output carries (h_out, h_out2, ht_out, c_out; gates_out keeps the activated gates).  Masks are [B][H] floats
+     * in [0, 1]: 0/1 draws in training (t2_philox_bernoulli), the rate itself in eval - one formula for both.  Either mask may be
+     * NULL (reads as 0); with both NULL the step is exactly the step without these fields.  h_prev [B][H] is required with a
+     * mask and may alias h_out (a thread reads only the element it then writes).  Masks together with `len` are an error. */
+    const float* zone_h; int64_t ldzone_h;
+    const float* zone_c; int64_t ldzone_c;
+    const float* h_prev; int64_t ldh_prev;
 } T2LstmStep;
 /* n = 1 or 2 independent cells in one launch (the two directions of the encoder BiLSTM). */
 int t2_lstm_step_fwd(const T2LstmStep* steps, int n, void* stream);
@@ -133,6 +142,7 @@ int t2_lstm_pack_bwd(const float* W, int64_t ldw, int N4, const float* W2, int64
 typedef struct {
     int64_t seg_x[3]; int64_t pre, c_prev, drop, h_out, h_out2, c_out, gates_out; int dt;
     int64_t xt, ht_out;
+    int64_t zone_h, zone_c, h_prev;  /* 0 = the same [B][H] block at every step (eval: a block filled with the rate) */
 } T2LstmStride;
 int t2_lstm_seq_fwd(const T2LstmStep* base, const T2LstmStride* inc, int n, int S, void* stream);
 /* The same S steps of ONE cell as ONE persistent, weight-stationary launch (csrc/t2_lstm.hip): every workgroup keeps its
@@ -143,7 +153,9 @@ int t2_lstm_seq_fwd(const T2LstmStep* base, const T2LstmStride* inc, int n, int 
  * of step s), inc->xt == inc->ht_out.  h_out2 (a second plain copy of h with its own stride) is written when given.
  * sync: >= 272 device words of scratch; words [0, 256) are the arrival counters (zeroed by every launch), word 256 is the
  * timeout flag: zeroed by the CALLER before first use and sticky - a wait that timed out (bounded spins) sets it, every launch
- * that sees it ends early (outputs unusable) until the caller has read and cleared it. */
+ * that sees it ends early (outputs unusable) until the caller has read and cleared it.
+ * Zoneout: the kernel keeps h of its own (row, unit) in a register across the steps as it keeps c; h_prev is read ONCE, at the first
+ * step of the launch (inc->h_prev is not used). */
 int t2_lstm_seq_fwd_persist(const T2LstmStep* base, const T2LstmStride* inc, int S, uint32_t* sync, void* stream);
 /* n = 1 or 2 INDEPENDENT cells of the same B and H in one persistent launch (grid.y = n; base[i], inc[i]): the two directions of
  * the encoder BiLSTM (model/encoder.py:47-52), each walking its own way through time (inc[i] may be negative; base[i].len and
@@ -216,9 +228,19 @@ typedef struct {
     int off_chain;                          /* 1: this step is NOT on the critical chain of its stream schedule (the decoder-LSTM BPTT,
                                                a chunk ahead on the side stream): its waves keep the default issue priority instead
                                                of the chain kernels' raised one */
+    /* Zoneout (T2LstmStep), epi = 1 only.  With Dh = (dx + ext1 + ext2) + dhz and Dc = dc going in:
+     *   dh~ = (1 - zone_h) * Dh * drop ;  dhz <- zone_h * Dh  (the share of h_{t-1}, read by the next launch = step t-1)
+     *   tc  = tanh(c~), c~ = f * c_prev + i * g RECOMPUTED from the stash (where zone_c > 0, c_cur is not c~; c_cur is not read)
+     *   dc~ = (1 - zone_c) * Dc + dh~ * o * (1 - tc^2) ;  d_o = dh~ * tc * o (1 - o) ;  d_i, d_f, d_g from dc~ as without masks
+     *   dc <- dc~ * f + zone_c * Dc
+     * dhz [B][H] is an in/out carry like dc (the caller zero-fills both before the last step), required with a mask.  With both
+     * masks NULL, dhz is not touched and the step is exactly the step without these fields.  Not together with `len`. */
+    const float* zone_h; int64_t ldzone_h;
+    const float* zone_c; int64_t ldzone_c;
+    float* dhz; int64_t lddhz;
 } T2LstmBwdStep;
 int t2_lstm_step_bwd(const T2LstmBwdStep* steps, int n, void* stream);
-typedef struct { int64_t dg, dg2, ext1, ext2, drop, gates, c_prev, c_cur; int dt; int64_t dgt; } T2LstmBwdStride;
+typedef struct { int64_t dg, dg2, ext1, ext2, drop, gates, c_prev, c_cur; int dt; int64_t dgt; int64_t zone_h, zone_c; } T2LstmBwdStride;
 /* S steps; every pointer advances by its stride each step.  The caller lays the dgates stash out with one extra
  * zero-filled slot so that base[i].dg_next (the slot 'after' the first processed step) is valid and zero. */
 int t2_lstm_seq_bwd(const T2LstmBwdStep* base, const T2LstmBwdStride* inc, int n, int S, void* stream);
@@ -388,6 +410,19 @@ int t2_attn_seq_bwd_stash(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_sta
  * its layout.) */
 int t2_attn_seq_bwd_forward(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, float* dprior, void* stream);
 int t2_attn_acc_bwd(const T2AttnSeqBwd* a, const float* de_stash, int64_t ld_stash, int t_begin, int t_end, void* stream);
+/* Zoneout on the attention-LSTM cell of the chain (T2LstmStep.zone_h / zone_c).  The masks travel as an operand block of their own, as
+ * the stash and the forward-attention workspace travel as arguments: `forward` stays the last field of T2AttnSeq and `dalign` the last
+ * of T2AttnSeqBwd, which the ABI tests of those two options assert (tests/test_forward_attention_chain_host.py,
+ * tests/test_guided_attention_host.py: the field's offset against the struct's size).
+ *   zone_h, zone_c: frame t reads the [B][A] block at zone_x + t * stride (stride 0 = one block for every frame: eval); either may be
+ *                   NULL.  h_prev of frame t is slot t of xdec; att_c then holds the zoned c and xdec the zoned h.
+ *   dhz           : backward only, required with a mask: in/out carry [B][A] (T2LstmBwdStep.dhz), zero-filled by the caller where dc
+ *                   is.  The cell backward of the chain adds it where it forms dh = dh_rec + dq.Wq.
+ * t2_attn_seq_fwd_zone is t2_attn_seq_fwd with the masks; t2_attn_seq_bwd_zone is t2_attn_seq_bwd_stash (de_stash may be NULL) or, with
+ * dprior != NULL, t2_attn_seq_bwd_forward, with the masks.  z == NULL or both masks NULL: exactly those calls. */
+typedef struct { const float* zone_h; const float* zone_c; int64_t stride; float* dhz; } T2AttnZone;
+int t2_attn_seq_fwd_zone(const T2AttnSeq* a, const T2AttnZone* z, void* stream);
+int t2_attn_seq_bwd_zone(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, float* dprior, const T2AttnZone* z, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Conv stacks (encoder model/encoder.py:31-46,57; postnet model/postnet.py:8-49).
@@ -549,6 +584,12 @@ typedef struct {
                                         cumulative weights kept in place in cum slot 0 (slot 1 unused) */
     int forward;                     /* 0 = off; else forward attention in every frame (T2AttnStep.forward; frame 0 starts from the
                                         one-hot prior).  Not together with win_peak */
+    float zone_p;                    /* zoneout rate of both cells in decoding (the expectation rule: every mask element is the rate);
+                                        0 = off.  Otherwise zone_att [B][A] and zone_dec [B][D] are blocks the caller has FILLED with
+                                        zone_p (each serves as zone_h and zone_c of its cell).  The cells write h in place (att_h, the
+                                        dec_h columns of xproj), so h_prev aliases h_out - a thread reads only the element it then
+                                        writes; both buffers must therefore be zero-filled before frame 0, like the c slots */
+    const float* zone_att; const float* zone_dec;
 } T2Infer;
 int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream);
 /* proj[g] [nframes][Bg[g]][ld_proj] for g < ngroups (<= 64 groups of up to 64 utterances) -> lengths [sum Bg] int64,
@@ -626,6 +667,8 @@ int t2_logmel_batch_fwd(const float* wavs, int64_t ld_wav, const int64_t* n_dev,
 /* dropout scale masks (Philox4x32-10, counter = element index) and the optimizer of model/tts_model.py:78-91 +
  * Lightning gradient_clip_val=1.0 (run/train.py:240) on one flat fp32 parameter buffer. */
 int t2_philox_mask(float* out, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream);
+/* zoneout masks: 1 with probability p, else 0 - no rescaling; the same counter convention (0 <= p <= 1) */
+int t2_philox_bernoulli(float* out, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream);
 int t2_sumsq(const float* g, int64_t n, double* out, void* stream);
 /* A step whose global gradient norm (sumsq) is NaN or infinite is SKIPPED: parameters and moments stay as they are (the
  * reference would write NaN into every weight, torch clip_grad_norm_ + Adam; there is nothing to match in that state). */

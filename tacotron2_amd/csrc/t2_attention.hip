@@ -685,7 +685,7 @@ extern "C" int t2_attn_step_fwd(const T2AttnStep* s, void* stream) {
 }
 
 // Teacher-forced attention chain over frames [t_begin, t_end): per frame  attention-LSTMCell -> energies -> softmax/context.
-extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) {
+static int attn_seq_fwd(const T2AttnSeq* a, const T2AttnZone* z, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(a != nullptr, "t2_attn_seq_fwd: null");
     hipStream_t st = (hipStream_t)stream;
@@ -717,6 +717,9 @@ extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) {
         s.h_out = slot1; s.ldh = ldx;
         s.c_out = a->att_c + (long)(t + 1) * B * A; s.ldc_out = A;
         if (a->gates) { s.gates_out = a->gates + (long)t * B * 4 * A; s.ldg = 4 * A; }
+        if (z && z->zone_h) { s.zone_h = z->zone_h + (long)t * z->stride; s.ldzone_h = A; }
+        if (z && z->zone_c) { s.zone_c = z->zone_c + (long)t * z->stride; s.ldzone_c = A; }
+        if (s.zone_h || s.zone_c) { s.h_prev = slot; s.ldh_prev = ldx; }
         T2_TRY(t2_lstm_step_fwd_launch(&s, 1, st));
 
         T2AttnStep q;
@@ -739,6 +742,8 @@ extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) {
     }
     return T2_OK;
 }
+extern "C" int t2_attn_seq_fwd(const T2AttnSeq* a, void* stream) { return attn_seq_fwd(a, nullptr, stream); }
+extern "C" int t2_attn_seq_fwd_zone(const T2AttnSeq* a, const T2AttnZone* z, void* stream) { return attn_seq_fwd(a, z, stream); }
 
 // =================================================================================================
 // Backward through one attention frame (autograd of the kernels above), again spread over many CUs.
@@ -1351,7 +1356,7 @@ size_t ds_mfma_lds(int L, int mode = DS_FULL) {
 }  // namespace
 
 static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, void* stream, const bool forward = false,
-                        float* dprior = nullptr) {
+                        float* dprior = nullptr, const T2AttnZone* z = nullptr) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(a != nullptr, "t2_attn_seq_bwd: null");
     T2_REQUIRE(a->Kl == KL && a->Ad % 16 == 0 && a->Ef % 32 == 0, "t2_attn_seq_bwd: unsupported dims");
@@ -1443,6 +1448,9 @@ static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, v
         c.c_prev = a->att_c + (long)t * B * A; c.ldcp = A;
         c.c_cur = a->att_c + (long)(t + 1) * B * A; c.ldcc = A;
         c.dc = a->dc; c.lddc = A;
+        if (z && z->zone_h) { c.zone_h = z->zone_h + (long)t * z->stride; c.ldzone_h = A; }
+        if (z && z->zone_c) { c.zone_c = z->zone_c + (long)t * z->stride; c.ldzone_c = A; }
+        if (z) { c.dhz = z->dhz; c.lddhz = A; }
         c.dg_out = Z + (long)t * B * ldz; c.ldgo = ldz;
         if (a->dgates_t) c.dgt_out = a->dgates_t + (long)t * zts;
         T2_TRY(t2_lstm_step_bwd_launch(&c, 1, st, (unsigned long long*)a->clk));
@@ -1452,6 +1460,10 @@ static int attn_seq_bwd(const T2AttnSeqBwd* a, float* de_stash, long ld_stash, v
 }
 
 extern "C" int t2_attn_seq_bwd(const T2AttnSeqBwd* a, void* stream) { return attn_seq_bwd(a, nullptr, 0, stream); }
+extern "C" int t2_attn_seq_bwd_zone(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, float* dprior, const T2AttnZone* z,
+                                    void* stream) {
+    return attn_seq_bwd(a, de_stash, (long)ld_stash, stream, dprior != nullptr, dprior, z);
+}
 
 extern "C" int t2_attn_seq_bwd_stash(const T2AttnSeqBwd* a, float* de_stash, int64_t ld_stash, void* stream) {
     return attn_seq_bwd(a, de_stash, (long)ld_stash, stream);

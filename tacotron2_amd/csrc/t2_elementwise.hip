@@ -634,6 +634,21 @@ __global__ void philox_mask_kernel(float* out, long n, float p, uint64_t seed, u
     }
 }
 
+// zoneout mask: 1 with probability p, 0 otherwise, no rescaling; the same generator, counter and uniform as above
+__global__ void philox_bernoulli_kernel(float* out, long n, float p, uint64_t seed, uint64_t stream_id) {
+    const long n4 = (n + 3) / 4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        uint32_t r[4];
+        t2_philox4((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32), (uint32_t)seed,
+                   (uint32_t)(seed >> 32), r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long e = 4 * i + j;
+            if (e < n) out[e] = (float)(r[j] >> 8) * (1.0f / 16777216.0f) < p ? 1.f : 0.f;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // optimizer: global-norm clip + Adam with L2-in-gradient weight decay on one flat fp32 buffer
 // ---------------------------------------------------------------------------------------------
@@ -1018,6 +1033,13 @@ extern "C" int t2_philox_mask(float* out, int64_t n, float p, uint64_t seed, uin
     T2_REQUIRE(out && n >= 0 && p >= 0.f && p < 1.f, "t2_philox_mask: bad arguments");
     if (n == 0) return T2_OK;
     hipLaunchKernelGGL(philox_mask_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, ST, out, (long)n, p, seed, stream_id);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_philox_bernoulli(float* out, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(out && n >= 0 && p >= 0.f && p <= 1.f, "t2_philox_bernoulli: bad arguments");
+    if (n == 0) return T2_OK;
+    hipLaunchKernelGGL(philox_bernoulli_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, ST, out, (long)n, p, seed, stream_id);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_sumsq(const float* g, int64_t n, double* out, void* stream) {

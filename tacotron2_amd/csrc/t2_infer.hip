@@ -280,6 +280,9 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
     T2_REQUIRE(a->W_comb && a->W_pre2 && a->proj && a->xs, "t2_decoder_infer: null operand");
     T2_REQUIRE(!a->win_peak || (a->win_back >= 0 && a->win_fwd >= 0), "t2_decoder_infer: attention window bounds must be >= 0");
     T2_REQUIRE(!(a->forward && a->win_peak), "t2_decoder_infer: forward attention does not compose with the attention window");
+    T2_REQUIRE(a->zone_p >= 0.f && a->zone_p <= 1.f && (a->zone_p == 0.f || (a->zone_att && a->zone_dec)),
+               "t2_decoder_infer: zone_p in [0, 1], with the two filled blocks zone_att and zone_dec");
+    const bool zoned = a->zone_p != 0.f;
     const long ldp = D + Ef, ldo = a->ld_proj;
     const int Bp = (B + 15) / 16 * 16;
     const long cs = (long)Bp * 16;                               // chunk stride of the tiled state
@@ -333,6 +336,7 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
         s.h_out = a->att_h; s.ldh = A;
         s.ht_out = xs_nxt; s.ht_col0 = P;
         s.c_out = a->att_c + (long)((t + 1) & 1) * B * A; s.ldc_out = A;
+        if (zoned) { s.zone_h = s.zone_c = a->zone_att; s.ldzone_h = s.ldzone_c = A; s.h_prev = a->att_h; s.ldh_prev = A; }
         T2_TRY(t2_lstm_step_fwd_launch(&s, 1, st));
         // attention
         T2AttnStep q;
@@ -364,6 +368,7 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
         d.h_out = a->xproj; d.ldh = ldp;
         d.ht_out = xs_cur; d.ht_col0 = P + A + Ef;
         d.c_out = a->dec_c + (long)((t + 1) & 1) * B * D; d.ldc_out = D;
+        if (zoned) { d.zone_h = d.zone_c = a->zone_dec; d.ldzone_h = d.ldzone_c = D; d.h_prev = a->xproj; d.ldh_prev = ldp; }
         T2_TRY(t2_lstm_step_fwd_launch(&d, 1, st));
     }
     if (t1 > t0) {

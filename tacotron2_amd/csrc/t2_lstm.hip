@@ -44,6 +44,8 @@ inline void adv(T*& p, int64_t inc) { if (p) p += inc; }
 struct FwdEpi {      // (as initialised: what absent operands read as)
     float pre[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f}, b2[4] = {0.f, 0.f, 0.f, 0.f}, cp = 0.f, drop = 1.f;
     int len = 0x7fffffff;
+    float zh = 0.f, zc = 0.f, hp = 0.f;      // zoneout: the two masks and the previous h
+    bool zoned = false;                      // a mask was given (uniform over the launch)
 };
 struct FwdCell { float h, c, gi, gf, gg, go; };
 
@@ -62,6 +64,10 @@ __device__ __forceinline__ void fwd_epi_load_bias(FwdEpi& e, const LstmK& p, int
 // Operands of the thread that owns (row b, unit u).  The row is clamped, so every thread may issue the loads: the packed
 // kernels do so BEFORE the GEMM (hoisted: consumed after it, they never add a memory round trip).  Absent operands read as
 // 0 (pre, biases, c_prev), 1 (drop) and INT_MAX (len).
+// ZONED: the kernel was instantiated for launches with zone masks; without it the zoneout operands cost no register and no branch
+// (the instantiation is the code from before the masks existed: four more registers in the packed kernels were 0.5 ms per training
+// step on the bench, where the chain kernels share their CUs with the side stream's)
+template <bool ZONED>
 __device__ __forceinline__ FwdEpi fwd_epi_load(const LstmK& p, int b, int u) {
     FwdEpi e;
     const int H = p.H;
@@ -74,6 +80,12 @@ __device__ __forceinline__ FwdEpi fwd_epi_load(const LstmK& p, int b, int u) {
     if (p.c_prev) e.cp = p.c_prev[bc * p.ldc_prev + u];
     if (p.drop) e.drop = p.drop[bc * p.lddrop + u];
     if (p.len) e.len = p.len[bc];
+    e.zoned = ZONED;
+    if (ZONED) {
+        if (p.zone_h) e.zh = p.zone_h[bc * p.ldzh + u];
+        if (p.zone_c) e.zc = p.zone_c[bc * p.ldzc + u];
+        e.hp = p.h_prev[bc * p.ldhp + u];
+    }
     return e;
 }
 
@@ -82,6 +94,9 @@ __device__ __forceinline__ FwdEpi fwd_epi_load(const LstmK& p, int b, int u) {
 // of the sums: (((waves 0..3) + pre) + bias1) + bias2.  Rows past their length (t >= len) give exact zeros.
 // FUSED_C: c = fma(gf, c_prev, gi * gg) - what the compiler had made of the packed kernel's c = gf * c_prev + gi * gg, and of no
 // other kernel's.  Each keeps its rounding, now spelled out, so that every kernel's results stay what they were bit for bit.
+// Zoneout (e.zoned: a mask was given): the carried state is c = zc * c_prev + (1 - zc) * c~, h = zh * h_prev + (1 - zh) * h~ with
+// h~ = o * tanh(c~) * drop - one formula for 0/1 and fractional masks.  Without masks nothing is added to the arithmetic (a
+// multiplication by a zero mask would turn the -0 of a dropped h into +0).
 template <bool FUSED_C>
 __device__ __forceinline__ FwdCell fwd_cell(const FwdEpi& e, const float* red, int wstride, int t) {
     float gsum[4];
@@ -101,6 +116,10 @@ __device__ __forceinline__ FwdCell fwd_cell(const FwdEpi& e, const float* red, i
         o.c = o.gf * e.cp + o.gi * o.gg;
     }
     o.h = o.go * t2_tanh(o.c) * e.drop;
+    if (e.zoned) {
+        o.c = e.zc * e.cp + (1.f - e.zc) * o.c;
+        o.h = e.zh * e.hp + (1.f - e.zh) * o.h;
+    }
     if (!(t < e.len)) { o.h = 0.f; o.c = 0.f; o.gi = o.gf = o.gg = o.go = 0.f; }
     return o;
 }
@@ -117,15 +136,17 @@ __device__ __forceinline__ void fwd_epi_store(const LstmK& p, int b, int u, cons
 // ---------------------------------------------------------------------------------------------------------
 // The backward pointwise cell, shared by every backward kernel: thread tid owns (row b0 + tid/16, column u0 + tid%16).
 // ---------------------------------------------------------------------------------------------------------
-struct BwdEpi { float ext, drop, gi, gf, gg, go, cp, cc, dc; int len; };
+struct BwdEpi { float ext, drop, gi, gf, gg, go, cp, cc, dc; int len; float zh, zc, dhz; };
 
 // (row and column clamped: every thread may issue the loads, the packed kernels do so before the GEMM)
+template <bool ZONED>
 __device__ __forceinline__ BwdEpi bwd_epi_load(const BwdK& p, int tid, int u0, int b0) {
     BwdEpi e;
     const int bl = tid >> 4, ul = tid & 15;
     const long b = (b0 + bl) < p.B ? (b0 + bl) : p.B - 1;
     const int u = (u0 + ul) < p.ncols ? (u0 + ul) : p.ncols - 1;
     e.ext = 0.f; e.drop = 1.f; e.gi = e.gf = e.gg = e.go = 0.f; e.cp = 0.f; e.cc = 0.f; e.dc = 0.f; e.len = 0x7fffffff;
+    e.zh = e.zc = e.dhz = 0.f;
     if (p.ext1) e.ext = p.ext1[b * p.ldx1 + u];
     if (p.ext2) e.ext += p.ext2[b * p.ldx2 + u];
     if (p.epi == 1) {
@@ -136,12 +157,19 @@ __device__ __forceinline__ BwdEpi bwd_epi_load(const BwdK& p, int tid, int u0, i
         e.cc = p.c_cur[b * p.ldcc + u];
         e.dc = p.dc[b * p.lddc + u];
         if (p.len) e.len = p.len[b];
+        if (ZONED && p.zone_h) e.zh = p.zone_h[b * p.ldzh + u];
+        if (ZONED && p.zone_c) e.zc = p.zone_c[b * p.ldzc + u];
+        if (ZONED && (p.zone_h || p.zone_c)) e.dhz = p.dhz[b * p.lddhz + u];
     }
     return e;
 }
 
-// dx = (ext1 + ext2) + the K shares of waves 0..NW-1 from LDS, in that order; then the plain store or the cell backward
-template <int NW>
+// dx = (ext1 + ext2) + the K shares of waves 0..NW-1 from LDS, in that order; then the plain store or the cell backward.
+// Zoneout (a mask was given): Dh = dx + dhz; dh~ = (1 - zh) Dh drop and dhz <- zh Dh; tanh of c~ RECOMPUTED from the stash (the
+// stored c_cur is zc c_prev + (1 - zc) c~, not c~) with the rounding of the forward kernel of the same path - FUSED_C: the packed
+// kernels' fma, else the separate product and sum (the square-tile and persistent forwards round c~ that way too; against the
+// packed backward their c~ can differ by one ulp); dc~ = (1 - zc) Dc + ...; dc <- dc~ f + zc Dc.
+template <int NW, bool FUSED_C, bool ZONED>
 __device__ __forceinline__ void bwd_epi_apply(const BwdK& p, const BwdEpi& e, const float* red, int tid, int u0, int b0) {
     const int bl = tid >> 4, ul = tid & 15;
     const int b = b0 + bl, u = u0 + ul;
@@ -154,14 +182,32 @@ __device__ __forceinline__ void bwd_epi_apply(const BwdK& p, const BwdEpi& e, co
         } else {
             const int H = p.H;
             const bool active = p.t < e.len;
-            const float dh = dx * e.drop;
-            const float tc = t2_tanh(e.cc);
-            const float dcv = e.dc + dh * e.go * (1.f - tc * tc);
+            // ONE copy of the derivative below, fed by selected inputs: without masks every expression is the one it was before the
+            // masks existed, used as often as it was, so the compiler contracts it as it did and the results keep their bits (a
+            // second, zoned copy of the same expressions shares sub-expressions with the first and changes what gets fused)
+            const bool zoned = ZONED && (p.zone_h || p.zone_c);     // (per descriptor: the two of one launch may differ)
+            float dh = dx * e.drop, cc = e.cc, dcin = e.dc;
+            if (zoned) {
+                const float Dh = dx + e.dhz;
+                dh = (1.f - e.zh) * Dh * e.drop;
+                p.dhz[(long)b * p.lddhz + u] = e.zh * Dh;
+                float fc = e.gf * e.cp, ig = e.gi * e.gg;
+                if (FUSED_C) {
+                    cc = __builtin_fmaf(e.gf, e.cp, ig);
+                } else {      // both products rounded before the sum: opaque to the contraction of the back end
+                    asm volatile("" : "+v"(fc), "+v"(ig));
+                    cc = fc + ig;
+                }
+                dcin = (1.f - e.zc) * e.dc;
+            }
+            const float tc = t2_tanh(cc);
+            const float dcv = dcin + dh * e.go * (1.f - tc * tc);
             float d_o = dh * tc * e.go * (1.f - e.go);
             float d_i = dcv * e.gg * e.gi * (1.f - e.gi);
             float d_f = dcv * e.cp * e.gf * (1.f - e.gf);
             float d_g = dcv * e.gi * (1.f - e.gg * e.gg);
             float dcp = dcv * e.gf;
+            if (zoned) dcp += e.zc * e.dc;
             if (!active) { d_i = d_f = d_g = d_o = 0.f; dcp = 0.f; }
             p.dc[(long)b * p.lddc + u] = dcp;
             float* dgo = p.dg_out + (long)b * p.ldgo + u;
@@ -218,7 +264,7 @@ __device__ __forceinline__ void pipe_groups(const int G, const Load& load_chunk,
     }
 }
 
-template <int MT>
+template <int MT, bool ZONED>
 __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmK2 pp) {
     const LstmK& p = pp.s[blockIdx.y];
     __shared__ float red[4 * MT * 256];
@@ -302,7 +348,7 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmK2 pp) {
         for (int g = 0; g < 4; ++g) red[((w * MT + m) * 16 + (q * 4 + g)) * 16 + r] = acc[m][g];
     __syncthreads();
     const int b = tid >> 2, u = u0 + (tid & 3);      // tile b>>4, its row b&15: word b*16 of a wave's share
-    if (tid < MT * 64 && b < p.B) fwd_epi_store(p, b, u, fwd_cell<false>(fwd_epi_load(p, b, u), red + b * 16 + (tid & 3), MT * 256, p.t));
+    if (tid < MT * 64 && b < p.B) fwd_epi_store(p, b, u, fwd_cell<false>(fwd_epi_load<ZONED>(p, b, u), red + b * 16 + (tid & 3), MT * 256, p.t));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -311,7 +357,7 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmK2 pp) {
 // real K multiply the all-zero padding chunks of the weight stream with (clamped, finite) activations, so no guard, select
 // or wait sits between a load and the next load: two groups (2 x 12 x 1 KB per wave) are in flight while one is in the MFMAs.
 // ---------------------------------------------------------------------------------------------------------
-template <int MT, int U>
+template <int MT, int U, bool ZONED>
 __device__ __forceinline__ void t2_lstm_fwd_fast_body(const LstmK& p, const int bx, float* red /* [4*MT*256] */,
                                                       unsigned long long* clk = nullptr /* diagnostic stamps [2..4] */) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -336,7 +382,7 @@ __device__ __forceinline__ void t2_lstm_fwd_fast_body(const LstmK& p, const int 
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int eb = tid >> 2, eu = u0 + (tid & 3);
-    const FwdEpi epi = fwd_epi_load(p, eb, eu);      // hoisted: in flight during the GEMM
+    const FwdEpi epi = fwd_epi_load<ZONED>(p, eb, eu);      // hoisted: in flight during the GEMM
     struct Chunk { f32x4 bw, ax[MT]; };
     auto load_chunk = [&](int g, int j, Chunk& k) {
         const int c = 4 * U * g + 4 * j + w;
@@ -367,17 +413,17 @@ __device__ __forceinline__ void t2_lstm_fwd_fast_body(const LstmK& p, const int 
     if (tid < MT * 64 && eb < p.B) fwd_epi_store(p, eb, eu, fwd_cell<true>(epi, red + eb * 16 + (tid & 3), MT * 256, p.t));
 }
 
-template <int MT, int U>
+template <int MT, int U, bool ZONED>
 __global__ __launch_bounds__(256, 1) void lstm_step_fwd_fast_kernel(LstmK2 pp) {
     T2_CHAIN_PRIO();
     __shared__ float red[4 * MT * 256];
 #ifdef T2_STAMPS      // diagnostic build only: every stamp is a branch the instruction scheduler does not move work across
     const bool stamp = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && g_t2_clk_enable;
     if (stamp) { g_t2_clk[0] = __builtin_amdgcn_s_memtime(); g_t2_clk[1] = __builtin_amdgcn_s_memrealtime(); }
-    t2_lstm_fwd_fast_body<MT, U>(pp.s[blockIdx.y], blockIdx.x, red, stamp ? g_t2_clk : nullptr);
+    t2_lstm_fwd_fast_body<MT, U, ZONED>(pp.s[blockIdx.y], blockIdx.x, red, stamp ? g_t2_clk : nullptr);
     if (stamp) { g_t2_clk[6] = __builtin_amdgcn_s_memtime(); g_t2_clk[7] = __builtin_amdgcn_s_memrealtime(); }
 #else
-    t2_lstm_fwd_fast_body<MT, U>(pp.s[blockIdx.y], blockIdx.x, red);
+    t2_lstm_fwd_fast_body<MT, U, ZONED>(pp.s[blockIdx.y], blockIdx.x, red);
 #endif
 }
 
@@ -389,7 +435,7 @@ __global__ __launch_bounds__(256, 1) void lstm_step_fwd_fast_kernel(LstmK2 pp) {
 // dispatch (H/8 is a multiple of 8) - so their common weight tile is fetched into that XCD's L2 once.  Same packed weight stream
 // (two consecutive 16-column blocks), same x16-tiled activations, same chunk-granular software pipeline, same epilogue.
 // ---------------------------------------------------------------------------------------------------------
-template <int U>
+template <int U, bool ZONED>
 __global__ __launch_bounds__(256, 1) void lstm_step_fwd_sq_kernel(LstmK2 pp) {
     T2_CHAIN_PRIO();
     __shared__ float red[4 * 4 * 256];
@@ -415,7 +461,7 @@ __global__ __launch_bounds__(256, 1) void lstm_step_fwd_sq_kernel(LstmK2 pp) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) acc[m][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int bl = tid >> 3, uu8 = tid & 7, eb = b0 + bl, eu = u0 + uu8;
-    const FwdEpi epi = fwd_epi_load(p, eb, eu);      // hoisted: in flight during the GEMM
+    const FwdEpi epi = fwd_epi_load<ZONED>(p, eb, eu);      // hoisted: in flight during the GEMM
     struct Chunk { f32x4 bw[2], ax[2]; };
     auto load_chunk = [&](int g, int j, Chunk& k) {
         const int c = 4 * U * g + 4 * j + w;
@@ -453,6 +499,9 @@ int launch_fwd(const T2LstmStep* steps, int n, hipStream_t st) {
     T2_REQUIRE(n == 1 || n == 2, "lstm step: n must be 1 or 2");
     for (int i = 0; i < n; ++i) T2_TRY(t2_lstm_check_step(steps[i]));
     if (n == 2) T2_REQUIRE(steps[0].B == steps[1].B && steps[0].H == steps[1].H, "lstm step: cells must share B,H");
+    // (the cells of one launch share the instantiation: both zoned or neither)
+    const bool zoned = steps[0].zone_h || steps[0].zone_c;
+    if (n == 2) T2_REQUIRE(zoned == (steps[1].zone_h || steps[1].zone_c), "lstm step: zone masks on both cells of a launch or on neither");
     const int B = steps[0].B;
     for (int b0 = 0; b0 < B; b0 += 64) {
         const int bn = (B - b0) < 64 ? (B - b0) : 64;
@@ -470,16 +519,22 @@ int launch_fwd(const T2LstmStep* steps, int n, hipStream_t st) {
             static const int sq_tile = T2_KNOB("T2_CELL_SQ", 1);
             bool tiled_in = true;
             for (int i = 0; i < n; ++i) tiled_in = tiled_in && steps[i].xt != nullptr;
-            if (bn <= 16) hipLaunchKernelGGL((lstm_step_fwd_fast_kernel<1, 4>), grid, block, 0, st, kk);
-            else if (bn <= 32) hipLaunchKernelGGL((lstm_step_fwd_fast_kernel<2, 4>), grid, block, 0, st, kk);
-            else if (sq_tile && tiled_in && steps[0].H % 64 == 0)      // 33..64 rows: 32 x 32 tiles, both row blocks of a column block on one XCD
-                hipLaunchKernelGGL((lstm_step_fwd_sq_kernel<4>), dim3(steps[0].H / 8, t2_cdiv(bn, 32), n), block, 0, st, kk);
-            else hipLaunchKernelGGL((lstm_step_fwd_fast_kernel<4, 4>), grid, block, 0, st, kk);
+#define T2_FWD_FAST(MT, Z) hipLaunchKernelGGL((lstm_step_fwd_fast_kernel<MT, 4, Z>), grid, block, 0, st, kk)
+#define T2_FWD_SQ(Z) hipLaunchKernelGGL((lstm_step_fwd_sq_kernel<4, Z>), dim3(steps[0].H / 8, t2_cdiv(bn, 32), n), block, 0, st, kk)
+#define T2_FWD_GEN(MT, Z) hipLaunchKernelGGL((lstm_step_fwd_kernel<MT, Z>), grid, block, 0, st, kk)
+            if (bn <= 16) { if (zoned) T2_FWD_FAST(1, true); else T2_FWD_FAST(1, false); }
+            else if (bn <= 32) { if (zoned) T2_FWD_FAST(2, true); else T2_FWD_FAST(2, false); }
+            else if (sq_tile && tiled_in && steps[0].H % 64 == 0) {     // 33..64 rows: 32 x 32 tiles, both row blocks of a column block on one XCD
+                if (zoned) T2_FWD_SQ(true); else T2_FWD_SQ(false);
+            } else { if (zoned) T2_FWD_FAST(4, true); else T2_FWD_FAST(4, false); }
         } else {
-            if (bn <= 16) hipLaunchKernelGGL((lstm_step_fwd_kernel<1>), grid, block, 0, st, kk);
-            else if (bn <= 32) hipLaunchKernelGGL((lstm_step_fwd_kernel<2>), grid, block, 0, st, kk);
-            else hipLaunchKernelGGL((lstm_step_fwd_kernel<4>), grid, block, 0, st, kk);
+            if (bn <= 16) { if (zoned) T2_FWD_GEN(1, true); else T2_FWD_GEN(1, false); }
+            else if (bn <= 32) { if (zoned) T2_FWD_GEN(2, true); else T2_FWD_GEN(2, false); }
+            else { if (zoned) T2_FWD_GEN(4, true); else T2_FWD_GEN(4, false); }
         }
+#undef T2_FWD_FAST
+#undef T2_FWD_SQ
+#undef T2_FWD_GEN
     }
     T2_CHECK_LAUNCH();
     return T2_OK;
@@ -506,7 +561,7 @@ int launch_fwd(const T2LstmStep* steps, int n, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 struct PersistK {
     LstmK s;                 // operand block of step 0
-    long i_pre, i_drop, i_h_out, i_h_out2, i_c_out, i_gates, i_xt, i_ht;    // element increments per step
+    long i_pre, i_drop, i_h_out, i_h_out2, i_c_out, i_gates, i_xt, i_ht, i_zone_h, i_zone_c;    // element increments per step
     int i_dt, steps;
     unsigned* sync;          // this cell's arrival counters: [8 shards] x 16 words
     unsigned* tmo;           // the timeout flag (shared by all persistent launches of an engine, sticky)
@@ -519,7 +574,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // inside one workgroup - no faster, a step is a chain of four dependent memory round trips (drain, counter, poll, sc1 loads)
 // either way; one workgroup per group, two per CU - the 136 KB of LDS lock the attention kernels out of the CUs, the whole
 // forward gets 6 ms slower.)
-template <int MT>
+template <int MT, bool ZONED>
 __global__ __launch_bounds__(256, 1) void lstm_seq_persist_fwd_kernel(PersistK2 pq) {
     T2_CHAIN_PRIO();      // (default priority for this launch: +0.25 ms per step, profiles/r03_ab_bptt_priority_chunks.txt)
     extern __shared__ __attribute__((aligned(16))) float plds[];
@@ -545,13 +600,17 @@ __global__ __launch_bounds__(256, 1) void lstm_seq_persist_fwd_kernel(PersistK2 
     const long ebc = eb < p.B ? eb : p.B - 1;
     float c_reg = (p.c_prev && tid < MT * 64) ? p.c_prev[ebc * p.ldc_prev + eu] : 0.f;
     const int e_len = p.len ? p.len[ebc] : 0x7fffffff;
+    // zoneout: h of this (row, unit) stays in a register across the steps, as c does; h_prev is read here only
+    float h_reg = (ZONED && tid < MT * 64) ? p.h_prev[ebc * p.ldhp + eu] : 0.f;
     __syncthreads();
     const long xt_bytes = (long)NT * p.xt_cs * 4;      // one tiled slot of h
     bool alive = true;
     for (int s = 0; s < pp.steps && alive; ++s) {
         // epilogue operands of this step: independent of the other workgroups, requested before the wait
-        float e_pre[4] = {0.f, 0.f, 0.f, 0.f}, e_drop = 1.f;
+        float e_pre[4] = {0.f, 0.f, 0.f, 0.f}, e_drop = 1.f, e_zh = 0.f, e_zc = 0.f;
         if (tid < MT * 64) {
+            if (ZONED && p.zone_h) e_zh = (p.zone_h + (long)s * pp.i_zone_h)[ebc * p.ldzh + eu];
+            if (ZONED && p.zone_c) e_zc = (p.zone_c + (long)s * pp.i_zone_c)[ebc * p.ldzc + eu];
             const float* pre = p.pre + (long)s * pp.i_pre;
 #pragma unroll
             for (int g = 0; g < 4; ++g) e_pre[g] = pre[ebc * p.ldpre + g * H + eu];
@@ -618,10 +677,12 @@ __global__ __launch_bounds__(256, 1) void lstm_seq_persist_fwd_kernel(PersistK2 
 #pragma unroll
             for (int g = 0; g < 4; ++g) e.pre[g] = e_pre[g];
             e.cp = c_reg; e.drop = e_drop; e.len = e_len;
+            e.zoned = ZONED; e.zh = e_zh; e.zc = e_zc; e.hp = h_reg;
             fwd_epi_load_bias(e, p, H, eu);
             const FwdCell o = fwd_cell<false>(e, red + eb * 16 + euu, MT * 256, p.t + s * pp.i_dt);
             const float hn = o.h, cn = o.c, gi = o.gi, gf = o.gf, gg = o.gg, go = o.go;
             c_reg = cn;
+            if (ZONED) h_reg = hn;
             (p.h_out + (long)s * pp.i_h_out)[(long)eb * p.ldh + eu] = hn;
             if (p.h_out2) (p.h_out2 + (long)s * pp.i_h_out2)[(long)eb * p.ldh2 + eu] = hn;
             {   // the exchanged copy: write-through
@@ -642,6 +703,7 @@ __global__ __launch_bounds__(256, 1) void lstm_seq_persist_fwd_kernel(PersistK2 
 // backward
 // ------------------------------------------------------------------------------------------------
 
+template <bool ZONED>
 __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(BwdK2 pp) {
     const BwdK& p = pp.s[blockIdx.z];
     __shared__ float red[4 * 256];
@@ -711,13 +773,13 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(BwdK2 pp) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) red[(w * 16 + (q * 4 + g)) * 16 + r] = acc0[g] + acc1[g];
     __syncthreads();
-    bwd_epi_apply<4>(p, bwd_epi_load(p, tid, u0, b0), red, tid, u0, b0);
+    bwd_epi_apply<4, false, ZONED>(p, bwd_epi_load<ZONED>(p, tid, u0, b0), red, tid, u0, b0);
 }
 
 // Fast path of the backward step: ONE contiguous gradient row block dg[b][0:K) (K = N4 + N2) against the packed,
 // zero-padded transposed weight stream; same branch-free double-buffered structure as the forward fast path.
 // One 16 x 16 (batch x unit) tile of dx = dgates . W + epilogue; NW waves split K (NW*U must divide 32).
-template <int NW, int U>
+template <int NW, int U, bool ZONED>
 __device__ __forceinline__ void t2_lstm_bwd_fast_body(const BwdK& p, const int bx, const int by, float* red /* [NW*256] */) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -732,7 +794,7 @@ __device__ __forceinline__ void t2_lstm_bwd_fast_body(const BwdK& p, const int b
     const float* ab = p.dgt ? p.dgt + (long)(b0 + r) * 16 + 4 * q
                             : p.dg_next + (long)((b0 + r) < p.B ? (b0 + r) : 0) * p.lddg + 4 * q;
     const long acs = p.dgt ? p.dgt_cs : 16;
-    const BwdEpi epi = bwd_epi_load(p, tid & 255, u0, b0);   // hoisted: in flight during the GEMM
+    const BwdEpi epi = bwd_epi_load<ZONED>(p, tid & 255, u0, b0);   // hoisted: in flight during the GEMM
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     struct Chunk { f32x4 a, b; };
     auto load_chunk = [&](int g, int j, Chunk& k) {
@@ -753,22 +815,24 @@ __device__ __forceinline__ void t2_lstm_bwd_fast_body(const BwdK& p, const int b
     for (int g = 0; g < 4; ++g) red[(w * 16 + (q * 4 + g)) * 16 + r] = acc0[g] + acc1[g];
     __syncthreads();
     T2_RING(6);                              // K shares of the waves in LDS
-    if (tid < 256) bwd_epi_apply<NW>(p, epi, red, tid, u0, b0);
+    if (tid < 256) bwd_epi_apply<NW, true, ZONED>(p, epi, red, tid, u0, b0);
     T2_RING_END();
 }
 
+template <bool ZONED>
 __global__ __launch_bounds__(256, 1) void lstm_step_bwd_fast_kernel(BwdK2 pp) {
     if (!pp.s[blockIdx.z].off_chain) T2_CHAIN_PRIO();
     __shared__ float red[4 * 256];
-    t2_lstm_bwd_fast_body<4, 4>(pp.s[blockIdx.z], blockIdx.x, blockIdx.y, red);
+    t2_lstm_bwd_fast_body<4, 4, ZONED>(pp.s[blockIdx.z], blockIdx.x, blockIdx.y, red);
 }
 
 // The same with eight waves splitting K, for launches of few workgroups (the encoder BiLSTM backward: 64 workgroups with K = 1024
 // on a chip of 256 compute units): half the chunks, loads and MFMAs per wave.
+template <bool ZONED>
 __global__ __launch_bounds__(512, 1) void lstm_step_bwd_fast8_kernel(BwdK2 pp) {
     if (!pp.s[blockIdx.z].off_chain) T2_CHAIN_PRIO();
     __shared__ float red[8 * 256];
-    t2_lstm_bwd_fast_body<8, 2>(pp.s[blockIdx.z], blockIdx.x, blockIdx.y, red);
+    t2_lstm_bwd_fast_body<8, 2, ZONED>(pp.s[blockIdx.z], blockIdx.x, blockIdx.y, red);
 }
 static int g_bwd8_max_wgs = T2_KNOB("T2_BWD8_MAX_WGS", 64);
 
@@ -787,9 +851,18 @@ int launch_bwd(const T2LstmBwdStep* steps, int n, hipStream_t st, unsigned long 
     int maxcols = steps[0].ncols;
     for (int i = 1; i < n; ++i) maxcols = steps[i].ncols > maxcols ? steps[i].ncols : maxcols;
     dim3 grid(t2_cdiv(maxcols, 16), t2_cdiv(steps[0].B, 16), n), block(256);
-    if (fast && (int)(grid.x * grid.y * grid.z) <= g_bwd8_max_wgs) hipLaunchKernelGGL(lstm_step_bwd_fast8_kernel, grid, dim3(512), 0, st, kk);
-    else if (fast) hipLaunchKernelGGL(lstm_step_bwd_fast_kernel, grid, block, 0, st, kk);
-    else hipLaunchKernelGGL(lstm_step_bwd_kernel, grid, block, 0, st, kk);
+    bool zoned = false;       // (any descriptor with masks: the zoned instantiation, which tests each descriptor's own pointers)
+    for (int i = 0; i < n; ++i) zoned = zoned || steps[i].zone_h || steps[i].zone_c;
+    if (fast && (int)(grid.x * grid.y * grid.z) <= g_bwd8_max_wgs) {
+        if (zoned) hipLaunchKernelGGL(lstm_step_bwd_fast8_kernel<true>, grid, dim3(512), 0, st, kk);
+        else hipLaunchKernelGGL(lstm_step_bwd_fast8_kernel<false>, grid, dim3(512), 0, st, kk);
+    } else if (fast) {
+        if (zoned) hipLaunchKernelGGL(lstm_step_bwd_fast_kernel<true>, grid, block, 0, st, kk);
+        else hipLaunchKernelGGL(lstm_step_bwd_fast_kernel<false>, grid, block, 0, st, kk);
+    } else {
+        if (zoned) hipLaunchKernelGGL(lstm_step_bwd_kernel<true>, grid, block, 0, st, kk);
+        else hipLaunchKernelGGL(lstm_step_bwd_kernel<false>, grid, block, 0, st, kk);
+    }
     T2_CHECK_LAUNCH();
     return T2_OK;
 }
@@ -848,6 +921,7 @@ void t2_lstm_fwd_advance(T2LstmStep& c, const T2LstmStride& inc) {
     adv(c.h_out, inc.h_out); adv(c.h_out2, inc.h_out2); adv(c.c_out, inc.c_out);
     adv(c.gates_out, inc.gates_out);
     adv(c.xt, inc.xt); adv(c.ht_out, inc.ht_out);
+    adv(c.zone_h, inc.zone_h); adv(c.zone_c, inc.zone_c); adv(c.h_prev, inc.h_prev);
     c.t += inc.dt;
 }
 void t2_lstm_bwd_advance(T2LstmBwdStep& c, const T2LstmBwdStride& inc) {
@@ -857,6 +931,7 @@ void t2_lstm_bwd_advance(T2LstmBwdStep& c, const T2LstmBwdStride& inc) {
     adv(c.dg_out, inc.dg);
     adv(c.dg_out2, inc.dg2);
     adv(c.dgt_next, inc.dgt); adv(c.dgt_out, inc.dgt);
+    adv(c.zone_h, inc.zone_h); adv(c.zone_c, inc.zone_c);
     c.t += inc.dt;
 }
 // internal entries used by the attention sequence (t2_attention.hip)
@@ -907,21 +982,30 @@ extern "C" int t2_debug_persist_spin_limit(int polls) {
 }
 
 // All H/4 workgroups of the persistent launch must be resident at once (they wait for each other): compute units of the
-// current device x the occupancy the runtime reports for this kernel with its LDS slice.  The answer is cached per (MT, LDS).
-static int persist_resident(int nwg, int MT, size_t lds) {
+// current device x the occupancy the runtime reports for this kernel with its LDS slice.  The answer is cached per (MT, ZONED, LDS):
+// it is asked of the instantiation that will be launched.
+static const void* persist_kernel(int MT, bool zoned) {
+    if (MT == 1) return zoned ? (const void*)lstm_seq_persist_fwd_kernel<1, true> : (const void*)lstm_seq_persist_fwd_kernel<1, false>;
+    return zoned ? (const void*)lstm_seq_persist_fwd_kernel<2, true> : (const void*)lstm_seq_persist_fwd_kernel<2, false>;
+}
+// (the dynamic-LDS grant of both row-tile counts of one ZONED value: a launch of more than 32 rows uses either)
+static bool persist_allow_lds(bool zoned, size_t lds) {
+    return zoned ? t2_allow_lds(lstm_seq_persist_fwd_kernel<1, true>, lds) && t2_allow_lds(lstm_seq_persist_fwd_kernel<2, true>, lds)
+                 : t2_allow_lds(lstm_seq_persist_fwd_kernel<1, false>, lds) && t2_allow_lds(lstm_seq_persist_fwd_kernel<2, false>, lds);
+}
+static int persist_resident(int nwg, int MT, size_t lds, bool zoned) {
     static std::mutex mu;
     static std::unordered_map<long, int> cap;
     std::lock_guard<std::mutex> lock(mu);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { t2_set_error("hipGetDevice failed", __FILE__, __LINE__); return T2_ERR_LAUNCH; }
-    const long key = ((long)dev << 40) | ((long)MT << 32) | (long)lds;
+    const long key = ((long)dev << 40) | ((long)(2 * MT + (zoned ? 1 : 0)) << 32) | (long)lds;
     auto it = cap.find(key);
     if (it == cap.end()) {
         int cus = 0, per_cu = 0;
         hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (e == hipSuccess)
-            e = MT == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_seq_persist_fwd_kernel<1>, 256, lds)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_seq_persist_fwd_kernel<2>, 256, lds);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persist_kernel(MT, zoned), 256, lds);
         if (e != hipSuccess) { t2_set_error(hipGetErrorString(e), __FILE__, __LINE__); (void)hipGetLastError(); return T2_ERR_LAUNCH; }
         it = cap.emplace(key, cus * per_cu).first;
     }
@@ -943,13 +1027,14 @@ extern "C" int t2_lstm_persist_resident_n(int H, int K, int B, int n) {
     T2_REQUIRE(H >= 4 && H % 4 == 0 && K >= 16 && K % 16 == 0 && B >= 1 && n >= 1, "t2_lstm_persist_resident: bad arguments");
     const size_t lds = persist_lds_bytes(K);
     // "cannot run as ONE co-resident launch" is an answer, not an error: the caller falls back to step launches (T2_ERR_RESIDENCY)
-    if (n * (H / 4) > 256 || n > 2 ||
-        !(t2_allow_lds(lstm_seq_persist_fwd_kernel<1>, lds) && t2_allow_lds(lstm_seq_persist_fwd_kernel<2>, lds))) {
+    // (the answer holds with and without zone masks: both instantiations are granted their LDS and asked)
+    if (n * (H / 4) > 256 || n > 2 || !(persist_allow_lds(false, lds) && persist_allow_lds(true, lds))) {
         t2_set_error("t2_lstm_persist_resident: cannot be ONE co-resident launch (more than 256 workgroups, more than two cells, or a "
                      "weight slice that does not fit the LDS); use t2_lstm_seq_fwd", __FILE__, __LINE__);
         return T2_ERR_RESIDENCY;
     }
-    return persist_resident(n * (H / 4), B <= 16 ? 1 : 2, lds);
+    T2_TRY(persist_resident(n * (H / 4), B <= 16 ? 1 : 2, lds, false));
+    return persist_resident(n * (H / 4), B <= 16 ? 1 : 2, lds, true);
 }
 extern "C" int t2_lstm_persist_resident(int H, int K, int B) { return t2_lstm_persist_resident_n(H, K, B, 1); }
 
@@ -968,13 +1053,15 @@ static int persist_launch(const T2LstmStep* base, const T2LstmStride* inc, int n
         T2_REQUIRE(b.seg[0].K == b.H && b.ht_col0 == 0 && inc[i].xt == inc[i].ht_out && b.ht_out == b.xt + inc[i].xt,
                    "t2_lstm_seq_fwd_persist: the input of step s+1 must be the tiled h of step s (K = H)");
         T2_REQUIRE(b.B == base[0].B && b.H == base[0].H, "t2_lstm_seq_fwd_persist: the cells of one launch share B and H");
+        T2_REQUIRE((b.zone_h || b.zone_c) == (base[0].zone_h || base[0].zone_c),
+                   "t2_lstm_seq_fwd_persist: zone masks on both cells of a launch or on neither");
     }
     const T2LstmStep& b = base[0];
     T2_REQUIRE(n * (b.H / 4) <= 256, "t2_lstm_seq_fwd_persist: at most 256 workgroups (one per CU)");
     const size_t lds = persist_lds_bytes(b.seg[0].K);
-    T2_REQUIRE(t2_allow_lds(lstm_seq_persist_fwd_kernel<1>, lds) && t2_allow_lds(lstm_seq_persist_fwd_kernel<2>, lds),
-               "t2_lstm_seq_fwd_persist: weight slice does not fit the LDS");
-    T2_TRY(persist_resident(n * (b.H / 4), (b.B < 32 ? b.B : 32) <= 16 ? 1 : 2, lds));
+    const bool zoned_launch = b.zone_h || b.zone_c;
+    T2_REQUIRE(persist_allow_lds(zoned_launch, lds), "t2_lstm_seq_fwd_persist: weight slice does not fit the LDS");
+    T2_TRY(persist_resident(n * (b.H / 4), (b.B < 32 ? b.B : 32) <= 16 ? 1 : 2, lds, zoned_launch));
     hipStream_t st = (hipStream_t)stream;
     // Rows are independent: blocks of up to 32 rows (two 16-row tiles) run as consecutive launches of the same chunk.  Each
     // launch zeroes the arrival counters (128 words per cell); the timeout flag (word 256) is sticky - only the host clears it.
@@ -987,14 +1074,21 @@ static int persist_launch(const T2LstmStep* base, const T2LstmStride* inc, int n
             k.i_pre = inc[i].pre; k.i_drop = inc[i].drop; k.i_h_out = inc[i].h_out; k.i_h_out2 = inc[i].h_out2;
             k.i_c_out = inc[i].c_out; k.i_gates = inc[i].gates_out;
             k.i_xt = inc[i].xt; k.i_ht = inc[i].ht_out; k.i_dt = inc[i].dt; k.steps = S;
+            k.i_zone_h = inc[i].zone_h; k.i_zone_c = inc[i].zone_c;
             k.sync = sync + i * 128; k.tmo = flag; k.spin_limit = g_persist_spin_limit;
         }
         if (n == 1) kk.c[1] = kk.c[0];
         if (prezeroed) sync += 256;          // (the next row block's own counters)
         else (void)hipMemsetAsync(sync, 0, 16 * 16 * sizeof(uint32_t), st);
         dim3 grid(b.H / 4, n), block(256);
-        if (bn <= 16) hipLaunchKernelGGL((lstm_seq_persist_fwd_kernel<1>), grid, block, lds, st, kk);
-        else hipLaunchKernelGGL((lstm_seq_persist_fwd_kernel<2>), grid, block, lds, st, kk);
+        const bool zoned = kk.c[0].s.h_prev != nullptr;       // (checked above: the cells of one launch agree)
+        if (bn <= 16) {
+            if (zoned) hipLaunchKernelGGL((lstm_seq_persist_fwd_kernel<1, true>), grid, block, lds, st, kk);
+            else hipLaunchKernelGGL((lstm_seq_persist_fwd_kernel<1, false>), grid, block, lds, st, kk);
+        } else {
+            if (zoned) hipLaunchKernelGGL((lstm_seq_persist_fwd_kernel<2, true>), grid, block, lds, st, kk);
+            else hipLaunchKernelGGL((lstm_seq_persist_fwd_kernel<2, false>), grid, block, lds, st, kk);
+        }
     }
     T2_CHECK_LAUNCH();
     return T2_OK;

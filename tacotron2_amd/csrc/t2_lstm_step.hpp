@@ -20,6 +20,9 @@ struct LstmK {
     const float* xt; long xt_cs;        // x16-tiled input (chunk stride Bp*16 floats) or null
     int xt_rows;                        // tiled rows that exist from this row block's first row (round_up(B_total, 16) - b0)
     float* ht_out; int ht_col0;
+    const float* zone_h; long ldzh;     // zoneout masks and the previous h (all null = off)
+    const float* zone_c; long ldzc;
+    const float* h_prev; long ldhp;
 };
 struct LstmK2 { LstmK s[2]; };
 
@@ -36,6 +39,10 @@ inline int t2_lstm_check_step(const T2LstmStep& s) {
     T2_REQUIRE((!s.xt && !s.ht_out) || (s.wpacked && s.nseg == 1), "lstm step: x16-tiled operands need the packed single-segment path");
     T2_REQUIRE(!s.xt || t2_aligned16(s.xt), "lstm step: xt must be 16-byte aligned");
     T2_REQUIRE(!s.ht_out || s.ht_col0 >= 0, "lstm step: ht_col0 must be >= 0");
+    if (s.zone_h || s.zone_c) {
+        T2_REQUIRE(s.h_prev != nullptr, "lstm step: zone masks need h_prev");
+        T2_REQUIRE(s.len == nullptr, "lstm step: zone masks do not combine with len");
+    }
     return T2_OK;
 }
 
@@ -59,6 +66,10 @@ inline void t2_lstm_to_k(const T2LstmStep& s, LstmK& k, int b0, int bn) {
     k.xt_rows = (s.B + 15) / 16 * 16 - b0;         // tiled rows that exist from this row block's first row on
     k.xt = s.xt ? s.xt + (long)b0 * 16 : nullptr;
     k.ht_out = s.ht_out ? s.ht_out + (long)b0 * 16 : nullptr; k.ht_col0 = s.ht_col0;
+    const bool zoned = s.zone_h || s.zone_c;
+    k.zone_h = s.zone_h ? s.zone_h + (long)b0 * s.ldzone_h : nullptr; k.ldzh = s.ldzone_h;
+    k.zone_c = s.zone_c ? s.zone_c + (long)b0 * s.ldzone_c : nullptr; k.ldzc = s.ldzone_c;
+    k.h_prev = zoned ? s.h_prev + (long)b0 * s.ldh_prev : nullptr; k.ldhp = s.ldh_prev;
 }
 
 // Backward step: dx = dgates . W over one or two K segments, then a plain store (epi 0) or the cell's pointwise backward (epi 1).
@@ -81,6 +92,8 @@ struct BwdK {
     const int32_t* len; int t;
     const float* dgt; long dgt_cs; float* dgt_out;   // x16-tiled dg_next / dg_out (chunk stride Bp*16 floats)
     int off_chain;                      // T2LstmBwdStep.off_chain
+    const float* zone_h; long ldzh; const float* zone_c; long ldzc;   // zoneout masks (both null = off)
+    float* dhz; long lddhz;             // in/out carry of the zoned share of dh
     unsigned long long* clk;            // diagnostic build: the caller's stamp buffer (event ring, t2_common.hpp) or null
 };
 struct BwdK2 { BwdK s[2]; };
@@ -96,6 +109,7 @@ inline void t2_lstm_to_bk(const T2LstmBwdStep& s, BwdK& k) {
     k.dc = s.dc; k.lddc = s.lddc; k.dg_out = s.dg_out; k.ldgo = s.ldgo; k.len = s.len; k.t = s.t;
     k.dgt = s.dgt_next; k.dgt_out = s.dgt_out; k.dgt_cs = (long)((s.B + 15) / 16 * 16) * 16;
     k.off_chain = s.off_chain;
+    k.zone_h = s.zone_h; k.ldzh = s.ldzone_h; k.zone_c = s.zone_c; k.ldzc = s.ldzone_c; k.dhz = s.dhz; k.lddhz = s.lddhz;
     k.clk = nullptr;
 }
 
@@ -110,8 +124,13 @@ inline int t2_lstm_check_bwd(const T2LstmBwdStep& s) {
     }
     if (s.epi == 1) {
         T2_REQUIRE(s.gates && s.c_cur && s.dc && s.dg_out && s.ncols == s.H, "lstm bwd step: epilogue operands");
+        if (s.zone_h || s.zone_c) {
+            T2_REQUIRE(s.dhz != nullptr, "lstm bwd step: zone masks need the carry dhz");
+            T2_REQUIRE(s.len == nullptr, "lstm bwd step: zone masks do not combine with len");
+        }
     } else {
         T2_REQUIRE(s.dx_out != nullptr, "lstm bwd step: dx_out required");
+        T2_REQUIRE(!s.zone_h && !s.zone_c, "lstm bwd step: zone masks need the cell epilogue (epi = 1)");
     }
     return T2_OK;
 }

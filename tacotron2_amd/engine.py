@@ -107,6 +107,18 @@ def check_forward_attention(forward, window=None):
     return forward
 
 
+def check_rate(p, name: str, closed: bool = False) -> float:
+    """A probability in [0, 1) - or [0, 1] with closed=True - as a float; anything else is a ValueError that names the option."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0 or (closed and float(p) == 1.0)):
+        raise ValueError(f"{name} must be a number in [0, 1{']' if closed else ')'}, got {p!r}")
+    return float(p)
+
+
+def zone_stride(z, n: int) -> int:
+    """Per-step element increment of a zone mask [S][B][H]: 0 for ONE (B, H) block that serves every step (eval: filled with the rate)."""
+    return 0 if z is None or z.shape[0] == 1 else n
+
+
 def check_guided_attention(guided):
     """None, or (sigma, alpha) of the guided-attention loss as two real numbers, sigma > 0 and alpha >= 0 -> a tuple of floats;
     anything else raises ValueError."""
@@ -289,6 +301,10 @@ class Engine:
         self.d = ps.dims
         self.r = reduction_factor(ps.dims)   # mel frames per decoder step (missing key: 1); the chains walk ceil(T / r) steps
         self.dev = ps.device
+        # zoneout rate of the decoder's two LSTM cells (0 = off, the default) and the rate of the dropout on their outputs (the
+        # reference's two nn.Dropout(0.1), model/decoder.py:29,43; 0 = no mask tensors at all)
+        self.zoneout = check_rate(ps.dims.get("zoneout", 0.0), "zoneout", closed=True)
+        self.cell_dropout = check_rate(ps.dims.get("cell_dropout", 0.1), "cell_dropout")
         self._ws: Dict[str, torch.Tensor] = {}
         self._cleared: Dict[tuple, tuple] = {}   # (data_ptr, bytes) -> (workspace name, view): regions put on the zero list ahead
                                                  # of the code that needs them zero and not consumed yet (clear_ahead / need_zero)
@@ -448,7 +464,10 @@ class Engine:
 
     def make_masks(self, B: int, L: int, T: int, training: bool, seed: int, step: int) -> dict:
         """Dropout scale masks for one step from the device Philox generator (t2_philox_mask).  Sites and rates as
-        the reference: encoder/postnet p, prenet p always on (model/modules.py), LSTMCell outputs 0.1 (model/decoder.py:29,43)."""
+        the reference: encoder/postnet p, prenet p always on (model/modules.py), LSTMCell outputs dims["cell_dropout"] = 0.1
+        (model/decoder.py:29,43).  With dims["zoneout"] = z > 0 also the zone masks of the two decoder cells: training - four
+        [S][B][H] tensors of independent 0/1 draws (t2_philox_bernoulli, stream ids of their own: the ids of the dropout masks are
+        what they are without the option); eval - ONE (B, H) block filled with z per cell, read by every step (the expectation)."""
         d = self.d
         p = float(d["dropout"])
         E, Pd, A, D, M, Pn = d["encoded_dim"], d["prenet_dim"], d["att_rnn_dim"], d["rnn_hidden_dim"], d["num_mels"], d["postnet_dim"]
@@ -470,8 +489,17 @@ class Engine:
                 masks["enc_drop"] = [gen(f"enc{i}", B * L * E, p).view(B, L, E) for i in range(3)]
                 chans = [Pn, Pn, Pn, Pn, M]
                 masks["post_drop"] = [gen(f"post{i}", B * Tf * c, p).view(B, Tf, c) for i, c in enumerate(chans)]
-            masks["att_drop"] = gen("att", T * B * A, 0.1).view(T, B, A)
-            masks["dec_drop"] = gen("dec", T * B * D, 0.1).view(T, B, D)
+            if self.cell_dropout > 0.0:
+                masks["att_drop"] = gen("att", T * B * A, self.cell_dropout).view(T, B, A)
+                masks["dec_drop"] = gen("dec", T * B * D, self.cell_dropout).view(T, B, D)
+        if self.zoneout > 0.0 and training:
+            for i, (key, H) in enumerate((("att_zone_h", A), ("att_zone_c", A), ("dec_zone_h", D), ("dec_zone_c", D))):
+                masks[key] = self.buf("mask." + key, T, B, H)
+                call("t2_philox_bernoulli", masks[key], T * B * H, self.zoneout, seed, step * 64 + 48 + i, st)
+        elif self.zoneout > 0.0:
+            for cell, H in (("att", A), ("dec", D)):     # ONE block of the rate per cell, both of its masks
+                block = self.buf(f"mask.{cell}_zone_p", 1, B, H).fill_(self.zoneout)
+                masks[cell + "_zone_h"] = masks[cell + "_zone_c"] = block
         return masks
 
     # ---- workspace --------------------------------------------------------------------------------
@@ -921,12 +949,18 @@ class Engine:
                    att_drop=masks.get("att_drop"), xdec=xdec, att_c=att_c, gates=gates_att, align=align, cum=cum, th=th,
                    xproj_ctx=_ptr(xproj, B * (D + Ef) + D), ld_xproj=D + Ef, e_part=e_part, xdec_t=xdec_t,
                    forward=int(forward_attention))
+        azh, azc = masks.get("att_zone_h"), masks.get("att_zone_c")
+        # (the attention cell's zone masks travel beside the chain's operand block: T2AttnZone)
+        zatt = make("T2AttnZone", zone_h=azh, zone_c=azc, stride=zone_stride(azh if azh is not None else azc, B * A)) \
+            if azh is not None or azc is not None else None
         # decoder-LSTM chain operands (prepared before the pipeline below)
         pre_dec = self.buf("pre_dec", T, B, 4 * D)
         dec_c = self.buf("dec_c", T + 1, B, D)
         zero_later(dec_c[0])
         gates_dec = self.buf("gates_dec", T, B, 4 * D) if save_for_backward else None
         dd = masks.get("dec_drop")
+        dzh, dzc = masks.get("dec_zone_h"), masks.get("dec_zone_c")
+        dzs = zone_stride(dzh if dzh is not None else dzc, B * D)
         ldp = D + Ef
         wp_dec = self.pack_fwd("dec", [(P["decoder.lstm.weight_hh"], D, D)], D)
         # Software pipeline over chunks of CH frames.  In teacher-forced mode the attention chain never reads the decoder
@@ -941,11 +975,14 @@ class Engine:
                        drop=_ptr(dd, c0 * B * D) if dd is not None else None, lddrop=D,
                        h_out=_ptr(xproj, (c0 + 1) * B * ldp), ldh=ldp, c_out=_ptr(dec_c, (c0 + 1) * B * D), ldc_out=D,
                        gates_out=_ptr(gates_dec, c0 * B * 4 * D) if gates_dec is not None else None, ldg=4 * D,
-                       xt=_ptr(dech_t, c0 * D * Bp), ht_out=_ptr(dech_t, (c0 + 1) * D * Bp), ht_col0=0)
+                       xt=_ptr(dech_t, c0 * D * Bp), ht_out=_ptr(dech_t, (c0 + 1) * D * Bp), ht_col0=0,
+                       zone_h=_ptr(dzh, c0 * dzs) if dzh is not None else None, ldzone_h=D,
+                       zone_c=_ptr(dzc, c0 * dzs) if dzc is not None else None, ldzone_c=D,
+                       h_prev=_ptr(xproj, c0 * B * ldp) if dzh is not None or dzc is not None else None, ldh_prev=ldp)
             stp.seg[0].x = _ptr(xproj, c0 * B * ldp); stp.seg[0].ldx = ldp
             stp.seg[0].w = P["decoder.lstm.weight_hh"].data_ptr(); stp.seg[0].ldw = D; stp.seg[0].K = D
             inc = make("T2LstmStride", pre=B * 4 * D, c_prev=B * D, drop=B * D, h_out=B * ldp, c_out=B * D,
-                       gates_out=B * 4 * D, dt=0, xt=D * Bp, ht_out=D * Bp)
+                       gates_out=B * 4 * D, dt=0, xt=D * Bp, ht_out=D * Bp, zone_h=dzs, zone_c=dzs, h_prev=B * ldp)
             inc.seg_x[0] = B * ldp
             return stp, inc
 
@@ -973,7 +1010,10 @@ class Engine:
         sync = self.persist_sync() if persist else None
         for c0, c1, sk, cleared in sched:
             seq.t_begin, seq.t_end = c0, c1
-            call("t2_attn_seq_fwd", seq, st)
+            if zatt is not None:
+                call("t2_attn_seq_fwd_zone", seq, zatt, st)
+            else:
+                call("t2_attn_seq_fwd", seq, st)
             ev = self._record(main)
             with torch.cuda.stream(side):
                 self._wait(side, ev)
@@ -1167,6 +1207,12 @@ class Engine:
         zero_later(Zt[T])
         dc_dec = self.buf("dc_dec", B, D, zero=True)
         dd = masks.get("dec_drop")
+        dzh, dzc = masks.get("dec_zone_h"), masks.get("dec_zone_c")
+        azh, azc = masks.get("att_zone_h"), masks.get("att_zone_c")
+        dzs = zone_stride(dzh if dzh is not None else dzc, B * D)
+        # the zoned share of dh that a step hands to the step before it (T2LstmBwdStep.dhz): carries like dc, cleared with it
+        dhz_dec = self.buf("dhz_dec", B, D, zero=True) if dzh is not None or dzc is not None else None
+        dhz_att = self.buf("dhz_att", B, A, zero=True) if azh is not None or azc is not None else None
         wtp_dec = self.pack_bwd("dec.t", P["decoder.lstm.weight_hh"], D, 4 * D, D)
         dxdec = self.buf("dxdec", T, B, ldx)
         ldz = 4 * A + Ad
@@ -1203,6 +1249,8 @@ class Engine:
                   dgates=Z, dctx_tot=dctx_tot, dq=None, dpmT=dpmT, dv_part=dv_part, dU_part=dU_part,
                   dc=dc_att, G=Gc, de=de, din_part=din_part, dgates_t=Zt, clk=getattr(self, "clk_bwd", None), dalign=d_align,
                   ws_bd=self.buf("attn.ws_bd", Ad // 16 * 16896))
+        zatt = make("T2AttnZone", zone_h=azh, zone_c=azc, stride=zone_stride(azh if azh is not None else azc, B * A), dhz=dhz_att) \
+            if dhz_att is not None else None
         self.mark("bwd.dec.proj")
         main, side = torch.cuda.current_stream(), self.side_stream()
         self._wait(side, main)
@@ -1216,9 +1264,11 @@ class Engine:
                      c_prev=_ptr(ctx["dec_c"], (hi - 1) * B * D), ldcp=D, c_cur=_ptr(ctx["dec_c"], hi * B * D), ldcc=D,
                      dc=dc_dec, lddc=D, dg_out=_ptr(dgd, (hi - 1) * B * 4 * D), ldgo=4 * D,
                      dgt_next=_ptr(dgd_t, hi * Bp * 4 * D), dgt_out=_ptr(dgd_t, (hi - 1) * Bp * 4 * D),
-                     off_chain=1 if self.bptt_off_chain else 0)
+                     off_chain=1 if self.bptt_off_chain else 0,
+                     zone_h=_ptr(dzh, (hi - 1) * dzs) if dzh is not None else None, ldzone_h=D,
+                     zone_c=_ptr(dzc, (hi - 1) * dzs) if dzc is not None else None, ldzone_c=D, dhz=dhz_dec, lddhz=D)
             inc = make("T2LstmBwdStride", dg=-B * 4 * D, ext1=-B * ldp, drop=-B * D, gates=-B * 4 * D, c_prev=-B * D,
-                       c_cur=-B * D, dt=0, dgt=-Bp * 4 * D)
+                       c_cur=-B * D, dt=0, dgt=-Bp * 4 * D, zone_h=-dzs, zone_c=-dzs)
             return s, inc
 
         def dec_wgrads_chunk(hi, lo):    # decoder-LSTM weight gradients over frames [lo, hi) (accumulating)
@@ -1271,7 +1321,9 @@ class Engine:
                     side_op(op)
             self._wait(main, ev)
             sb.t_hi, sb.t_lo = hi, lo
-            if fwd_att:
+            if zatt is not None:      # (dprior selects the forward-attention backward there)
+                call("t2_attn_seq_bwd_zone", sb, de_stash, B * L, dprior, zatt, st)
+            elif fwd_att:
                 call("t2_attn_seq_bwd_forward", sb, de_stash, B * L, dprior, st)
             else:
                 call("t2_attn_seq_bwd_stash", sb, de_stash, B * L, st)
@@ -1488,7 +1540,12 @@ class Engine:
         att_c = self.buf(pf + "att_c", 2, B, A, zero=True)
         dec_c = self.buf(pf + "dec_c", 2, B, D, zero=True)
         cum = self.buf(pf + "cum", 2, B, L, zero=True)
-        xproj = self.buf(pf + "xproj", B, ldp)
+        zone = {}
+        if self.zoneout > 0.0:   # decoding uses the expectation: every mask element is the rate (T2Infer.zone_p)
+            zone = dict(zone_p=self.zoneout, zone_att=self.buf(pf + "zone_att", B, A).fill_(self.zoneout),
+                        zone_dec=self.buf(pf + "zone_dec", B, D).fill_(self.zoneout))
+        # (with zoneout the decoder cell of frame 0 reads its previous h from the dec_h columns: zeros)
+        xproj = self.buf(pf + "xproj", B, ldp, zero=bool(zone))
         p1 = self.buf(pf + "p1", B, Pd)
         e_part = self.buf(pf + "e_part", B, Ad // 16, L)
         proj = self.buf(pf + "proj", Tcap, B, ldo)
@@ -1520,7 +1577,7 @@ class Engine:
                  wp_dec=self._wp_dec_inf, b_dec_ih=P["decoder.lstm.bias_ih"], b_dec_hh=P["decoder.lstm.bias_hh"],
                  Wq=P["decoder.attention.query_layer.weight"], U=self._U_inf, v=P["decoder.attention.v.weight"],
                  pmT=pmT, memory=memory, len=len32, prenet_mask=pm, xs=xs, att_h=att_h, att_c=att_c, dec_c=dec_c, cum=cum,
-                 xproj=xproj, p1=p1, e_part=e_part, proj=proj, ld_proj=ldo, align=align, done=done, state=state, dec_pre=cterm)
+                 xproj=xproj, p1=p1, e_part=e_part, proj=proj, ld_proj=ldo, align=align, done=done, state=state, dec_pre=cterm, **zone)
         return dict(a=a, B=B, proj=proj, align=align, state=state, pm=pm, philox=prenet_masks is None and pm is not None)
 
     def infer(self, chars_idx, chars_len, max_len, speaker_id=None, description_embeddings=None, training=False,

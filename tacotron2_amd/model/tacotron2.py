@@ -16,7 +16,7 @@ import torch
 from torch import Tensor, nn
 
 from .._lib import call
-from ..engine import Engine, _stream, check_attention_window, check_forward_attention
+from ..engine import check_rate, Engine, _stream, check_attention_window, check_forward_attention
 from ..init import init_parameters
 from ..params import ParamStore, check_reduction_factor
 
@@ -88,13 +88,20 @@ class Tacotron2(nn.Module):
                  att_rnn_dim: int, att_dim: int, rnn_hidden_dim: int, postnet_dim: int, dropout: float,
                  speaker_tokens: bool = False, speaker_tokens_dim: Optional[int] = 128, num_speakers: int = 1,
                  controls: bool = False, controls_dim: int = 0, description_embeddings: bool = False,
-                 description_embeddings_dim: int = 0, device=None, seed: int = 0, reduction_factor: int = 1):
-        """reduction_factor r >= 1: every decoder step emits r consecutive mel frames (`decoder.mel_out` has r * num_mels rows), so
+                 description_embeddings_dim: int = 0, device=None, seed: int = 0, reduction_factor: int = 1,
+                 zoneout: float = 0.0, cell_dropout: float = 0.1):
+        """zoneout z in [0, 1] (Krueger et al. 2017; ESPnet's `zoneout_rate`, customary 0.1): in training every unit of the two decoder
+        LSTM cells keeps its previous h / c with probability z per step (independent 0/1 masks for h and c, no rescaling); in eval and
+        decoding the carried state is z * previous + (1 - z) * new.  0 (default): the reference's cells.  cell_dropout in [0, 1): the
+        rate of the dropout on the two cells' outputs (the reference's hard-coded nn.Dropout(0.1)); 0 = none - the paper's setting
+        is zoneout=0.1, cell_dropout=0.  Neither changes a parameter.
+        reduction_factor r >= 1: every decoder step emits r consecutive mel frames (`decoder.mel_out` has r * num_mels rows), so
         the recurrences run ceil(T / r) times for T frames.  mels, mels_post and gates keep frame resolution (a step's stop logit
         is repeated over its frames); `alignments` has one row per step, (B, ceil(T / r), L).  1: the reference's model."""
         super().__init__()
         reduction_factor = check_reduction_factor(reduction_factor)
         self.reduction_factor = reduction_factor
+        self.zoneout, self.cell_dropout = check_rate(zoneout, "zoneout", closed=True), check_rate(cell_dropout, "cell_dropout")
         assert not speaker_tokens or num_speakers is not None, "If speaker tokens are enabled, you must give a num_speakers!"
         assert encoder_kernel_size == 5, "the conv-as-GEMM kernels are specialised for the reference's k=5"
         self.embedding_dim = self.char_embedding_dim = encoded_dim
@@ -111,6 +118,10 @@ class Tacotron2(nn.Module):
                          controls=bool(controls), controls_dim=int(controls_dim) if controls else 0)
         if reduction_factor != 1:     # (a missing key means 1: the dims of an r = 1 model are what they always were)
             self.dims["reduction_factor"] = reduction_factor
+        if self.zoneout != 0.0:       # (likewise: missing keys mean zoneout 0 and cell_dropout 0.1)
+            self.dims["zoneout"] = self.zoneout
+        if self.cell_dropout != 0.1:
+            self.dims["cell_dropout"] = self.cell_dropout
         if device is None:
             device = "cuda:0" if torch.cuda.is_available() else "cpu"
         self._seed, self._calls = seed, 0

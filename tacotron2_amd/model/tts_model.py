@@ -91,7 +91,8 @@ class TTSModel(nn.Module):
                  scheduler_milestones: List[int] = (), speaker_tokens: bool = False, num_speakers: int = 1,
                  controls: bool = False, controls_dim: int = 0, max_len_override: Optional[int] = None,
                  description_embeddings: bool = False, description_embeddings_dim: int = 0,
-                 char_embedding_dim: Optional[int] = None, device=None, reduction_factor: int = 1):
+                 char_embedding_dim: Optional[int] = None, device=None, reduction_factor: int = 1,
+                 zoneout: float = 0.0, cell_dropout: float = 0.1):
         super().__init__()
         reduction_factor = check_reduction_factor(reduction_factor)    # mel frames per decoder step (Tacotron2)
         if char_embedding_dim is not None:     # stale configs name encoded_dim `char_embedding_dim`
@@ -103,7 +104,8 @@ class TTSModel(nn.Module):
                             speaker_tokens=speaker_tokens, num_speakers=num_speakers, controls=controls,
                             controls_dim=controls_dim, max_len_override=max_len_override,
                             description_embeddings=description_embeddings,
-                            description_embeddings_dim=description_embeddings_dim, reduction_factor=reduction_factor)
+                            description_embeddings_dim=description_embeddings_dim, reduction_factor=reduction_factor,
+                            zoneout=float(zoneout), cell_dropout=float(cell_dropout))
         self.lr, self.weight_decay = lr, weight_decay
         self.scheduler_milestones = list(scheduler_milestones)
         self.speaker_tokens, self.controls = speaker_tokens, controls
@@ -124,7 +126,7 @@ class TTSModel(nn.Module):
                                    speaker_tokens=speaker_tokens, num_speakers=num_speakers, controls=controls,
                                    controls_dim=controls_dim, description_embeddings=description_embeddings,
                                    description_embeddings_dim=description_embeddings_dim, device=device,
-                                   reduction_factor=reduction_factor)
+                                   reduction_factor=reduction_factor, zoneout=zoneout, cell_dropout=cell_dropout)
 
     def configure_optimizers(self):
         optimizer = torch.optim.Adam(self.tacotron2.parameters(), lr=self.lr, weight_decay=self.weight_decay)
@@ -218,7 +220,12 @@ class TTSModel(nn.Module):
     def load_from_checkpoint(cls, path: str, map_location=None, device=None, **overrides):
         ck = torch.load(path, map_location="cpu", weights_only=True)
         hp = dict(ck.get("hyper_parameters", {}))
-        hp.update({k: v for k, v in overrides.items() if k in hp or k in ("lr", "weight_decay", "num_chars", "reduction_factor")})
+        # zoneout / cell_dropout change no parameter, so the configured value always loads; a file that recorded another one says so
+        for k in ("zoneout", "cell_dropout"):
+            if k in overrides and k in hp and float(hp[k]) != float(overrides[k]):
+                print(f"warning: checkpoint {path} was written with {k} = {hp[k]}, the configuration says {overrides[k]}: using {overrides[k]}")
+        hp.update({k: v for k, v in overrides.items()
+                   if k in hp or k in ("lr", "weight_decay", "num_chars", "reduction_factor", "zoneout", "cell_dropout")})
         hp = {k: v for k, v in hp.items() if k in cls.__init__.__code__.co_varnames}
         model = cls(device=device, **hp)
         model.load_checkpoint_dict(ck)
