@@ -522,6 +522,30 @@ int t2_outgrad_pack_r(const float* d_mels, const float* d_post, const float* d_g
 int t2_loss_fwd_bwd_r(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
                       const int32_t* len, int B, int T, int M, int r, double* loss3, float* d_post, float* dproj,
                       float grad_scale, void* stream);
+/* Loss options (no reference counterpart: model/tts_model.py:197-201 is the plain mean of three terms over the padded batch).
+ * With len[b] the utterance's mel length a frame (b, t) is VALID when t < min(len[b], T); n_f = the number of valid frames.
+ *   mel_loss    0 = l2 (the reference), 1 = l1: |e|, gradient sign(e) with sign(0) = 0, 2 = l1+l2: the sum of the two means; for both
+ *               mel terms.  loss3 stays {gate, mel, post}.
+ *   masked      != 0: the three sums run over the valid frames only; the gate term is divided by n_f, the mel terms by n_f * M.  n_f is
+ *               formed on the device inside the same launch (every workgroup sums min(len[b], T) before its loop: no host read, no
+ *               second launch).  Invalid positions of the five tensors are not READ (NaN or Inf there reaches neither loss3 nor a
+ *               gradient); their gradients are written as 0.  n_f == 0: zero terms and zero gradients.
+ *   stop_weight w > 0 on the STOP class (gate target 0: one frame per utterance, datasets/tts_dataset.py:213-214): per frame
+ *               y softplus(-x) + w (1 - y) softplus(x), gradient sigmoid(x) (y + w (1 - y)) - y; the divisor stays the plain count
+ *               (B*T, or n_f when masked) - torch's pos_weight convention mirrored onto the other class.  w == 1 is the unweighted
+ *               expression, not the general formula.
+ * t2_loss_fwd_bwd_opt = t2_loss_fwd_bwd_r (r >= 1) and t2_loss_terms_opt = t2_loss_terms with the options; {0, 0, 1.0f} forwards to those
+ * entries after this entry's own checks (bit for bit their results), anything else launches a further instantiation of the same
+ * kernel body.  With a reduction factor the gate term still counts frames and dproj's gate column is the sum over the step's frames.
+ * NULL options, mel_loss outside {0, 1, 2}, a stop_weight that is not finite or <= 0, and B, T or M < 1 are refused (rc = 1) before
+ * anything is launched. */
+typedef struct { int mel_loss; int masked; float stop_weight; } T2LossOpts;
+int t2_loss_fwd_bwd_opt(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
+                        const int32_t* len, int B, int T, int M, int r, double* loss3, float* d_post, float* dproj,
+                        float grad_scale, const T2LossOpts* opts, void* stream);
+int t2_loss_terms_opt(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
+                      const int32_t* len, int B, int T, int M, double* loss3, float* d_mels, float* d_post, float* d_gates,
+                      float grad_scale, const T2LossOpts* opts, void* stream);
 int t2_relu_mask_bwd(const float* g, const float* y, const float* mask, float* out, int64_t n, void* stream);
 int t2_condition_fwd(const float* enc, const float* spk_table, const int32_t* spk, const float* desc, float* memory, int B,
                      int L, int E, int Ef, void* stream);
@@ -590,6 +614,10 @@ typedef struct {
                                         dec_h columns of xproj), so h_prev aliases h_out - a thread reads only the element it then
                                         writes; both buffers must therefore be zero-filled before frame 0, like the c slots */
     const float* zone_att; const float* zone_dec;
+    float stop_logit;                /* stop threshold as a logit: a step stops when its stop logit < stop_logit.  0 = the reference's
+                                        rule (model/tacotron2.py:319-322: gate < 0, sigmoid < 0.5); for a threshold 0 < tau < 1 the
+                                        caller passes log(tau / (1 - tau)) formed in double and rounded to float - the SAME float it
+                                        gives t2_stop_scan_thr, so the in-loop flags and the scan agree exactly.  Must be finite */
 } T2Infer;
 int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream);
 /* proj[g] [nframes][Bg[g]][ld_proj] for g < ngroups (<= 64 groups of up to 64 utterances) -> lengths [sum Bg] int64,
@@ -602,6 +630,11 @@ int t2_stop_scan(const T2StopScan* s, int64_t* lengths, int32_t* out2, void* str
  * r * num_mels): lengths [sum Bg] = min(r * counted steps, max_len) frames, out2 = {frames emitted = min(r * steps, max_len), steps
  * emitted}.  At r = 1 that is t2_stop_scan's result cut at max_len, with the steps in out2[1]. */
 int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream);
+/* The same scan against a stop threshold (T2Infer.stop_logit; departs from model/tacotron2.py:319-322, which compares with 0): a step
+ * stops when logit < stop_logit, and the count rule counts the steps with logit >= stop_logit; the break after the last utterance's
+ * first stop, the steps and the max_len cut are unchanged.  t2_stop_scan_r is the stop_logit = 0.0f call of the same body.  A
+ * stop_logit that is not finite is refused (rc = 1). */
+int t2_stop_scan_thr(const T2StopScan* s, int r, int max_len, float stop_logit, int64_t* lengths, int32_t* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Per-character durations from alignments (no reference counterpart; the teacher export that duration-based models such as

@@ -3,12 +3,14 @@
 
     python main.py --config C --device N train --speech-dir S [--results-dir R] [--resume-ckpt K] [--finetune --finetune-steps n]
                                                   [--guided-attention SIGMA,ALPHA]
+                                                  [--mel-loss l2|l1|l1+l2] [--masked-loss | --no-masked-loss] [--stop-weight W]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
                                                   [--attention-window BACK,FWD | --forward-attention] [--durations-out PATH]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention]
+    (say, test and test-correlation also take --stop-threshold P)
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
     python main.py --config C --device N duration-export --speech-dir S --checkpoint K [--results-dir R] [--mode monotonic|argmax]
 
@@ -61,6 +63,34 @@ forward_attention_option = click.option(
          "the flag wins. Not together with --attention-window. Default: off.")
 
 
+def parse_stop_threshold(ctx, param, value):
+    """--stop-threshold P -> a float with 0 < P < 1, anything else a usage error."""
+    if value is None:
+        return None
+    from tacotron2_amd.engine import check_stop_threshold
+    try:
+        return check_stop_threshold(float(value))
+    except ValueError:
+        raise click.BadParameter(f"expected a number with 0 < P < 1 (e.g. 0.4), got {value!r}") from None
+
+
+stop_threshold_option = click.option(
+    "--stop-threshold", required=False, type=str, default=None, callback=parse_stop_threshold, metavar="P",
+    help="Stop probability below which an utterance ends (NVIDIA's gate_threshold): lower decodes longer, higher stops earlier. "
+         "Wins over model.stop_threshold of the config. Default: 0.5, the reference's rule.")
+
+
+def parse_stop_weight(ctx, param, value):
+    """--stop-weight W -> a finite float > 0, anything else a usage error."""
+    if value is None:
+        return None
+    from tacotron2_amd.engine import check_loss_options
+    try:
+        return check_loss_options({"stop_weight": float(value)})[2]
+    except ValueError:
+        raise click.BadParameter(f"expected a finite number > 0 (e.g. 8), got {value!r}") from None
+
+
 def forward_attention_arg(forward_attention, attention_window):
     """The drivers' forward_attention argument: True for the flag, None (= the config's model.forward_attention) without it; the
     flag together with --attention-window is a usage error."""
@@ -97,8 +127,19 @@ def main(ctx, config, device):
               help="Train under forward attention (Zhang et al. 2018): every teacher-forced frame's weights are the softmax times the "
                    "prior 0.5 a[t-1][n] + 0.5 a[t-1][n-1], renormalised, forward and backward. Decode such a model with "
                    "--forward-attention. Wins over training.forward_attention of the config. Default: off.")
+@click.option("--mel-loss", required=False, type=click.Choice(["l2", "l1", "l1+l2"]), default=None,
+              help="The two mel terms: l2 = mean squared error (the reference), l1 = mean absolute error, l1+l2 = their sum (ESPnet's "
+                   "default). Wins over training.loss.mel of the config. Default: l2.")
+@click.option("--masked-loss/--no-masked-loss", default=None,
+              help="Average the three loss terms over the valid frames of the batch only, not over its padding (ESPnet's use_masking); "
+                   "--no-masked-loss is the plain mean. Either wins over training.loss.masked of the config. Default: the config's "
+                   "value, else the plain mean.")
+@click.option("--stop-weight", required=False, type=str, default=None, callback=parse_stop_weight, metavar="W",
+              help="Weight of the stop class (the one last frame of an utterance) in the stop-token loss; 5 to 20 is customary "
+                   "(ESPnet's bce_pos_weight, on the class that is rare here). Wins over training.loss.stop_weight. Default: 1.")
 def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_checkpoint=None, finetune=False,
-          finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None, forward_attention=False):
+          finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None, forward_attention=False, mel_loss=None,
+          masked_loss=None, stop_weight=None):
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for training!")
     if finetune and finetune_steps is None:
@@ -108,7 +149,8 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
     do_train(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
              extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, results_dir=results_dir,
              resume_ckpt=resume_ckpt, finetune=finetune, finetune_steps=finetune_steps, max_steps_override=max_steps,
-             synthetic=synthetic, guided_attention=guided_attention, forward_attention=True if forward_attention else None)
+             synthetic=synthetic, guided_attention=guided_attention, forward_attention=True if forward_attention else None,
+             mel_loss=mel_loss, masked_loss=masked_loss, stop_weight=stop_weight)
 
 
 @main.command()
@@ -126,8 +168,9 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--durations-out", required=False, type=str, default=None, metavar="PATH",
               help="Write character timestamps as JSON: per text the encoded symbols, the mel frames each one lasts (the best "
                    "monotonic path through the decode's own alignments), start_s / end_s, focus_rate and feasible. Default: off.")
+@stop_threshold_option
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
-        forward_attention, durations_out=None):
+        forward_attention, durations_out=None, stop_threshold=None):
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for speech!")
@@ -137,7 +180,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
            extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, text=text, output=out,
            speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
            description=description, attention_window=attention_window, forward_attention=forward_attention,
-           durations_out=durations_out)
+           durations_out=durations_out, stop_threshold=stop_threshold)
 
 
 @main.command()
@@ -151,8 +194,9 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
 @click.option("--limit", required=False, type=int, default=None, help="Only the first n utterances of the test manifest.")
 @attention_window_option
 @forward_attention_option
+@stop_threshold_option
 def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window,
-         forward_attention):
+         forward_attention, stop_threshold=None):
     """Synthesise the test manifest (run/test.py of the reference): one wav per utterance + failures.csv."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
@@ -162,7 +206,7 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
     do_test(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
             extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
             hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit,
-            attention_window=attention_window, forward_attention=forward_attention)
+            attention_window=attention_window, forward_attention=forward_attention, stop_threshold=stop_threshold)
 
 
 @main.command()
@@ -176,8 +220,9 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
 @click.option("--limit-overrides", required=False, type=int, default=None, help="Only the first n of the 51 control overrides.")
 @attention_window_option
 @forward_attention_option
+@stop_threshold_option
 def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides,
-                     attention_window, forward_attention):
+                     attention_window, forward_attention, stop_threshold=None):
     """The test manifest under 51 control-vector overrides (run/test_correlation.py of the reference)."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
@@ -187,6 +232,8 @@ def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_d
     model_config = c["model"] if attention_window is None else dict(c["model"], attention_window=list(attention_window))
     if forward_attention:      # load_test_model reads it from the model config, as it does the window
         model_config = dict(model_config, forward_attention=True)
+    if stop_threshold is not None:
+        model_config = dict(model_config, stop_threshold=stop_threshold)
     do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=model_config,
                         extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
                         hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, samples_per_speaker=samples_per_speaker,

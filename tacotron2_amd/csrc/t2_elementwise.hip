@@ -8,6 +8,7 @@
 // floats starting at padded row r (lda = C, K = 5C); outputs land in the 'shifted' row layout r = b*Lp + l
 // (l < L valid, 4 junk rows per sample that every consumer skips or zeroes).
 #include "t2_common.hpp"
+#include <cmath>
 
 namespace {
 
@@ -397,17 +398,45 @@ __global__ void finalize_fwd_kernel(const float* proj, long ldp, const int32_t* 
 //   d_post, d_mels (B,T,M) and d_gates (B,T) dense;  dproj [S][B][r*M+1] time-major gets d_mels + d_post in the mel columns (zero in
 //   the columns of frames >= T) and the stop-logit gradient in column r*M: the sum over the step's frames below T and below len[b],
 //   formed by the ONE thread that owns the (b, s) pair - no atomics.  Each of the four is optional.
-template <bool GROUPED>
+// Options (include/tacotron2_amd.h: T2LossOpts) are template parameters of the ONE kernel; <GROUPED, 0, false, false> is the
+// loss above, expression for expression:
+//   MEL      0 = squared error, 1 = |e| with gradient sign(e), sign(0) = 0, 2 = the sum of the two means
+//   MASKED   the sums run over the valid frames t < min(len[b], T) only and are divided by their count n_f (gate) and n_f * M (mels);
+//            every workgroup forms n_f from `len` itself before its loop, and an invalid position is not READ (a branch, not a
+//            product with 0: a NaN in the padding reaches nothing); n_f = 0 gives zero terms and zero gradients
+//   WEIGHTED the gate term is y softplus(-x) + w (1 - y) softplus(x), gradient sigmoid(x) (y + w (1 - y)) - y; the divisor stays the count
+// The kernel IS the body (no inlined helper: inside one the block size is no longer folded to the launch's uniform one), and the stop
+// weight is a trailing argument that exists only in the weighted instantiations (W = float; else the pack is empty), so the
+// default instantiation has the argument list, the kernarg layout and the code the kernel had before the options.
+__device__ __forceinline__ float loss_stop_w() { return 1.f; }
+__device__ __forceinline__ float loss_stop_w(float w) { return w; }
+template <bool GROUPED, int MEL = 0, bool MASKED = false, bool WEIGHTED = false, typename... W>
 __global__ __launch_bounds__(256) void loss_kernel(const float* mels, const float* post, const float* gates, const float* mel_tgt,
                                                    const float* gate_tgt, const int32_t* len, int B, int T, int M, int r_, int S_,
                                                    double* loss3, float* d_post, float* dproj, float gscale, float* d_mels,
-                                                   float* d_gates) {
+                                                   float* d_gates, W... stop_weight) {
+    static_assert(sizeof...(W) == (WEIGHTED ? 1 : 0), "the weight argument comes with WEIGHTED only");
     __shared__ double red[3][4];
+    __shared__ unsigned long long nf_s;
+    const float stop_w = loss_stop_w(stop_weight...);
     const int r = GROUPED ? r_ : 1, S = GROUPED ? S_ : T;
     const long nm = (long)B * T * M, ng = (long)B * T;
     const long nv = (long)B * S * r * M, ns = (long)B * S;       // virtual frames S*r >= T; one gate entry per step
     const long ldq = (long)r * M + 1;
-    const float sm = 1.f / (float)nm, sg = 1.f / (float)ng;
+    float sm = 1.f / (float)nm, sg = 1.f / (float)ng;
+    double dm = (double)nm, dg = (double)ng;                      // the divisors of the mel sums and of the gate sum
+    if (MASKED) {
+        if (threadIdx.x == 0) nf_s = 0ull;
+        __syncthreads();
+        unsigned long long c = 0ull;
+        for (int b = threadIdx.x; b < B; b += blockDim.x) c += (unsigned long long)min(max(len[b], 0), T);
+        if (c) atomicAdd(&nf_s, c);
+        __syncthreads();
+        const double nf = (double)nf_s;
+        dg = nf; dm = nf * (double)M;
+        sg = nf > 0.0 ? (float)(1.0 / dg) : 0.f;
+        sm = nf > 0.0 ? (float)(1.0 / dm) : 0.f;
+    }
     double a_g = 0, a_m = 0, a_p = 0;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv + ns; i += (long)gridDim.x * blockDim.x) {
         if (i < nv) {
@@ -419,11 +448,22 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* mels, const floa
             if (tv < T) {
                 const long k = ((long)b * T + tv) * M + m;
                 const bool masked = tv >= len[b];
-                const float tg = mel_tgt[k];
-                const float e1 = mels[k] - tg, e2 = post[k] - tg;
-                a_m += (double)e1 * e1; a_p += (double)e2 * e2;
-                const float g1 = masked ? 0.f : 2.f * e1 * sm * gscale;
-                const float g2 = masked ? 0.f : 2.f * e2 * sm * gscale;
+                float g1 = 0.f, g2 = 0.f;
+                if (!MASKED || !masked) {
+                    const float tg = mel_tgt[k];
+                    const float e1 = mels[k] - tg, e2 = post[k] - tg;
+                    if (MEL == 0) {
+                        a_m += (double)e1 * e1; a_p += (double)e2 * e2;
+                        g1 = masked ? 0.f : 2.f * e1 * sm * gscale;
+                        g2 = masked ? 0.f : 2.f * e2 * sm * gscale;
+                    } else {
+                        const float s1 = (float)(e1 > 0.f) - (float)(e1 < 0.f), s2 = (float)(e2 > 0.f) - (float)(e2 < 0.f);
+                        a_m += (double)fabsf(e1) + (MEL == 2 ? (double)e1 * e1 : 0.0);
+                        a_p += (double)fabsf(e2) + (MEL == 2 ? (double)e2 * e2 : 0.0);
+                        g1 = masked ? 0.f : (MEL == 2 ? 2.f * e1 + s1 : s1) * sm * gscale;
+                        g2 = masked ? 0.f : (MEL == 2 ? 2.f * e2 + s2 : s2) * sm * gscale;
+                    }
+                }
                 if (d_post) d_post[k] = g2;
                 if (d_mels) d_mels[k] = g1;
                 g = g1 + g2;
@@ -436,9 +476,18 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* mels, const floa
             for (int j = 0; j < r; ++j) {
                 const int t = s * r + j;
                 if (t >= T) break;
-                const float x = gates[(long)b * T + t], y = gate_tgt[(long)b * T + t];
-                a_g += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
-                const float g = t >= len[b] ? 0.f : (t2_sigmoid(x) - y) * sg * gscale;
+                float g = 0.f;
+                if (!MASKED || t < len[b]) {
+                    const float x = gates[(long)b * T + t], y = gate_tgt[(long)b * T + t];
+                    if (!WEIGHTED) {
+                        a_g += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
+                        g = t >= len[b] ? 0.f : (t2_sigmoid(x) - y) * sg * gscale;
+                    } else {
+                        const float l1p = log1pf(expf(-fabsf(x)));          // softplus(x) = max(x, 0) + l1p, softplus(-x) = max(-x, 0) + l1p
+                        a_g += (double)(y * (fmaxf(-x, 0.f) + l1p) + stop_w * (1.f - y) * (fmaxf(x, 0.f) + l1p));
+                        g = t >= len[b] ? 0.f : (t2_sigmoid(x) * (y + stop_w * (1.f - y)) - y) * sg * gscale;
+                    }
+                }
                 if (d_gates) d_gates[(long)b * T + t] = g;
                 gsum = GROUPED ? gsum + g : g;       // (r = 1: the value itself, a signed zero included)
             }
@@ -451,10 +500,10 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* mels, const floa
     __syncthreads();
     if (threadIdx.x < 3) {
         const double s = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-        atomicAdd(&loss3[threadIdx.x], s / (threadIdx.x == 0 ? (double)ng : (double)nm));
+        if (!MASKED) atomicAdd(&loss3[threadIdx.x], s / (threadIdx.x == 0 ? (double)ng : (double)nm));
+        else if (dg > 0.0) atomicAdd(&loss3[threadIdx.x], s / (threadIdx.x == 0 ? dg : dm));
     }
 }
-
 // Guided-attention loss and its gradient w.r.t. the alignments (include/tacotron2_amd.h: t2_guided_attn).  One WAVE walks whole
 // (b, t) rows - four rows in flight per workgroup - so the lengths and the row's scale are wave-uniform and no thread divides by L.
 // The exponent's argument is formed in double from the exact integer l*T_b - t*N_b (its rounding would otherwise dominate the
@@ -949,6 +998,66 @@ extern "C" int t2_loss_fwd_bwd_r(const float* mels, const float* post, const flo
     (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
     hipLaunchKernelGGL(loss_kernel<true>, dim3(ew_grid((long)B * S * ((long)r * M + 1))), dim3(256), 0, ST, mels, post, gates, mel_tgt,
                        gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, grad_scale, (float*)nullptr, (float*)nullptr);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+// loss options (T2LossOpts): the defaults are the entries above, after this entry's own checks; anything else is a further
+// instantiation of the one loss body
+static int loss_opts_check(const T2LossOpts* o, const char* what) {
+    T2_REQUIRE(o != nullptr, what);
+    T2_REQUIRE(o->mel_loss >= 0 && o->mel_loss <= 2, what);
+    T2_REQUIRE(std::isfinite(o->stop_weight) && o->stop_weight > 0.f, what);
+    return T2_OK;
+}
+template <bool GROUPED>
+static void loss_opt_launch(const T2LossOpts* o, unsigned grid, hipStream_t st, const float* mels, const float* post, const float* gates,
+                            const float* mel_tgt, const float* gate_tgt, const int32_t* len, int B, int T, int M, int r, int S,
+                            double* loss3, float* d_post, float* dproj, float gs, float* d_mels, float* d_gates) {
+    const int key = o->mel_loss * 4 + (o->masked ? 2 : 0) + (o->stop_weight != 1.f ? 1 : 0);
+#define T2_LOSS_CASE(MEL, MASKED)          /* the plain and the weighted instantiation of one (MEL, MASKED) pair */                     \
+    case (MEL) * 4 + (MASKED) * 2:                                                                                                   \
+        hipLaunchKernelGGL((loss_kernel<GROUPED, MEL, (MASKED) != 0, false>), dim3(grid), dim3(256), 0, st, mels, post, gates, mel_tgt, \
+                           gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, gs, d_mels, d_gates);                                  \
+        break;                                                                                                                       \
+    case (MEL) * 4 + (MASKED) * 2 + 1:                                                                                               \
+        hipLaunchKernelGGL((loss_kernel<GROUPED, MEL, (MASKED) != 0, true, float>), dim3(grid), dim3(256), 0, st, mels, post, gates,  \
+                           mel_tgt, gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, gs, d_mels, d_gates, o->stop_weight);         \
+        break;
+    switch (key) {      // (key 0, the defaults, never gets here: its instantiation is the kernel the entries above launch)
+        T2_LOSS_CASE(0, 0) T2_LOSS_CASE(0, 1) T2_LOSS_CASE(1, 0) T2_LOSS_CASE(1, 1) T2_LOSS_CASE(2, 0) T2_LOSS_CASE(2, 1)
+    }
+#undef T2_LOSS_CASE
+}
+static bool loss_opts_default(const T2LossOpts* o) { return o->mel_loss == 0 && !o->masked && o->stop_weight == 1.f; }
+extern "C" int t2_loss_fwd_bwd_opt(const float* mels, const float* post, const float* gates, const float* mel_tgt,
+                                   const float* gate_tgt, const int32_t* len, int B, int T, int M, int r, double* loss3, float* d_post,
+                                   float* dproj, float grad_scale, const T2LossOpts* opts, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(mels && post && gates && mel_tgt && gate_tgt && len && loss3 && d_post && dproj, "t2_loss_fwd_bwd_opt: null");
+    T2_REQUIRE_GROUPED("t2_loss_fwd_bwd_opt");
+    T2_TRY(loss_opts_check(opts, "t2_loss_fwd_bwd_opt: need options with mel_loss in {0, 1, 2} and a finite stop_weight > 0"));
+    if (loss_opts_default(opts))
+        return t2_loss_fwd_bwd_r(mels, post, gates, mel_tgt, gate_tgt, len, B, T, M, r, loss3, d_post, dproj, grad_scale, stream);
+    const int S = (T + r - 1) / r;
+    (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
+    const unsigned grid = ew_grid((long)B * S * ((long)r * M + 1));
+    if (r == 1) loss_opt_launch<false>(opts, grid, ST, mels, post, gates, mel_tgt, gate_tgt, len, B, T, M, 1, T, loss3, d_post, dproj,
+                                       grad_scale, nullptr, nullptr);
+    else loss_opt_launch<true>(opts, grid, ST, mels, post, gates, mel_tgt, gate_tgt, len, B, T, M, r, S, loss3, d_post, dproj, grad_scale,
+                               nullptr, nullptr);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+extern "C" int t2_loss_terms_opt(const float* mels, const float* post, const float* gates, const float* mel_tgt, const float* gate_tgt,
+                                 const int32_t* len, int B, int T, int M, double* loss3, float* d_mels, float* d_post, float* d_gates,
+                                 float grad_scale, const T2LossOpts* opts, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(mels && post && gates && mel_tgt && gate_tgt && len && loss3, "t2_loss_terms_opt: null");
+    T2_REQUIRE(B >= 1 && T >= 1 && M >= 1, "t2_loss_terms_opt: need B, T, M >= 1");
+    T2_TRY(loss_opts_check(opts, "t2_loss_terms_opt: need options with mel_loss in {0, 1, 2} and a finite stop_weight > 0"));
+    if (loss_opts_default(opts))
+        return t2_loss_terms(mels, post, gates, mel_tgt, gate_tgt, len, B, T, M, loss3, d_mels, d_post, d_gates, grad_scale, stream);
+    (void)hipMemsetAsync(loss3, 0, 3 * sizeof(double), ST);
+    loss_opt_launch<false>(opts, ew_grid((long)B * T * (M + 1)), ST, mels, post, gates, mel_tgt, gate_tgt, len, B, T, M, 1, T, loss3, d_post,
+                           nullptr, grad_scale, d_mels, d_gates);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
 extern "C" int t2_outgrad_pack_r(const float* d_mels, const float* d_post, const float* d_gates, const int32_t* len,

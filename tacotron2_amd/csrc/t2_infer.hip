@@ -22,6 +22,7 @@
 // Writers: prenet -> slot t&1; attention cell / context kernel -> slot (t+1)&1; decoder cell -> slot t&1 (read next frame).
 // Row-major copies exist only where another kernel needs rows: att_h [B][A] (query projection) and xproj = [dec_h | ctx].
 #include "t2_common.hpp"
+#include <cmath>
 
 int t2_lstm_step_fwd_launch(const T2LstmStep* steps, int n, hipStream_t st);
 int t2_attn_step_launch(const T2AttnStep* s, hipStream_t st);
@@ -47,20 +48,22 @@ struct LinK {
     const float* xt1; long xt_cs;              // ... chunks [nch0, K/16): from xt1; chunk stride xt_cs = Bp*16 floats
     // optional stop logic of the PREVIOUS frame, run by one extra workgroup next to the linear (saves one dependent launch per frame)
     const float* stop_proj; long stop_ldp; int stop_M, stop_t;
+    float stop_thr;                // a frame stops when its logit < stop_thr (0 = the reference's sigmoid < 0.5; T2Infer.stop_logit)
     int32_t* stop_done; int32_t* stop_state;
 };
 
 // model/tacotron2.py:319-322: done[gate < 0] = True; if done.all(): break.  The device keeps the sticky per-utterance flags
 // and state = {every utterance of this group has stopped, frames emitted}; the exact break frame and the `lengths` count
 // (every emitted frame whose stop logit is >= 0, Appendix C.4) are derived from the stored logits afterwards (stop_scan),
+// A threshold other than 0.5 moves the comparison to logit < thr = logit(tau) (T2Infer.stop_logit; 0.f is the reference's rule),
 // so a group that is decoded a few frames past the break - the host looks only every `check_every` frames, and with several
 // groups every group runs until ALL have stopped, as the reference's single loop does - still reports the reference's values.
-__device__ __forceinline__ void stop_logic(const float* proj, long ldp, int M, int B, int t, int32_t* done, int32_t* state,
+__device__ __forceinline__ void stop_logic(const float* proj, long ldp, int M, int B, int t, float thr, int32_t* done, int32_t* state,
                                            int* notdone /* LDS */) {
     if (threadIdx.x == 0) *notdone = 0;
     __syncthreads();
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        if (proj[(long)b * ldp + M] < 0.f) done[b] = 1;
+        if (proj[(long)b * ldp + M] < thr) done[b] = 1;
         if (!done[b]) atomicAdd(notdone, 1);
     }
     __syncthreads();
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(64 * NW, 1) void linear_rows_kernel(LinK p) {
     __shared__ float red[NW * MT * 256];
     __shared__ int notdone;
     if (p.stop_proj && blockIdx.x == gridDim.x - 1) {   // one extra workgroup: the stop logic runs next to the linear, not in front
-        if (blockIdx.y == 0) stop_logic(p.stop_proj, p.stop_ldp, p.stop_M, p.B, p.stop_t, p.stop_done, p.stop_state, &notdone);
+        if (blockIdx.y == 0) stop_logic(p.stop_proj, p.stop_ldp, p.stop_M, p.B, p.stop_t, p.stop_thr, p.stop_done, p.stop_state, &notdone);
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63;
@@ -176,20 +179,20 @@ int launch_linear(const LinK& k, hipStream_t st) {
     return T2_OK;
 }
 
-__global__ void stop_kernel(const float* proj, long ldp, int M, int B, int t, int32_t* done, int32_t* state) {
+__global__ void stop_kernel(const float* proj, long ldp, int M, int B, int t, float thr, int32_t* done, int32_t* state) {
     __shared__ int notdone;
-    stop_logic(proj, ldp, M, B, t, done, state, &notdone);
+    stop_logic(proj, ldp, M, B, t, thr, done, state, &notdone);
 }
 
 // Exact break frame and lengths from the stored stop logits of ALL utterances (several groups: proj_g [n][B_g][ldp]):
-// first[b] = first row with logit < 0; the loop breaks after row n* = max_b first[b] (or runs to `nframes` if some
-// utterance never stops); counted[b] = #{t <= n* : logit[t][b] >= 0}.  One workgroup.
+// first[b] = first row with logit < thr (thr = 0 unless a stop threshold is set: t2_stop_scan_thr); the loop breaks after row
+// n* = max_b first[b] (or runs to `nframes` if some utterance never stops); counted[b] = #{t <= n* : logit[t][b] >= thr}.  One workgroup.
 //   GROUPED = false: a row is a frame; lengths[b] = counted[b], out2 = {frames emitted n* + 1, 0}.
 //   GROUPED = true : a row is a decoder STEP of r >= 1 frames, column M (= r * num_mels) the step's one stop logit; the count rule
 //                    runs on steps, lengths[b] = min(r * counted[b], max_len) frames, out2 = {min(r * (n* + 1), max_len), n* + 1}.
 struct StopScan { const float* proj[64]; int Bg[64]; int ng; long ldp; int M; int nframes; int64_t* lengths; int32_t* out2; };
 template <bool GROUPED>
-__global__ void stop_scan_kernel(StopScan p, int r, int max_len) {
+__global__ void stop_scan_kernel(StopScan p, int r, int max_len, float thr) {
     __shared__ int nstar;
     if (threadIdx.x == 0) nstar = 0;
     __syncthreads();
@@ -200,7 +203,7 @@ __global__ void stop_scan_kernel(StopScan p, int r, int max_len) {
         while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
         int first = p.nframes - 1;     // never stops: the loop runs to the cap
         for (int t = 0; t < p.nframes; ++t)
-            if (p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] < 0.f) { first = t; break; }
+            if (p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] < thr) { first = t; break; }
         atomicMax(&nstar, first);
     }
     __syncthreads();
@@ -209,7 +212,7 @@ __global__ void stop_scan_kernel(StopScan p, int r, int max_len) {
         int g = 0, b = bb;
         while (b >= p.Bg[g]) { b -= p.Bg[g]; ++g; }
         long cnt = 0;
-        for (int t = 0; t < n; ++t) cnt += p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] >= 0.f ? 1 : 0;
+        for (int t = 0; t < n; ++t) cnt += p.proj[g][((long)t * p.Bg[g] + b) * p.ldp + p.M] >= thr ? 1 : 0;
         if (GROUPED) { cnt *= r; cnt = cnt < (long)max_len ? cnt : (long)max_len; }
         p.lengths[bb] = cnt;
     }
@@ -222,20 +225,33 @@ __global__ void stop_scan_kernel(StopScan p, int r, int max_len) {
 
 }  // namespace
 
-extern "C" int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream) {
-    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
-    T2_REQUIRE(s && lengths && out2 && s->ngroups >= 1 && s->ngroups <= 64 && s->nframes >= 1, "t2_stop_scan_r: bad arguments");
-    T2_REQUIRE(r >= 1 && max_len >= 1 && (long)s->nframes * r < (1L << 31), "t2_stop_scan_r: need r >= 1 and max_len >= 1");
+// the grouped scan against a threshold: t2_stop_scan_r is its 0.f call (`name` heads the messages of the entry that was called)
+static int stop_scan_thr(const char* name, const T2StopScan* s, int r, int max_len, float thr, int64_t* lengths, int32_t* out2,
+                         void* stream) {
+    T2_REQUIRE(s && lengths && out2 && s->ngroups >= 1 && s->ngroups <= 64 && s->nframes >= 1, name);
+    T2_REQUIRE(r >= 1 && max_len >= 1 && (long)s->nframes * r < (1L << 31), name);
     StopScan p;
     memset(&p, 0, sizeof(p));
     for (int g = 0; g < s->ngroups; ++g) {
-        T2_REQUIRE(s->proj[g] && s->Bg[g] >= 1, "t2_stop_scan_r: bad group");
+        T2_REQUIRE(s->proj[g] && s->Bg[g] >= 1, name);
         p.proj[g] = s->proj[g]; p.Bg[g] = s->Bg[g];
     }
     p.ng = s->ngroups; p.ldp = s->ld_proj; p.M = s->M; p.nframes = s->nframes; p.lengths = lengths; p.out2 = out2;
-    hipLaunchKernelGGL(stop_scan_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, r, max_len);
+    hipLaunchKernelGGL(stop_scan_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, r, max_len, thr);
     T2_CHECK_LAUNCH();
     return T2_OK;
+}
+
+extern "C" int t2_stop_scan_r(const T2StopScan* s, int r, int max_len, int64_t* lengths, int32_t* out2, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    return stop_scan_thr("t2_stop_scan_r: bad arguments (groups, nframes >= 1, r >= 1, max_len >= 1)", s, r, max_len, 0.f, lengths, out2, stream);
+}
+extern "C" int t2_stop_scan_thr(const T2StopScan* s, int r, int max_len, float stop_logit, int64_t* lengths, int32_t* out2,
+                                void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(std::isfinite(stop_logit), "t2_stop_scan_thr: stop_logit must be finite");
+    return stop_scan_thr("t2_stop_scan_thr: bad arguments (groups, nframes >= 1, r >= 1, max_len >= 1)", s, r, max_len, stop_logit, lengths,
+                         out2, stream);
 }
 
 extern "C" int t2_linear_rows(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const float* mask,
@@ -265,7 +281,7 @@ extern "C" int t2_stop_scan(const T2StopScan* s, int64_t* lengths, int32_t* out2
         p.proj[g] = s->proj[g]; p.Bg[g] = s->Bg[g];
     }
     p.ng = s->ngroups; p.ldp = s->ld_proj; p.M = s->M; p.nframes = s->nframes; p.lengths = lengths; p.out2 = out2;
-    hipLaunchKernelGGL(stop_scan_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, 1, 0);
+    hipLaunchKernelGGL(stop_scan_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, 1, 0, 0.f);
     T2_CHECK_LAUNCH();
     return T2_OK;
 }
@@ -282,6 +298,7 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
     T2_REQUIRE(!(a->forward && a->win_peak), "t2_decoder_infer: forward attention does not compose with the attention window");
     T2_REQUIRE(a->zone_p >= 0.f && a->zone_p <= 1.f && (a->zone_p == 0.f || (a->zone_att && a->zone_dec)),
                "t2_decoder_infer: zone_p in [0, 1], with the two filled blocks zone_att and zone_dec");
+    T2_REQUIRE(std::isfinite(a->stop_logit), "t2_decoder_infer: stop_logit must be finite");
     const bool zoned = a->zone_p != 0.f;
     const long ldp = D + Ef, ldo = a->ld_proj;
     const int Bp = (B + 15) / 16 * 16;
@@ -321,7 +338,7 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
             k.out_t = xs_cur; k.out_col0 = 0; k.out_cs = cs;
             if (t > t0) {
                 k.stop_proj = a->proj + (long)(t - 1) * B * ldo; k.stop_ldp = ldo; k.stop_M = M; k.stop_t = t - 1;
-                k.stop_done = a->done; k.stop_state = a->state;
+                k.stop_thr = a->stop_logit; k.stop_done = a->done; k.stop_state = a->state;
             }
             T2_TRY(launch_linear(k, st));
         }
@@ -375,8 +392,8 @@ extern "C" int t2_decoder_infer(const T2Infer* a, int t0, int t1, void* stream) 
         // the last frame of the call: its outputs (mel, stop logit) and stop logic, so that the host can look at the flags.  The
         // next call's first L1 recomputes the same row bit for bit (and the p1 scratch written here, with its mask).
         T2_TRY(combined(t1, false));
-        hipLaunchKernelGGL(stop_kernel, dim3(1), dim3(256), 0, st, a->proj + (long)(t1 - 1) * B * ldo, ldo, M, B, t1 - 1, a->done,
-                           a->state);
+        hipLaunchKernelGGL(stop_kernel, dim3(1), dim3(256), 0, st, a->proj + (long)(t1 - 1) * B * ldo, ldo, M, B, t1 - 1, a->stop_logit,
+                           a->done, a->state);
     }
     T2_CHECK_LAUNCH();
     return T2_OK;

@@ -14,6 +14,8 @@ the hardware:
 from __future__ import annotations
 
 import contextlib
+import ctypes
+import math
 import numbers
 import threading as _threading
 from typing import Dict, NamedTuple, Optional
@@ -134,6 +136,59 @@ def check_guided_attention(guided):
     if sigma <= 0 or alpha < 0:
         raise ValueError(f"guided_attention needs sigma > 0 and alpha >= 0, got {guided!r}")
     return float(sigma), float(alpha)
+
+
+MEL_LOSSES = ("l2", "l1", "l1+l2")       # T2LossOpts.mel_loss = the index
+LOSS_DEFAULTS = ("l2", False, 1.0)
+
+
+def check_loss_options(loss):
+    """None, a dict with any of the keys "mel" / "masked" / "stop_weight", or a 3-tuple (mel, masked, stop_weight) -> the tuple
+    (mel in MEL_LOSSES, masked bool, stop_weight float > 0), missing keys at their defaults ("l2", False, 1.0: the reference's loss);
+    anything else raises ValueError naming the offending value."""
+    if loss is None:
+        return LOSS_DEFAULTS
+    if isinstance(loss, dict):
+        unknown = sorted(set(loss) - {"mel", "masked", "stop_weight"})
+        if unknown:
+            raise ValueError(f"loss options: unknown key {unknown[0]!r} (known: mel, masked, stop_weight)")
+        mel, masked, w = (loss.get(k, dflt) for k, dflt in zip(("mel", "masked", "stop_weight"), LOSS_DEFAULTS))
+    else:
+        try:
+            mel, masked, w = loss
+        except (TypeError, ValueError):
+            raise ValueError(f"loss options must be a dict or (mel, masked, stop_weight), got {loss!r}") from None
+    if not isinstance(mel, str) or mel not in MEL_LOSSES:
+        raise ValueError(f"loss options: mel must be one of {', '.join(MEL_LOSSES)}, got {mel!r}")
+    if not isinstance(masked, bool):
+        raise ValueError(f"loss options: masked must be True or False, got {masked!r}")
+    if isinstance(w, bool) or not isinstance(w, numbers.Real) or w != w or abs(w) == float("inf") or w <= 0:
+        raise ValueError(f"loss options: stop_weight must be a finite number > 0, got {w!r}")
+    if not 0.0 < float(ctypes.c_float(float(w)).value) < float("inf"):
+        raise ValueError(f"loss options: stop_weight must be a finite float32 > 0, got {w!r}")
+    return mel, masked, float(w)
+
+
+def loss_opts_struct(loss):
+    """The T2LossOpts block of checked options."""
+    mel, masked, w = loss
+    return make("T2LossOpts", mel_loss=MEL_LOSSES.index(mel), masked=int(masked), stop_weight=w)
+
+
+def check_stop_threshold(tau) -> float:
+    """A stop threshold 0 < tau < 1 as a float (0.5: the reference's rule); anything else raises ValueError."""
+    if isinstance(tau, bool) or not isinstance(tau, numbers.Real) or not 0.0 < float(tau) < 1.0:
+        raise ValueError(f"stop_threshold must be a number with 0 < threshold < 1, got {tau!r}")
+    return float(tau)
+
+
+def stop_logit(tau: float) -> float:
+    """logit(tau) = log(tau / (1 - tau)) formed in double and rounded to float32: the ONE value the decode loop's flags, the scan
+    and the drivers' length rule compare against.  0.5 gives 0.0, the reference's comparison."""
+    v = float(ctypes.c_float(math.log(tau / (1.0 - tau))).value)
+    if v != v or abs(v) == float("inf"):
+        raise ValueError(f"stop_threshold {tau!r} has no finite float32 logit")
+    return v
 
 
 def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
@@ -1475,12 +1530,16 @@ class Engine:
     # =============================================================================================
     # loss + one optimisation step
     # =============================================================================================
-    def loss_and_grads(self, outs, ctx, mel_tgt, gate_tgt, grad_scale=1.0, guided=None):
+    def loss_and_grads(self, outs, ctx, mel_tgt, gate_tgt, grad_scale=1.0, guided=None, loss=None):
         """3-term loss of model/tts_model.py:197-201 and the full backward.  Returns loss3 (device, float64[3]).
         guided=(sigma, alpha): the guided-attention term on the alignments joins the loss (t2_guided_attn: one launch for its value
         and its gradient, which goes into the attention backward); its value is `self.guided_loss` (device, float64[1]) - None when
-        the term is off - and loss3 stays the three terms."""
+        the term is off - and loss3 stays the three terms.
+        loss: None, a dict or (mel, masked, stop_weight) - check_loss_options: "l1" / "l1+l2" mel terms, the mean over valid frames only,
+        a weight on the stop class (t2_loss_fwd_bwd_opt).  The defaults are the reference's loss through the entry this
+        method always called.  Composes with guided."""
         mels, post, gates, align = outs
+        loss = check_loss_options(loss)
         B, T, M = mels.shape
         r, S = ctx["r"], ctx["S"]
         guided = check_guided_attention(guided)
@@ -1498,8 +1557,12 @@ class Engine:
         loss3 = self.buf("loss3", 3, dtype=torch.float64)
         d_post = self.buf("d_post", B, T, M)
         dproj = self.buf("dproj", S, B, r * M + 1)
-        call("t2_loss_fwd_bwd_r", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, r, loss3, d_post, dproj,
-             float(grad_scale), _stream())
+        if loss == LOSS_DEFAULTS:
+            call("t2_loss_fwd_bwd_r", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, r, loss3, d_post, dproj,
+                 float(grad_scale), _stream())
+        else:
+            call("t2_loss_fwd_bwd_opt", mels, post, gates, mel_tgt, gate_tgt, ctx["mlen32"], B, T, M, r, loss3, d_post, dproj,
+                 float(grad_scale), loss_opts_struct(loss), _stream())
         self.backward_tf(ctx, d_post, dproj, d_align=d_align)
         return loss3
 
@@ -1520,7 +1583,7 @@ class Engine:
     # autoregressive inference: forward(teacher_forcing=False, max_len_override=N)  (model/tacotron2.py:262-325)
     # =============================================================================================
     def _infer_group(self, g, enc, chars_len, Tcap, speaker_id, description_embeddings, training, prenet_masks, controls,
-                     attention_window=None, forward_attention=False):
+                     attention_window=None, forward_attention=False, stop_logit_=0.0):
         """Conditioning and decode-loop operands of one group of <= 64 utterances (workspaces prefixed inf<g>.); `enc` is the
         group's slice of the encoder output, computed for the WHOLE batch by the caller."""
         d, P, ps = self.d, self.ps.P, self.ps
@@ -1577,11 +1640,13 @@ class Engine:
                  wp_dec=self._wp_dec_inf, b_dec_ih=P["decoder.lstm.bias_ih"], b_dec_hh=P["decoder.lstm.bias_hh"],
                  Wq=P["decoder.attention.query_layer.weight"], U=self._U_inf, v=P["decoder.attention.v.weight"],
                  pmT=pmT, memory=memory, len=len32, prenet_mask=pm, xs=xs, att_h=att_h, att_c=att_c, dec_c=dec_c, cum=cum,
-                 xproj=xproj, p1=p1, e_part=e_part, proj=proj, ld_proj=ldo, align=align, done=done, state=state, dec_pre=cterm, **zone)
+                 xproj=xproj, p1=p1, e_part=e_part, proj=proj, ld_proj=ldo, align=align, done=done, state=state, dec_pre=cterm, **zone,
+                 stop_logit=stop_logit_)
         return dict(a=a, B=B, proj=proj, align=align, state=state, pm=pm, philox=prenet_masks is None and pm is not None)
 
     def infer(self, chars_idx, chars_len, max_len, speaker_id=None, description_embeddings=None, training=False,
-              prenet_masks=None, seed=0, check_every=32, controls=None, attention_window=None, forward_attention=False):
+              prenet_masks=None, seed=0, check_every=32, controls=None, attention_window=None, forward_attention=False,
+              stop_threshold=0.5):
         """Returns (mels, mels_post, gates, alignments, lengths) exactly as the reference's non-teacher-forced forward: ONE loop
         over the whole batch that ends when every utterance has produced a negative stop logit (model/tacotron2.py:319-322).
         Batches above 64 utterances are decoded as groups of 64 in lock-step chunks of `check_every` frames; the break frame
@@ -1596,8 +1661,11 @@ class Engine:
         returned alignments and the next frame's location features all use alpha.  Not together with attention_window.
         With a reduction factor r > 1 `max_len` stays in frames: the loop runs at most ceil(max_len / r) decoder steps (one row of
         prenet_masks and of the alignments per step), the count rule applies to steps, lengths = min(r * counted steps, max_len), and
-        the outputs have n = min(r * steps run, max_len) frames; window and forward attention act per step."""
+        the outputs have n = min(r * steps run, max_len) frames; window and forward attention act per step.
+        stop_threshold: 0 < tau < 1 - a step stops when sigmoid(stop logit) < tau, i.e. logit < logit(tau), and the count rule counts
+        logit >= logit(tau) (NVIDIA's gate_threshold; T2Infer.stop_logit, t2_stop_scan_thr).  0.5 is the reference's `gate < 0`."""
         attention_window = check_attention_window(attention_window)
+        thr = stop_logit(check_stop_threshold(stop_threshold))
         forward_attention = check_forward_attention(forward_attention, attention_window)
         d, P, ps = self.d, self.ps.P, self.ps
         B, L = chars_idx.shape
@@ -1654,7 +1722,7 @@ class Engine:
                 speaker_id[sl] if speaker_id is not None else None,
                 description_embeddings[sl].contiguous() if description_embeddings is not None else None, training,
                 prenet_masks[:, :, sl].contiguous() if (prenet_masks is not None and B > 64) else prenet_masks,
-                controls[sl] if controls is not None else None, attention_window, forward_attention))
+                controls[sl] if controls is not None else None, attention_window, forward_attention, thr))
         p = float(d["dropout"])
         t0 = 0
         self.mark("inf.encoder")
@@ -1694,7 +1762,10 @@ class Engine:
         scan = make("T2StopScan", proj=[G["proj"] for G in groups] + [0] * (64 - len(groups)),
                     Bg=[G["B"] for G in groups] + [0] * (64 - len(groups)), ngroups=len(groups), ld_proj=ldo, M=M, nframes=t0)
         # the count rule on steps; lengths and the emitted count n in frames, cut at max_len (nfr[1]: steps)
-        call("t2_stop_scan_r", scan, r, max_len, lengths, nfr, st)
+        if thr == 0.0:
+            call("t2_stop_scan_r", scan, r, max_len, lengths, nfr, st)
+        else:
+            call("t2_stop_scan_thr", scan, r, max_len, thr, lengths, nfr, st)
         nfr_h = nfr.cpu()
         n = max(int(nfr_h[0]), 1)
         ns = max(int(nfr_h[1]), 1)

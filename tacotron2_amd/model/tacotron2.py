@@ -16,7 +16,7 @@ import torch
 from torch import Tensor, nn
 
 from .._lib import call
-from ..engine import check_rate, Engine, _stream, check_attention_window, check_forward_attention
+from ..engine import check_rate, Engine, _stream, check_attention_window, check_forward_attention, check_stop_threshold
 from ..init import init_parameters
 from ..params import ParamStore, check_reduction_factor
 
@@ -181,7 +181,7 @@ class Tacotron2(nn.Module):
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
                 dropout_masks: Optional[dict] = None, attention_window: Optional[Tuple[int, int]] = None,
-                forward_attention: bool = False, train_forward_attention: bool = False):
+                forward_attention: bool = False, train_forward_attention: bool = False, stop_threshold: float = 0.5):
         """attention_window (autoregressive decoding only): (back, fwd) integers >= 0 - each frame attends only to the positions
         max(0, m - back) .. min(len - 1, m + fwd) around the previous frame's attention peak m (ESPnet's `use_att_constraint`);
         None attends to the whole text, as the reference does.
@@ -190,7 +190,12 @@ class Tacotron2(nn.Module):
         the softmax times the prior 0.5 alpha_{t-1}(n) + 0.5 alpha_{t-1}(n-1) + 1e-8, renormalised (Engine.infer).
         train_forward_attention (teacher forcing only): True runs the teacher-forced attention chain under the same prior, forward
         and backward (Engine.forward_tf(forward_attention=True)) - training-time forward attention; such a model is decoded with
-        forward_attention=True."""
+        forward_attention=True.
+        stop_threshold (autoregressive decoding only): 0 < tau < 1 - an utterance stops at the first step whose stop probability
+        sigmoid(logit) falls below tau (NVIDIA's `gate_threshold`; Engine.infer).  0.5 is the reference's rule, `gate < 0`; a lower
+        value decodes longer, a higher one stops earlier."""
+        if check_stop_threshold(stop_threshold) != 0.5 and teacher_forcing:
+            raise ValueError("stop_threshold applies to autoregressive decoding only (teacher_forcing=False)")
         if check_forward_attention(train_forward_attention) and not teacher_forcing:
             raise ValueError("train_forward_attention applies to teacher forcing only (teacher_forcing=True); decode with "
                              "forward_attention=True")
@@ -229,7 +234,8 @@ class Tacotron2(nn.Module):
                                    description_embeddings=description_embeddings.contiguous().float()
                                    if description_embeddings is not None else None,
                                    training=self.training, prenet_masks=pm, seed=self._seed + self._calls, controls=controls,
-                                   attention_window=attention_window, forward_attention=forward_attention)
+                                   attention_window=attention_window, forward_attention=forward_attention,
+                                   stop_threshold=stop_threshold)
             self._calls += 1
         return o[:4]
 

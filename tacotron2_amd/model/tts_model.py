@@ -10,7 +10,7 @@ import torch
 from torch import Tensor, nn
 
 from .._lib import call
-from ..engine import check_guided_attention
+from ..engine import LOSS_DEFAULTS, check_guided_attention, check_loss_options, loss_opts_struct
 from ..params import check_reduction_factor
 from .tacotron2 import Tacotron2
 
@@ -37,18 +37,26 @@ def check_loss_inputs(mel, post, gate, mel_tgt, gate_tgt, mel_len) -> None:
 class _LossTermsFn(torch.autograd.Function):
     """(gate BCE-with-logits, mel MSE, post MSE) of model/tts_model.py:197-199 - plain means over the padded tensors - as ONE
     device kernel (t2_loss_terms); with autograd on, the same launch also writes the three dense gradients, which backward scales
-    by the upstream gradient of each term."""
+    by the upstream gradient of each term.  `loss`: checked loss options (engine.check_loss_options); anything but the defaults goes
+    through t2_loss_terms_opt - l1 / l1+l2 mel terms, the mean over valid frames, the stop-class weight."""
 
     @staticmethod
-    def forward(ctx, mel, post, gate, mel_tgt, gate_tgt, mel_len):
+    def forward(ctx, mel, post, gate, mel_tgt, gate_tgt, mel_len, *options):
         check_loss_inputs(mel, post, gate, mel_tgt, gate_tgt, mel_len)
+        loss = check_loss_options(options[0] if options else None)     # (an optional seventh argument: callers without it are served as before)
+        ctx.n_options = len(options)
         B, T, M = mel.shape
         need = any(ctx.needs_input_grad[:3])
         mel, post, gate = mel.contiguous().float(), post.contiguous().float(), gate.contiguous().float()
         loss3 = torch.empty(3, dtype=torch.float64, device=mel.device)
         grads = [torch.empty_like(t) if need else None for t in (mel, post, gate)]
-        call("t2_loss_terms", mel, post, gate, mel_tgt.contiguous().float(), gate_tgt.contiguous().float(),
-             mel_len.to(torch.int32), B, T, M, loss3, grads[0], grads[1], grads[2], 1.0, torch.cuda.current_stream().cuda_stream)
+        if loss == LOSS_DEFAULTS:
+            call("t2_loss_terms", mel, post, gate, mel_tgt.contiguous().float(), gate_tgt.contiguous().float(),
+                 mel_len.to(torch.int32), B, T, M, loss3, grads[0], grads[1], grads[2], 1.0, torch.cuda.current_stream().cuda_stream)
+        else:
+            call("t2_loss_terms_opt", mel, post, gate, mel_tgt.contiguous().float(), gate_tgt.contiguous().float(),
+                 mel_len.to(torch.int32), B, T, M, loss3, grads[0], grads[1], grads[2], 1.0, loss_opts_struct(loss),
+                 torch.cuda.current_stream().cuda_stream)
         ctx.grads = grads
         return loss3.float()
 
@@ -56,7 +64,7 @@ class _LossTermsFn(torch.autograd.Function):
     def backward(ctx, g3):
         d_mel, d_post, d_gate = ctx.grads
         return (d_mel * g3[1] if d_mel is not None else None, d_post * g3[2] if d_post is not None else None,
-                d_gate * g3[0] if d_gate is not None else None, None, None, None)
+                d_gate * g3[0] if d_gate is not None else None, None, None, None) + (None,) * ctx.n_options
 
 
 class _GuidedAttnFn(torch.autograd.Function):
@@ -120,6 +128,12 @@ class TTSModel(nn.Module):
         # forward attention under teacher forcing in training_step / validation_step (Tacotron2.forward(train_forward_attention=True)).
         # Set by the driver like guided_attention: not a constructor argument, not in hparams
         self.train_forward_attention: bool = False
+        # loss options of training_step / validation_step: None, a dict or (mel, masked, stop_weight) - engine.check_loss_options:
+        # "l1" / "l1+l2" mel terms, the mean over valid frames only, a weight on the stop class.  Training settings that change no
+        # parameter: set by the driver like guided_attention, not a constructor argument, not in hparams.  None = the reference's loss
+        self.loss_options = None
+        # stop threshold of predict_step and the run drivers' decoding (Tacotron2.forward(stop_threshold=...)); 0.5 = the reference
+        self.stop_threshold: float = 0.5
         self.tacotron2 = Tacotron2(num_chars=num_chars, encoded_dim=encoded_dim, encoder_kernel_size=encoder_kernel_size,
                                    num_mels=num_mels, prenet_dim=prenet_dim, att_rnn_dim=att_rnn_dim, att_dim=att_dim,
                                    rnn_hidden_dim=rnn_hidden_dim, postnet_dim=postnet_dim, dropout=dropout,
@@ -141,12 +155,13 @@ class TTSModel(nn.Module):
                 speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
                 max_len_override: Optional[int] = None, description_embeddings: Optional[Tensor] = None,
                 attention_window: Optional[Tuple[int, int]] = None, forward_attention: bool = False,
-                train_forward_attention: bool = False):
+                train_forward_attention: bool = False, stop_threshold: float = 0.5):
         return self.tacotron2(chars_idx=chars_idx, chars_idx_len=chars_idx_len, teacher_forcing=teacher_forcing,
                               mel_spectrogram=mel_spectrogram, mel_spectrogram_len=mel_spectrogram_len,
                               speaker_id=speaker_id, controls=controls, max_len_override=max_len_override,
                               description_embeddings=description_embeddings, attention_window=attention_window,
-                              forward_attention=forward_attention, train_forward_attention=train_forward_attention)
+                              forward_attention=forward_attention, train_forward_attention=train_forward_attention,
+                              stop_threshold=stop_threshold)
 
     def durations(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
                   mode: str = "monotonic", speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None,
@@ -171,12 +186,13 @@ class TTSModel(nn.Module):
     def _loss(self, batch):
         data, meta = batch[0], batch[1]
         guided = check_guided_attention(self.guided_attention)
+        loss_options = check_loss_options(self.loss_options)
         mel, post, gate, alignment = self(chars_idx=data["chars_idx"], chars_idx_len=meta["chars_idx_len"],
                                           teacher_forcing=True, mel_spectrogram=data["mel_spectrogram"],
                                           mel_spectrogram_len=meta["mel_spectrogram_len"],
                                           train_forward_attention=self.train_forward_attention, **self._args(meta))
         # the three terms of model/tts_model.py:197-199 from the library's loss kernel (no ATen arithmetic on this path)
-        l3 = _LossTermsFn.apply(mel, post, gate, data["mel_spectrogram"], data["gate"], meta["mel_spectrogram_len"])
+        l3 = _LossTermsFn.apply(mel, post, gate, data["mel_spectrogram"], data["gate"], meta["mel_spectrogram_len"], loss_options)
         gate_loss, mel_loss, post_loss = l3[0], l3[1], l3[2]
         loss = l3.sum()
         if guided is not None:
@@ -202,7 +218,7 @@ class TTSModel(nn.Module):
         with torch.no_grad():
             return self(chars_idx=data["chars_idx"], chars_idx_len=meta["chars_idx_len"], teacher_forcing=False,
                         max_len_override=self.max_len_override or 5000, attention_window=self.attention_window,
-                        forward_attention=self.forward_attention,
+                        forward_attention=self.forward_attention, stop_threshold=self.stop_threshold,
                         **self._args(meta))
 
     # Lightning-style checkpoint exchange: {"state_dict": {"tacotron2.<name>": tensor}, "hyper_parameters": {...}}

@@ -44,6 +44,32 @@ def train_forward_attention_setting(training_config: dict, override=None) -> boo
     return check_forward_attention(training_config.get("forward_attention", False))
 
 
+def loss_options_setting(training_config: dict, mel=None, masked=None, stop_weight=None):
+    """(mel, masked, stop_weight) of the training loss (engine.check_loss_options): each of `mel` (--mel-loss), `masked` (True / False for
+    --masked-loss / --no-masked-loss) and `stop_weight` (--stop-weight) wins, when it is not None, over its key of
+    `"training": {"loss": {"mel": "l1+l2", "masked": true, "stop_weight": 8.0}}`; any key may be left out ("l2", false, 1.0: the
+    reference's loss).  A section of another form or a bad value raises ValueError naming it."""
+    from ..engine import check_loss_options
+    sec = training_config.get("loss")
+    if sec is None:
+        sec = {}
+    if not isinstance(sec, dict):
+        raise ValueError('training.loss must be an object with the keys "mel", "masked" and "stop_weight" '
+                         f'(e.g. {{"mel": "l1+l2", "masked": true, "stop_weight": 8.0}}), got {sec!r}')
+    sec = dict(sec)
+    for key, v in (("mel", mel), ("masked", masked), ("stop_weight", stop_weight)):
+        if v is not None:
+            sec[key] = v
+    return check_loss_options(sec)
+
+
+def stop_threshold_setting(model_config: dict, override=None) -> float:
+    """The decode stop threshold 0 < tau < 1: `override` (the --stop-threshold option) wins over `"model": {"stop_threshold": 0.4}`;
+    default 0.5, the reference's rule.  Anything else raises ValueError."""
+    from ..engine import check_stop_threshold
+    return check_stop_threshold(override if override is not None else model_config.get("stop_threshold", 0.5))
+
+
 def guided_attention_setting(training_config: dict, override=None):
     """(sigma, alpha) of the guided-attention loss, or None when it is off: `override` (the --guided-attention option) wins over
     `"training": {"guided_attention": {"sigma": 0.4, "alpha": 1.0}}` (either key may be left out: 0.4 and 1.0).  A section of

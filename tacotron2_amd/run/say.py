@@ -13,7 +13,7 @@ import torch
 from ..datasets.text import TextEncoder
 from ..engine import check_attention_window, check_forward_attention
 from ..model.tts_model import TTSModel
-from .common import model_kwargs
+from .common import model_kwargs, stop_threshold_setting
 
 
 def load_description(description: Optional[str], dim: int, n: int, dev) -> torch.Tensor:
@@ -63,8 +63,11 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
            description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
-           forward_attention: Optional[bool] = None, durations_out: Optional[str] = None):
-    """durations_out: a path - character timestamps of the decode are written there as a JSON list with one object per text:
+           forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
+           stop_threshold: Optional[float] = None):
+    """stop_threshold: 0 < tau < 1, the stop probability below which an utterance ends (Tacotron2.forward); None takes the config's
+    `model.stop_threshold` if there is one, else 0.5, the reference's rule.
+    durations_out: a path - character timestamps of the decode are written there as a JSON list with one object per text:
     `symbols` (the encoded sequence, end token included), `frames` per symbol (the monotonic path through the decode's own
     alignments, Engine.durations; they sum to the frames of the mel that is written), `start_s` / `end_s` per symbol (hop of 256
     samples at the dataset's sample rate), `focus_rate` and `feasible`.  None: nothing of this runs."""
@@ -87,6 +90,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     if forward_attention is None:      # likewise the config's model.forward_attention (a bool)
         forward_attention = model_config.get("forward_attention", False)
     model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
+    model.stop_threshold = stop_threshold_setting(model_config, stop_threshold)
     kw = {}
     if model.speaker_tokens:
         kw["speaker_id"] = torch.full((len(texts),), int(speaker_id or 0), dtype=torch.int32, device=dev)
@@ -100,11 +104,13 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         kw["controls"] = torch.tensor([vals] * len(texts), dtype=torch.float32, device=dev)
     with torch.no_grad():
         _, post, gates, align = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                      attention_window=model.attention_window, forward_attention=model.forward_attention, **kw)
+                                      attention_window=model.attention_window, forward_attention=model.forward_attention,
+                                      stop_threshold=model.stop_threshold, **kw)
     post = post.cpu().numpy()
     # run/say.py:155,161 keeps mel_spectrogram_post[:, :-1]: all emitted frames but the last.  The stop frame itself is already
     # masked (gate -1000 from `lengths` on), so an utterance that stopped keeps its `lengths` = n - 1 frames; one that ran into
-    # max_len without stopping has n unmasked frames and loses the last one, as in the reference.
+    # max_len without stopping has n unmasked frames and loses the last one, as in the reference.  (A stop threshold changes
+    # `lengths`, not this rule: it reads the mask, never a logit's sign.)
     valid = (gates.cpu().numpy()[:, :, 0] != -1000.0).sum(1)
     n_emitted = post.shape[1]
     mels = [post[b, :max(min(int(valid[b]), n_emitted - 1), 1)] for b in range(len(texts))]

@@ -23,19 +23,21 @@ import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
-from ..engine import check_attention_window, check_forward_attention
+from ..engine import check_attention_window, check_forward_attention, stop_logit
 from ..model.tts_model import TTSModel
-from .common import model_kwargs
+from .common import model_kwargs, stop_threshold_setting
 
 
 def load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed=None,
-                    attention_window=None, forward_attention=None):
+                    attention_window=None, forward_attention=None, stop_threshold=None):
     """TTSModel.load_from_checkpoint as run/test.py:116-130 calls it (max_len_override 5000, no scheduler), in eval mode.
     attention_window: (back, fwd) of the windowed attention the model decodes with (TTSModel.attention_window); None takes the
     config's `model.attention_window` if there is one (`main.py --attention-window` puts it there for test-correlation), else off.
     forward_attention: True decodes with forward attention (TTSModel.forward_attention); None takes the config's
     `model.forward_attention` (a bool; `main.py --forward-attention` puts it there for test-correlation), else off.  Forward
-    attention together with a window is refused."""
+    attention together with a window is refused.
+    stop_threshold: 0 < tau < 1 of the decode's stop rule (TTSModel.stop_threshold); None takes the config's `model.stop_threshold`
+    (`main.py --stop-threshold` puts it there for test-correlation), else 0.5."""
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
     kw["scheduler_milestones"] = []
@@ -49,6 +51,7 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
     if forward_attention is None:
         forward_attention = model_config.get("forward_attention", False)
     model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
+    model.stop_threshold = stop_threshold_setting(model_config, stop_threshold)
     return model
 
 
@@ -74,6 +77,12 @@ def make_vocoders(hifi_gan_checkpoint, pre, dev):
     return None, GriffinLim(n_mels=int(pre.get("num_mels", 80)), sample_rate=sr, device=dev), sr
 
 
+def mel_lengths_of(gate: torch.Tensor, stop_threshold: float = 0.5) -> torch.Tensor:
+    """run/test.py:172,205 `(gate < 0).argmax` against the decode's own stop threshold: the first frame of (B, n, 1) gates below
+    logit(threshold) - the first masked frame (-1000) of an utterance that stopped -, 0 when there is none.  0.5 compares with 0."""
+    return (gate[:, :, 0] < stop_logit(stop_threshold)).to(torch.int64).argmax(dim=-1)
+
+
 def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=8, max_len=5000,
                         random_seed=None, zero_length="test") -> List[str]:
     """The prediction + "Saving WAVs" loops of run/test.py:132-227 and run/test_correlation.py:171-250 over one manifest:
@@ -87,7 +96,9 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     becomes -1 and is applied twice: the row minus its last two samples); "correlation" = run/test_correlation.py:196-209 (an
     empty file).  Both log the utterance.  Griffin-Lim (librosa raises on an empty spectrogram): logged, nothing written.
     The decode uses the model's attention window (TTSModel.attention_window, set by load_test_model; None = off) or its forward
-    attention (TTSModel.forward_attention; False = off)."""
+    attention (TTSModel.forward_attention; False = off), and its stop threshold (TTSModel.stop_threshold): `mel_lengths` is then the
+    first frame with gate < logit(threshold) - under a threshold below 0.5 a kept frame may have a logit in [logit(threshold), 0) -,
+    which at 0.5 is the reference's `gate < 0`."""
     from ..vocoder import write_wav
     dev = model.tacotron2.store.device
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
@@ -124,8 +135,9 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
         with torch.no_grad():
             _, post, gate, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
                                      attention_window=model.attention_window,
-                                     forward_attention=getattr(model, "forward_attention", False), **args)
-        mel_lengths = (gate[:, :, 0] < 0).to(torch.int64).argmax(dim=-1).cpu().tolist()
+                                     forward_attention=getattr(model, "forward_attention", False),
+                                     stop_threshold=getattr(model, "stop_threshold", 0.5), **args)
+        mel_lengths = mel_lengths_of(gate, getattr(model, "stop_threshold", 0.5)).cpu().tolist()
         for k, j in enumerate(sel):
             i += 1
             n = int(mel_lengths[k])
@@ -152,7 +164,7 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
             speech_dir: Optional[str], checkpoint: str, hifi_gan_checkpoint: Optional[str] = None,
             results_dir: Optional[str] = None, batch_size: int = 8, max_len: int = 5000, limit: Optional[int] = None,
             random_seed: Optional[int] = None, attention_window: Optional[Tuple[int, int]] = None,
-            forward_attention: Optional[bool] = None) -> List[str]:
+            forward_attention: Optional[bool] = None, stop_threshold: Optional[float] = None) -> List[str]:
     import pandas as pd
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
@@ -163,7 +175,7 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
     if limit is not None:
         df = df.iloc[:int(limit)].reset_index(drop=True)
     model = load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
-                            attention_window, forward_attention)
+                            attention_window, forward_attention, stop_threshold)
     ctl_cfg = extensions_config.get("controls", {"active": False})
     feats = df[ctl_cfg["features"]].values.tolist() if model.controls else None
     if results_dir is None:

@@ -15,7 +15,7 @@ import torch.distributed as dist
 
 from ..model.tts_model import TTSModel
 from ..trainer import Trainer
-from .common import guided_attention_setting, model_kwargs, train_forward_attention_setting
+from .common import guided_attention_setting, loss_options_setting, model_kwargs, train_forward_attention_setting
 
 
 def _to_dev(batch, dev):
@@ -34,8 +34,11 @@ def _to_dev(batch, dev):
 def do_train(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
              speech_dir: str, results_dir: Optional[str], resume_ckpt: Optional[str], finetune: bool = False,
              finetune_steps: Optional[int] = None, max_steps_override: Optional[int] = None, synthetic: bool = False,
-             guided_attention=None, forward_attention=None):
-    """forward_attention: True trains under the forward-attention prior (Trainer(forward_attention=True)); None takes the config's
+             guided_attention=None, forward_attention=None, mel_loss=None, masked_loss=None, stop_weight=None):
+    """mel_loss / masked_loss / stop_weight: the loss options (Trainer(loss_options=...), TTSModel.loss_options): "l2" | "l1" | "l1+l2"
+    mel terms, the mean over valid frames only, the weight of the stop class.  None takes the key of the config's `training.loss`
+    (`main.py train --mel-loss / --masked-loss / --stop-weight` win over it), else the reference's loss.
+    forward_attention: True trains under the forward-attention prior (Trainer(forward_attention=True)); None takes the config's
     `training.forward_attention` (`main.py train --forward-attention` wins over it), else off.  Decode such a model with
     `--forward-attention`.
     guided_attention: (sigma, alpha) of the guided-attention loss on the alignments (Trainer(guided_attention=...)); None takes the
@@ -78,6 +81,8 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
     guided = guided_attention_setting(training_config, guided_attention)
     model = TTSModel(device=dev, **kw)
     model.guided_attention = guided          # (the validation loss includes the term)
+    loss_options = loss_options_setting(training_config, mel_loss, masked_loss, stop_weight)
+    model.loss_options = loss_options        # (the validation loss is the loss that is trained)
     fwd_att = train_forward_attention_setting(training_config, forward_attention)
     model.train_forward_attention = fwd_att  # (the validation pass runs the recursion the training steps run)
     if fwd_att and rank == 0:
@@ -89,7 +94,7 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
                  scheduler_milestones=kw["scheduler_milestones"], max_norm=1.0,
                  sync_bn=bool(training_config.get("sync_batchnorm", False)),
                  overlap_allreduce=bool(training_config.get("overlap_allreduce", False)),
-                 force_collectives=force_dp, guided_attention=guided, forward_attention=fwd_att)
+                 force_collectives=force_dp, guided_attention=guided, forward_attention=fwd_att, loss_options=loss_options)
     if world > 1 and os.environ.get("T2_SHARE_GPU") == "1":
         # rehearsal of N ranks on ONE card: persistent launches of different processes cannot promise each other co-residency
         tr.engine.dec_chain = "steps"; tr.engine.enc_chain = "steps"

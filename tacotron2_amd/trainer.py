@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import torch
 import torch.distributed as dist
 
-from .engine import Engine, check_forward_attention, check_guided_attention, zero_later
+from .engine import Engine, check_forward_attention, check_guided_attention, check_loss_options, zero_later
 from .params import ParamStore
 
 
@@ -26,7 +26,7 @@ class Trainer:
     def __init__(self, ps: ParamStore, lr: float, weight_decay: float, scheduler_milestones: Sequence[int] = (),
                  max_norm: float = 1.0, seed: int = 1234, sync_bn: bool = False, overlap_allreduce: bool = False,
                  force_collectives: bool = False, shape_timeout_s: float = 300.0, guided_attention=None,
-                 forward_attention: bool = False):
+                 forward_attention: bool = False, loss_options=None):
         self.ps = ps
         self.engine = Engine(ps)
         # (sigma, alpha): the guided-attention loss on the alignments joins the three terms (Engine.loss_and_grads); None = off.
@@ -36,6 +36,9 @@ class Trainer:
         # True: every step runs the attention chain under the forward-attention prior, forward and backward (Engine.forward_tf);
         # composes with guided_attention (the guided term then judges the forward weights alpha, the alignments as returned)
         self.forward_attention = check_forward_attention(forward_attention)
+        # (mel, masked, stop_weight) of Engine.loss_and_grads(loss=...); the defaults are the reference's loss.  Under data parallelism
+        # a masked mean is normalised by the RANK's own valid frames and the all-reduce averages the ranks (no global count)
+        self.loss_options = check_loss_options(loss_options)
         self.last_guided_loss = None     # device float64[1] of the latest step when the term is on (no host read on the step path)
         self.base_lr, self.weight_decay, self.max_norm = lr, weight_decay, max_norm
         self.milestones = sorted(int(m) for m in scheduler_milestones)
@@ -207,7 +210,7 @@ class Trainer:
                                    description_embeddings=batch.get("description_embeddings"), training=True, masks=masks,
                                    controls=batch.get("controls"), forward_attention=self.forward_attention)
         zero_later(ps.grad)       # (one region of the backward's first t2_zero_regions launch)
-        loss3 = eng.loss_and_grads(outs, ctx, mel, batch["gate"], guided=self.guided_attention)
+        loss3 = eng.loss_and_grads(outs, ctx, mel, batch["gate"], guided=self.guided_attention, loss=self.loss_options)
         self.last_guided_loss = eng.guided_loss
         if self.dp:
             if self._tail_work is not None:       # two buckets: the tail has been in flight since the frame loop ended
