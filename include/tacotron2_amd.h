@@ -674,6 +674,60 @@ typedef struct {
 int t2_align_durations(const T2AlignDur* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Objective scoring of a free-running decode against the recording: mel-cepstral distortion under dynamic time warping
+ * (MCD-DTW; no reference counterpart - the reference's `test` decodes the recordings and drops them).  Two entries
+ * (csrc/t2_dtw.hip), the rule in DESIGN 5.9, restated in float64 in tests/mcd_dtw_ref.py.
+ *
+ * t2_mel_cepstra: log-mels (B, T, M) -> mel-cepstral coefficients (B, T, K), the orthonormal DCT-II without c[0]:
+ *     out[b][t][k-1] = sum_m mel[b][t][m] * basis[m][k-1],  basis[m][k-1] = sqrt(2/M) cos(pi k (m + 1/2) / M),  k = 1 .. K
+ *   basis [M][K] row-major is built by the HOST in float64 and rounded once to float32.  Plain fp32 FMAs in the order m = 0 .. M-1
+ *   (not t2_gemm: the result does not depend on any matmul-precision setting).  Rows t >= clip(len[b], 0, T) are neither read nor
+ *   written.  mel[b*ld_b + t*ld_t + m] and out[b*ld_ob + t*ld_ot + k], last dimension contiguous.
+ *   T2_ERR_ARG before any launch: a null pointer, B, T, M < 1, M > T2_CEPS_MAX_M, K outside 1 .. T2_DTW_MAX_K, overlapping strides
+ *   (ld_t < M, ld_b < (T-1)*ld_t + M, ld_ot < K, ld_ob < (T-1)*ld_ot + K).
+ *
+ * t2_dtw: for every pair b, the cheapest warping path between a[b] (la = clip(len_a[b], 0, Ta) rows of K features) and b[b]
+ * (lb rows) under the frame distance d(i, j) = scale * sqrtf(sum_k (a[i][k] - b[j][k])^2), formed in fp32 on the fly (no Ta x Tb
+ * distance matrix in memory):
+ *     D[0][0] = d(0,0);   D[i][j] = d(i,j) + min(D[i-1][j-1], D[i-1][j], D[i][j-1])   (predecessors outside the matrix excluded)
+ *   ties: the diagonal first, then (i-1, j), then (i, j-1) - a later candidate wins only when STRICTLY smaller.  D and the minimum
+ *   are fp64: totals reach ~1e5 over a few thousand cells, where an fp32 ulp is the size of real decision margins.
+ *   cost[b] = D[la-1][lb-1]; path_len[b] = the number of cells of that path (max(la, lb) .. la + lb - 1), carried through the
+ *   recurrence beside D (length of the chosen predecessor + 1), so the score needs no workspace.  la == 0 or lb == 0: cost 0,
+ *   path_len 0, nothing of the pair's rows is read.  scale = 10 sqrt(2) / ln 10 on cepstra gives the MCD distance in dB.
+ *   back: optional workspace [B][Ta][Tb] bytes (0 diagonal, 1 = (i-1, j), 2 = (i, j-1)); with it, path [B][Ta+Tb-1][2] int32
+ *   receives the cells (i, j) in FORWARD order, path_len[b] of them (the rest of the row is not written).
+ *   One 256-thread workgroup per pair walks the anti-diagonals i + j = k (each depends on k-1 and k-2 only), one barrier per
+ *   diagonal; three rotating rows of fp64 D and of int32 lengths, indexed by i, in dynamic LDS: 3 * Ta * (8 + 4) bytes =
+ *   147 456 at Ta = T2_DTW_MAX_T = 4096, inside the 160 KB (163 840) a workgroup may take.  No cross-workgroup synchronisation,
+ *   no global atomics.
+ *   T2_ERR_ARG before any launch: a null pointer, B, Ta, Tb < 1, Ta or Tb above T2_DTW_MAX_T, K outside 1 .. T2_DTW_MAX_K, a path
+ *   without back, overlapping strides (ld_at < K, ld_ab < (Ta-1)*ld_at + K, the same for b), a scale that is not finite. */
+#define T2_DTW_MAX_T 4096
+#define T2_DTW_MAX_K 32
+#define T2_CEPS_MAX_M 1024
+typedef struct {
+    const float* mel; int64_t ld_b, ld_t;     /* mel[b*ld_b + t*ld_t + m], m contiguous */
+    int B, T, M, K;
+    const int32_t* len;                       /* [B] device; rows t < clip(., 0, T) are transformed */
+    const float* basis;                       /* [M][K] device */
+    float* out; int64_t ld_ob, ld_ot;         /* out[b*ld_ob + t*ld_ot + k] */
+} T2MelCeps;
+int t2_mel_cepstra(const T2MelCeps* a, void* stream);
+typedef struct {
+    const float* a; int64_t ld_ab, ld_at;     /* a[b*ld_ab + i*ld_at + k], k contiguous */
+    const float* b; int64_t ld_bb, ld_bt;     /* b[b*ld_bb + j*ld_bt + k] */
+    int B, Ta, Tb, K;
+    const int32_t* len_a; const int32_t* len_b;   /* [B] device each */
+    float scale;
+    double* cost;                             /* [B] */
+    int32_t* path_len;                        /* [B] */
+    uint8_t* back;                            /* optional workspace [B][Ta][Tb] */
+    int32_t* path;                            /* optional [B][Ta+Tb-1][2]; needs back */
+} T2Dtw;
+int t2_dtw(const T2Dtw* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

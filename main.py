@@ -7,7 +7,7 @@
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
                                                   [--attention-window BACK,FWD | --forward-attention] [--durations-out PATH]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
-                                                  [--attention-window BACK,FWD | --forward-attention]
+                                                  [--attention-window BACK,FWD | --forward-attention] [--score [--no-audio]]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention]
     (say, test and test-correlation also take --stop-threshold P)
@@ -195,10 +195,18 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
 @attention_window_option
 @forward_attention_option
 @stop_threshold_option
+@click.option("--score", is_flag=True, default=False,
+              help="Also score every decode against its recording (the manifest's wav column under --speech-dir): mel-cepstral "
+                   "distortion under dynamic time warping (MCD-DTW, 13 coefficients, dB), duration ratio, stop failures and "
+                   "focus rate, as scores.csv and scores.json in the results directory. Default: off.")
+@click.option("--no-audio", is_flag=True, default=False,
+              help="With --score: skip vocoding and the WAV files, write the scores only.")
 def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window,
-         forward_attention, stop_threshold=None):
+         forward_attention, stop_threshold=None, score=False, no_audio=False):
     """Synthesise the test manifest (run/test.py of the reference): one wav per utterance + failures.csv."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
+    if no_audio and not score:
+        raise click.UsageError("--no-audio needs --score: without either there would be nothing to write")
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
     from tacotron2_amd.run.test import do_test
@@ -206,7 +214,8 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
     do_test(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
             extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
             hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit,
-            attention_window=attention_window, forward_attention=forward_attention, stop_threshold=stop_threshold)
+            attention_window=attention_window, forward_attention=forward_attention, stop_threshold=stop_threshold, score=score,
+            audio=not no_audio)
 
 
 @main.command()

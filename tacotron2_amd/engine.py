@@ -361,6 +361,7 @@ class Engine:
         self.zoneout = check_rate(ps.dims.get("zoneout", 0.0), "zoneout", closed=True)
         self.cell_dropout = check_rate(ps.dims.get("cell_dropout", 0.1), "cell_dropout")
         self._ws: Dict[str, torch.Tensor] = {}
+        self._ceps_bases: Dict[tuple, torch.Tensor] = {}     # (M, K) -> the DCT basis of mel_cepstra on the device
         self._cleared: Dict[tuple, tuple] = {}   # (data_ptr, bytes) -> (workspace name, view): regions put on the zero list ahead
                                                  # of the code that needs them zero and not consumed yet (clear_ahead / need_zero)
         self._bn_clean: set = set()   # BatchNorm workspace slots cleared by begin_phase and not used since
@@ -1830,3 +1831,119 @@ class Engine:
                  frames_len=flen32, dur=dur, ld_dur=L, stats=stats, back=back)
         call("t2_align_durations", a, _stream())
         return dur.clone(), stats.clone()      # (the workspaces belong to the next call)
+
+    # =============================================================================================
+    # objective scoring: mel-cepstral distortion under dynamic time warping (include/tacotron2_amd.h: t2_mel_cepstra, t2_dtw;
+    # DESIGN 5.9)
+    # =============================================================================================
+    DTW_MAX_T = 4096            # T2_DTW_MAX_T: three fp64 rows and three int32 rows of the recurrence in LDS
+    DTW_MAX_K = 32              # T2_DTW_MAX_K
+    DTW_BACK_BYTES = 256 << 20  # the `back` workspace of one t2_dtw call with a path stays at or below this
+    MCD_SCALE = 10.0 * math.sqrt(2.0) / math.log(10.0)
+
+    def _check_seq(self, fn: str, name: str, x, lname: str, lens, last: str):
+        """The up-front checks of a (B, T, C) float32 sequence tensor and its B integer lengths: ValueError, never a device fault."""
+        dev = self.ps.flat.device
+        if not torch.is_tensor(x) or x.dim() != 3 or x.dtype != torch.float32:
+            raise ValueError(f"{fn}: {name} must be a float32 (B, T, {last}) tensor")
+        if x.device != dev:
+            raise ValueError(f"{fn}: {name} must be a tensor on the engine's device {dev}")
+        B, T, C = x.shape
+        if B < 1 or T < 1 or C < 1:
+            raise ValueError(f"{fn}: empty {name} {tuple(x.shape)}")
+        if T > self.DTW_MAX_T:
+            raise ValueError(f"{fn}: {name} has {T} frames, above the limit of {self.DTW_MAX_T} (T2_DTW_MAX_T)")
+        if x.stride(2) != 1 and C > 1:
+            raise ValueError(f"{fn}: the last dimension of {name} must be contiguous")
+        ld_t = x.stride(1) if T > 1 else C
+        ld_b = x.stride(0) if B > 1 else T * ld_t
+        if ld_t < C or (B > 1 and ld_b < (T - 1) * ld_t + C):
+            raise ValueError(f"{fn}: overlapping rows of {name} (strides {tuple(x.stride())})")
+        if not torch.is_tensor(lens) or lens.device != dev:
+            raise ValueError(f"{fn}: {lname} must be a tensor on the engine's device {dev}")
+        if lens.dim() != 1 or lens.shape[0] != B or lens.is_floating_point() or lens.dtype == torch.bool:
+            raise ValueError(f"{fn}: {lname} must be {B} integers")
+        return ld_b, ld_t
+
+    def _ceps_basis(self, M: int, K: int) -> torch.Tensor:
+        """(M, K) columns k = 1 .. K of the orthonormal DCT-II, built in float64 and rounded once to float32."""
+        key = (M, K)
+        if key not in self._ceps_bases:
+            m = torch.arange(M, dtype=torch.float64).view(M, 1) + 0.5
+            k = torch.arange(1, K + 1, dtype=torch.float64).view(1, K)
+            self._ceps_bases[key] = (math.sqrt(2.0 / M) * torch.cos(math.pi * k * m / M)).float().to(self.ps.flat.device)
+        return self._ceps_bases[key]
+
+    def _mel_cepstra(self, fn: str, name: str, mel, lname: str, lens, n_ceps, ws: str) -> torch.Tensor:
+        if isinstance(n_ceps, bool) or not isinstance(n_ceps, int) or not 1 <= n_ceps <= self.DTW_MAX_K:
+            raise ValueError(f"{fn}: n_ceps must be an integer in 1 .. {self.DTW_MAX_K}, got {n_ceps!r}")
+        ld_b, ld_t = self._check_seq(fn, name, mel, lname, lens, "num_mels")
+        B, T, M = mel.shape
+        if n_ceps >= M:
+            raise ValueError(f"{fn}: n_ceps = {n_ceps} needs more than {M} mel channels (coefficients 1 .. num_mels - 1)")
+        out = self.buf(ws, B, T, n_ceps)
+        out.zero_()               # (rows behind an utterance's length are not written by the kernel: zeros)
+        a = make("T2MelCeps", mel=mel, ld_b=ld_b, ld_t=ld_t, B=B, T=T, M=M, K=n_ceps, len=lens.to(torch.int32).contiguous(),
+                 basis=self._ceps_basis(M, n_ceps), out=out, ld_ob=T * n_ceps, ld_ot=n_ceps)
+        call("t2_mel_cepstra", a, _stream())
+        return out
+
+    def mel_cepstra(self, mel, lens, n_ceps=13):
+        """Mel-cepstral coefficients (B, T, n_ceps) float32 of log-mels (B, T, num_mels) - any strides with a contiguous last
+        dimension: c[k] = sqrt(2/M) sum_m x[m] cos(pi k (m + 1/2) / M) for k = 1 .. n_ceps, the orthonormal DCT-II without the
+        frame energy c[0].  Plain fp32 FMAs in a kernel of its own: the result does not depend on
+        float32_matmul_precision.  Rows at or behind lens[b] are not read; they come back as zeros."""
+        return self._mel_cepstra("mel_cepstra", "mel", mel, "lens", lens, n_ceps, "mcd.ceps").clone()
+
+    def dtw(self, a, len_a, b, len_b, scale=1.0, return_path=False):
+        """Dynamic time warping of every pair (a[i] cut at len_a[i], b[i] cut at len_b[i]) of float32 feature sequences (B, Ta, K)
+        and (B, Tb, K) under the frame distance scale * Euclidean: (cost float64 (B,), path_len int32 (B,)[, path int32
+        (B, Ta + Tb - 1, 2)]).  The path runs from (0, 0) to (len_a - 1, len_b - 1) by steps (1, 1), (1, 0), (0, 1); on ties the
+        diagonal, then (1, 0); D in fp64.  path_len cells of `path` are (i, j) in forward order, the rest -1.  A pair
+        with a zero length has cost 0 and path_len 0.  With return_path the batch runs in groups whose predecessor workspace
+        stays at or below 256 MB."""
+        lda_b, lda_t = self._check_seq("dtw", "a", a, "len_a", len_a, "K")
+        ldb_b, ldb_t = self._check_seq("dtw", "b", b, "len_b", len_b, "K")
+        B, Ta, K = a.shape
+        if b.shape[0] != B or b.shape[2] != K:
+            raise ValueError(f"dtw: a {tuple(a.shape)} and b {tuple(b.shape)} must agree in batch and feature size")
+        Tb = b.shape[1]
+        if K > self.DTW_MAX_K:
+            raise ValueError(f"dtw: {K} features per frame, above the limit of {self.DTW_MAX_K} (T2_DTW_MAX_K)")
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"dtw: scale must be finite, got {scale!r}")
+        la32, lb32 = len_a.to(torch.int32).contiguous(), len_b.to(torch.int32).contiguous()
+        cost = self.buf("dtw.cost", B, dtype=torch.float64)
+        plen = self.buf("dtw.path_len", B, dtype=torch.int32)
+        if not return_path:
+            s = make("T2Dtw", a=a, ld_ab=lda_b, ld_at=lda_t, b=b, ld_bb=ldb_b, ld_bt=ldb_t, B=B, Ta=Ta, Tb=Tb, K=K, len_a=la32,
+                     len_b=lb32, scale=scale, cost=cost, path_len=plen, back=None, path=None)
+            call("t2_dtw", s, _stream())
+            return cost.clone(), plen.clone()
+        G = max(1, min(B, self.DTW_BACK_BYTES // (Ta * Tb)))
+        back = self.buf("dtw.back", G, Ta, Tb, dtype=torch.uint8)
+        path = self.buf("dtw.path", B, Ta + Tb - 1, 2, dtype=torch.int32)
+        path.fill_(-1)
+        for g0 in range(0, B, G):
+            g1 = min(B, g0 + G)
+            s = make("T2Dtw", a=a[g0:g1], ld_ab=lda_b, ld_at=lda_t, b=b[g0:g1], ld_bb=ldb_b, ld_bt=ldb_t, B=g1 - g0, Ta=Ta, Tb=Tb,
+                     K=K, len_a=la32[g0:g1], len_b=lb32[g0:g1], scale=scale, cost=cost[g0:g1], path_len=plen[g0:g1], back=back,
+                     path=path[g0:g1])
+            call("t2_dtw", s, _stream())
+        return cost.clone(), plen.clone(), path.clone()
+
+    def mcd_dtw(self, mel_a, len_a, mel_b, len_b, n_ceps=13, return_path=False):
+        """Mel-cepstral distortion under dynamic time warping between log-mels (B, Ta, num_mels) cut at len_a and (B, Tb, num_mels)
+        cut at len_b: (mcd float64 (B,), cost, path_len[, path]) - mel_cepstra on both, dtw under (10 / ln 10) sqrt(2 sum_k (.)^2)
+        dB, mcd = cost / path_len, the mean over the warped pairs.  mcd is NaN where path_len is 0 (an empty side: an utterance
+        that never stopped is a failure, not a number)."""
+        if not torch.is_tensor(mel_a) or not torch.is_tensor(mel_b) or mel_a.dim() != 3 or mel_b.dim() != 3 \
+                or mel_a.shape[0] != mel_b.shape[0] or mel_a.shape[2] != mel_b.shape[2]:
+            raise ValueError("mcd_dtw: mel_a and mel_b must be (B, Ta, num_mels) and (B, Tb, num_mels) tensors of one batch")
+        ca = self._mel_cepstra("mcd_dtw", "mel_a", mel_a, "len_a", len_a, n_ceps, "mcd.ceps_a")
+        cb = self._mel_cepstra("mcd_dtw", "mel_b", mel_b, "len_b", len_b, n_ceps, "mcd.ceps_b")
+        out = self.dtw(ca, len_a, cb, len_b, scale=self.MCD_SCALE, return_path=return_path)
+        cost, plen = out[0], out[1]
+        mcd = torch.where(plen > 0, cost / plen.clamp(min=1).to(torch.float64), torch.full_like(cost, float("nan")))
+        return (mcd,) + tuple(out)

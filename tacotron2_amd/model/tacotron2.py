@@ -261,6 +261,58 @@ class Tacotron2(nn.Module):
             self.train(was_training)
         return dur, stats, align
 
+    def score(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
+              max_len_override: int = 5000, n_ceps: int = 13, **kw):
+        """Objective score of a free-running decode against the recording: an EVAL-mode forward(teacher_forcing=False, ...) with the
+        same arguments (speaker_id, controls, description_embeddings, dropout_masks, attention_window, forward_attention,
+        stop_threshold; the reduction factor is the model's), then score_decode on its outputs.  Returns (mels_post, scores).  The
+        module's train / eval state is kept."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                _, post, gates, align = self.forward(chars_idx, chars_idx_len, False, max_len_override=max_len_override, **kw)
+                scores = self.score_decode(post, gates, align, chars_idx_len, mel_spectrogram, mel_spectrogram_len,
+                                           stop_threshold=kw.get("stop_threshold", 0.5), n_ceps=n_ceps)
+        finally:
+            self.train(was_training)
+        return post, scores
+
+    def score_decode(self, post: Tensor, gates: Tensor, align: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor,
+                     mel_spectrogram_len: Tensor, stop_threshold: float = 0.5, n_ceps: int = 13) -> dict:
+        """MCD-DTW (Engine.mcd_dtw) between the post-net mels of a decode - (mels_post, gates, alignments) as
+        forward(teacher_forcing=False) returns them - cut at the decode's own lengths, and the recordings `mel_spectrogram`
+        (B, T, num_mels) cut at `mel_spectrogram_len`.  A dict of per-utterance tensors:
+          mcd         float64 dB, the mean distance over the warped frame pairs; NaN for an utterance that never stopped
+          path_len    int32 warped pairs (0 when it never stopped)
+          syn_frames  int64 - the first frame whose stop logit is below logit(stop_threshold), 0 when there is none (the rule of
+                      run/test.py's mel_lengths_of)
+          ref_frames  int64, mel_spectrogram_len cut at T
+          stopped     bool, syn_frames > 0
+          focus_rate  float32, the mean over the decoder steps of the largest attention weight (Engine.durations, mode "argmax",
+                      over the syn_frames of a stopped utterance, over the whole decode of one that never stopped)"""
+        from ..engine import stop_logit
+        B = post.shape[0]
+        if not torch.is_tensor(mel_spectrogram) or mel_spectrogram.dim() != 3 or mel_spectrogram.shape[0] != B \
+                or mel_spectrogram.shape[2] != self.num_mels:
+            raise ValueError(f"score: mel_spectrogram must be ({B}, T, {self.num_mels}), got "
+                             f"{tuple(mel_spectrogram.shape) if torch.is_tensor(mel_spectrogram) else type(mel_spectrogram)}")
+        if not torch.is_tensor(mel_spectrogram_len) or mel_spectrogram_len.numel() != B or mel_spectrogram_len.is_floating_point():
+            raise ValueError(f"score: mel_spectrogram_len must be {B} integers")
+        tau = check_stop_threshold(stop_threshold)
+        with torch.no_grad():
+            dev = post.device
+            syn = (gates[:, :, 0] < stop_logit(tau)).to(torch.int64).argmax(dim=-1)
+            stopped = syn > 0
+            ref = mel_spectrogram_len.reshape(B).to(dev).to(torch.int64).clamp(min=0, max=mel_spectrogram.shape[1])
+            # (cut at the longest utterance of each side: a decode that ran into max_len is longer than the warping's cap, its
+            # stopped utterances are not)
+            ta, tb = max(int(syn.max()), 1), max(int(ref.max()), 1)
+            mcd, _, path_len = self._engine.mcd_dtw(post[:, :ta], syn, mel_spectrogram.to(dev).float()[:, :tb], ref, n_ceps=n_ceps)
+            frames = torch.where(stopped, syn, torch.full_like(syn, post.shape[1]))
+            stats = self._engine.durations(align, chars_idx_len.to(dev), frames, mode="argmax")[1]
+        return dict(mcd=mcd, path_len=path_len, syn_frames=syn, ref_frames=ref, stopped=stopped, focus_rate=stats[:, 0].clone())
+
     def inference(self, chars_idx, chars_idx_len, max_len: int = 5000, **kw):
         """Alias of forward(teacher_forcing=False, max_len_override=max_len) (north_star's "inference() surface")."""
         return self.forward(chars_idx, chars_idx_len, False, max_len_override=max_len, **kw)

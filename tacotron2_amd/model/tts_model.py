@@ -173,6 +173,18 @@ class TTSModel(nn.Module):
                                         description_embeddings=description_embeddings,
                                         train_forward_attention=train_forward_attention)
 
+    def score(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
+              max_len_override: Optional[int] = None, n_ceps: int = 13, speaker_id: Optional[Tensor] = None,
+              controls: Optional[Tensor] = None, description_embeddings: Optional[Tensor] = None,
+              attention_window: Optional[Tuple[int, int]] = None, forward_attention: bool = False, stop_threshold: float = 0.5):
+        """(mels_post, scores) of an eval-mode free-running decode scored against the recording by MCD-DTW: Tacotron2.score.
+        max_len_override None takes the model's (else 5000), as predict_step does."""
+        return self.tacotron2.score(chars_idx, chars_idx_len, mel_spectrogram, mel_spectrogram_len,
+                                    max_len_override=max_len_override or self.max_len_override or 5000, n_ceps=n_ceps,
+                                    speaker_id=speaker_id, controls=controls, description_embeddings=description_embeddings,
+                                    attention_window=attention_window, forward_attention=forward_attention,
+                                    stop_threshold=stop_threshold)
+
     def _args(self, meta):
         args = {}
         if self.speaker_tokens:

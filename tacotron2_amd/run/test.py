@@ -11,11 +11,20 @@ consistency checks (:81-100), controls from the manifest's feature columns (:102
 `mel_lengths = (gate < 0).argmax` - the first masked frame, 0 when the utterance never stopped (:172,205) -, numbering from
 1 in manifest order, `failures.csv` rows `i|text` (:187-193,223-227), 22050 Hz output; see synthesize_manifest for the
 vocoding details.  `main.py test-correlation` (run/test_correlation.py) runs the same loop under 51 control-vector overrides.
+
+`test --score` (no reference counterpart) also scores every decode against its recording: the manifest's wav column
+under --speech-dir goes through the dataset's item path (TTSDataset: the same trim, silence pad and device log-mel as training),
+and the post-net mels cut at `mel_lengths` are compared with it by mel-cepstral distortion under dynamic time warping on the
+device (Tacotron2.score_decode).  `scores.csv`, `|`-separated with the header SCORE_HEADER, one row per utterance in manifest
+order (`i` as in the WAV names; an utterance that never stopped has an empty mcd_dtw and dur_ratio), and `scores.json` with
+the aggregates.  `--no-audio` skips vocoding and the WAVs.
 """
 from __future__ import annotations
 
 import csv
 import datetime
+import json
+import math
 import os
 from typing import List, Optional, Tuple
 
@@ -83,8 +92,44 @@ def mel_lengths_of(gate: torch.Tensor, stop_threshold: float = 0.5) -> torch.Ten
     return (gate[:, :, 0] < stop_logit(stop_threshold)).to(torch.int64).argmax(dim=-1)
 
 
+SCORE_HEADER = ["i", "wav", "n_chars", "ref_frames", "syn_frames", "stopped", "mcd_dtw", "path_len", "dur_ratio", "focus_rate"]
+
+
+def check_recordings(df, speech_dir) -> None:
+    """`test --score` reads every recording of the manifest: a missing one is an error that names the file, before any decoding."""
+    if "wav" not in df.columns:
+        raise ValueError("test --score: the test manifest has no `wav` column")
+    for wav in df.wav:
+        path = os.path.join(str(speech_dir), str(wav))
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"test --score: recording not found: {path}")
+
+
+def write_scores(results_dir: str, rows: List[dict], settings: dict) -> dict:
+    """scores.csv (SCORE_HEADER) and scores.json of `test --score`; returns the aggregates."""
+    with open(os.path.join(results_dir, "scores.csv"), "w", newline="") as f:
+        wr = csv.writer(f, delimiter="|", quoting=csv.QUOTE_NONE, escapechar="\\")
+        wr.writerow(SCORE_HEADER)
+        for r in rows:
+            ok = r["stopped"]
+            wr.writerow([r["i"], r["wav"], r["n_chars"], r["ref_frames"], r["syn_frames"], int(ok),
+                         f"{r['mcd']:.6f}" if ok else "", r["path_len"], f"{r['dur_ratio']:.6f}" if ok else "",
+                         f"{r['focus_rate']:.6f}"])
+    ok = [r for r in rows if r["stopped"]]
+    mcds = sorted(r["mcd"] for r in ok)
+    mean = lambda v: (sum(v) / len(v)) if v else None
+    median = (mcds[len(mcds) // 2] if len(mcds) % 2 else 0.5 * (mcds[len(mcds) // 2 - 1] + mcds[len(mcds) // 2])) if mcds else None
+    agg = {"n": len(rows), "n_stopped": len(ok), "failure_rate": (1.0 - len(ok) / len(rows)) if rows else None,
+           "mcd_dtw_mean": mean(mcds), "mcd_dtw_median": median,
+           "abs_log_dur_ratio_mean": mean([abs(math.log(r["dur_ratio"])) for r in ok if r["dur_ratio"] > 0]),
+           "focus_rate_mean": mean([r["focus_rate"] for r in rows]), "settings": settings}
+    with open(os.path.join(results_dir, "scores.json"), "w") as f:
+        json.dump(agg, f, indent=1)
+    return agg
+
+
 def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=8, max_len=5000,
-                        random_seed=None, zero_length="test") -> List[str]:
+                        random_seed=None, zero_length="test", score=False, audio=True, n_ceps=13) -> List[str]:
     """The prediction + "Saving WAVs" loops of run/test.py:132-227 and run/test_correlation.py:171-250 over one manifest:
     batches of `batch_size` texts through the batched decode path, `mel_lengths = (gate < 0).argmax` (:172,205), numbering from
     1 in manifest order, `failures.csv` rows `i|text`.
@@ -98,7 +143,9 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     The decode uses the model's attention window (TTSModel.attention_window, set by load_test_model; None = off) or its forward
     attention (TTSModel.forward_attention; False = off), and its stop threshold (TTSModel.stop_threshold): `mel_lengths` is then the
     first frame with gate < logit(threshold) - under a threshold below 0.5 a kept frame may have a logit in [logit(threshold), 0) -,
-    which at 0.5 is the reference's `gate < 0`."""
+    which at 0.5 is the reference's `gate < 0`.
+    score: also compare every decode with its recording (module docstring) and write scores.csv / scores.json.  audio False
+    (`--no-audio`, with score only): no vocoding, no WAVs; failures.csv is still written."""
     from ..vocoder import write_wav
     dev = model.tacotron2.store.device
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
@@ -111,6 +158,12 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     os.makedirs(results_dir, exist_ok=True)
     speaker_ids = list(df.speaker_id) if model.speaker_tokens else None
     written: List[str] = []
+    recordings, score_rows = None, []
+    if score:
+        from ..datasets.tts_dataset import TTSDataset
+        check_recordings(df, speech_dir)
+        recordings = TTSDataset(filenames=[str(w) for w in df.wav], texts=list(df.text), base_dir=speech_dir, device=dev,
+                                **dict(pre, cache=False))
 
     def fail(i, text):
         print(f"Error: {i}: {text}")
@@ -133,16 +186,31 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                     if desc_paths[j] is not None else torch.zeros(dim) for j in sel]
             args["description_embeddings"] = torch.stack(rows).to(dev)
         with torch.no_grad():
-            _, post, gate, _ = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
+            _, post, gate, align = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
                                      attention_window=model.attention_window,
                                      forward_attention=getattr(model, "forward_attention", False),
                                      stop_threshold=getattr(model, "stop_threshold", 0.5), **args)
         mel_lengths = mel_lengths_of(gate, getattr(model, "stop_threshold", 0.5)).cpu().tolist()
+        if score:
+            refs = [recordings[j][0]["mel_spectrogram"] for j in sel]
+            sc = model.tacotron2.score_decode(post, gate, align, lens, torch.nn.utils.rnn.pad_sequence(refs, batch_first=True),
+                                              torch.tensor([len(m) for m in refs], dtype=torch.int64, device=dev),
+                                              stop_threshold=getattr(model, "stop_threshold", 0.5), n_ceps=n_ceps)
+            sc = {k: v.cpu().tolist() for k, v in sc.items()}
+            assert sc["syn_frames"] == [int(n) for n in mel_lengths]
+            for k, j in enumerate(sel):
+                score_rows.append(dict(i=i + k + 1, wav=str(df.wav[j]), n_chars=len(ids[j]), ref_frames=sc["ref_frames"][k],
+                                       syn_frames=sc["syn_frames"][k], stopped=bool(sc["stopped"][k]), mcd=sc["mcd"][k],
+                                       path_len=sc["path_len"][k], focus_rate=sc["focus_rate"][k],
+                                       dur_ratio=sc["syn_frames"][k] / max(sc["ref_frames"][k], 1)))
         for k, j in enumerate(sel):
             i += 1
             n = int(mel_lengths[k])
             name = os.path.join(results_dir, f"{i}.wav")
-            if gen is not None:
+            if not audio:
+                if n == 0:
+                    fail(i, texts[j])
+            elif gen is not None:
                 row = gen(post[k].t().contiguous())[0, 0]          # the padded row, as the reference vocodes it
                 if n == 0:
                     fail(i, texts[j])
@@ -157,6 +225,12 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                     continue
                 write_wav(name, gl.mel_to_audio(post[k, :n], seed=int(random_seed or 0)), sr)
                 written.append(name)
+    if score:
+        write_scores(results_dir, score_rows, {
+            "n_ceps": n_ceps, "attention_window": list(model.attention_window) if model.attention_window is not None else None,
+            "forward_attention": bool(getattr(model, "forward_attention", False)),
+            "stop_threshold": float(getattr(model, "stop_threshold", 0.5)), "r": int(model.tacotron2.reduction_factor),
+            "max_len": int(max_len)})
     return written
 
 
@@ -164,8 +238,11 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
             speech_dir: Optional[str], checkpoint: str, hifi_gan_checkpoint: Optional[str] = None,
             results_dir: Optional[str] = None, batch_size: int = 8, max_len: int = 5000, limit: Optional[int] = None,
             random_seed: Optional[int] = None, attention_window: Optional[Tuple[int, int]] = None,
-            forward_attention: Optional[bool] = None, stop_threshold: Optional[float] = None) -> List[str]:
+            forward_attention: Optional[bool] = None, stop_threshold: Optional[float] = None, score: bool = False,
+            audio: bool = True, n_ceps: int = 13) -> List[str]:
     import pandas as pd
+    if not audio and not score:
+        raise ValueError("test: audio=False (--no-audio) needs score=True (--score)")
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
@@ -174,12 +251,15 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
         df = df[df.speaker_id == extensions_config["speaker_tokens"]["force_speaker"]].reset_index(drop=True)
     if limit is not None:
         df = df.iloc[:int(limit)].reset_index(drop=True)
+    if score:
+        check_recordings(df, speech_dir)
     model = load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
                             attention_window, forward_attention, stop_threshold)
     ctl_cfg = extensions_config.get("controls", {"active": False})
     feats = df[ctl_cfg["features"]].values.tolist() if model.controls else None
     if results_dir is None:
         results_dir = f"results_{training_config['name']}_test {datetime.datetime.now()}"
-    gen, gl, sr = make_vocoders(hifi_gan_checkpoint, pre, dev)
+    gen, gl, sr = make_vocoders(hifi_gan_checkpoint, pre, dev) if audio else (None, None, int(pre.get("sample_rate", 22050)))
     return synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=batch_size,
-                               max_len=max_len, random_seed=random_seed, zero_length="test")
+                               max_len=max_len, random_seed=random_seed, zero_length="test", score=score, audio=audio,
+                               n_ceps=n_ceps)
