@@ -728,6 +728,56 @@ typedef struct {
 int t2_dtw(const T2Dtw* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Prosody measurement of synthesised audio (no reference counterpart in this repository - the reference extracts its features with
+ * Praat; csrc/t2_prosody.hip, the rule in DESIGN 5.10, restated in float64 in tests/prosody_ref.py).
+ *
+ * t2_yin: the YIN pitch tracker (de Cheveigne & Kawahara 2002, steps 2 to 5) on the mel grid.  wav[b*ld_wav + i] is a padded batch
+ *   of signals, n [B] their sample counts (DEVICE array, int64, as t2_logmel_batch_fwd takes it; clipped to 0 .. n_max).
+ *   T = 1 + n_max / hop frames per utterance; frame t analyses the S = W + tau_max samples [s0, s0 + S), s0 = t*hop - S/2.  A frame
+ *   is VALID iff s0 >= 0 and s0 + S <= n[b]; an invalid frame reads nothing and gets f0 = 0, aper = 1, power = 0 (cmnd: all 1).
+ *   Nothing at or behind n[b] is ever read.  With x the span of a valid frame:
+ *     d(tau)  = sum_{j<W} (x[j] - x[j+tau])^2, tau = 1 .. tau_max;  cm(0) = 1, cm(tau) = d(tau) * tau / sum_{k<=tau} d(k), 1 where
+ *               that sum is not positive;  power = sum_{j<W} x[j]^2 / W;
+ *     pick    = the smallest c in [tau_min, tau_max) with cm(c) < thr, walked down while c + 1 < tau_max and cm(c+1) < cm(c); without
+ *               one, the first argmin of cm over [tau_min, tau_max);  aper = cm(pick);
+ *     voiced iff aper < vthr and power > power_floor; then off = 0.5 (cm(pick-1) - cm(pick+1)) / (cm(pick-1) - 2 cm(pick) + cm(pick+1)),
+ *               0 when that denominator is not positive, clamped to [-1, 1], and f0 = sr / (pick + off) Hz; f0 = 0 otherwise.
+ *   Outputs f0, aper, power [B][T]; cmnd [B][T][tau_max + 1] is optional (NULL: not written).
+ *   One 256-thread workgroup per (frame, utterance); the span and four rows of partial d (one per wave) in dynamic LDS,
+ *   (S + 4 (tau_max + 1)) floats - at most 5 * T2_YIN_MAX_SPAN * 4 = 81 920 bytes.  fp32 throughout, no atomics, every sum in a fixed
+ *   order: two calls give bit-identical outputs.
+ *   T2_ERR_ARG before any launch: a null pointer (cmnd excepted), B < 1 or > 65535, n_max < 0, hop < 1, sr < 1, W < 16, tau_min < 2,
+ *   tau_max <= tau_min + 1, S > T2_YIN_MAX_SPAN, ld_wav < n_max.
+ *
+ * t2_prosody_stats: one row of T2_PROSODY_NSTAT floats per utterance from t2_yin's [B][T] outputs.  Frame t of utterance b is valid
+ *   under the same rule (n, hop, S); voiced = valid and f0 > 0.  out[b] = { valid frames, voiced frames, mean logf(f0), p5_hz, p95_hz,
+ *   mean 10 log10(power), mean aper, 0 }, the means and percentiles over the voiced frames: with v the voiced f0 sorted ascending and
+ *   n_v their count, p5_hz = v[(5 (n_v - 1) + 50) / 100] and p95_hz = v[(95 (n_v - 1) + 50) / 100] (integer division) - elements of
+ *   the track, found by rank counting in LDS (rank by (value, frame index): exact, ties included).  Means in fp64, fixed order.
+ *   Without a voiced frame fields 2 .. 6 are NaN.  One 256-thread workgroup per utterance.
+ *   T2_ERR_ARG before any launch: a null pointer, B < 1 or > 65535, T < 1 or > T2_PROSODY_MAX_T, hop < 1, S < 1. */
+#define T2_YIN_MAX_SPAN 4096
+#define T2_PROSODY_NSTAT 8
+#define T2_PROSODY_MAX_T 4096
+typedef struct {
+    const float* wav; int64_t ld_wav;         /* wav[b*ld_wav + i] */
+    const int64_t* n;                         /* [B] device */
+    int B; int64_t n_max;
+    int sr, hop, W, tau_min, tau_max;
+    float thr, vthr, power_floor;
+    float* f0; float* aper; float* power;     /* [B][T], T = 1 + n_max / hop */
+    float* cmnd;                              /* optional [B][T][tau_max + 1] */
+} T2Yin;
+int t2_yin(const T2Yin* a, void* stream);
+typedef struct {
+    const float* f0; const float* aper; const float* power;      /* [B][T] */
+    const int64_t* n;                         /* [B] device */
+    int B, T, hop, S;                         /* S = W + tau_max of the t2_yin call */
+    float* out;                               /* [B][T2_PROSODY_NSTAT] */
+} T2ProsodyStats;
+int t2_prosody_stats(const T2ProsodyStats* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

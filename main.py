@@ -9,7 +9,8 @@
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention] [--score [--no-audio]]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
-                                                  [--attention-window BACK,FWD | --forward-attention]
+                                                  [--attention-window BACK,FWD | --forward-attention] [--measure]
+    python main.py --config C --device N measure-correlation --results-dir R [--features a,b,...]
     (say, test and test-correlation also take --stop-threshold P)
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
     python main.py --config C --device N duration-export --speech-dir S --checkpoint K [--results-dir R] [--mode monotonic|argmax]
@@ -230,8 +231,13 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
 @attention_window_option
 @forward_attention_option
 @stop_threshold_option
+@click.option("--measure", is_flag=True, default=False,
+              help="Also measure what comes out, on the GPU: pitch level and range (YIN), intensity, aperiodicity and speaking rate "
+                   "of every waveform as prosody.csv in each override directory, and the correlation of every requested control "
+                   "with its measure (Pearson, Spearman, slope, and the control x measure leakage matrix) as correlation.json in the "
+                   "results directory. Default: off.")
 def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides,
-                     attention_window, forward_attention, stop_threshold=None):
+                     attention_window, forward_attention, stop_threshold=None, measure=False):
     """The test manifest under 51 control-vector overrides (run/test_correlation.py of the reference)."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
@@ -243,10 +249,43 @@ def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_d
         model_config = dict(model_config, forward_attention=True)
     if stop_threshold is not None:
         model_config = dict(model_config, stop_threshold=stop_threshold)
+    if measure:                # the meter travels with the model (load_test_model), the tables need the directory's name afterwards
+        import datetime
+        model_config = dict(model_config, measure_prosody=True)
+        if results_dir is None:
+            results_dir = f"results_{c['training']['name']}_test_correlation {datetime.datetime.now()}"
     do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=model_config,
                         extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
                         hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, samples_per_speaker=samples_per_speaker,
                         max_len=max_len, limit_overrides=limit_overrides)
+    if measure:
+        from tacotron2_amd.prosody import ProsodyMeter
+        from tacotron2_amd.run.correlation import correlate_tree
+        sr = int(c["dataset"].get("preprocessing", {}).get("sample_rate", 22050))
+        correlate_tree(results_dir, c["extensions"]["controls"]["features"], ProsodyMeter(sr, f"cuda:{ctx.obj['device']}").describe())
+
+
+@main.command()
+@click.pass_context
+@click.option("--results-dir", required=True, type=str, help="A results tree of test-correlation: one directory per override.")
+@click.option("--features", required=False, type=str, default=None, metavar="a,b,...",
+              help="The control names in the order of the override tuples. Default: extensions.controls.features of --config.")
+def measure_correlation(ctx, results_dir, features=None):
+    """Measure the WAVs of an existing test-correlation tree: rewrites prosody.csv per override and correlation.json."""
+    if features is not None:
+        names = [f.strip() for f in features.split(",")]
+        if not all(names):
+            raise click.UsageError(f"--features: expected a comma-separated list of names, got {features!r}")
+    elif ctx.obj["config"] is not None and ctx.obj["config"].get("extensions", {}).get("controls", {}).get("features"):
+        names = list(ctx.obj["config"]["extensions"]["controls"]["features"])
+    else:
+        raise click.UsageError("measure-correlation needs the control names: --features a,b,... or a --config with "
+                               "extensions.controls.features")
+    from tacotron2_amd.run.correlation import do_measure_correlation
+    try:
+        do_measure_correlation(results_dir, names, device=ctx.obj["device"])
+    except ValueError as e:
+        raise click.UsageError(str(e)) from None
 
 
 @main.command()

@@ -1,0 +1,246 @@
+// Prosody measurement of synthesised audio (include/tacotron2_amd.h: t2_yin, t2_prosody_stats): the YIN pitch tracker on
+// the mel grid and per-utterance statistics of its track.  An evaluation path beside a ~50 ms decode, so both kernels are plain, in
+// the style of t2_dtw.hip: no cross-workgroup synchronisation, nothing persistent, no atomics.
+//
+//   t2_yin: ONE 256-thread workgroup per (frame, utterance).  The span x[0 .. W + tau_max) is staged once in LDS.  Lanes run along
+//     tau: at a fixed j the 64 lanes of a wave read x[j + tau] at consecutive addresses (conflict-free) and x[j] at one address (a
+//     broadcast).  The j range is cut into four contiguous quarters, one per wave; every wave walks ALL lags (two per lane and pass, so
+//     tau_max > 128 wraps into further passes) and leaves its partial d(tau) in its own LDS row; the rows are added in wave order.
+//     The prefix sum over tau: every thread owns ceil(tau_max / 256) consecutive lags, then a wave scan by shuffles and the wave totals
+//     in order.  The pick is a min-reduction of (index) and of (value, index) - order-independent - and a short walk by thread 0.
+//     Every sum has a fixed association: two launches are bit-identical.
+//   t2_prosody_stats: ONE workgroup per utterance; the track's voiced f0 in LDS, percentiles by rank counting over (value, index).
+#include "t2_common.hpp"
+
+namespace {
+
+#define ST ((hipStream_t)stream)
+#define PR_THREADS 256
+#define PR_WAVES (PR_THREADS / T2_WAVE)
+
+__device__ __forceinline__ bool yin_valid(long t, int hop, int S, long nb, long* s0_out) {
+    const long s0 = t * hop - S / 2;
+    *s0_out = s0;
+    return s0 >= 0 && s0 + S <= nb;
+}
+
+__global__ __launch_bounds__(PR_THREADS) void yin_kernel(T2Yin p, int T) {
+    extern __shared__ float lds[];
+    __shared__ float red[PR_WAVES];
+    __shared__ float red_v[PR_WAVES];
+    __shared__ int red_i[PR_WAVES], red_f[PR_WAVES];
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int W = p.W, TM = p.tau_max, S = W + TM, NT = TM + 1;
+    float* x = lds;                 // [S] the span
+    float* part = lds + S;          // [PR_WAVES][NT] partial d per wave; row 0 becomes d, then cm; row 1 the thread-local prefix
+    const long o = (long)b * T + t;
+    long nb = p.n[b];
+    nb = nb < 0 ? 0 : (nb > p.n_max ? p.n_max : nb);
+    long s0;
+    if (!yin_valid(t, p.hop, S, nb, &s0)) {           // (uniform over the workgroup) nothing is read
+        if (tid == 0) { p.f0[o] = 0.f; p.aper[o] = 1.f; p.power[o] = 0.f; }
+        if (p.cmnd) for (int k = tid; k < NT; k += PR_THREADS) p.cmnd[o * NT + k] = 1.f;
+        return;
+    }
+    const float* src = p.wav + (long)b * p.ld_wav + s0;
+    for (int i = tid; i < S; i += PR_THREADS) x[i] = src[i];
+    __syncthreads();
+
+    // partial difference function of this wave's quarter of j, all lags
+    const int Wq = (W + PR_WAVES - 1) / PR_WAVES, j0 = min(W, w * Wq), j1 = min(W, j0 + Wq);
+    for (int tau0 = 0; tau0 < NT; tau0 += 2 * T2_WAVE) {
+        const int ta = tau0 + lane, tb = ta + T2_WAVE;
+        const float* xa = x + min(ta, TM);            // (lags behind tau_max: clamped to stay inside the span, not stored)
+        const float* xb = x + min(tb, TM);
+        float sa = 0.f, sb = 0.f;
+#pragma unroll 4
+        for (int j = j0; j < j1; ++j) {
+            const float xj = x[j];
+            const float da = xj - xa[j], db = xj - xb[j];
+            sa = fmaf(da, da, sa);
+            sb = fmaf(db, db, sb);
+        }
+        if (ta < NT) part[w * NT + ta] = sa;
+        if (tb < NT) part[w * NT + tb] = sb;
+    }
+    float ps = 0.f;
+    for (int j = tid; j < W; j += PR_THREADS) ps = fmaf(x[j], x[j], ps);
+    const float power = t2_block_sum(ps, red) / (float)W;      // (its barriers also complete `part`)
+
+    // d(tau) in wave order, and the prefix sum over tau: C consecutive lags per thread
+    const int C = (TM + PR_THREADS - 1) / PR_THREADS;
+    const int c0 = 1 + tid * C;
+    float tot = 0.f;
+    for (int i = 0; i < C; ++i) {
+        const int tau = c0 + i;
+        if (tau <= TM) {
+            float d = part[tau];
+#pragma unroll
+            for (int r = 1; r < PR_WAVES; ++r) d += part[r * NT + tau];
+            tot += d;
+            part[tau] = d;
+            part[NT + tau] = tot;
+        }
+    }
+    float inc = tot;
+#pragma unroll
+    for (int s = 1; s < T2_WAVE; s <<= 1) {
+        const float v = __shfl_up(inc, s, T2_WAVE);
+        if (lane >= s) inc += v;
+    }
+    float excl = __shfl_up(inc, 1, T2_WAVE);
+    if (lane == 0) excl = 0.f;
+    __syncthreads();                                   // (red was read by every thread in t2_block_sum)
+    if (lane == T2_WAVE - 1) red[w] = inc;
+    __syncthreads();
+    float base = 0.f;
+    for (int r = 0; r < w; ++r) base += red[r];
+    base += excl;
+    for (int i = 0; i < C; ++i) {
+        const int tau = c0 + i;
+        if (tau <= TM) {
+            const float sum = base + part[NT + tau];
+            part[tau] = sum > 0.f ? part[tau] * (float)tau / sum : 1.f;
+        }
+    }
+    if (tid == 0) part[0] = 1.f;
+    __syncthreads();
+    const float* cm = part;
+    if (p.cmnd) for (int k = tid; k < NT; k += PR_THREADS) p.cmnd[o * NT + k] = cm[k];
+
+    // the pick: the first lag under thr, and the first argmin, over [tau_min, tau_max)
+    int first = 0x7fffffff, mi = 0x7fffffff;
+    float mv = __builtin_inff();
+    for (int c = p.tau_min + tid; c < TM; c += PR_THREADS) {
+        const float v = cm[c];
+        if (v < p.thr && c < first) first = c;
+        if (v < mv) { mv = v; mi = c; }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const int of = __shfl_xor(first, s, T2_WAVE), oi = __shfl_xor(mi, s, T2_WAVE);
+        const float ov = __shfl_xor(mv, s, T2_WAVE);
+        first = min(first, of);
+        if (ov < mv || (ov == mv && oi < mi)) { mv = ov; mi = oi; }
+    }
+    if (lane == 0) { red_f[w] = first; red_v[w] = mv; red_i[w] = mi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int r = 1; r < PR_WAVES; ++r) {
+            first = min(first, red_f[r]);
+            if (red_v[r] < mv || (red_v[r] == mv && red_i[r] < mi)) { mv = red_v[r]; mi = red_i[r]; }
+        }
+        int c = mi;
+        if (first != 0x7fffffff) {
+            c = first;
+            while (c + 1 < TM && cm[c + 1] < cm[c]) ++c;
+        }
+        const float ap = cm[c];
+        float f0 = 0.f;
+        if (ap < p.vthr && power > p.power_floor) {
+            const float a = cm[c - 1], e = cm[c + 1];          // (tau_min >= 2 and c < tau_max: both inside the row)
+            const float den = a - 2.f * ap + e;
+            float off = den > 0.f ? 0.5f * (a - e) / den : 0.f;
+            off = fminf(fmaxf(off, -1.f), 1.f);
+            f0 = (float)p.sr / ((float)c + off);
+        }
+        p.f0[o] = f0; p.aper[o] = ap; p.power[o] = power;
+    }
+}
+
+__global__ __launch_bounds__(PR_THREADS) void prosody_stats_kernel(T2ProsodyStats p) {
+    __shared__ float v[T2_PROSODY_MAX_T];              // f0 of the voiced frames, 0 elsewhere
+    __shared__ double redd[3][PR_WAVES];
+    __shared__ int redn[2][PR_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, T = p.T;
+    const long nb = p.n[b] < 0 ? 0 : p.n[b];
+    const float* f0 = p.f0 + (long)b * T;
+    const float* ap = p.aper + (long)b * T;
+    const float* pw = p.power + (long)b * T;
+    int n_valid = 0, n_voiced = 0;
+    double s_lf = 0.0, s_db = 0.0, s_ap = 0.0;
+    for (int t = tid; t < T; t += PR_THREADS) {
+        long s0;
+        const bool valid = yin_valid(t, p.hop, p.S, nb, &s0);
+        const float f = valid ? f0[t] : 0.f;
+        const bool voiced = f > 0.f;
+        v[t] = voiced ? f : 0.f;
+        n_valid += valid;
+        if (voiced) {
+            ++n_voiced;
+            s_lf += (double)logf(f);
+            s_db += (double)(10.f * log10f(pw[t]));
+            s_ap += (double)ap[t];
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        n_valid += __shfl_xor(n_valid, s, T2_WAVE);
+        n_voiced += __shfl_xor(n_voiced, s, T2_WAVE);
+    }
+    s_lf = t2_wave_sum_d(s_lf); s_db = t2_wave_sum_d(s_db); s_ap = t2_wave_sum_d(s_ap);
+    if (lane == 0) { redn[0][w] = n_valid; redn[1][w] = n_voiced; redd[0][w] = s_lf; redd[1][w] = s_db; redd[2][w] = s_ap; }
+    __syncthreads();
+    n_valid = 0; n_voiced = 0;
+    for (int r = 0; r < PR_WAVES; ++r) { n_valid += redn[0][r]; n_voiced += redn[1][r]; }
+    float* out = p.out + (long)b * T2_PROSODY_NSTAT;
+    if (tid == 0) {
+        double m[3] = {0.0, 0.0, 0.0};
+        for (int q = 0; q < 3; ++q)
+            for (int r = 0; r < PR_WAVES; ++r) m[q] += redd[q][r];
+        const float nan = __builtin_nanf("");
+        out[0] = (float)n_valid; out[1] = (float)n_voiced;
+        out[2] = n_voiced ? (float)(m[0] / n_voiced) : nan;
+        out[5] = n_voiced ? (float)(m[1] / n_voiced) : nan;
+        out[6] = n_voiced ? (float)(m[2] / n_voiced) : nan;
+        out[7] = 0.f;
+        if (!n_voiced) { out[3] = nan; out[4] = nan; }
+    }
+    if (!n_voiced) return;
+    // rank of every voiced frame among the voiced frames by (value, index): a permutation of 0 .. n_voiced - 1, so exactly one frame
+    // holds each of the two wanted ranks
+    const int k5 = (5 * (n_voiced - 1) + 50) / 100, k95 = (95 * (n_voiced - 1) + 50) / 100;
+    for (int t = tid; t < T; t += PR_THREADS) {
+        const float f = v[t];
+        if (f > 0.f) {
+            int rank = 0;
+            for (int j = 0; j < T; ++j) {
+                const float g = v[j];
+                rank += (g > 0.f && (g < f || (g == f && j < t))) ? 1 : 0;
+            }
+            if (rank == k5) out[3] = f;
+            if (rank == k95) out[4] = f;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int t2_yin(const T2Yin* a, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(a && a->wav && a->n && a->f0 && a->aper && a->power, "t2_yin: null");
+    T2_REQUIRE(a->B >= 1 && a->B <= 65535, "t2_yin: B outside 1 .. 65535");
+    T2_REQUIRE(a->n_max >= 0, "t2_yin: n_max < 0");
+    T2_REQUIRE(a->hop >= 1 && a->sr >= 1, "t2_yin: need hop, sr >= 1");
+    T2_REQUIRE(a->W >= 16, "t2_yin: W below 16");
+    T2_REQUIRE(a->tau_min >= 2, "t2_yin: tau_min below 2");
+    T2_REQUIRE(a->tau_max > a->tau_min + 1, "t2_yin: need tau_max > tau_min + 1");
+    T2_REQUIRE((int64_t)a->W + a->tau_max <= T2_YIN_MAX_SPAN, "t2_yin: W + tau_max above T2_YIN_MAX_SPAN (4096)");
+    T2_REQUIRE(a->ld_wav >= a->n_max, "t2_yin: ld_wav < n_max");
+    const int64_t T = 1 + a->n_max / a->hop;
+    T2_REQUIRE(T <= 0x7fffffff, "t2_yin: more than 2^31 - 1 frames");
+    const size_t bytes = ((size_t)a->W + a->tau_max + (size_t)PR_WAVES * (a->tau_max + 1)) * sizeof(float);
+    T2_REQUIRE(t2_allow_lds(yin_kernel, bytes), "t2_yin: LDS request refused");
+    hipLaunchKernelGGL(yin_kernel, dim3((unsigned)T, (unsigned)a->B), dim3(PR_THREADS), bytes, ST, *a, (int)T);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+
+extern "C" int t2_prosody_stats(const T2ProsodyStats* a, void* stream) {
+    (void)hipGetLastError();
+    T2_REQUIRE(a && a->f0 && a->aper && a->power && a->n && a->out, "t2_prosody_stats: null");
+    T2_REQUIRE(a->B >= 1 && a->B <= 65535, "t2_prosody_stats: B outside 1 .. 65535");
+    T2_REQUIRE(a->T >= 1 && a->T <= T2_PROSODY_MAX_T, "t2_prosody_stats: T outside 1 .. T2_PROSODY_MAX_T (4096)");
+    T2_REQUIRE(a->hop >= 1 && a->S >= 1, "t2_prosody_stats: need hop, S >= 1");
+    hipLaunchKernelGGL(prosody_stats_kernel, dim3((unsigned)a->B), dim3(PR_THREADS), 0, ST, *a);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}

@@ -75,6 +75,101 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, alpha=1.0, bias=None, bi
     call("t2_gemm", g, _stream())
 
 
+YIN_MAX_SPAN = 4096         # T2_YIN_MAX_SPAN: W + tau_max floats of one frame's span in LDS
+PROSODY_MAX_T = 4096        # T2_PROSODY_MAX_T: frames of one utterance in t2_prosody_stats
+PROSODY_NSTAT = 8           # T2_PROSODY_NSTAT
+YIN_DEFAULTS = dict(sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=0.3, power_floor=1e-10)
+
+
+def yin_lags(sr: int, fmin: float, fmax: float):
+    """(tau_min, tau_max) of a pitch range in Hz: sr // fmax and sr // fmin (22050, 60, 500 -> 44, 367)."""
+    if not (isinstance(sr, int) and not isinstance(sr, bool) and sr >= 1):
+        raise ValueError(f"yin: sr must be an integer >= 1, got {sr!r}")
+    if not (math.isfinite(fmin) and math.isfinite(fmax) and 0 < fmin < fmax):
+        raise ValueError(f"yin: need 0 < fmin < fmax, got fmin = {fmin!r}, fmax = {fmax!r}")
+    return int(sr // fmax), int(sr // fmin)
+
+
+def _check_lengths(fn: str, n, B: int, dev):
+    if not torch.is_tensor(n) or n.device != dev:
+        raise ValueError(f"{fn}: n must be a tensor on the device of the signals, {dev}")
+    if n.dim() != 1 or n.shape[0] != B or n.is_floating_point() or n.dtype == torch.bool:
+        raise ValueError(f"{fn}: n must be {B} integers")
+    return n.to(torch.int64).contiguous()
+
+
+def yin(wav, n, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=0.3, power_floor=1e-10, n_max=None,
+        return_cmnd=False):
+    """The YIN pitch tracker on the mel grid (C-ABI t2_yin) of a padded batch wav (B, ld) float32 on the GPU with the
+    sample counts n (B,) integers on the same device: (f0 Hz, aperiodicity, power), each (B, T) float32 with T = 1 + n_max // hop,
+    and the normalised difference (B, T, tau_max + 1) with return_cmnd.  n_max (default: ld) is the largest count; nothing at or
+    behind n[b] is read.  Frame t is centred on sample t * hop and needs W + tau_max samples around it: a frame whose span leaves
+    [0, n[b]) is invalid and comes back as f0 0, aperiodicity 1, power 0; f0 is 0 for an unvoiced frame.  Needs no model."""
+    if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype != torch.float32:
+        raise ValueError("yin: wav must be a float32 (B, samples) tensor")
+    if wav.device.type != "cuda":
+        raise ValueError(f"yin: wav must be on the GPU, got {wav.device}")
+    B, ld = wav.shape
+    if B < 1 or B > 65535:
+        raise ValueError(f"yin: batch of {B}, outside 1 .. 65535")
+    if ld > 1 and wav.stride(1) != 1:
+        raise ValueError("yin: the last dimension of wav must be contiguous")
+    n_max = ld if n_max is None else int(n_max)
+    ld_wav = wav.stride(0) if B > 1 else max(ld, 1)
+    if not 0 <= n_max <= ld or (B > 1 and ld_wav < n_max):
+        raise ValueError(f"yin: n_max = {n_max} outside 0 .. {ld}, the row length of wav (row stride {ld_wav})")
+    n64 = _check_lengths("yin", n, B, wav.device)
+    for name, val in (("hop", hop), ("W", W)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise ValueError(f"yin: {name} must be an integer, got {val!r}")
+    tau_min, tau_max = yin_lags(sr, fmin, fmax)
+    if hop < 1 or W < 16:
+        raise ValueError(f"yin: need hop >= 1 and W >= 16, got hop = {hop}, W = {W}")
+    if tau_min < 2 or tau_max <= tau_min + 1:
+        raise ValueError(f"yin: lags {tau_min} .. {tau_max} of {fmin} .. {fmax} Hz at {sr} Hz: need tau_min >= 2 and "
+                         "tau_max > tau_min + 1")
+    if W + tau_max > YIN_MAX_SPAN:
+        raise ValueError(f"yin: W + tau_max = {W + tau_max} samples per frame, above the limit of {YIN_MAX_SPAN} (T2_YIN_MAX_SPAN)")
+    for name, val in (("thr", thr), ("vthr", vthr), ("power_floor", power_floor)):
+        if not isinstance(val, numbers.Real) or not math.isfinite(val):
+            raise ValueError(f"yin: {name} must be a finite number, got {val!r}")
+    T = 1 + n_max // hop
+    with torch.cuda.device(wav.device):
+        f0, aper, power = (torch.empty(B, T, dtype=torch.float32, device=wav.device) for _ in range(3))
+        cmnd = torch.empty(B, T, tau_max + 1, dtype=torch.float32, device=wav.device) if return_cmnd else None
+        a = make("T2Yin", wav=wav, ld_wav=ld_wav, n=n64, B=B, n_max=n_max, sr=sr, hop=hop, W=W, tau_min=tau_min, tau_max=tau_max,
+                 thr=float(thr), vthr=float(vthr), power_floor=float(power_floor), f0=f0, aper=aper, power=power, cmnd=cmnd)
+        call("t2_yin", a, _stream())
+    return (f0, aper, power, cmnd) if return_cmnd else (f0, aper, power)
+
+
+def prosody_stats(f0, aper, power, n, hop=256, span=1024 + 367):
+    """Per-utterance statistics (C-ABI t2_prosody_stats) of yin's (B, T) outputs, with n, hop and span = W + tau_max of that call:
+    (B, 8) float32 rows [valid frames, voiced frames, mean ln f0, p5 Hz, p95 Hz, mean 10 log10 power, mean aperiodicity, 0], means
+    and percentiles over the voiced frames (NaN without one); the percentiles are elements of the track, nearest rank."""
+    for name, x in (("f0", f0), ("aper", aper), ("power", power)):
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError(f"prosody_stats: {name} must be a float32 (B, T) tensor")
+        if x.device.type != "cuda" or x.device != f0.device:
+            raise ValueError(f"prosody_stats: {name} must be on the GPU, all three on one device")
+        if x.shape != f0.shape or not x.is_contiguous():
+            raise ValueError(f"prosody_stats: {name} must be contiguous and of the shape of f0 {tuple(f0.shape)}")
+    B, T = f0.shape
+    if B < 1 or B > 65535:
+        raise ValueError(f"prosody_stats: batch of {B}, outside 1 .. 65535")
+    if T < 1 or T > PROSODY_MAX_T:
+        raise ValueError(f"prosody_stats: {T} frames, outside 1 .. {PROSODY_MAX_T} (T2_PROSODY_MAX_T)")
+    for name, val in (("hop", hop), ("span", span)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"prosody_stats: {name} must be an integer >= 1, got {val!r}")
+    n64 = _check_lengths("prosody_stats", n, B, f0.device)
+    with torch.cuda.device(f0.device):
+        out = torch.empty(B, PROSODY_NSTAT, dtype=torch.float32, device=f0.device)
+        a = make("T2ProsodyStats", f0=f0, aper=aper, power=power, n=n64, B=B, T=T, hop=hop, S=span, out=out)
+        call("t2_prosody_stats", a, _stream())
+    return out
+
+
 def fill_splits(M: int, N: int, K: int) -> bool:
     return ((M + 127) // 128) * ((N + 127) // 128) < 256 and K >= 1024
 

@@ -46,7 +46,9 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
     `model.forward_attention` (a bool; `main.py --forward-attention` puts it there for test-correlation), else off.  Forward
     attention together with a window is refused.
     stop_threshold: 0 < tau < 1 of the decode's stop rule (TTSModel.stop_threshold); None takes the config's `model.stop_threshold`
-    (`main.py --stop-threshold` puts it there for test-correlation), else 0.5."""
+    (`main.py --stop-threshold` puts it there for test-correlation), else 0.5.
+    The config's `model.measure_prosody` (a bool; `main.py test-correlation --measure` puts it there, as it does the settings above)
+    gives the model a prosody.ProsodyMeter as `model.prosody_meter`, which synthesize_manifest then measures with."""
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
     kw["scheduler_milestones"] = []
@@ -61,6 +63,9 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
         forward_attention = model_config.get("forward_attention", False)
     model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
     model.stop_threshold = stop_threshold_setting(model_config, stop_threshold)
+    if model_config.get("measure_prosody", False):
+        from ..prosody import ProsodyMeter
+        model.prosody_meter = ProsodyMeter(int(dataset_config["preprocessing"].get("sample_rate", 22050)), dev)
     return model
 
 
@@ -128,8 +133,20 @@ def write_scores(results_dir: str, rows: List[dict], settings: dict) -> dict:
     return agg
 
 
+def measure_batch(meter, pending, n_chars, sr, dev) -> List[dict]:
+    """The prosody.csv rows of one batch: pending = (i, manifest index, mel length, waveform as it went to write_wav)."""
+    wavs = [torch.as_tensor(w, dtype=torch.float32).reshape(-1).to(dev) if n > 0 else torch.zeros(0, device=dev)
+            for _, _, n, w in pending]
+    rows = []
+    for (i, _, n, written), c, m in zip(pending, n_chars, meter.measure(wavs, n_chars)):
+        if n == 0:               # never stopped: whatever was written is not an utterance, and an empty waveform measures nothing
+            m = dict(m, rate=None)
+        rows.append(dict(m, i=i, wav=f"{i}.wav", n_chars=c, seconds=int(torch.as_tensor(written).numel()) / sr, stopped=int(n > 0)))
+    return rows
+
+
 def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=8, max_len=5000,
-                        random_seed=None, zero_length="test", score=False, audio=True, n_ceps=13) -> List[str]:
+                        random_seed=None, zero_length="test", score=False, audio=True, n_ceps=13, meter=None) -> List[str]:
     """The prediction + "Saving WAVs" loops of run/test.py:132-227 and run/test_correlation.py:171-250 over one manifest:
     batches of `batch_size` texts through the batched decode path, `mel_lengths = (gate < 0).argmax` (:172,205), numbering from
     1 in manifest order, `failures.csv` rows `i|text`.
@@ -145,7 +162,11 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     first frame with gate < logit(threshold) - under a threshold below 0.5 a kept frame may have a logit in [logit(threshold), 0) -,
     which at 0.5 is the reference's `gate < 0`.
     score: also compare every decode with its recording (module docstring) and write scores.csv / scores.json.  audio False
-    (`--no-audio`, with score only): no vocoding, no WAVs; failures.csv is still written."""
+    (`--no-audio`, with score only): no vocoding, no WAVs; failures.csv is still written.
+    meter: a prosody.ProsodyMeter (None: the model's `prosody_meter`, if load_test_model gave it one) measures every waveform as it
+    goes to write_wav (before quantisation; one measure() call per batch) and the rows go to `prosody.csv` of results_dir
+    (run/correlation.py: PROSODY_HEADER); an utterance that never stopped has stopped = 0 and empty measures.  Without a meter
+    nothing of this happens."""
     from ..vocoder import write_wav
     dev = model.tacotron2.store.device
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
@@ -158,7 +179,9 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     os.makedirs(results_dir, exist_ok=True)
     speaker_ids = list(df.speaker_id) if model.speaker_tokens else None
     written: List[str] = []
-    recordings, score_rows = None, []
+    recordings, score_rows, prosody_rows = None, [], []
+    if meter is None:
+        meter = getattr(model, "prosody_meter", None)
     if score:
         from ..datasets.tts_dataset import TTSDataset
         check_recordings(df, speech_dir)
@@ -203,6 +226,7 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                                        syn_frames=sc["syn_frames"][k], stopped=bool(sc["stopped"][k]), mcd=sc["mcd"][k],
                                        path_len=sc["path_len"][k], focus_rate=sc["focus_rate"][k],
                                        dur_ratio=sc["syn_frames"][k] / max(sc["ref_frames"][k], 1)))
+        pending = []              # (i, j, n, waveform as written) of this batch, for the meter
         for k, j in enumerate(sel):
             i += 1
             n = int(mel_lengths[k])
@@ -219,12 +243,24 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                     wav = row[:n * 256]
                 write_wav(name, wav.cpu(), sr)
                 written.append(name)
+                if meter is not None:
+                    pending.append((i, j, n, wav))
             else:
                 if n == 0:
                     fail(i, texts[j])
+                    if meter is not None:
+                        pending.append((i, j, 0, torch.zeros(0)))
                     continue
-                write_wav(name, gl.mel_to_audio(post[k, :n], seed=int(random_seed or 0)), sr)
+                wav = gl.mel_to_audio(post[k, :n], seed=int(random_seed or 0))
+                write_wav(name, wav, sr)
                 written.append(name)
+                if meter is not None:
+                    pending.append((i, j, n, wav))
+        if meter is not None and pending:
+            prosody_rows += measure_batch(meter, pending, [len(ids[j]) for _, j, _, _ in pending], sr, dev)
+    if meter is not None:
+        from .correlation import write_prosody_csv
+        write_prosody_csv(results_dir, prosody_rows)
     if score:
         write_scores(results_dir, score_rows, {
             "n_ceps": n_ceps, "attention_window": list(model.attention_window) if model.attention_window is not None else None,
