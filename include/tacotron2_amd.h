@@ -778,6 +778,71 @@ typedef struct {
 int t2_prosody_stats(const T2ProsodyStats* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Smoothed pitch and F0 metrics along a warping path (no reference counterpart; csrc/t2_pitch.hip, the rules in DESIGN 5.11,
+ * restated in float64 in tests/pitch_ref.py).
+ *
+ * t2_pitch_viterbi: the cheapest state sequence through t2_yin's normalised difference function, one per utterance - the decoding
+ *   toolkits run on the host (pYIN's second stage), with one candidate per integer lag.  cmnd[b*ld_b + t*ld_t + tau], tau = 0 ..
+ *   tau_max, float32, and power [B][T] are t2_yin's outputs.  States: the N = tau_max - tau_min lags tau_min .. tau_max-1 in this
+ *   order (state k = lag tau_min + k), then one unvoiced state U (index N).  len[b] (DEVICE int32, clipped to 0 .. T) frames are
+ *   decoded; frames behind it get f0 = 0, aper = 1, lag = 0 and nothing of them is read.  All accumulation in fp64, additions only:
+ *     local(t, k) = (double) cmnd[b][t][tau_min + k] if power[b][t] > power_floor, else +inf;   local(t, U) = u;
+ *     trans(k', k) = fabs(lw[k] - lw[k']), allowed iff <= trans_max;  voiced -> U and U -> voiced cost c_sw;  U -> U costs 0;
+ *     D_0[s] = local(0, s);   D_t[s] = (D_{t-1}[s'] + trans) + local(t, s), the additions in exactly this association.
+ *   lw [N] fp64 (DEVICE) is built by the HOST: lw[k] = w * log2(tau_min + k) with w >= 0, so it does not decrease and the allowed
+ *   predecessors of a target are ONE run of states around it; the kernel takes that run (it walks from the target outwards until
+ *   the first transition above trans_max), which for a table that does not decrease is the rule above.
+ *   ties: a voiced target takes its voiced predecessors in ascending lag, then U - a later candidate wins only when STRICTLY
+ *   smaller; target U takes U first, then the voiced predecessors ascending, under the same rule; termination takes the first
+ *   minimum over the voiced states ascending, then U.
+ *   Outputs [B][T]: lag = the lag of the chosen state, 0 for U;  aper = cmnd[t][lag] for a voiced frame, 1 for U;  f0 = t2_yin's own
+ *   parabolic formula on cmnd[t][lag-1 .. lag+1] in fp32 (off clamped to [-1, 1], 0 when the denominator is not positive; f0 =
+ *   sr / (lag + off)), 0 for U.  cost [B] fp64 = the minimum, 0 for len[b] == 0.  back: workspace uint16 [B][T][N+1], the chosen
+ *   predecessor state of every (frame >= 1, state).
+ *   One 256-thread workgroup per utterance, one barrier per frame; in dynamic LDS two rotating fp64 rows of D [N+1] and the lw
+ *   table [N]: (3 N + 2) * 8 bytes = 98 320 at N = T2_PITCH_MAX_STATES = 4096, inside the 160 KB (163 840) a workgroup may take.
+ *   The runs do not depend on t and are found once per launch (registers of the thread that owns the target).  Target U's minimum
+ *   over the voiced predecessors of frame t is reduced as frame t-1 writes them (wave minima by shuffles, left beside D in front of
+ *   that frame's barrier).  No cross-workgroup synchronisation, no atomics; two calls give bit-identical outputs.
+ *   T2_ERR_ARG before any launch: a null pointer, B < 1 or > 65535, T < 1 or > T2_PROSODY_MAX_T, sr < 1, tau_min < 2, tau_max <=
+ *   tau_min + 1, N > T2_PITCH_MAX_STATES, overlapping strides (ld_t < tau_max + 1, ld_b < (T-1)*ld_t + tau_max + 1), a trans_max, u or
+ *   c_sw that is not finite or is negative, a power_floor that is NaN.
+ *
+ * t2_f0_path_stats: two pitch tracks compared along t2_dtw's path.  path [B][P][2] int32 holds path_len[b] (clipped to 0 .. P) cells
+ *   (i, j); f0_a [B][Ta] and f0_b [B][Tb] are in Hz, 0 = unvoiced; n_a, n_b [B] (DEVICE int64) the sample counts.  Frame t of a
+ *   track is valid under t2_prosody_stats' rule (t*hop - S/2 >= 0 and t*hop - S/2 + S <= n) and only inside the track (0 <= t <
+ *   Ta resp. Tb); a cell is scored only when both of its frames are valid, and the tracks are read at valid frames only.
+ *   out[b] = T2_F0_NSTAT doubles: { scored cells, cells with both frames voiced, only a voiced, only b voiced, sum d, sum d^2 with
+ *   d = 1200 (log2 fa - log2 fb) over the both-voiced cells, then over the same cells sum la, sum lb, sum la^2, sum lb^2, sum la*lb
+ *   with la = log2 fa, lb = log2 fb (what a Pearson correlation needs), 0 }.  fp64 throughout, every sum in a fixed order.
+ *   path_len[b] == 0: a row of zeros, nothing is read.  One 256-thread workgroup per pair.
+ *   T2_ERR_ARG before any launch: a null pointer, B < 1 or > 65535, P, Ta, Tb < 1, hop < 1, S < 1. */
+#define T2_PITCH_MAX_STATES 4096
+#define T2_F0_NSTAT 12
+typedef struct {
+    const float* cmnd; int64_t ld_b, ld_t;    /* cmnd[b*ld_b + t*ld_t + tau], tau = 0 .. tau_max contiguous */
+    const float* power;                       /* [B][T] */
+    const int32_t* len;                       /* [B] device; clipped to 0 .. T */
+    const double* lw;                         /* [N] device, N = tau_max - tau_min */
+    int B, T, sr, tau_min, tau_max;
+    float power_floor;
+    double trans_max, u, c_sw;
+    float* f0; float* aper; int32_t* lag;     /* [B][T] */
+    double* cost;                             /* [B] */
+    uint16_t* back;                           /* workspace [B][T][N+1] */
+} T2PitchViterbi;
+int t2_pitch_viterbi(const T2PitchViterbi* a, void* stream);
+typedef struct {
+    const int32_t* path;                      /* [B][P][2] */
+    const int32_t* path_len;                  /* [B] device; clipped to 0 .. P */
+    const float* f0_a; const float* f0_b;     /* [B][Ta], [B][Tb] */
+    const int64_t* n_a; const int64_t* n_b;   /* [B] device each */
+    int B, P, Ta, Tb, hop, S;
+    double* out;                              /* [B][T2_F0_NSTAT] */
+} T2F0PathStats;
+int t2_f0_path_stats(const T2F0PathStats* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

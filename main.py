@@ -7,9 +7,9 @@
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
                                                   [--attention-window BACK,FWD | --forward-attention] [--durations-out PATH]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
-                                                  [--attention-window BACK,FWD | --forward-attention] [--score [--no-audio]]
+                                                  [--attention-window BACK,FWD | --forward-attention] [--score [--no-audio | --f0]]
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
-                                                  [--attention-window BACK,FWD | --forward-attention] [--measure]
+                                                  [--attention-window BACK,FWD | --forward-attention] [--measure [--smooth-pitch]]
     python main.py --config C --device N measure-correlation --results-dir R [--features a,b,...]
     (say, test and test-correlation also take --stop-threshold P)
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
@@ -202,12 +202,20 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                    "focus rate, as scores.csv and scores.json in the results directory. Default: off.")
 @click.option("--no-audio", is_flag=True, default=False,
               help="With --score: skip vocoding and the WAV files, write the scores only.")
+@click.option("--f0", is_flag=True, default=False,
+              help="With --score: also compare intonation. Every synthesised waveform and its recording are pitch-tracked on the GPU "
+                   "(YIN with Viterbi smoothing) and compared along the MCD warping path: F0 RMSE and bias in cents, log-F0 "
+                   "correlation and voicing-decision error, as f0_scores.csv and four means in scores.json. Default: off.")
 def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window,
-         forward_attention, stop_threshold=None, score=False, no_audio=False):
+         forward_attention, stop_threshold=None, score=False, no_audio=False, f0=False):
     """Synthesise the test manifest (run/test.py of the reference): one wav per utterance + failures.csv."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if no_audio and not score:
         raise click.UsageError("--no-audio needs --score: without either there would be nothing to write")
+    if f0 and not score:
+        raise click.UsageError("--f0 needs --score: the tracks are compared along the path of the MCD score")
+    if f0 and no_audio:
+        raise click.UsageError("--f0 cannot go with --no-audio: there would be no waveform to track")
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
     from tacotron2_amd.run.test import do_test
@@ -216,7 +224,7 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
             extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
             hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit,
             attention_window=attention_window, forward_attention=forward_attention, stop_threshold=stop_threshold, score=score,
-            audio=not no_audio)
+            audio=not no_audio, **({"f0": True} if f0 else {}))
 
 
 @main.command()
@@ -236,10 +244,15 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
                    "of every waveform as prosody.csv in each override directory, and the correlation of every requested control "
                    "with its measure (Pearson, Spearman, slope, and the control x measure leakage matrix) as correlation.json in the "
                    "results directory. Default: off.")
+@click.option("--smooth-pitch", is_flag=True, default=False,
+              help="With --measure: decode every pitch track with the Viterbi smoother before its statistics (no octave jumps in "
+                   "the pitch range). Default: off.")
 def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides,
-                     attention_window, forward_attention, stop_threshold=None, measure=False):
+                     attention_window, forward_attention, stop_threshold=None, measure=False, smooth_pitch=False):
     """The test manifest under 51 control-vector overrides (run/test_correlation.py of the reference)."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
+    if smooth_pitch and not measure:
+        raise click.UsageError("--smooth-pitch needs --measure: without it no pitch is tracked")
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for testing!")
     from tacotron2_amd.run.test_correlation import do_test_correlation
@@ -251,7 +264,7 @@ def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_d
         model_config = dict(model_config, stop_threshold=stop_threshold)
     if measure:                # the meter travels with the model (load_test_model), the tables need the directory's name afterwards
         import datetime
-        model_config = dict(model_config, measure_prosody=True)
+        model_config = dict(model_config, measure_prosody=True, **({"smooth_pitch": True} if smooth_pitch else {}))
         if results_dir is None:
             results_dir = f"results_{c['training']['name']}_test_correlation {datetime.datetime.now()}"
     do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=model_config,
@@ -262,7 +275,7 @@ def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_d
         from tacotron2_amd.prosody import ProsodyMeter
         from tacotron2_amd.run.correlation import correlate_tree
         sr = int(c["dataset"].get("preprocessing", {}).get("sample_rate", 22050))
-        correlate_tree(results_dir, c["extensions"]["controls"]["features"], ProsodyMeter(sr, f"cuda:{ctx.obj['device']}").describe())
+        correlate_tree(results_dir, c["extensions"]["controls"]["features"], ProsodyMeter(sr, f"cuda:{ctx.obj['device']}", smooth=smooth_pitch).describe())
 
 
 @main.command()

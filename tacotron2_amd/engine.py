@@ -170,6 +170,125 @@ def prosody_stats(f0, aper, power, n, hop=256, span=1024 + 367):
     return out
 
 
+PITCH_MAX_STATES = 4096     # T2_PITCH_MAX_STATES: voiced states (integer lags) of t2_pitch_viterbi
+F0_NSTAT = 12               # T2_F0_NSTAT
+# w: transition cost per octave of lag change; max_jump: the largest allowed change in octaves per frame; u: local cost of the
+# unvoiced state (YIN's voicing threshold: a frame whose best lag is worse than that is cheaper unvoiced); c_sw: a voicing switch
+VITERBI_DEFAULTS = dict(w=1.0, max_jump=0.25, u=YIN_DEFAULTS["vthr"], c_sw=0.15)
+
+
+def pitch_viterbi(cmnd, power, n, sr=22050, hop=256, fmin=60.0, fmax=500.0, power_floor=1e-10, w=1.0, max_jump=0.25,
+                  u=VITERBI_DEFAULTS["u"], c_sw=0.15):
+    """The cheapest lag sequence through yin's normalised difference (C-ABI t2_pitch_viterbi): cmnd (B, T, tau_max + 1)
+    and power (B, T) as yin(return_cmnd=True) of the same sr, hop, fmin, fmax gives them, n (B,) the sample counts - the first
+    min(T, 1 + n[b] // hop) frames are decoded.  States are the integer lags tau_min .. tau_max - 1 and one unvoiced state; a lag
+    costs its cmnd (nothing voiced where power <= power_floor), the unvoiced state u, a lag change w * |log2 ratio| and at most
+    max_jump octaves per frame, a voicing switch c_sw.  (f0 Hz, aperiodicity, lag int32, each (B, T); cost float64 (B,)): f0 and lag
+    0, aperiodicity 1 for an unvoiced frame and behind the decoded frames.  Needs no model."""
+    if not torch.is_tensor(cmnd) or cmnd.dim() != 3 or cmnd.dtype != torch.float32:
+        raise ValueError("pitch_viterbi: cmnd must be a float32 (B, T, tau_max + 1) tensor")
+    if cmnd.device.type != "cuda":
+        raise ValueError(f"pitch_viterbi: cmnd must be on the GPU, got {cmnd.device}")
+    B, T, NT = cmnd.shape
+    if B < 1 or B > 65535:
+        raise ValueError(f"pitch_viterbi: batch of {B}, outside 1 .. 65535")
+    if T < 1 or T > PROSODY_MAX_T:
+        raise ValueError(f"pitch_viterbi: {T} frames, outside 1 .. {PROSODY_MAX_T} (T2_PROSODY_MAX_T)")
+    if not torch.is_tensor(power) or power.dtype != torch.float32 or power.device != cmnd.device or power.shape != (B, T) \
+            or not power.is_contiguous():
+        raise ValueError(f"pitch_viterbi: power must be a contiguous float32 ({B}, {T}) tensor on {cmnd.device}")
+    if isinstance(hop, bool) or not isinstance(hop, int) or hop < 1:
+        raise ValueError(f"pitch_viterbi: hop must be an integer >= 1, got {hop!r}")
+    try:
+        tau_min, tau_max = yin_lags(sr, fmin, fmax)
+    except ValueError as e:
+        raise ValueError("pitch_viterbi" + str(e)[3:]) from None
+    if tau_min < 2 or tau_max <= tau_min + 1:
+        raise ValueError(f"pitch_viterbi: lags {tau_min} .. {tau_max} of {fmin} .. {fmax} Hz at {sr} Hz: need tau_min >= 2 and "
+                         "tau_max > tau_min + 1")
+    N = tau_max - tau_min
+    if N > PITCH_MAX_STATES:
+        raise ValueError(f"pitch_viterbi: {N} lags, above the limit of {PITCH_MAX_STATES} (T2_PITCH_MAX_STATES)")
+    if NT != tau_max + 1:
+        raise ValueError(f"pitch_viterbi: cmnd has {NT} lags per frame, {fmin} .. {fmax} Hz at {sr} Hz need tau_max + 1 = {tau_max + 1}")
+    if NT > 1 and cmnd.stride(2) != 1:
+        raise ValueError("pitch_viterbi: the last dimension of cmnd must be contiguous")
+    ld_t = cmnd.stride(1) if T > 1 else NT
+    ld_b = cmnd.stride(0) if B > 1 else (T - 1) * ld_t + NT
+    if ld_t < NT or ld_b < (T - 1) * ld_t + NT:
+        raise ValueError(f"pitch_viterbi: overlapping strides of cmnd {tuple(cmnd.stride())}")
+    for name, val in (("w", w), ("max_jump", max_jump), ("u", u), ("c_sw", c_sw)):
+        if isinstance(val, bool) or not isinstance(val, numbers.Real) or not math.isfinite(val) or val < 0:
+            raise ValueError(f"pitch_viterbi: {name} must be a finite number >= 0, got {val!r}")
+    if isinstance(power_floor, bool) or not isinstance(power_floor, numbers.Real) or not math.isfinite(power_floor):
+        raise ValueError(f"pitch_viterbi: power_floor must be a finite number, got {power_floor!r}")
+    n64 = _check_lengths("pitch_viterbi", n, B, cmnd.device)
+    with torch.cuda.device(cmnd.device):
+        dev = cmnd.device
+        frames = (1 + torch.div(n64.clamp(min=0), hop, rounding_mode="floor")).clamp(max=T).to(torch.int32)
+        lw = (float(w) * torch.log2(torch.arange(tau_min, tau_max, dtype=torch.float64))).to(dev)     # built on the host
+        f0, aper = (torch.empty(B, T, dtype=torch.float32, device=dev) for _ in range(2))
+        lag = torch.empty(B, T, dtype=torch.int32, device=dev)
+        cost = torch.empty(B, dtype=torch.float64, device=dev)
+        back = torch.empty(B, T, N + 1, dtype=torch.int16, device=dev)       # (the kernel's uint16 workspace)
+        a = make("T2PitchViterbi", cmnd=cmnd, ld_b=ld_b, ld_t=ld_t, power=power, len=frames, lw=lw, B=B, T=T, sr=sr, tau_min=tau_min,
+                 tau_max=tau_max, power_floor=float(power_floor), trans_max=float(w) * float(max_jump), u=float(u), c_sw=float(c_sw),
+                 f0=f0, aper=aper, lag=lag, cost=cost, back=back)
+        call("t2_pitch_viterbi", a, _stream())
+    return f0, aper, lag, cost
+
+
+def f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=256, span=1024 + 367):
+    """Two pitch tracks compared along a warping path (C-ABI t2_f0_path_stats): path (B, P, 2) int32 and path_len (B,) as
+    Engine.dtw(return_path=True) gives them - cell (i, j) pairs frame i of f0_a (B, Ta) with frame j of f0_b (B, Tb), Hz, 0 =
+    unvoiced -, n_a and n_b the sample counts, hop and span = W + tau_max of the yin call (the validity rule of prosody_stats; cells
+    outside a track count as invalid).  (B, 12) float64 rows [scored cells, both voiced, only a voiced, only b voiced, sum d, sum d^2
+    with d = 1200 (log2 fa - log2 fb) cents over the both-voiced cells, sum la, sum lb, sum la^2, sum lb^2, sum la lb with la =
+    log2 fa, 0]; f0_figures turns a row into RMSE, bias, correlation and voicing error."""
+    if not torch.is_tensor(path) or path.dim() != 3 or path.shape[2] != 2 or path.dtype != torch.int32 or not path.is_contiguous():
+        raise ValueError("f0_path_stats: path must be a contiguous int32 (B, P, 2) tensor")
+    if path.device.type != "cuda":
+        raise ValueError(f"f0_path_stats: path must be on the GPU, got {path.device}")
+    B, P, _ = path.shape
+    if B < 1 or B > 65535 or P < 1:
+        raise ValueError(f"f0_path_stats: path of shape {tuple(path.shape)}: need 1 .. 65535 pairs and P >= 1")
+    if not torch.is_tensor(path_len) or path_len.dtype != torch.int32 or path_len.device != path.device or path_len.shape != (B,):
+        raise ValueError(f"f0_path_stats: path_len must be {B} int32 on {path.device}")
+    for name, x in (("f0_a", f0_a), ("f0_b", f0_b)):
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device != path.device or x.shape[0] != B \
+                or x.shape[1] < 1 or not x.is_contiguous():
+            raise ValueError(f"f0_path_stats: {name} must be a contiguous float32 ({B}, T >= 1) tensor on {path.device}")
+    for name, val in (("hop", hop), ("span", span)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"f0_path_stats: {name} must be an integer >= 1, got {val!r}")
+    na64 = _check_lengths("f0_path_stats", n_a, B, path.device)
+    nb64 = _check_lengths("f0_path_stats", n_b, B, path.device)
+    with torch.cuda.device(path.device):
+        out = torch.empty(B, F0_NSTAT, dtype=torch.float64, device=path.device)
+        a = make("T2F0PathStats", path=path, path_len=path_len.contiguous(), f0_a=f0_a, f0_b=f0_b, n_a=na64, n_b=nb64, B=B, P=P,
+                 Ta=f0_a.shape[1], Tb=f0_b.shape[1], hop=hop, S=span, out=out)
+        call("t2_f0_path_stats", a, _stream())
+    return out
+
+
+def f0_figures(row) -> dict:
+    """The figures of one f0_path_stats row (12 numbers): n_pairs, n_voiced_both, f0_rmse_cents, f0_bias_cents (a minus b), f0_corr
+    (Pearson of log2 f0; None with fewer than 2 both-voiced cells or a column without variance), vuv_error = (only a + only b) /
+    scored.  None where undefined."""
+    n, nb = int(row[0]), int(row[1])
+    out = dict(n_pairs=n, n_voiced_both=nb, f0_rmse_cents=None, f0_bias_cents=None, f0_corr=None, vuv_error=None)
+    if n > 0:
+        out["vuv_error"] = (row[2] + row[3]) / n
+    if nb > 0:
+        out["f0_rmse_cents"] = math.sqrt(max(row[5], 0.0) / nb)
+        out["f0_bias_cents"] = row[4] / nb
+    if nb >= 2:
+        va, vb = row[8] - row[6] * row[6] / nb, row[9] - row[7] * row[7] / nb
+        if va > 1e-12 * row[8] and vb > 1e-12 * row[9]:      # (a constant column leaves rounding noise, not variance)
+            out["f0_corr"] = (row[10] - row[6] * row[7] / nb) / math.sqrt(va * vb)
+    return out
+
+
 def fill_splits(M: int, N: int, K: int) -> bool:
     return ((M + 127) // 128) * ((N + 127) // 128) < 256 and K >= 1024
 

@@ -279,7 +279,7 @@ class Tacotron2(nn.Module):
         return post, scores
 
     def score_decode(self, post: Tensor, gates: Tensor, align: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor,
-                     mel_spectrogram_len: Tensor, stop_threshold: float = 0.5, n_ceps: int = 13) -> dict:
+                     mel_spectrogram_len: Tensor, stop_threshold: float = 0.5, n_ceps: int = 13, return_path: bool = False) -> dict:
         """MCD-DTW (Engine.mcd_dtw) between the post-net mels of a decode - (mels_post, gates, alignments) as
         forward(teacher_forcing=False) returns them - cut at the decode's own lengths, and the recordings `mel_spectrogram`
         (B, T, num_mels) cut at `mel_spectrogram_len`.  A dict of per-utterance tensors:
@@ -290,7 +290,9 @@ class Tacotron2(nn.Module):
           ref_frames  int64, mel_spectrogram_len cut at T
           stopped     bool, syn_frames > 0
           focus_rate  float32, the mean over the decoder steps of the largest attention weight (Engine.durations, mode "argmax",
-                      over the syn_frames of a stopped utterance, over the whole decode of one that never stopped)"""
+                      over the syn_frames of a stopped utterance, over the whole decode of one that never stopped)
+        return_path adds  path  int32 (B, P, 2): the first path_len[b] rows are the warped pairs (frame of the decode, frame of
+                      the recording) in forward order (Engine.dtw), the rest -1"""
         from ..engine import stop_logit
         B = post.shape[0]
         if not torch.is_tensor(mel_spectrogram) or mel_spectrogram.dim() != 3 or mel_spectrogram.shape[0] != B \
@@ -308,10 +310,14 @@ class Tacotron2(nn.Module):
             # (cut at the longest utterance of each side: a decode that ran into max_len is longer than the warping's cap, its
             # stopped utterances are not)
             ta, tb = max(int(syn.max()), 1), max(int(ref.max()), 1)
-            mcd, _, path_len = self._engine.mcd_dtw(post[:, :ta], syn, mel_spectrogram.to(dev).float()[:, :tb], ref, n_ceps=n_ceps)
+            mcd, _, path_len, *path = self._engine.mcd_dtw(post[:, :ta], syn, mel_spectrogram.to(dev).float()[:, :tb], ref,
+                                                           n_ceps=n_ceps, return_path=return_path)
             frames = torch.where(stopped, syn, torch.full_like(syn, post.shape[1]))
             stats = self._engine.durations(align, chars_idx_len.to(dev), frames, mode="argmax")[1]
-        return dict(mcd=mcd, path_len=path_len, syn_frames=syn, ref_frames=ref, stopped=stopped, focus_rate=stats[:, 0].clone())
+        out = dict(mcd=mcd, path_len=path_len, syn_frames=syn, ref_frames=ref, stopped=stopped, focus_rate=stats[:, 0].clone())
+        if return_path:
+            out["path"] = path[0]
+        return out
 
     def inference(self, chars_idx, chars_idx_len, max_len: int = 5000, **kw):
         """Alias of forward(teacher_forcing=False, max_len_override=max_len) (north_star's "inference() surface")."""

@@ -1,8 +1,9 @@
 """What came out of a synthesis, measured on the GPU: pitch level and range, intensity, noisiness and speaking rate of a batch of
 waveforms.  The YIN pitch tracker (engine.yin, C-ABI t2_yin) analyses frames on the mel grid - hop 256, frame t
 centred on sample 256 t - and engine.prosody_stats (t2_prosody_stats) reduces every track to one row; this module only packs the
-batch and names the fields.  No smoothing of the track, no jitter / shimmer, no parity with Praat's absolute values: the numbers
-are for correlating with the requested controls (run/correlation.py)."""
+batch and names the fields.  No jitter / shimmer, no parity with Praat's absolute values: the numbers are for correlating with the
+requested controls (run/correlation.py).  ProsodyMeter(smooth=True) decodes the track with engine.pitch_viterbi, and
+f0_scores compares the tracks of two batches along a warping path (engine.f0_path_stats): what `test --score --f0` reports."""
 from __future__ import annotations
 
 import math
@@ -16,20 +17,63 @@ MEASURES = ["pitch_mean_log", "pitch_range_log", "intensity_mean_db", "aperiodic
 
 
 class ProsodyMeter:
-    """measure() of a list of waveforms in one launch of each kernel.  The settings are engine.yin's (engine.YIN_DEFAULTS)."""
+    """measure() of a list of waveforms in one launch of each kernel.  The settings are engine.yin's (engine.YIN_DEFAULTS).
+    smooth=True decodes the track with engine.pitch_viterbi before the statistics: further settings are then
+    engine.VITERBI_DEFAULTS' (w, max_jump, u - default: this meter's vthr -, c_sw)."""
 
-    def __init__(self, sample_rate: int = 22050, device=None, **yin_settings):
-        unknown = set(yin_settings) - (set(engine.YIN_DEFAULTS) - {"sr"})
+    def __init__(self, sample_rate: int = 22050, device=None, smooth: bool = False, **settings):
+        yin_keys, vit_keys = set(engine.YIN_DEFAULTS) - {"sr"}, set(engine.VITERBI_DEFAULTS)
+        unknown = set(settings) - yin_keys - (vit_keys if smooth else set())
         if unknown:
             raise ValueError(f"ProsodyMeter: unknown YIN settings {sorted(unknown)}")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.settings = dict(engine.YIN_DEFAULTS, sr=int(sample_rate), **yin_settings)
+        self.smooth = bool(smooth)
+        self.settings = dict(engine.YIN_DEFAULTS, sr=int(sample_rate), **{k: v for k, v in settings.items() if k in yin_keys})
+        self.viterbi = None
+        if self.smooth:
+            self.viterbi = dict(engine.VITERBI_DEFAULTS, u=self.settings["vthr"])
+            self.viterbi.update({k: v for k, v in settings.items() if k in vit_keys})
         self.tau_min, self.tau_max = engine.yin_lags(self.settings["sr"], self.settings["fmin"], self.settings["fmax"])
         self.span = self.settings["W"] + self.tau_max
 
     def describe(self) -> dict:
-        """The settings as they go into correlation.json."""
-        return dict(self.settings, tau_min=self.tau_min, tau_max=self.tau_max)
+        """The settings as they go into correlation.json; with smooth also `smooth` and the Viterbi settings."""
+        d = dict(self.settings, tau_min=self.tau_min, tau_max=self.tau_max)
+        if self.smooth:
+            d.update(smooth=True, **self.viterbi)
+        return d
+
+    def _pack(self, fn: str, wavs):
+        for w in wavs:
+            if not torch.is_tensor(w) or w.dim() != 1 or w.dtype != torch.float32 or w.device != self.device:
+                raise ValueError(f"{fn}: every waveform must be a 1-D float32 tensor on {self.device}")
+        lens = [int(w.shape[0]) for w in wavs]
+        n_max = max(lens)
+        s = self.settings
+        if 1 + n_max // s["hop"] > engine.PROSODY_MAX_T:
+            raise ValueError(f"{fn}: a waveform of {n_max} samples has more than {engine.PROSODY_MAX_T} frames (T2_PROSODY_MAX_T)")
+        batch = torch.zeros(len(wavs), max(n_max, 1), dtype=torch.float32, device=self.device)
+        for k, w in enumerate(wavs):
+            batch[k, :lens[k]] = w
+        return batch, lens, n_max, torch.tensor(lens, dtype=torch.int64, device=self.device)
+
+    def _track(self, batch, n, n_max):
+        """(f0, aper, power) of a packed batch: yin's own pick, or with smooth the Viterbi decode of its cmnd."""
+        s = self.settings
+        if not self.smooth:
+            return engine.yin(batch, n, n_max=n_max, **s)
+        _, _, power, cmnd = engine.yin(batch, n, n_max=n_max, return_cmnd=True, **s)
+        f0, aper, _, _ = engine.pitch_viterbi(cmnd, power, n, sr=s["sr"], hop=s["hop"], fmin=s["fmin"], fmax=s["fmax"],
+                                              power_floor=s["power_floor"], **self.viterbi)
+        return f0, aper, power
+
+    def tracks(self, wavs: Sequence[torch.Tensor]):
+        """(f0 (B, T) Hz, n (B,) int64 sample counts) of a batch of waveforms, padded to the longest: the track measure() reduces
+        (0 = unvoiced or invalid frame; frame t is centred on sample t * hop)."""
+        if not wavs:
+            raise ValueError("tracks: no waveform")
+        batch, _, n_max, n = self._pack("tracks", wavs)
+        return self._track(batch, n, n_max)[0], n
 
     def measure(self, wavs: Sequence[torch.Tensor], n_chars: Sequence[int]) -> List[dict]:
         """One dict per waveform (1-D float32 tensors on the meter's device, any lengths, empty ones included): n_frames (valid
@@ -40,19 +84,9 @@ class ProsodyMeter:
             raise ValueError(f"measure: {len(wavs)} waveforms, {len(n_chars)} character counts")
         if not wavs:
             return []
-        for w in wavs:
-            if not torch.is_tensor(w) or w.dim() != 1 or w.dtype != torch.float32 or w.device != self.device:
-                raise ValueError(f"measure: every waveform must be a 1-D float32 tensor on {self.device}")
-        lens = [int(w.shape[0]) for w in wavs]
-        n_max = max(lens)
+        batch, lens, n_max, n = self._pack("measure", wavs)
         s = self.settings
-        if 1 + n_max // s["hop"] > engine.PROSODY_MAX_T:
-            raise ValueError(f"measure: a waveform of {n_max} samples has more than {engine.PROSODY_MAX_T} frames (T2_PROSODY_MAX_T)")
-        batch = torch.zeros(len(wavs), max(n_max, 1), dtype=torch.float32, device=self.device)
-        for k, w in enumerate(wavs):
-            batch[k, :lens[k]] = w
-        n = torch.tensor(lens, dtype=torch.int64, device=self.device)
-        f0, aper, power = engine.yin(batch, n, n_max=n_max, **s)
+        f0, aper, power = self._track(batch, n, n_max)
         st = engine.prosody_stats(f0, aper, power, n, hop=s["hop"], span=self.span).cpu().tolist()
         out = []
         for k, row in enumerate(st):
@@ -66,3 +100,20 @@ class ProsodyMeter:
                 aperiodicity_mean=row[6] if voiced else None,
                 rate=(int(n_chars[k]) / seconds) if lens[k] > 0 else None))
         return out
+
+
+F0_MEASURES = ["f0_rmse_cents", "f0_bias_cents", "f0_corr", "vuv_error"]
+
+
+def f0_scores(meter: ProsodyMeter, syn_wavs: Sequence[torch.Tensor], ref_wavs: Sequence[torch.Tensor], path, path_len) -> List[dict]:
+    """One dict per pair (engine.f0_figures: n_pairs, n_voiced_both and the F0_MEASURES, None where undefined): the meter's tracks of
+    syn_wavs[k] and ref_wavs[k] compared along the first path_len[k] cells (i = frame of the synthesis, j = frame of the recording)
+    of path (B, P, 2) int32 - Tacotron2.score_decode(return_path=True) - whose frames lie on the meter's hop."""
+    if len(syn_wavs) != len(ref_wavs):
+        raise ValueError(f"f0_scores: {len(syn_wavs)} synthesised waveforms, {len(ref_wavs)} recordings")
+    if not syn_wavs:
+        return []
+    f0_a, n_a = meter.tracks(syn_wavs)
+    f0_b, n_b = meter.tracks(ref_wavs)
+    st = engine.f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=meter.settings["hop"], span=meter.span)
+    return [engine.f0_figures(row) for row in st.cpu().tolist()]

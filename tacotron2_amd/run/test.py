@@ -18,6 +18,12 @@ and the post-net mels cut at `mel_lengths` are compared with it by mel-cepstral 
 device (Tacotron2.score_decode).  `scores.csv`, `|`-separated with the header SCORE_HEADER, one row per utterance in manifest
 order (`i` as in the WAV names; an utterance that never stopped has an empty mcd_dtw and dur_ratio), and `scores.json` with
 the aggregates.  `--no-audio` skips vocoding and the WAVs.
+
+`test --score --f0` also compares intonation: every waveform as it goes to write_wav and the recording's waveform
+(TTSDataset.load_audio - the trimmed, padded signal the reference mel came from, frame t centred on sample 256 t as the mel frame
+is) are pitch-tracked with prosody.ProsodyMeter(smooth=True), and the two tracks are compared along the MCD path
+(prosody.f0_scores).  `f0_scores.csv`, `|`-separated with the header F0_HEADER, one row per utterance in manifest order, empty
+where undefined (every measure of an utterance that never stopped), and four means plus `settings.f0` in scores.json.
 """
 from __future__ import annotations
 
@@ -48,7 +54,8 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
     stop_threshold: 0 < tau < 1 of the decode's stop rule (TTSModel.stop_threshold); None takes the config's `model.stop_threshold`
     (`main.py --stop-threshold` puts it there for test-correlation), else 0.5.
     The config's `model.measure_prosody` (a bool; `main.py test-correlation --measure` puts it there, as it does the settings above)
-    gives the model a prosody.ProsodyMeter as `model.prosody_meter`, which synthesize_manifest then measures with."""
+    gives the model a prosody.ProsodyMeter as `model.prosody_meter`, which synthesize_manifest then measures with; the config's
+    `model.smooth_pitch` (`--smooth-pitch`) builds it with smooth=True."""
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
     kw["scheduler_milestones"] = []
@@ -65,7 +72,8 @@ def load_test_model(dataset_config, training_config, model_config, extensions_co
     model.stop_threshold = stop_threshold_setting(model_config, stop_threshold)
     if model_config.get("measure_prosody", False):
         from ..prosody import ProsodyMeter
-        model.prosody_meter = ProsodyMeter(int(dataset_config["preprocessing"].get("sample_rate", 22050)), dev)
+        model.prosody_meter = ProsodyMeter(int(dataset_config["preprocessing"].get("sample_rate", 22050)), dev,
+                                           smooth=bool(model_config.get("smooth_pitch", False)))
     return model
 
 
@@ -100,6 +108,9 @@ def mel_lengths_of(gate: torch.Tensor, stop_threshold: float = 0.5) -> torch.Ten
 SCORE_HEADER = ["i", "wav", "n_chars", "ref_frames", "syn_frames", "stopped", "mcd_dtw", "path_len", "dur_ratio", "focus_rate"]
 
 
+F0_HEADER = ["i", "wav", "stopped", "n_pairs", "n_voiced_both", "f0_rmse_cents", "f0_bias_cents", "f0_corr", "vuv_error"]
+
+
 def check_recordings(df, speech_dir) -> None:
     """`test --score` reads every recording of the manifest: a missing one is an error that names the file, before any decoding."""
     if "wav" not in df.columns:
@@ -110,8 +121,27 @@ def check_recordings(df, speech_dir) -> None:
             raise FileNotFoundError(f"test --score: recording not found: {path}")
 
 
-def write_scores(results_dir: str, rows: List[dict], settings: dict) -> dict:
-    """scores.csv (SCORE_HEADER) and scores.json of `test --score`; returns the aggregates."""
+def write_f0_scores(results_dir: str, rows: List[dict]) -> dict:
+    """f0_scores.csv (F0_HEADER) of `test --score --f0`; returns the means that go into scores.json, each over the stopped
+    utterances where it is defined."""
+    from ..prosody import F0_MEASURES
+    with open(os.path.join(results_dir, "f0_scores.csv"), "w", newline="") as f:
+        wr = csv.writer(f, delimiter="|", quoting=csv.QUOTE_NONE, escapechar="\\")
+        wr.writerow(F0_HEADER)
+        for r in rows:
+            ok = r["stopped"]
+            wr.writerow([r["i"], r["wav"], int(ok), r["n_pairs"] if ok else "", r["n_voiced_both"] if ok else ""]
+                        + [f"{r[m]:.6f}" if ok and r[m] is not None else "" for m in F0_MEASURES])
+    out = {}
+    for m in F0_MEASURES:
+        v = [r[m] for r in rows if r["stopped"] and r[m] is not None]
+        out[f"{m}_mean"] = (sum(v) / len(v)) if v else None
+    return out
+
+
+def write_scores(results_dir: str, rows: List[dict], settings: dict, f0_means: Optional[dict] = None) -> dict:
+    """scores.csv (SCORE_HEADER) and scores.json of `test --score`; returns the aggregates.  f0_means (write_f0_scores, with --f0
+    only) are added to scores.json in front of `settings`."""
     with open(os.path.join(results_dir, "scores.csv"), "w", newline="") as f:
         wr = csv.writer(f, delimiter="|", quoting=csv.QUOTE_NONE, escapechar="\\")
         wr.writerow(SCORE_HEADER)
@@ -127,7 +157,7 @@ def write_scores(results_dir: str, rows: List[dict], settings: dict) -> dict:
     agg = {"n": len(rows), "n_stopped": len(ok), "failure_rate": (1.0 - len(ok) / len(rows)) if rows else None,
            "mcd_dtw_mean": mean(mcds), "mcd_dtw_median": median,
            "abs_log_dur_ratio_mean": mean([abs(math.log(r["dur_ratio"])) for r in ok if r["dur_ratio"] > 0]),
-           "focus_rate_mean": mean([r["focus_rate"] for r in rows]), "settings": settings}
+           "focus_rate_mean": mean([r["focus_rate"] for r in rows]), **(f0_means or {}), "settings": settings}
     with open(os.path.join(results_dir, "scores.json"), "w") as f:
         json.dump(agg, f, indent=1)
     return agg
@@ -146,7 +176,8 @@ def measure_batch(meter, pending, n_chars, sr, dev) -> List[dict]:
 
 
 def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=8, max_len=5000,
-                        random_seed=None, zero_length="test", score=False, audio=True, n_ceps=13, meter=None) -> List[str]:
+                        random_seed=None, zero_length="test", score=False, audio=True, n_ceps=13, meter=None,
+                        f0=False) -> List[str]:
     """The prediction + "Saving WAVs" loops of run/test.py:132-227 and run/test_correlation.py:171-250 over one manifest:
     batches of `batch_size` texts through the batched decode path, `mel_lengths = (gate < 0).argmax` (:172,205), numbering from
     1 in manifest order, `failures.csv` rows `i|text`.
@@ -166,8 +197,11 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     meter: a prosody.ProsodyMeter (None: the model's `prosody_meter`, if load_test_model gave it one) measures every waveform as it
     goes to write_wav (before quantisation; one measure() call per batch) and the rows go to `prosody.csv` of results_dir
     (run/correlation.py: PROSODY_HEADER); an utterance that never stopped has stopped = 0 and empty measures.  Without a meter
-    nothing of this happens."""
+    nothing of this happens.
+    f0 (`--f0`; needs score and audio): also f0_scores.csv and the F0 means in scores.json (module docstring)."""
     from ..vocoder import write_wav
+    if f0 and not (score and audio):
+        raise ValueError("test: f0=True (--f0) needs score=True (--score) and audio (no --no-audio): it tracks the waveforms")
     dev = model.tacotron2.store.device
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
     texts = [enc.clean(t) for t in df.text]
@@ -179,7 +213,7 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     os.makedirs(results_dir, exist_ok=True)
     speaker_ids = list(df.speaker_id) if model.speaker_tokens else None
     written: List[str] = []
-    recordings, score_rows, prosody_rows = None, [], []
+    recordings, score_rows, prosody_rows, f0_rows, f0_meter = None, [], [], [], None
     if meter is None:
         meter = getattr(model, "prosody_meter", None)
     if score:
@@ -187,6 +221,9 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
         check_recordings(df, speech_dir)
         recordings = TTSDataset(filenames=[str(w) for w in df.wav], texts=list(df.text), base_dir=speech_dir, device=dev,
                                 **dict(pre, cache=False))
+        if f0:
+            from ..prosody import ProsodyMeter, f0_scores
+            f0_meter = ProsodyMeter(sr, dev, smooth=True)
 
     def fail(i, text):
         print(f"Error: {i}: {text}")
@@ -218,7 +255,9 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
             refs = [recordings[j][0]["mel_spectrogram"] for j in sel]
             sc = model.tacotron2.score_decode(post, gate, align, lens, torch.nn.utils.rnn.pad_sequence(refs, batch_first=True),
                                               torch.tensor([len(m) for m in refs], dtype=torch.int64, device=dev),
-                                              stop_threshold=getattr(model, "stop_threshold", 0.5), n_ceps=n_ceps)
+                                              stop_threshold=getattr(model, "stop_threshold", 0.5), n_ceps=n_ceps,
+                                              return_path=f0)
+            warp = (sc.pop("path"), sc["path_len"]) if f0 else None
             sc = {k: v.cpu().tolist() for k, v in sc.items()}
             assert sc["syn_frames"] == [int(n) for n in mel_lengths]
             for k, j in enumerate(sel):
@@ -227,6 +266,7 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                                        path_len=sc["path_len"][k], focus_rate=sc["focus_rate"][k],
                                        dur_ratio=sc["syn_frames"][k] / max(sc["ref_frames"][k], 1)))
         pending = []              # (i, j, n, waveform as written) of this batch, for the meter
+        voc = {}                  # k -> the waveform as written, of the utterances that stopped: for f0
         for k, j in enumerate(sel):
             i += 1
             n = int(mel_lengths[k])
@@ -243,6 +283,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                     wav = row[:n * 256]
                 write_wav(name, wav.cpu(), sr)
                 written.append(name)
+                if n > 0:
+                    voc[k] = wav
                 if meter is not None:
                     pending.append((i, j, n, wav))
             else:
@@ -254,19 +296,27 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
                 wav = gl.mel_to_audio(post[k, :n], seed=int(random_seed or 0))
                 write_wav(name, wav, sr)
                 written.append(name)
+                voc[k] = wav
                 if meter is not None:
                     pending.append((i, j, n, wav))
+        if f0:                    # an utterance that never stopped has path_len 0 and goes in as an empty waveform: nothing scored
+            as_dev = lambda x: torch.as_tensor(x, dtype=torch.float32).reshape(-1).to(dev)
+            syn_w = [as_dev(voc[k]) if k in voc else torch.zeros(0, device=dev) for k in range(len(sel))]
+            ref_w = [as_dev(recordings.load_audio(j)) for j in sel]
+            for k, (j, fig) in enumerate(zip(sel, f0_scores(f0_meter, syn_w, ref_w, warp[0], warp[1]))):
+                f0_rows.append(dict(fig, i=i - len(sel) + k + 1, wav=str(df.wav[j]), stopped=int(mel_lengths[k]) > 0))
         if meter is not None and pending:
             prosody_rows += measure_batch(meter, pending, [len(ids[j]) for _, j, _, _ in pending], sr, dev)
     if meter is not None:
         from .correlation import write_prosody_csv
         write_prosody_csv(results_dir, prosody_rows)
     if score:
+        f0_means = write_f0_scores(results_dir, f0_rows) if f0 else None
         write_scores(results_dir, score_rows, {
-            "n_ceps": n_ceps, "attention_window": list(model.attention_window) if model.attention_window is not None else None,
+            **({"f0": f0_meter.describe()} if f0 else {}), "n_ceps": n_ceps, "attention_window": list(model.attention_window) if model.attention_window is not None else None,
             "forward_attention": bool(getattr(model, "forward_attention", False)),
             "stop_threshold": float(getattr(model, "stop_threshold", 0.5)), "r": int(model.tacotron2.reduction_factor),
-            "max_len": int(max_len)})
+            "max_len": int(max_len)}, f0_means)
     return written
 
 
@@ -275,10 +325,12 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
             results_dir: Optional[str] = None, batch_size: int = 8, max_len: int = 5000, limit: Optional[int] = None,
             random_seed: Optional[int] = None, attention_window: Optional[Tuple[int, int]] = None,
             forward_attention: Optional[bool] = None, stop_threshold: Optional[float] = None, score: bool = False,
-            audio: bool = True, n_ceps: int = 13) -> List[str]:
+            audio: bool = True, n_ceps: int = 13, f0: bool = False) -> List[str]:
     import pandas as pd
     if not audio and not score:
         raise ValueError("test: audio=False (--no-audio) needs score=True (--score)")
+    if f0 and not (score and audio):
+        raise ValueError("test: f0=True (--f0) needs score=True (--score) and audio (no --no-audio): it tracks the waveforms")
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
@@ -298,4 +350,4 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
     gen, gl, sr = make_vocoders(hifi_gan_checkpoint, pre, dev) if audio else (None, None, int(pre.get("sample_rate", 22050)))
     return synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=batch_size,
                                max_len=max_len, random_seed=random_seed, zero_length="test", score=score, audio=audio,
-                               n_ceps=n_ceps)
+                               n_ceps=n_ceps, f0=f0)
