@@ -778,6 +778,64 @@ typedef struct {
 int t2_prosody_stats(const T2ProsodyStats* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Voice quality of a corpus or a synthesis (no reference counterpart - the reference extracts jitter, shimmer and nhr with Praat;
+ * csrc/t2_prosody.hip, the rule in DESIGN 5.12, restated in float64 in tests/voice_quality_ref.py).
+ *
+ * t2_voice_quality: per-frame cycle matching on the mel grid.  wav / ld_wav / n / n_max and the framing are t2_yin's: S = W + tau_max,
+ *   frame t spans [s0, s0 + S) with s0 = t*hop - S/2 and is VALID iff s0 >= 0 and s0 + S <= n[b] (n clipped to 0 .. n_max), T = 1 +
+ *   n_max / hop.  f0 [B][T] is a pitch track in Hz - t2_yin's or t2_pitch_viterbi's - with 0 (or anything not > 0) = unvoiced.
+ *   For a valid frame with f0 > 0, x its span:
+ *     L = lrintf(sr / f0) (fp32 quotient, clamped to [tau_min, tau_max - 1]);  d = max(2, (L + 7) / 8);
+ *     K = min((S - 2 L - d) / L + 1, T2_VQ_MAX_CYCLES) (integer division);  the frame is MEASURED iff K >= 3.
+ *   Cycle i = 0 .. K-1 has its anchor at c = i L:  a = x[c .. c+L),  b_tau = x[c+tau .. c+tau+L) for tau = L-d .. L+d,
+ *     ncc(tau) = sum a b_tau / sqrt(sum a^2 * sum b_tau^2), 0 when that product is not positive;  tau* = the FIRST argmax;
+ *     off = 0.5 (ncc(tau*-1) - ncc(tau*+1)) / (ncc(tau*-1) - 2 ncc(tau*) + ncc(tau*+1)) clamped to [-1, 1], 0 when tau* is L-d or L+d
+ *     or that denominator is not negative;  T_i = tau* + off,  r_i = ncc(tau*),  A_i = sqrt(sum a^2 / L).
+ *   Per frame, sums over i ascending:  jitter = mean_{i<K-1} |T_{i+1} - T_i| / mean_i T_i;  shimmer the same over A, 0 when mean A is
+ *     0;  r = mean r_i clamped to [1e-3, 1 - 1e-6];  nhr = (1 - r) / r;  hnr_db = 10 log10(r / (1 - r)) (Boersma's harmonicity).
+ *   Outputs [B][T]: jitter, shimmer, nhr, hnr_db and cycles (int32, K of a measured frame).  Every other frame - invalid, unvoiced,
+ *   K < 3 - gets exactly 0, 0, 0, 0, 0 and nothing of its signal is read (of an invalid frame not f0 either).  Nothing at or behind
+ *   n[b] is ever read.  cyc [B][T][T2_VQ_MAX_CYCLES][3] is optional (NULL: not written): T_i, r_i, A_i in the rows i < K and ZEROS in
+ *   the rows behind, all zeros for a frame that is not measured - every element is written.
+ *   One 256-thread workgroup per (frame, utterance).  Dynamic LDS: the span and two tables of S/2 + 160 floats ((cycle, tau) products
+ *   and window energies; K (2 d + 1) <= 7 S / 16 for L >= 16 and <= 160 below), at most (2 S + 320) * 4 = 34 048 bytes.  One thread per
+ *   (cycle, tau) pair sums its product left to right; the K + 1 window energies sum x[i L .. i L + L)^2 are summed left to right by
+ *   one thread each (the energy of b_L of cycle i IS that of a of cycle i + 1) and sum b_tau^2 runs from tau = L outwards, one sample
+ *   dropped and one added per step - never recomputed per tau.  fp32 throughout, no atomics, every sum in a fixed order: two calls
+ *   give bit-identical outputs.
+ *   T2_ERR_ARG before any launch: what t2_yin rejects (thr, vthr, power_floor and its outputs do not exist here), a null f0 or output
+ *   (cyc excepted).
+ *
+ * t2_corpus_stats: one row of T2_CORPUS_NSTAT floats per utterance from the [B][T] arrays of t2_yin (f0 or t2_pitch_viterbi's, power)
+ *   and t2_voice_quality.  Frame t is valid under the same rule (n, hop, S); voiced = valid and f0 > 0; measured = valid and cycles >
+ *   0; loud = valid and power > power_floor.  out[b] = { valid, voiced, measured, loud frames, mean f0 (Hz) over the voiced frames,
+ *   mean jitter, shimmer, nhr, hnr_db over the measured frames, mean 10 log10(power) over the loud frames, 0, 0 }.  A mean over an
+ *   empty set is 0 (its count says so).  Invalid frames are not read.  fp64 accumulation in a fixed order, one 256-thread workgroup
+ *   per utterance, one launch.
+ *   T2_ERR_ARG before any launch: a null pointer, B < 1 or > 65535, T < 1, hop < 1, S < 1, a power_floor that is NaN. */
+#define T2_VQ_MAX_CYCLES 32
+#define T2_CORPUS_NSTAT 12
+typedef struct {
+    const float* wav; int64_t ld_wav;         /* wav[b*ld_wav + i] */
+    const int64_t* n;                         /* [B] device */
+    int B; int64_t n_max;
+    int sr, hop, W, tau_min, tau_max;
+    const float* f0;                          /* [B][T], T = 1 + n_max / hop */
+    float* jitter; float* shimmer; float* nhr; float* hnr_db; int32_t* cycles;     /* [B][T] */
+    float* cyc;                               /* optional [B][T][T2_VQ_MAX_CYCLES][3] */
+} T2VoiceQuality;
+int t2_voice_quality(const T2VoiceQuality* a, void* stream);
+typedef struct {
+    const float* f0; const float* power;      /* [B][T] */
+    const float* jitter; const float* shimmer; const float* nhr; const float* hnr_db; const int32_t* cycles;     /* [B][T] */
+    const int64_t* n;                         /* [B] device */
+    int B, T, hop, S;                         /* S = W + tau_max of the t2_yin call */
+    float power_floor;
+    float* out;                               /* [B][T2_CORPUS_NSTAT] */
+} T2CorpusStats;
+int t2_corpus_stats(const T2CorpusStats* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Smoothed pitch and F0 metrics along a warping path (no reference counterpart; csrc/t2_pitch.hip, the rules in DESIGN 5.11,
  * restated in float64 in tests/pitch_ref.py).
  *

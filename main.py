@@ -14,9 +14,10 @@
     (say, test and test-correlation also take --stop-threshold P)
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
     python main.py --config C --device N duration-export --speech-dir S --checkpoint K [--results-dir R] [--mode monotonic|argmax]
+    python main.py --config C --device N prosody-export --speech-dir S [--results-dir R] [--no-smooth-pitch] [--batch-size 64]
 
 Other reference sub-commands (preprocess, server) are data preparation / demo tooling outside the hot-path scope
-(SURVEY.md section 2).  Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N
+(SURVEY.md section 2); prosody-export writes what preprocess and the split scripts write for the controls, with this project's meter.  Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N
 main.py --config C train ...` (one process per GPU, RCCL gradient all-reduce)."""
 import re
 
@@ -334,6 +335,31 @@ def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monoton
     do_duration_export(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
                        extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
                        results_dir=results_dir, mode=mode)
+
+
+@main.command()
+@click.pass_context
+@click.option("--speech-dir", required=True, type=str, help="A directory containing audio files from the dataset.")
+@click.option("--results-dir", required=False, type=str, default=None, help="The directory to save results. Defaults to the configuration name with a timestamp.")
+@click.option("--no-smooth-pitch", is_flag=True, default=False,
+              help="Measure on the raw YIN track instead of the Viterbi-smoothed one. Default: smoothed.")
+@click.option("--batch-size", required=False, type=click.IntRange(1, 65535), default=64, help="Utterances measured together. Default 64.")
+def prosody_export(ctx, speech_dir, results_dir=None, no_smooth_pitch=False, batch_size=64):
+    """Measure the train / val / test manifests on the GPU (pitch, intensity, jitter, shimmer, noise-to-harmonics ratio, rate) and
+    write them with the raw and the speaker- and dataset-normalised control columns, plus prosody_norm.json and
+    prosody_dropped.csv.  Needs no checkpoint."""
+    c = ctx.obj["config"]
+    if c is None:
+        raise click.UsageError("prosody-export needs --config: it names the manifests (dataset.train / val / test)")
+    if not isinstance(c.get("dataset"), dict) or not c["dataset"].get("train"):
+        raise click.UsageError("prosody-export: the config names no dataset.train: the statistics come from the train manifest")
+    from tacotron2_amd.run.prosody_export import ProsodyExportError, do_prosody_export
+    try:
+        do_prosody_export(dataset_config=c["dataset"], extensions_config=c["extensions"], device=ctx.obj["device"],
+                          speech_dir=speech_dir, results_dir=results_dir, smooth_pitch=not no_smooth_pitch, batch_size=batch_size,
+                          name=c.get("training", {}).get("name", "corpus"))
+    except ProsodyExportError as e:
+        raise click.ClickException(str(e)) from None
 
 
 if __name__ == "__main__":

@@ -10,6 +10,10 @@
 //     in order.  The pick is a min-reduction of (index) and of (value, index) - order-independent - and a short walk by thread 0.
 //     Every sum has a fixed association: two launches are bit-identical.
 //   t2_prosody_stats: ONE workgroup per utterance; the track's voiced f0 in LDS, percentiles by rank counting over (value, index).
+// Voice quality of a corpus (t2_voice_quality, t2_corpus_stats), in the same style:
+//   t2_voice_quality: ONE workgroup per (frame, utterance), the same span in LDS; one thread per (cycle, lag) pair sums its product
+//     left to right, the window energies are a running sum, the picks and the frame's means short serial walks (see vq_kernel).
+//   t2_corpus_stats: ONE workgroup per utterance; counts and fp64 sums per thread, a shuffle tree, then the waves in order.
 #include "t2_common.hpp"
 
 namespace {
@@ -214,7 +218,206 @@ __global__ __launch_bounds__(PR_THREADS) void prosody_stats_kernel(T2ProsodyStat
     }
 }
 
+// t2_voice_quality: ONE workgroup per (frame, utterance), the span in LDS.  Work items are the (cycle, tau) pairs, one
+// per thread and pass, in the order pair = cycle * ND + (tau - (L - d)): the lanes of a wave run along tau, so at a fixed j they read
+// b at consecutive LDS addresses (conflict-free) and a at one address per cycle (a broadcast; a wave spans more than one cycle only
+// when ND < 64, then with two or three distinct addresses).  The window energies are K + 1 left-to-right sums by the lanes of the
+// last wave and a running update from tau = L outwards; cycle picks and the frame's means are short serial walks.
+__global__ __launch_bounds__(PR_THREADS) void vq_kernel(T2VoiceQuality p, int T, int cap) {
+    extern __shared__ float lds[];
+    __shared__ float en[T2_VQ_MAX_CYCLES + 1];         // sum x[i L .. i L + L)^2
+    __shared__ float cT[T2_VQ_MAX_CYCLES], cR[T2_VQ_MAX_CYCLES], cA[T2_VQ_MAX_CYCLES];
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int S = p.W + p.tau_max;
+    const long o = (long)b * T + t;
+    long nb = p.n[b];
+    nb = nb < 0 ? 0 : (nb > p.n_max ? p.n_max : nb);
+    long s0;
+    int K = 0, L = 0, d = 0;
+    if (yin_valid(t, p.hop, S, nb, &s0)) {             // (uniform over the workgroup)
+        const float f = p.f0[o];
+        if (f > 0.f) {
+            const float q = fminf(fmaxf((float)p.sr / f, (float)p.tau_min), (float)(p.tau_max - 1));
+            L = (int)lrintf(q);
+            d = max(2, (L + 7) / 8);
+            const int room = S - 2 * L - d;
+            K = room < 0 ? 0 : min(room / L + 1, T2_VQ_MAX_CYCLES);
+        }
+    }
+    float* cyc = p.cyc ? p.cyc + o * (3 * T2_VQ_MAX_CYCLES) : nullptr;
+    if (K < 3) {                                       // not measured: nothing of the signal is read
+        if (tid == 0) { p.jitter[o] = 0.f; p.shimmer[o] = 0.f; p.nhr[o] = 0.f; p.hnr_db[o] = 0.f; p.cycles[o] = 0; }
+        if (cyc) for (int k = tid; k < 3 * T2_VQ_MAX_CYCLES; k += PR_THREADS) cyc[k] = 0.f;
+        return;
+    }
+    const int ND = 2 * d + 1;
+    K = min(K, cap / ND);                              // (never binds - K ND <= cap, t2_voice_quality below; keeps the tables' bounds local)
+    const int NP = K * ND;
+    float* x = lds;                                    // [S] the span
+    float* dot = lds + S;                              // [cap] sum a b per pair, then ncc
+    float* eb = dot + cap;                             // [cap] sum b^2 per pair
+    const float* src = p.wav + (long)b * p.ld_wav + s0;
+    for (int i = tid; i < S; i += PR_THREADS) x[i] = src[i];
+    __syncthreads();
+
+    if (tid >= PR_THREADS - T2_WAVE && tid - (PR_THREADS - T2_WAVE) <= K) {      // (K + 1 <= 33 lanes of the last wave)
+        const float* a = x + (tid - (PR_THREADS - T2_WAVE)) * L;                 // (K + 1) L <= S
+        float s = 0.f;
+        for (int j = 0; j < L; ++j) s = fmaf(a[j], a[j], s);
+        en[tid - (PR_THREADS - T2_WAVE)] = s;
+    }
+    for (int pp = tid; pp < NP; pp += PR_THREADS) {
+        const int i = pp / ND, k = pp - i * ND;
+        const float* a = x + i * L;
+        const float* bb = a + (L - d + k);             // last read: (K - 1) L + (L + d) + L - 1 <= S - 1
+        float s = 0.f;
+#pragma unroll 4
+        for (int j = 0; j < L; ++j) s = fmaf(a[j], bb[j], s);
+        dot[pp] = s;
+    }
+    __syncthreads();
+    if (tid < K) {                                     // sum b^2: the window of tau = L is that of the next cycle's a
+        const float* a = x + tid * L;
+        float* e = eb + tid * ND + d;
+        float s = en[tid + 1];
+        e[0] = s;
+        for (int k = 1; k <= d; ++k) {                 // tau = L + k from L + k - 1: x[c + tau - 1] leaves, x[c + tau - 1 + L] enters
+            const float lo = a[L + k - 1], hi = a[2 * L + k - 1];
+            s = fmaf(hi, hi, fmaf(-lo, lo, s));
+            e[k] = s;
+        }
+        s = en[tid + 1];
+        for (int k = 1; k <= d; ++k) {                 // tau = L - k from L - k + 1: x[c + tau] enters, x[c + tau + L] leaves
+            const float lo = a[L - k], hi = a[2 * L - k];
+            s = fmaf(lo, lo, fmaf(-hi, hi, s));
+            e[-k] = s;
+        }
+    }
+    __syncthreads();
+    for (int pp = tid; pp < NP; pp += PR_THREADS) {
+        const float den = en[pp / ND] * eb[pp];
+        dot[pp] = den > 0.f ? dot[pp] / sqrtf(den) : 0.f;
+    }
+    __syncthreads();
+    if (tid < K) {
+        const float* c = dot + tid * ND;
+        int ki = 0;
+        float m = c[0];
+        for (int k = 1; k < ND; ++k)
+            if (c[k] > m) { m = c[k]; ki = k; }
+        float off = 0.f;
+        if (ki > 0 && ki < ND - 1) {
+            const float a = c[ki - 1], e = c[ki + 1];
+            const float den = a - 2.f * m + e;
+            off = den < 0.f ? 0.5f * (a - e) / den : 0.f;
+            off = fminf(fmaxf(off, -1.f), 1.f);
+        }
+        cT[tid] = (float)(L - d + ki) + off;
+        cR[tid] = m;
+        cA[tid] = sqrtf(en[tid] / (float)L);
+    }
+    __syncthreads();
+    if (cyc)
+        for (int k = tid; k < 3 * T2_VQ_MAX_CYCLES; k += PR_THREADS) {
+            const int i = k / 3, q = k - 3 * i;
+            cyc[k] = i < K ? (q == 0 ? cT[i] : (q == 1 ? cR[i] : cA[i])) : 0.f;
+        }
+    if (tid == 0) {
+        float sT = 0.f, sA = 0.f, sR = 0.f, dT = 0.f, dA = 0.f;
+        for (int i = 0; i < K; ++i) { sT += cT[i]; sA += cA[i]; sR += cR[i]; }
+        for (int i = 0; i + 1 < K; ++i) { dT += fabsf(cT[i + 1] - cT[i]); dA += fabsf(cA[i + 1] - cA[i]); }
+        const float mT = sT / (float)K, mA = sA / (float)K;
+        const float r = fminf(fmaxf(sR / (float)K, 1e-3f), 1.f - 1e-6f);
+        p.jitter[o] = dT / (float)(K - 1) / mT;
+        p.shimmer[o] = mA > 0.f ? dA / (float)(K - 1) / mA : 0.f;
+        p.nhr[o] = (1.f - r) / r;
+        p.hnr_db[o] = 10.f * log10f(r / (1.f - r));
+        p.cycles[o] = K;
+    }
+}
+
+__global__ __launch_bounds__(PR_THREADS) void corpus_stats_kernel(T2CorpusStats p) {
+    __shared__ double redd[6][PR_WAVES];
+    __shared__ int redn[4][PR_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, T = p.T;
+    const long nb = p.n[b] < 0 ? 0 : p.n[b];
+    const long r0 = (long)b * T;
+    int cnt[4] = {0, 0, 0, 0};                         // valid, voiced, measured, loud
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // f0, jitter, shimmer, nhr, hnr_db, 10 log10 power
+    for (int t = tid; t < T; t += PR_THREADS) {
+        long s0;
+        if (!yin_valid(t, p.hop, p.S, nb, &s0)) continue;          // an invalid frame is not read
+        ++cnt[0];
+        const float f = p.f0[r0 + t], pw = p.power[r0 + t];
+        if (f > 0.f) { ++cnt[1]; s[0] += (double)f; }
+        if (p.cycles[r0 + t] > 0) {
+            ++cnt[2];
+            s[1] += (double)p.jitter[r0 + t]; s[2] += (double)p.shimmer[r0 + t];
+            s[3] += (double)p.nhr[r0 + t]; s[4] += (double)p.hnr_db[r0 + t];
+        }
+        if (pw > p.power_floor) { ++cnt[3]; s[5] += (double)(10.f * log10f(pw)); }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[q] += __shfl_xor(cnt[q], o, T2_WAVE);
+        if (lane == 0) redn[q][w] = cnt[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+        s[q] = t2_wave_sum_d(s[q]);
+        if (lane == 0) redd[q][w] = s[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n4[4] = {0, 0, 0, 0};
+        double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int r = 0; r < PR_WAVES; ++r) {
+            for (int q = 0; q < 4; ++q) n4[q] += redn[q][r];
+            for (int q = 0; q < 6; ++q) m[q] += redd[q][r];
+        }
+        float* out = p.out + (long)b * T2_CORPUS_NSTAT;
+        for (int q = 0; q < 4; ++q) out[q] = (float)n4[q];
+        out[4] = n4[1] ? (float)(m[0] / n4[1]) : 0.f;
+        for (int q = 1; q < 5; ++q) out[4 + q] = n4[2] ? (float)(m[q] / n4[2]) : 0.f;
+        out[9] = n4[3] ? (float)(m[5] / n4[3]) : 0.f;
+        out[10] = 0.f; out[11] = 0.f;
+    }
+}
+
 }  // namespace
+
+extern "C" int t2_voice_quality(const T2VoiceQuality* a, void* stream) {
+    (void)hipGetLastError();
+    T2_REQUIRE(a && a->wav && a->n && a->f0 && a->jitter && a->shimmer && a->nhr && a->hnr_db && a->cycles, "t2_voice_quality: null");
+    T2_REQUIRE(a->B >= 1 && a->B <= 65535, "t2_voice_quality: B outside 1 .. 65535");
+    T2_REQUIRE(a->n_max >= 0, "t2_voice_quality: n_max < 0");
+    T2_REQUIRE(a->hop >= 1 && a->sr >= 1, "t2_voice_quality: need hop, sr >= 1");
+    T2_REQUIRE(a->W >= 16, "t2_voice_quality: W below 16");
+    T2_REQUIRE(a->tau_min >= 2, "t2_voice_quality: tau_min below 2");
+    T2_REQUIRE(a->tau_max > a->tau_min + 1, "t2_voice_quality: need tau_max > tau_min + 1");
+    T2_REQUIRE((int64_t)a->W + a->tau_max <= T2_YIN_MAX_SPAN, "t2_voice_quality: W + tau_max above T2_YIN_MAX_SPAN (4096)");
+    T2_REQUIRE(a->ld_wav >= a->n_max, "t2_voice_quality: ld_wav < n_max");
+    const int64_t T = 1 + a->n_max / a->hop;
+    T2_REQUIRE(T <= 0x7fffffff, "t2_voice_quality: more than 2^31 - 1 frames");
+    // pairs of one frame: K <= S / L cycles of 2 d + 1 <= L / 4 + 3 lags for L >= 16 (<= S/4 + 3 S/16), 32 cycles of 5 lags below
+    const int S = a->W + a->tau_max, cap = S / 2 + 160;
+    const size_t bytes = ((size_t)S + 2 * (size_t)cap) * sizeof(float);
+    hipLaunchKernelGGL(vq_kernel, dim3((unsigned)T, (unsigned)a->B), dim3(PR_THREADS), bytes, ST, *a, (int)T, cap);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
+
+extern "C" int t2_corpus_stats(const T2CorpusStats* a, void* stream) {
+    (void)hipGetLastError();
+    T2_REQUIRE(a && a->f0 && a->power && a->jitter && a->shimmer && a->nhr && a->hnr_db && a->cycles && a->n && a->out,
+               "t2_corpus_stats: null");
+    T2_REQUIRE(a->B >= 1 && a->B <= 65535, "t2_corpus_stats: B outside 1 .. 65535");
+    T2_REQUIRE(a->T >= 1, "t2_corpus_stats: T < 1");
+    T2_REQUIRE(a->hop >= 1 && a->S >= 1, "t2_corpus_stats: need hop, S >= 1");
+    T2_REQUIRE(a->power_floor == a->power_floor, "t2_corpus_stats: power_floor is NaN");
+    hipLaunchKernelGGL(corpus_stats_kernel, dim3((unsigned)a->B), dim3(PR_THREADS), 0, ST, *a);
+    T2_CHECK_LAUNCH(); return T2_OK;
+}
 
 extern "C" int t2_yin(const T2Yin* a, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked

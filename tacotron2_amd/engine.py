@@ -170,6 +170,91 @@ def prosody_stats(f0, aper, power, n, hop=256, span=1024 + 367):
     return out
 
 
+VQ_MAX_CYCLES = 32          # T2_VQ_MAX_CYCLES: cycles matched per frame in t2_voice_quality
+CORPUS_NSTAT = 12           # T2_CORPUS_NSTAT
+
+
+def voice_quality(wav, n, f0, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, n_max=None, return_cycles=False):
+    """Jitter, shimmer and harmonicity per frame by cycle matching (C-ABI t2_voice_quality): wav (B, ld) float32, n (B,)
+    and n_max as yin takes them, with the same sr, hop, W, fmin, fmax, and f0 (B, T) float32 - yin's track or pitch_viterbi's, 0 =
+    unvoiced.  A valid frame (yin's rule) with f0 > 0 holds K = min((S - 2 L - d) // L + 1, 32) cycles of L = round(sr / f0) samples
+    and is measured iff K >= 3.  (jitter, shimmer, nhr, hnr_db float32, cycles int32), each (B, T); every frame that is not measured
+    has 0 in all five.  With return_cycles also (B, T, 32, 3) float32: period, correlation and RMS amplitude of every cycle, zeros
+    behind the K-th.  Needs no model."""
+    if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype != torch.float32:
+        raise ValueError("voice_quality: wav must be a float32 (B, samples) tensor")
+    if wav.device.type != "cuda":
+        raise ValueError(f"voice_quality: wav must be on the GPU, got {wav.device}")
+    B, ld = wav.shape
+    if B < 1 or B > 65535:
+        raise ValueError(f"voice_quality: batch of {B}, outside 1 .. 65535")
+    if ld > 1 and wav.stride(1) != 1:
+        raise ValueError("voice_quality: the last dimension of wav must be contiguous")
+    n_max = ld if n_max is None else int(n_max)
+    ld_wav = wav.stride(0) if B > 1 else max(ld, 1)
+    if not 0 <= n_max <= ld or (B > 1 and ld_wav < n_max):
+        raise ValueError(f"voice_quality: n_max = {n_max} outside 0 .. {ld}, the row length of wav (row stride {ld_wav})")
+    n64 = _check_lengths("voice_quality", n, B, wav.device)
+    for name, val in (("hop", hop), ("W", W)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise ValueError(f"voice_quality: {name} must be an integer, got {val!r}")
+    try:
+        tau_min, tau_max = yin_lags(sr, fmin, fmax)
+    except ValueError as e:
+        raise ValueError("voice_quality" + str(e)[3:]) from None
+    if hop < 1 or W < 16:
+        raise ValueError(f"voice_quality: need hop >= 1 and W >= 16, got hop = {hop}, W = {W}")
+    if tau_min < 2 or tau_max <= tau_min + 1:
+        raise ValueError(f"voice_quality: lags {tau_min} .. {tau_max} of {fmin} .. {fmax} Hz at {sr} Hz: need tau_min >= 2 and "
+                         "tau_max > tau_min + 1")
+    if W + tau_max > YIN_MAX_SPAN:
+        raise ValueError(f"voice_quality: W + tau_max = {W + tau_max} samples per frame, above the limit of {YIN_MAX_SPAN} "
+                         "(T2_YIN_MAX_SPAN)")
+    T = 1 + n_max // hop
+    if not torch.is_tensor(f0) or f0.dtype != torch.float32 or f0.device != wav.device or tuple(f0.shape) != (B, T) \
+            or not f0.is_contiguous():
+        raise ValueError(f"voice_quality: f0 must be a contiguous float32 ({B}, {T}) tensor on {wav.device}")
+    with torch.cuda.device(wav.device):
+        jitter, shimmer, nhr, hnr_db = (torch.empty(B, T, dtype=torch.float32, device=wav.device) for _ in range(4))
+        cycles = torch.empty(B, T, dtype=torch.int32, device=wav.device)
+        cyc = torch.empty(B, T, VQ_MAX_CYCLES, 3, dtype=torch.float32, device=wav.device) if return_cycles else None
+        a = make("T2VoiceQuality", wav=wav, ld_wav=ld_wav, n=n64, B=B, n_max=n_max, sr=sr, hop=hop, W=W, tau_min=tau_min, tau_max=tau_max,
+                 f0=f0, jitter=jitter, shimmer=shimmer, nhr=nhr, hnr_db=hnr_db, cycles=cycles, cyc=cyc)
+        call("t2_voice_quality", a, _stream())
+    return (jitter, shimmer, nhr, hnr_db, cycles, cyc) if return_cycles else (jitter, shimmer, nhr, hnr_db, cycles)
+
+
+def corpus_stats(f0, power, jitter, shimmer, nhr, hnr_db, cycles, n, hop=256, span=1024 + 367, power_floor=1e-10):
+    """Per-utterance means (C-ABI t2_corpus_stats) of yin's f0 (or pitch_viterbi's) and power and of voice_quality's five (B, T) arrays,
+    with n, hop and span = W + tau_max of those calls: (B, 12) float32 rows [valid, voiced, measured, loud frames, mean f0 Hz over the
+    voiced frames, mean jitter, shimmer, nhr, hnr_db over the measured frames, mean 10 log10 power over the loud frames (valid and
+    power > power_floor), 0, 0].  A mean over no frame is 0."""
+    B, T = (f0.shape if torch.is_tensor(f0) and f0.dim() == 2 else (0, 0))
+    for name, x in (("f0", f0), ("power", power), ("jitter", jitter), ("shimmer", shimmer), ("nhr", nhr), ("hnr_db", hnr_db),
+                    ("cycles", cycles)):
+        want = torch.int32 if name == "cycles" else torch.float32
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != want:
+            raise ValueError(f"corpus_stats: {name} must be a {str(want)[6:]} (B, T) tensor")
+        if x.device.type != "cuda" or x.device != f0.device:
+            raise ValueError(f"corpus_stats: {name} must be on the GPU, all on one device")
+        if x.shape != f0.shape or not x.is_contiguous():
+            raise ValueError(f"corpus_stats: {name} must be contiguous and of the shape of f0 {tuple(f0.shape)}")
+    if B < 1 or B > 65535 or T < 1:
+        raise ValueError(f"corpus_stats: arrays of shape ({B}, {T}): need 1 .. 65535 utterances and T >= 1")
+    for name, val in (("hop", hop), ("span", span)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"corpus_stats: {name} must be an integer >= 1, got {val!r}")
+    if isinstance(power_floor, bool) or not isinstance(power_floor, numbers.Real) or not math.isfinite(power_floor):
+        raise ValueError(f"corpus_stats: power_floor must be a finite number, got {power_floor!r}")
+    n64 = _check_lengths("corpus_stats", n, B, f0.device)
+    with torch.cuda.device(f0.device):
+        out = torch.empty(B, CORPUS_NSTAT, dtype=torch.float32, device=f0.device)
+        a = make("T2CorpusStats", f0=f0, power=power, jitter=jitter, shimmer=shimmer, nhr=nhr, hnr_db=hnr_db, cycles=cycles, n=n64, B=B,
+                 T=T, hop=hop, S=span, power_floor=float(power_floor), out=out)
+        call("t2_corpus_stats", a, _stream())
+    return out
+
+
 PITCH_MAX_STATES = 4096     # T2_PITCH_MAX_STATES: voiced states (integer lags) of t2_pitch_viterbi
 F0_NSTAT = 12               # T2_F0_NSTAT
 # w: transition cost per octave of lag change; max_jump: the largest allowed change in octaves per frame; u: local cost of the

@@ -1,8 +1,9 @@
 """What came out of a synthesis, measured on the GPU: pitch level and range, intensity, noisiness and speaking rate of a batch of
 waveforms.  The YIN pitch tracker (engine.yin, C-ABI t2_yin) analyses frames on the mel grid - hop 256, frame t
 centred on sample 256 t - and engine.prosody_stats (t2_prosody_stats) reduces every track to one row; this module only packs the
-batch and names the fields.  No jitter / shimmer, no parity with Praat's absolute values: the numbers are for correlating with the
-requested controls (run/correlation.py).  ProsodyMeter(smooth=True) decodes the track with engine.pitch_viterbi, and
+batch and names the fields.  No parity with Praat's absolute values: the numbers are for correlating with the requested controls
+(run/correlation.py).  ProsodyMeter.features adds jitter, shimmer and a noise-to-harmonics ratio by cycle matching
+(engine.voice_quality) and returns the reference's FEATURES_ALL columns: what `main.py prosody-export` writes.  ProsodyMeter(smooth=True) decodes the track with engine.pitch_viterbi, and
 f0_scores compares the tracks of two batches along a warping path (engine.f0_path_stats): what `test --score --f0` reports."""
 from __future__ import annotations
 
@@ -14,6 +15,10 @@ import torch
 from . import engine
 
 MEASURES = ["pitch_mean_log", "pitch_range_log", "intensity_mean_db", "aperiodicity_mean", "rate"]
+# the reference's feature columns (preprocessing/preprocessing_split/normalize.py: FEATURES_ALL), in its order
+FEATURES = ["duration", "duration_vcd", "pitch_mean", "pitch_5", "pitch_95", "pitch_range", "pitch_mean_log", "pitch_5_log",
+            "pitch_95_log", "pitch_range_log", "intensity_mean", "intensity_mean_vcd", "jitter", "shimmer", "nhr", "nhr_vcd", "rate",
+            "rate_vcd"]
 
 
 class ProsodyMeter:
@@ -99,6 +104,48 @@ class ProsodyMeter:
                 intensity_mean_db=row[5] if voiced else None,
                 aperiodicity_mean=row[6] if voiced else None,
                 rate=(int(n_chars[k]) / seconds) if lens[k] > 0 else None))
+        return out
+
+    def features(self, wavs: Sequence[torch.Tensor], n_chars: Sequence[int]) -> List[dict]:
+        """One dict per waveform (as measure() takes them) with n_frames, n_voiced, n_measured and the FEATURES, from the meter's own
+        track (smoothed or not, as the meter was built): duration = samples / sr and duration_vcd = n_voiced hop / sr in seconds;
+        pitch_mean (Hz, over the voiced frames), pitch_5, pitch_95 (nearest-rank percentiles of the track), pitch_range = pitch_95 -
+        pitch_5, and their _log twins - pitch_mean_log = mean ln f0 and pitch_range_log = ln p95 - ln p5, exactly measure()'s,
+        pitch_5_log = ln p5, pitch_95_log = ln p95; intensity_mean = mean 10 log10 of the frame power over the loud frames (power >
+        power_floor), intensity_mean_vcd over the voiced frames (measure()'s intensity_mean_db); jitter, shimmer, nhr = means over
+        the measured frames (engine.voice_quality); rate = n_chars / duration, rate_vcd = n_chars / duration_vcd.  nhr_vcd is a COPY
+        of nhr: every period-based measure here is taken on voiced frames by construction, there is no other kind of nhr.  None where
+        undefined: no voiced frame (pitch_*, intensity_mean_vcd, rate_vcd), no measured frame (jitter, shimmer, nhr, nhr_vcd), no loud
+        frame (intensity_mean), an empty waveform (rate)."""
+        if len(wavs) != len(n_chars):
+            raise ValueError(f"features: {len(wavs)} waveforms, {len(n_chars)} character counts")
+        if not wavs:
+            return []
+        batch, lens, n_max, n = self._pack("features", wavs)
+        s = self.settings
+        f0, aper, power = self._track(batch, n, n_max)
+        st = engine.prosody_stats(f0, aper, power, n, hop=s["hop"], span=self.span)
+        vq = engine.voice_quality(batch, n, f0, sr=s["sr"], hop=s["hop"], W=s["W"], fmin=s["fmin"], fmax=s["fmax"], n_max=n_max)
+        cs = engine.corpus_stats(f0, power, *vq, n, hop=s["hop"], span=self.span, power_floor=s["power_floor"])
+        st, cs = st.cpu().tolist(), cs.cpu().tolist()
+        out = []
+        for k, (row, c) in enumerate(zip(st, cs)):
+            n_voiced, n_measured, n_loud = int(row[1]), int(c[2]), int(c[3])
+            voiced, measured = n_voiced > 0, n_measured > 0
+            duration, duration_vcd = lens[k] / s["sr"], n_voiced * s["hop"] / s["sr"]
+            nhr = c[7] if measured else None
+            out.append(dict(
+                n_frames=int(row[0]), n_voiced=n_voiced, n_measured=n_measured,
+                duration=duration, duration_vcd=duration_vcd,
+                pitch_mean=c[4] if voiced else None, pitch_5=row[3] if voiced else None, pitch_95=row[4] if voiced else None,
+                pitch_range=(row[4] - row[3]) if voiced else None,
+                pitch_mean_log=row[2] if voiced else None, pitch_5_log=math.log(row[3]) if voiced else None,
+                pitch_95_log=math.log(row[4]) if voiced else None,
+                pitch_range_log=(math.log(row[4]) - math.log(row[3])) if voiced else None,
+                intensity_mean=c[9] if n_loud > 0 else None, intensity_mean_vcd=row[5] if voiced else None,
+                jitter=c[5] if measured else None, shimmer=c[6] if measured else None, nhr=nhr, nhr_vcd=nhr,
+                rate=(int(n_chars[k]) / duration) if lens[k] > 0 else None,
+                rate_vcd=(int(n_chars[k]) / duration_vcd) if voiced else None))
         return out
 
 
