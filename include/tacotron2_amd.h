@@ -924,8 +924,12 @@ int t2_logmel_batch_fwd(const float* wavs, int64_t ld_wav, const int64_t* n_dev,
                         const float* fb, float* padded, float* spec, float* mag, float* tmp, float* mel, int64_t T_out,
                         float* gate, int32_t* mel_len, int n_fft, int hop, int n_mels, void* stream);
 
-/* dropout scale masks (Philox4x32-10, counter = element index) and the optimizer of model/tts_model.py:78-91 +
- * Lightning gradient_clip_val=1.0 (run/train.py:240) on one flat fp32 parameter buffer. */
+/* dropout scale masks and the optimizer of model/tts_model.py:78-91 + Lightning gradient_clip_val=1.0 (run/train.py:240) on one
+ * flat fp32 parameter buffer.
+ * t2_philox_mask: Philox4x32-10, one counter per FOUR elements.  Element e = 4 i + j takes output word j of
+ *   counter (i & 0xffffffff, i >> 32, stream_id & 0xffffffff, stream_id >> 32) under key (seed & 0xffffffff, seed >> 32);
+ *   u = (word >> 8) * 2^-24 in [0, 1);  out[e] = 0 where u < p, else the float quotient 1 / (1 - p) - a tie u == p is kept.
+ *   0 <= p < 1; n = 0 is a no-op.  tests/philox_ref.py states this bit for bit (DESIGN.md 5.13 has the stream-id map). */
 int t2_philox_mask(float* out, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream);
 /* zoneout masks: 1 with probability p, else 0 - no rescaling; the same counter convention (0 <= p <= 1) */
 int t2_philox_bernoulli(float* out, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream);
