@@ -901,6 +901,30 @@ typedef struct {
 int t2_f0_path_stats(const T2F0PathStats* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sample-rate conversion (the reference resamples offline with librosa and pydub, preprocessing/hifi_tts.py:73-78, and its dataset
+ * discards the header's rate, datasets/tts_dataset.py:191; csrc/t2_resample.hip, the rule in DESIGN 5.14, restated in float64 in
+ * tests/resample_ref.py).
+ *
+ * t2_resample: a batched polyphase FIR for the rational ratio U / D in fp32.  x[b*ldx + i] is a padded batch of signals, n_in [B] their
+ *   sample counts (DEVICE array, int64; negative counts as 0).  Row b has n_out[b] = ceil(n_in[b] * U / D) outputs, computed on the
+ *   device and clipped to n_out_max, the caller's bound.  table [U][2K] fp32 holds the filter by phase: column c of row p is tap
+ *   k = c - K + 1, k = -K+1 .. K.  For m < n_out[b], with m * D formed in 64 bits:
+ *     i0 = floor(m * D / U),  p = (m * D) mod U,  y[b*ldy + m] = sum_{k = -K+1 .. K} table[p][k + K - 1] * x[b*ldx + i0 + k],
+ *   one fmaf per tap in ascending k.  A sample outside [0, n_in[b]) counts as zero and is never loaded; for n_out[b] <= m < ldy the
+ *   kernel writes 0.0f (t2_logmel_batch_fwd wants rows zero-filled behind their utterance).  Nothing behind ldy is written.
+ *   One 256-thread workgroup per 1024 consecutive outputs of one row, their input span, at most 1023 D / U + 2K + 2 floats, staged once
+ *   in dynamic LDS (up to 64 KB; a longer span is read from global memory, the same sum), the table read from global memory.  No
+ *   atomics, a fixed order: two calls give bit-identical outputs, and a row's outputs do not depend on B, ldx, ldy or the other rows.
+ *   T2_ERR_ARG before any launch: a null pointer, B < 1 or > 65535, U, D or K < 1, U * 2K > 2^20, n_out_max < 0, ldy < n_out_max. */
+typedef struct {
+    const float* x; int64_t ldx; const int64_t* n_in;   /* [B] device; rows are read only in [0, n_in[b]) */
+    float* y; int64_t ldy; int64_t n_out_max;           /* y[b][m] for m < ldy */
+    const float* table; int U, D, K;                    /* [U][2K] fp32, tap k = -K+1 .. K of phase p */
+    int B;
+} T2Resample;
+int t2_resample(const T2Resample* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

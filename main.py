@@ -171,8 +171,11 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
               help="Write character timestamps as JSON: per text the encoded symbols, the mel frames each one lasts (the best "
                    "monotonic path through the decode's own alignments), start_s / end_s, focus_rate and feasible. Default: off.")
 @stop_threshold_option
+@click.option("--out-sample-rate", required=False, type=click.IntRange(min=1), default=None, metavar="R",
+              help="Write the audio at R Hz (48000, 44100, 16000, 8000, ...) instead of the model's rate: the vocoded waveform is "
+                   "resampled on the GPU. Needs a .wav target; --durations-out times stay in model frames. Default: the model's rate.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
-        forward_attention, durations_out=None, stop_threshold=None):
+        forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None):
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for speech!")
@@ -182,7 +185,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
            extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, text=text, output=out,
            speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
            description=description, attention_window=attention_window, forward_attention=forward_attention,
-           durations_out=durations_out, stop_threshold=stop_threshold)
+           durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate)
 
 
 @main.command()

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .logmel import TacotronMelSpectrogram
+from .resample import Resampler, plan as plan_resample
 from .text import ALLOWED_CHARS, TextEncoder
 
 
@@ -68,7 +69,7 @@ class TTSDataset(torch.utils.data.Dataset):
                  trim: bool = True, trim_top_db: int = 60, trim_frame_length: int = 2048, expand_abbreviations=False,
                  include_text=False, include_filename=False, num_mels: int = 80, cache=False, cache_dir=None,
                  description_embeddings: Optional[List[Optional[str]]] = None, description_embeddings_dim: int = 768,
-                 sample_rate: int = 22050, device="cuda:0", **_ignored):
+                 sample_rate: int = 22050, resample: bool = True, device="cuda:0", **_ignored):
         assert (cache and cache_dir is not None) or not cache, "If caching spectrograms, a cache directory is required"
         if cache and not os.path.exists(cache_dir):
             os.makedirs(cache_dir, exist_ok=True)
@@ -82,6 +83,10 @@ class TTSDataset(torch.utils.data.Dataset):
         self.description_embeddings, self.description_embeddings_dim = description_embeddings, description_embeddings_dim
         self.include_text, self.include_filename = include_text, include_filename
         self.melspectrogram = TacotronMelSpectrogram(n_mels=num_mels, sample_rate=sample_rate, device=device)
+        # files at another rate than the model's: trimmed at their own rate, then resampled on the device
+        self.sample_rate, self.resample = int(sample_rate), bool(resample)
+        self.resampler = Resampler(self.sample_rate, device)
+        self._rate_noted, self._rate_lock = False, threading.Lock()
 
     def __len__(self):
         return len(self.filenames)
@@ -98,11 +103,41 @@ class TTSDataset(torch.utils.data.Dataset):
     def cache_path(self, i: int):
         return os.path.join(self.cache_dir, f"{self.filenames[i].replace('/', '_')}.pt") if self.cache else None
 
-    def load_audio(self, i: int) -> np.ndarray:
-        """Decoded, trimmed, silence-padded utterance i as contiguous float32 (datasets/tts_dataset.py:191-202): host work only."""
-        wav, _ = load_wav(os.path.join(self.base_dir, self.filenames[i]))
+    def decode(self, i: int):
+        """(decoded, trimmed utterance i at the FILE's rate, that rate): host work only.  A file at another rate than the model's is
+        trimmed with the frame and the hop scaled by sr_file / sample_rate (rounded: lengths stay host integers), or refused when
+        dataset.preprocessing.resample is false."""
+        path = os.path.join(self.base_dir, self.filenames[i])
+        wav, sr = load_wav(path)
+        if sr == self.sample_rate:
+            if self.trim:
+                wav = trim_silence(wav, self.trim_top_db, self.trim_frame_length)
+            return wav, sr
+        if not self.resample:
+            raise ValueError(f"{path}: sample rate {sr} Hz, the model's is {self.sample_rate} Hz and dataset.preprocessing.resample "
+                             "is false")
+        try:
+            plan_resample(sr, self.sample_rate)         # (host work, cached: a pair beyond the table limit is refused here)
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+        with self._rate_lock:          # (the loader decodes on several threads: ONE line, at the first such file)
+            noted, self._rate_noted = self._rate_noted, True
+        if not noted:
+            print(f"dataset: {self.filenames[i]} is at {sr} Hz, the model at {self.sample_rate} Hz: files at another rate are "
+                  "resampled on the device (dataset.preprocessing.resample)", flush=True)
         if self.trim:
-            wav = trim_silence(wav, self.trim_top_db, self.trim_frame_length)
+            scale = sr / self.sample_rate
+            wav = trim_silence(wav, self.trim_top_db, max(1, int(round(self.trim_frame_length * scale))),
+                               max(1, int(round(512 * scale))))
+        return wav, sr
+
+    def load_audio(self, i: int) -> np.ndarray:
+        """Decoded, trimmed, silence-padded utterance i at the model's rate as contiguous float32 (datasets/tts_dataset.py:191-202):
+        host work only for a file at that rate; any other is resampled on the device (one launch) behind the trim, and the silence
+        is appended behind that, in output samples."""
+        wav, sr = self.decode(i)
+        if sr != self.sample_rate:
+            wav = self.resampler.one(wav, sr)
         if self.silence:
             wav = np.pad(wav, (0, self.silence))
         return np.ascontiguousarray(wav, dtype=np.float32)
@@ -235,8 +270,12 @@ class HostWavBatch:
     integers (frames = 1 + samples // hop: no device value is needed to know the shape).  `set_global_shape` records the
     data-parallel step's global (L, T) (Trainer.negotiate_collated); `to_device` does the copies and the ONE batched log-mel pass."""
 
-    def __init__(self, ds, idxs, wav, n, hit_mels, frames):
+    def __init__(self, ds, idxs, wav, n, hit_mels, frames, rates=None, n_in=None):
         self.ds, self.idxs, self.wav, self.n, self.hit_mels, self.frames = ds, idxs, wav, n, hit_mels, frames
+        # files at another rate than the model's (DESIGN 5.14): rates[b] = the rate of a row that is packed at its OWN rate, n_in[b]
+        # samples of it (None: the row is packed as it goes to the log-mel pass); n[b] is then what the device will make of it
+        self.rates = rates if rates is not None else [None] * len(idxs)
+        self.n_in = n_in if n_in is not None else list(n)
         self.L = max(len(ds.ids[i]) for i in idxs)
         self.T = max(frames)
         self.Lg, self.Tg = self.L, self.T
@@ -244,6 +283,28 @@ class HostWavBatch:
     def set_global_shape(self, Lg: int, Tg: int):
         assert Lg >= self.L and Tg >= self.T
         self.Lg, self.Tg = int(Lg), int(Tg)
+
+    def resampled(self, wav, miss):
+        """The (rows, ld) matrix the log-mel pass takes, from the packed rows `wav` on the device: one t2_resample launch per distinct
+        input rate of the batch, rows already at the model's rate copied through; every row zero behind its n[b] samples (the
+        kernel fills its rows with zeros up to ld, which is where the appended silence comes from)."""
+        ld = (max(self.n[b] for b in miss) + 63) // 64 * 64
+        by_rate = defaultdict(list)
+        for r, b in enumerate(miss):
+            by_rate[self.rates[b]].append(r)
+        if len(by_rate) == 1:          # a corpus at one rate: the kernel's output IS the matrix
+            (rate, rows), = by_rate.items()
+            return self.ds.resampler.batch(wav, [self.n_in[b] for b in miss], rate, ldy=ld)[0]
+        mat = torch.zeros(len(miss), ld, device=wav.device)
+        for rate, rows in sorted(by_rate.items(), key=lambda kv: (kv[0] is not None, kv[0] or 0)):
+            at = torch.tensor(rows, device=wav.device)
+            if rate is None:
+                w = min(ld, wav.shape[1])
+                mat[at, :w] = wav[at, :w]
+            else:
+                out, _ = self.ds.resampler.batch(wav[at], [self.n_in[miss[r]] for r in rows], rate, ldy=ld)
+                mat[at] = out
+        return mat
 
     def to_device(self, dev):
         ds, idxs, B, M = self.ds, self.idxs, len(self.idxs), ds_num_mels(self.ds)
@@ -257,7 +318,10 @@ class HostWavBatch:
         mel = gate = mel_len = None
         if miss:
             n_dev = up(torch.tensor([self.n[b] for b in miss], dtype=torch.int64))
-            mel_m, gate_m, len_m = ds.melspectrogram.batch(up(self.wav), n_dev, max(self.n[b] for b in miss), T_out=self.Tg)
+            wav = up(self.wav)
+            if any(self.rates[b] is not None for b in miss):
+                wav = self.resampled(wav, miss)
+            mel_m, gate_m, len_m = ds.melspectrogram.batch(wav, n_dev, max(self.n[b] for b in miss), T_out=self.Tg)
             if ds.cache:       # side copy for the on-disk cache: leaves through the writer thread once the copy has landed
                 ds.cache_writer().submit([ds.cache_path(idxs[b]) for b in miss], [self.frames[b] for b in miss], mel_m)
             if len(miss) == B:
@@ -359,7 +423,12 @@ class DeviceBatchLoader:
                     return torch.load(cp, weights_only=True)
                 except Exception:       # unreadable entry (e.g. left by a killed run): a cache miss
                     pass
-        return ds.load_audio(i)
+        wav, sr = ds.decode(i)
+        if sr != ds.sample_rate:        # stays at its own rate on the host: (samples, rate), resampled with its batch on the device
+            return np.ascontiguousarray(wav, dtype=np.float32), sr
+        if ds.silence:
+            wav = np.pad(wav, (0, ds.silence))
+        return np.ascontiguousarray(wav, dtype=np.float32)
 
     def host_batch(self, idxs) -> HostWavBatch:
         import time
@@ -368,20 +437,25 @@ class DeviceBatchLoader:
         items = list(self.pool.map(self._load, idxs))
         hit_mels = {b: x for b, x in enumerate(items) if torch.is_tensor(x)}
         miss = [b for b in range(len(idxs)) if b not in hit_mels]
-        n = [0 if b in hit_mels else len(items[b]) for b in range(len(idxs))]
+        # a file at another rate than the model's comes as (samples at its own rate, rate) and is packed so; what the device makes of
+        # it is known here: n = ceil(n_in U / D) + silence, host integers (the data-parallel shape negotiation needs no device value)
+        rates = [items[b][1] if isinstance(items[b], tuple) else None for b in range(len(idxs))]
+        items = [x[0] if isinstance(x, tuple) else x for x in items]
+        n_in = [0 if b in hit_mels else len(items[b]) for b in range(len(idxs))]
+        n = [n_in[b] if rates[b] is None else ds.resampler.out_len(n_in[b], rates[b]) + ds.silence for b in range(len(idxs))]
         frames = [len(hit_mels[b]) if b in hit_mels else 1 + n[b] // hop for b in range(len(idxs))]
         wav = None
         if miss:
             short = [idxs[b] for b in miss if n[b] <= ds.melspectrogram.n_fft // 2]
             assert not short, f"utterances shorter than half an analysis window (reflect padding needs more): {short}"
-            ld = (max(n) + 63) // 64 * 64
+            ld = (max(n_in) + 63) // 64 * 64
             wav = torch.zeros(len(miss), ld, pin_memory=torch.cuda.is_available())
             w = wav.numpy()
             for r, b in enumerate(miss):
-                w[r, :n[b]] = items[b]
+                w[r, :n_in[b]] = items[b]
         self.decode_s += time.perf_counter() - t0
         self.batches += 1
-        return HostWavBatch(ds, list(idxs), wav, n, hit_mels, frames)
+        return HostWavBatch(ds, list(idxs), wav, n, hit_mels, frames, rates, n_in)
 
     def __iter__(self):
         for idxs in self.sampler:

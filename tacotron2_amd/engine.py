@@ -374,6 +374,24 @@ def f0_figures(row) -> dict:
     return out
 
 
+def resample(wav, n, sr_in: int, sr_out: int):
+    """A padded batch brought from sr_in to sr_out Hz (C-ABI t2_resample): wav (B, ld) float32 on the GPU, n the B sample
+    counts (host integers, or an integer tensor, which is read back).  Returns (out (B, ld') float32, zeros behind each row, and the
+    output counts ceil(n sr_out / sr_in) as host integers).  The Kaiser-windowed sinc of datasets/resample.py, designed once per
+    rate pair; sr_in == sr_out returns the input.  Needs no model."""
+    from .datasets.resample import Resampler
+    if not torch.is_tensor(wav) or wav.device.type != "cuda":
+        raise ValueError("resample: wav must be a float32 (B, samples) tensor on the GPU")
+    key = (int(sr_out), wav.device)
+    rs = _RESAMPLERS.get(key)
+    if rs is None:
+        rs = _RESAMPLERS.setdefault(key, Resampler(int(sr_out), wav.device))
+    return rs.batch(wav, n.tolist() if torch.is_tensor(n) else n, int(sr_in))
+
+
+_RESAMPLERS: dict = {}
+
+
 def fill_splits(M: int, N: int, K: int) -> bool:
     return ((M + 127) // 128) * ((N + 127) // 128) < 256 and K >= 1024
 

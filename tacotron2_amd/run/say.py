@@ -64,8 +64,11 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
            description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
            forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
-           stop_threshold: Optional[float] = None):
-    """stop_threshold: 0 < tau < 1, the stop probability below which an utterance ends (Tacotron2.forward); None takes the config's
+           stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None):
+    """out_sample_rate: R Hz - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is resampled from the model's
+    rate to R on the device (datasets/resample.py) before it is written, and the header carries R; `durations_out`
+    times stay in model frames.  None: the model's rate, nothing changes.
+    stop_threshold: 0 < tau < 1, the stop probability below which an utterance ends (Tacotron2.forward); None takes the config's
     `model.stop_threshold` if there is one, else 0.5, the reference's rule.
     durations_out: a path - character timestamps of the decode are written there as a JSON list with one object per text:
     `symbols` (the encoded sequence, end token included), `frames` per symbol (the monotonic path through the decode's own
@@ -74,6 +77,14 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
+    to_rate = None
+    if out_sample_rate is not None:
+        if hifi_gan_checkpoint is None and not output.endswith(".wav"):
+            raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
+        from ..datasets.resample import Resampler, plan
+        plan(int(pre.get("sample_rate", 22050)), int(out_sample_rate))      # (refuses a bad rate before anything is decoded)
+        resampler = Resampler(int(out_sample_rate), dev)
+        to_rate = lambda wav, sr: torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     ids = [torch.tensor(enc.encode(t), dtype=torch.int64) for t in texts]
@@ -125,7 +136,10 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         for i, m in enumerate(mels):
             wav = gen(torch.from_numpy(np.ascontiguousarray(m.T)).to(dev))[0, 0].cpu()
             name = output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav"
-            write_wav(name, wav, sr)
+            if to_rate is not None:
+                write_wav(name, to_rate(wav, sr), int(out_sample_rate))
+            else:
+                write_wav(name, wav, sr)
         return mels
     if output.endswith(".wav"):
         from ..vocoder import GriffinLim, write_wav
@@ -133,7 +147,11 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         gl = GriffinLim(n_mels=post.shape[2], sample_rate=sr, device=dev)
         for i, m in enumerate(mels):
             name = output if isinstance(text, str) else f"{output[:-4]}_{i}.wav"
-            write_wav(name, gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0)), sr)
+            wav = gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0))
+            if to_rate is not None:
+                write_wav(name, to_rate(wav, sr), int(out_sample_rate))
+            else:
+                write_wav(name, wav, sr)
         return mels
     np.save(output, mels[0] if isinstance(text, str) else np.array(mels, dtype=object), allow_pickle=not isinstance(text, str))
     return mels

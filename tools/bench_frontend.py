@@ -6,7 +6,9 @@ model, 16-bit PCM at 22.05 kHz), then, at batch 32 and vanilla dims, times
   * K training steps fed by the loader - cache off (the shipped configs' setting), cache cold (first epoch, entries written by the side
     copy), cache warm (every utterance from the cache), and the item-at-a-time loader (training.loader = "items");
   * the SAME K batches replayed from device memory (no loader at all): the reference point.
-usage: python tools/bench_frontend.py [--utterances 1536] [--steps 40] [--out profiles/r05_frontend_throughput.txt]"""
+--wav-rate R writes the same corpus at R Hz instead (each utterance as long in seconds, so R / 22050 as many samples): the loader then
+resamples every batch on the device, and the figures are to be read against the same tool's run at 22050.
+usage: python tools/bench_frontend.py [--utterances 1536] [--steps 40] [--wav-rate 24000] [--out profiles/r05_frontend_throughput.txt]"""
 import argparse, os, shutil, sys, tempfile, time, wave
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,8 +28,9 @@ def make_manifest(root, n_utt, sr=22050, seed=1234):
         ell = int(np.clip(round(rng.normal(101, 33.6)), 13, 188))
         t = int(np.clip(round(5.68 * ell + rng.normal(0, 54)), 99, 872))
         n = (t - 1) * 256 + int(rng.integers(0, 256)) - 512            # (512 samples of silence are appended by the dataset)
+        n = n * sr // 22050                                            # (as long in seconds at any rate)
         x = (rng.standard_normal(n) * 0.1).astype(np.float32)
-        head, tail = int(rng.integers(0, 4000)), int(rng.integers(0, 4000))
+        head, tail = int(rng.integers(0, 4000)) * sr // 22050, int(rng.integers(0, 4000)) * sr // 22050
         x = np.concatenate([np.zeros(head, np.float32), x, np.zeros(tail, np.float32)])
         with wave.open(os.path.join(root, f"u{i}.wav"), "wb") as w:
             w.setnchannels(1); w.setsampwidth(2); w.setframerate(sr); w.writeframes((x * 32767).astype("<i2").tobytes())
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--decode-threads", type=int, default=4)
+    ap.add_argument("--wav-rate", type=int, default=22050, help="sample rate of the generated corpus (the model's stays 22050)")
+    ap.add_argument("--cases", default="off,cold,warm,items", help="training cases to run: cache off / cold / warm, items")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import bench
@@ -58,8 +63,8 @@ def main():
         print(s, flush=True); lines.append(s)
     try:
         t0 = time.time()
-        files, texts = make_manifest(os.path.join(tmp, "wavs"), args.utterances)
-        say(f"# manifest: {args.utterances} noise WAVs (LJSpeech-shaped durations, 16-bit PCM 22.05 kHz) written in {time.time() - t0:.1f} s; "
+        files, texts = make_manifest(os.path.join(tmp, "wavs"), args.utterances, sr=args.wav_rate)
+        say(f"# manifest: {args.utterances} noise WAVs (LJSpeech-shaped durations, 16-bit PCM {args.wav_rate / 1000:g} kHz) written in {time.time() - t0:.1f} s; "
             f"batch {args.batch}, {args.steps} timed steps per case, vanilla dims, fp32, {args.decode_threads} decode threads, "
             f"{len(os.sched_getaffinity(0))} host cores")
         dims = dict(bench.VANILLA, speaker_tokens=False, num_speakers=1)
@@ -117,12 +122,17 @@ def main():
             return dt / len(kept), dr / len(kept)
 
         say("# case                               fed by the loader                     | replay (no loader)                     | replay / loader time")
-        run("batched", False, "batched loader, cache off")
-        run("batched", True, "batched loader, cache cold")
-        n_cached = len(os.listdir(os.path.join(tmp, "cache")))
-        run("batched", True, f"batched loader, cache warm*")
-        say(f"#   (* {n_cached} of {args.utterances} utterances were in the cache when the warm run started)")
-        run("items", False, "item-at-a-time loader, cache off")
+        cases = args.cases.split(",")
+        if "off" in cases:
+            run("batched", False, "batched loader, cache off")
+        if "cold" in cases:
+            run("batched", True, "batched loader, cache cold")
+        if "warm" in cases:
+            n_cached = len(os.listdir(os.path.join(tmp, "cache"))) if os.path.isdir(os.path.join(tmp, "cache")) else 0
+            run("batched", True, f"batched loader, cache warm*")
+            say(f"#   (* {n_cached} of {args.utterances} utterances were in the cache when the warm run started)")
+        if "items" in cases:
+            run("items", False, "item-at-a-time loader, cache off")
         tr.engine.check_persistent_kernels()
         if args.out:
             with open(args.out, "w") as f:
