@@ -24,7 +24,12 @@ import torch
 
 from . import _lib
 from . import guard as _guard
+from . import _args
 from ._lib import call, make
+# the documented module API: the model-free measurements live in analysis, and engine.<name> is the same object
+from .analysis import (CORPUS_NSTAT, F0_NSTAT, PITCH_MAX_STATES, PROSODY_MAX_T, PROSODY_NSTAT, VITERBI_DEFAULTS, VQ_MAX_CYCLES,  # noqa: F401
+                       YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, f0_figures, f0_path_stats, pitch_viterbi, prosody_stats,
+                       resample, voice_quality, yin, yin_lags)
 from .params import ParamStore, reduction_factor
 
 KL, KPAD = 31, 15
@@ -73,323 +78,6 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, alpha=1.0, bias=None, bi
              splitk=splitk, batch=batch, sA=sA, sB=sB, sC=sC, share_cu=getattr(_TLS, "share_cu", 0), native_fp32=GEMM_NATIVE_FP32[0],
              precision=GEMM_PRECISION[0], a_tap_len=a_tap_len, a_tap_stride=a_tap_stride, stat_out=stat_out, stat_Lp=stat_Lp, stat_L=stat_L)
     call("t2_gemm", g, _stream())
-
-
-YIN_MAX_SPAN = 4096         # T2_YIN_MAX_SPAN: W + tau_max floats of one frame's span in LDS
-PROSODY_MAX_T = 4096        # T2_PROSODY_MAX_T: frames of one utterance in t2_prosody_stats
-PROSODY_NSTAT = 8           # T2_PROSODY_NSTAT
-YIN_DEFAULTS = dict(sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=0.3, power_floor=1e-10)
-
-
-def yin_lags(sr: int, fmin: float, fmax: float):
-    """(tau_min, tau_max) of a pitch range in Hz: sr // fmax and sr // fmin (22050, 60, 500 -> 44, 367)."""
-    if not (isinstance(sr, int) and not isinstance(sr, bool) and sr >= 1):
-        raise ValueError(f"yin: sr must be an integer >= 1, got {sr!r}")
-    if not (math.isfinite(fmin) and math.isfinite(fmax) and 0 < fmin < fmax):
-        raise ValueError(f"yin: need 0 < fmin < fmax, got fmin = {fmin!r}, fmax = {fmax!r}")
-    return int(sr // fmax), int(sr // fmin)
-
-
-def _check_lengths(fn: str, n, B: int, dev):
-    if not torch.is_tensor(n) or n.device != dev:
-        raise ValueError(f"{fn}: n must be a tensor on the device of the signals, {dev}")
-    if n.dim() != 1 or n.shape[0] != B or n.is_floating_point() or n.dtype == torch.bool:
-        raise ValueError(f"{fn}: n must be {B} integers")
-    return n.to(torch.int64).contiguous()
-
-
-def yin(wav, n, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=0.3, power_floor=1e-10, n_max=None,
-        return_cmnd=False):
-    """The YIN pitch tracker on the mel grid (C-ABI t2_yin) of a padded batch wav (B, ld) float32 on the GPU with the
-    sample counts n (B,) integers on the same device: (f0 Hz, aperiodicity, power), each (B, T) float32 with T = 1 + n_max // hop,
-    and the normalised difference (B, T, tau_max + 1) with return_cmnd.  n_max (default: ld) is the largest count; nothing at or
-    behind n[b] is read.  Frame t is centred on sample t * hop and needs W + tau_max samples around it: a frame whose span leaves
-    [0, n[b]) is invalid and comes back as f0 0, aperiodicity 1, power 0; f0 is 0 for an unvoiced frame.  Needs no model."""
-    if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype != torch.float32:
-        raise ValueError("yin: wav must be a float32 (B, samples) tensor")
-    if wav.device.type != "cuda":
-        raise ValueError(f"yin: wav must be on the GPU, got {wav.device}")
-    B, ld = wav.shape
-    if B < 1 or B > 65535:
-        raise ValueError(f"yin: batch of {B}, outside 1 .. 65535")
-    if ld > 1 and wav.stride(1) != 1:
-        raise ValueError("yin: the last dimension of wav must be contiguous")
-    n_max = ld if n_max is None else int(n_max)
-    ld_wav = wav.stride(0) if B > 1 else max(ld, 1)
-    if not 0 <= n_max <= ld or (B > 1 and ld_wav < n_max):
-        raise ValueError(f"yin: n_max = {n_max} outside 0 .. {ld}, the row length of wav (row stride {ld_wav})")
-    n64 = _check_lengths("yin", n, B, wav.device)
-    for name, val in (("hop", hop), ("W", W)):
-        if isinstance(val, bool) or not isinstance(val, int):
-            raise ValueError(f"yin: {name} must be an integer, got {val!r}")
-    tau_min, tau_max = yin_lags(sr, fmin, fmax)
-    if hop < 1 or W < 16:
-        raise ValueError(f"yin: need hop >= 1 and W >= 16, got hop = {hop}, W = {W}")
-    if tau_min < 2 or tau_max <= tau_min + 1:
-        raise ValueError(f"yin: lags {tau_min} .. {tau_max} of {fmin} .. {fmax} Hz at {sr} Hz: need tau_min >= 2 and "
-                         "tau_max > tau_min + 1")
-    if W + tau_max > YIN_MAX_SPAN:
-        raise ValueError(f"yin: W + tau_max = {W + tau_max} samples per frame, above the limit of {YIN_MAX_SPAN} (T2_YIN_MAX_SPAN)")
-    for name, val in (("thr", thr), ("vthr", vthr), ("power_floor", power_floor)):
-        if not isinstance(val, numbers.Real) or not math.isfinite(val):
-            raise ValueError(f"yin: {name} must be a finite number, got {val!r}")
-    T = 1 + n_max // hop
-    with torch.cuda.device(wav.device):
-        f0, aper, power = (torch.empty(B, T, dtype=torch.float32, device=wav.device) for _ in range(3))
-        cmnd = torch.empty(B, T, tau_max + 1, dtype=torch.float32, device=wav.device) if return_cmnd else None
-        a = make("T2Yin", wav=wav, ld_wav=ld_wav, n=n64, B=B, n_max=n_max, sr=sr, hop=hop, W=W, tau_min=tau_min, tau_max=tau_max,
-                 thr=float(thr), vthr=float(vthr), power_floor=float(power_floor), f0=f0, aper=aper, power=power, cmnd=cmnd)
-        call("t2_yin", a, _stream())
-    return (f0, aper, power, cmnd) if return_cmnd else (f0, aper, power)
-
-
-def prosody_stats(f0, aper, power, n, hop=256, span=1024 + 367):
-    """Per-utterance statistics (C-ABI t2_prosody_stats) of yin's (B, T) outputs, with n, hop and span = W + tau_max of that call:
-    (B, 8) float32 rows [valid frames, voiced frames, mean ln f0, p5 Hz, p95 Hz, mean 10 log10 power, mean aperiodicity, 0], means
-    and percentiles over the voiced frames (NaN without one); the percentiles are elements of the track, nearest rank."""
-    for name, x in (("f0", f0), ("aper", aper), ("power", power)):
-        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
-            raise ValueError(f"prosody_stats: {name} must be a float32 (B, T) tensor")
-        if x.device.type != "cuda" or x.device != f0.device:
-            raise ValueError(f"prosody_stats: {name} must be on the GPU, all three on one device")
-        if x.shape != f0.shape or not x.is_contiguous():
-            raise ValueError(f"prosody_stats: {name} must be contiguous and of the shape of f0 {tuple(f0.shape)}")
-    B, T = f0.shape
-    if B < 1 or B > 65535:
-        raise ValueError(f"prosody_stats: batch of {B}, outside 1 .. 65535")
-    if T < 1 or T > PROSODY_MAX_T:
-        raise ValueError(f"prosody_stats: {T} frames, outside 1 .. {PROSODY_MAX_T} (T2_PROSODY_MAX_T)")
-    for name, val in (("hop", hop), ("span", span)):
-        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
-            raise ValueError(f"prosody_stats: {name} must be an integer >= 1, got {val!r}")
-    n64 = _check_lengths("prosody_stats", n, B, f0.device)
-    with torch.cuda.device(f0.device):
-        out = torch.empty(B, PROSODY_NSTAT, dtype=torch.float32, device=f0.device)
-        a = make("T2ProsodyStats", f0=f0, aper=aper, power=power, n=n64, B=B, T=T, hop=hop, S=span, out=out)
-        call("t2_prosody_stats", a, _stream())
-    return out
-
-
-VQ_MAX_CYCLES = 32          # T2_VQ_MAX_CYCLES: cycles matched per frame in t2_voice_quality
-CORPUS_NSTAT = 12           # T2_CORPUS_NSTAT
-
-
-def voice_quality(wav, n, f0, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, n_max=None, return_cycles=False):
-    """Jitter, shimmer and harmonicity per frame by cycle matching (C-ABI t2_voice_quality): wav (B, ld) float32, n (B,)
-    and n_max as yin takes them, with the same sr, hop, W, fmin, fmax, and f0 (B, T) float32 - yin's track or pitch_viterbi's, 0 =
-    unvoiced.  A valid frame (yin's rule) with f0 > 0 holds K = min((S - 2 L - d) // L + 1, 32) cycles of L = round(sr / f0) samples
-    and is measured iff K >= 3.  (jitter, shimmer, nhr, hnr_db float32, cycles int32), each (B, T); every frame that is not measured
-    has 0 in all five.  With return_cycles also (B, T, 32, 3) float32: period, correlation and RMS amplitude of every cycle, zeros
-    behind the K-th.  Needs no model."""
-    if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype != torch.float32:
-        raise ValueError("voice_quality: wav must be a float32 (B, samples) tensor")
-    if wav.device.type != "cuda":
-        raise ValueError(f"voice_quality: wav must be on the GPU, got {wav.device}")
-    B, ld = wav.shape
-    if B < 1 or B > 65535:
-        raise ValueError(f"voice_quality: batch of {B}, outside 1 .. 65535")
-    if ld > 1 and wav.stride(1) != 1:
-        raise ValueError("voice_quality: the last dimension of wav must be contiguous")
-    n_max = ld if n_max is None else int(n_max)
-    ld_wav = wav.stride(0) if B > 1 else max(ld, 1)
-    if not 0 <= n_max <= ld or (B > 1 and ld_wav < n_max):
-        raise ValueError(f"voice_quality: n_max = {n_max} outside 0 .. {ld}, the row length of wav (row stride {ld_wav})")
-    n64 = _check_lengths("voice_quality", n, B, wav.device)
-    for name, val in (("hop", hop), ("W", W)):
-        if isinstance(val, bool) or not isinstance(val, int):
-            raise ValueError(f"voice_quality: {name} must be an integer, got {val!r}")
-    try:
-        tau_min, tau_max = yin_lags(sr, fmin, fmax)
-    except ValueError as e:
-        raise ValueError("voice_quality" + str(e)[3:]) from None
-    if hop < 1 or W < 16:
-        raise ValueError(f"voice_quality: need hop >= 1 and W >= 16, got hop = {hop}, W = {W}")
-    if tau_min < 2 or tau_max <= tau_min + 1:
-        raise ValueError(f"voice_quality: lags {tau_min} .. {tau_max} of {fmin} .. {fmax} Hz at {sr} Hz: need tau_min >= 2 and "
-                         "tau_max > tau_min + 1")
-    if W + tau_max > YIN_MAX_SPAN:
-        raise ValueError(f"voice_quality: W + tau_max = {W + tau_max} samples per frame, above the limit of {YIN_MAX_SPAN} "
-                         "(T2_YIN_MAX_SPAN)")
-    T = 1 + n_max // hop
-    if not torch.is_tensor(f0) or f0.dtype != torch.float32 or f0.device != wav.device or tuple(f0.shape) != (B, T) \
-            or not f0.is_contiguous():
-        raise ValueError(f"voice_quality: f0 must be a contiguous float32 ({B}, {T}) tensor on {wav.device}")
-    with torch.cuda.device(wav.device):
-        jitter, shimmer, nhr, hnr_db = (torch.empty(B, T, dtype=torch.float32, device=wav.device) for _ in range(4))
-        cycles = torch.empty(B, T, dtype=torch.int32, device=wav.device)
-        cyc = torch.empty(B, T, VQ_MAX_CYCLES, 3, dtype=torch.float32, device=wav.device) if return_cycles else None
-        a = make("T2VoiceQuality", wav=wav, ld_wav=ld_wav, n=n64, B=B, n_max=n_max, sr=sr, hop=hop, W=W, tau_min=tau_min, tau_max=tau_max,
-                 f0=f0, jitter=jitter, shimmer=shimmer, nhr=nhr, hnr_db=hnr_db, cycles=cycles, cyc=cyc)
-        call("t2_voice_quality", a, _stream())
-    return (jitter, shimmer, nhr, hnr_db, cycles, cyc) if return_cycles else (jitter, shimmer, nhr, hnr_db, cycles)
-
-
-def corpus_stats(f0, power, jitter, shimmer, nhr, hnr_db, cycles, n, hop=256, span=1024 + 367, power_floor=1e-10):
-    """Per-utterance means (C-ABI t2_corpus_stats) of yin's f0 (or pitch_viterbi's) and power and of voice_quality's five (B, T) arrays,
-    with n, hop and span = W + tau_max of those calls: (B, 12) float32 rows [valid, voiced, measured, loud frames, mean f0 Hz over the
-    voiced frames, mean jitter, shimmer, nhr, hnr_db over the measured frames, mean 10 log10 power over the loud frames (valid and
-    power > power_floor), 0, 0].  A mean over no frame is 0."""
-    B, T = (f0.shape if torch.is_tensor(f0) and f0.dim() == 2 else (0, 0))
-    for name, x in (("f0", f0), ("power", power), ("jitter", jitter), ("shimmer", shimmer), ("nhr", nhr), ("hnr_db", hnr_db),
-                    ("cycles", cycles)):
-        want = torch.int32 if name == "cycles" else torch.float32
-        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != want:
-            raise ValueError(f"corpus_stats: {name} must be a {str(want)[6:]} (B, T) tensor")
-        if x.device.type != "cuda" or x.device != f0.device:
-            raise ValueError(f"corpus_stats: {name} must be on the GPU, all on one device")
-        if x.shape != f0.shape or not x.is_contiguous():
-            raise ValueError(f"corpus_stats: {name} must be contiguous and of the shape of f0 {tuple(f0.shape)}")
-    if B < 1 or B > 65535 or T < 1:
-        raise ValueError(f"corpus_stats: arrays of shape ({B}, {T}): need 1 .. 65535 utterances and T >= 1")
-    for name, val in (("hop", hop), ("span", span)):
-        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
-            raise ValueError(f"corpus_stats: {name} must be an integer >= 1, got {val!r}")
-    if isinstance(power_floor, bool) or not isinstance(power_floor, numbers.Real) or not math.isfinite(power_floor):
-        raise ValueError(f"corpus_stats: power_floor must be a finite number, got {power_floor!r}")
-    n64 = _check_lengths("corpus_stats", n, B, f0.device)
-    with torch.cuda.device(f0.device):
-        out = torch.empty(B, CORPUS_NSTAT, dtype=torch.float32, device=f0.device)
-        a = make("T2CorpusStats", f0=f0, power=power, jitter=jitter, shimmer=shimmer, nhr=nhr, hnr_db=hnr_db, cycles=cycles, n=n64, B=B,
-                 T=T, hop=hop, S=span, power_floor=float(power_floor), out=out)
-        call("t2_corpus_stats", a, _stream())
-    return out
-
-
-PITCH_MAX_STATES = 4096     # T2_PITCH_MAX_STATES: voiced states (integer lags) of t2_pitch_viterbi
-F0_NSTAT = 12               # T2_F0_NSTAT
-# w: transition cost per octave of lag change; max_jump: the largest allowed change in octaves per frame; u: local cost of the
-# unvoiced state (YIN's voicing threshold: a frame whose best lag is worse than that is cheaper unvoiced); c_sw: a voicing switch
-VITERBI_DEFAULTS = dict(w=1.0, max_jump=0.25, u=YIN_DEFAULTS["vthr"], c_sw=0.15)
-
-
-def pitch_viterbi(cmnd, power, n, sr=22050, hop=256, fmin=60.0, fmax=500.0, power_floor=1e-10, w=1.0, max_jump=0.25,
-                  u=VITERBI_DEFAULTS["u"], c_sw=0.15):
-    """The cheapest lag sequence through yin's normalised difference (C-ABI t2_pitch_viterbi): cmnd (B, T, tau_max + 1)
-    and power (B, T) as yin(return_cmnd=True) of the same sr, hop, fmin, fmax gives them, n (B,) the sample counts - the first
-    min(T, 1 + n[b] // hop) frames are decoded.  States are the integer lags tau_min .. tau_max - 1 and one unvoiced state; a lag
-    costs its cmnd (nothing voiced where power <= power_floor), the unvoiced state u, a lag change w * |log2 ratio| and at most
-    max_jump octaves per frame, a voicing switch c_sw.  (f0 Hz, aperiodicity, lag int32, each (B, T); cost float64 (B,)): f0 and lag
-    0, aperiodicity 1 for an unvoiced frame and behind the decoded frames.  Needs no model."""
-    if not torch.is_tensor(cmnd) or cmnd.dim() != 3 or cmnd.dtype != torch.float32:
-        raise ValueError("pitch_viterbi: cmnd must be a float32 (B, T, tau_max + 1) tensor")
-    if cmnd.device.type != "cuda":
-        raise ValueError(f"pitch_viterbi: cmnd must be on the GPU, got {cmnd.device}")
-    B, T, NT = cmnd.shape
-    if B < 1 or B > 65535:
-        raise ValueError(f"pitch_viterbi: batch of {B}, outside 1 .. 65535")
-    if T < 1 or T > PROSODY_MAX_T:
-        raise ValueError(f"pitch_viterbi: {T} frames, outside 1 .. {PROSODY_MAX_T} (T2_PROSODY_MAX_T)")
-    if not torch.is_tensor(power) or power.dtype != torch.float32 or power.device != cmnd.device or power.shape != (B, T) \
-            or not power.is_contiguous():
-        raise ValueError(f"pitch_viterbi: power must be a contiguous float32 ({B}, {T}) tensor on {cmnd.device}")
-    if isinstance(hop, bool) or not isinstance(hop, int) or hop < 1:
-        raise ValueError(f"pitch_viterbi: hop must be an integer >= 1, got {hop!r}")
-    try:
-        tau_min, tau_max = yin_lags(sr, fmin, fmax)
-    except ValueError as e:
-        raise ValueError("pitch_viterbi" + str(e)[3:]) from None
-    if tau_min < 2 or tau_max <= tau_min + 1:
-        raise ValueError(f"pitch_viterbi: lags {tau_min} .. {tau_max} of {fmin} .. {fmax} Hz at {sr} Hz: need tau_min >= 2 and "
-                         "tau_max > tau_min + 1")
-    N = tau_max - tau_min
-    if N > PITCH_MAX_STATES:
-        raise ValueError(f"pitch_viterbi: {N} lags, above the limit of {PITCH_MAX_STATES} (T2_PITCH_MAX_STATES)")
-    if NT != tau_max + 1:
-        raise ValueError(f"pitch_viterbi: cmnd has {NT} lags per frame, {fmin} .. {fmax} Hz at {sr} Hz need tau_max + 1 = {tau_max + 1}")
-    if NT > 1 and cmnd.stride(2) != 1:
-        raise ValueError("pitch_viterbi: the last dimension of cmnd must be contiguous")
-    ld_t = cmnd.stride(1) if T > 1 else NT
-    ld_b = cmnd.stride(0) if B > 1 else (T - 1) * ld_t + NT
-    if ld_t < NT or ld_b < (T - 1) * ld_t + NT:
-        raise ValueError(f"pitch_viterbi: overlapping strides of cmnd {tuple(cmnd.stride())}")
-    for name, val in (("w", w), ("max_jump", max_jump), ("u", u), ("c_sw", c_sw)):
-        if isinstance(val, bool) or not isinstance(val, numbers.Real) or not math.isfinite(val) or val < 0:
-            raise ValueError(f"pitch_viterbi: {name} must be a finite number >= 0, got {val!r}")
-    if isinstance(power_floor, bool) or not isinstance(power_floor, numbers.Real) or not math.isfinite(power_floor):
-        raise ValueError(f"pitch_viterbi: power_floor must be a finite number, got {power_floor!r}")
-    n64 = _check_lengths("pitch_viterbi", n, B, cmnd.device)
-    with torch.cuda.device(cmnd.device):
-        dev = cmnd.device
-        frames = (1 + torch.div(n64.clamp(min=0), hop, rounding_mode="floor")).clamp(max=T).to(torch.int32)
-        lw = (float(w) * torch.log2(torch.arange(tau_min, tau_max, dtype=torch.float64))).to(dev)     # built on the host
-        f0, aper = (torch.empty(B, T, dtype=torch.float32, device=dev) for _ in range(2))
-        lag = torch.empty(B, T, dtype=torch.int32, device=dev)
-        cost = torch.empty(B, dtype=torch.float64, device=dev)
-        back = torch.empty(B, T, N + 1, dtype=torch.int16, device=dev)       # (the kernel's uint16 workspace)
-        a = make("T2PitchViterbi", cmnd=cmnd, ld_b=ld_b, ld_t=ld_t, power=power, len=frames, lw=lw, B=B, T=T, sr=sr, tau_min=tau_min,
-                 tau_max=tau_max, power_floor=float(power_floor), trans_max=float(w) * float(max_jump), u=float(u), c_sw=float(c_sw),
-                 f0=f0, aper=aper, lag=lag, cost=cost, back=back)
-        call("t2_pitch_viterbi", a, _stream())
-    return f0, aper, lag, cost
-
-
-def f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=256, span=1024 + 367):
-    """Two pitch tracks compared along a warping path (C-ABI t2_f0_path_stats): path (B, P, 2) int32 and path_len (B,) as
-    Engine.dtw(return_path=True) gives them - cell (i, j) pairs frame i of f0_a (B, Ta) with frame j of f0_b (B, Tb), Hz, 0 =
-    unvoiced -, n_a and n_b the sample counts, hop and span = W + tau_max of the yin call (the validity rule of prosody_stats; cells
-    outside a track count as invalid).  (B, 12) float64 rows [scored cells, both voiced, only a voiced, only b voiced, sum d, sum d^2
-    with d = 1200 (log2 fa - log2 fb) cents over the both-voiced cells, sum la, sum lb, sum la^2, sum lb^2, sum la lb with la =
-    log2 fa, 0]; f0_figures turns a row into RMSE, bias, correlation and voicing error."""
-    if not torch.is_tensor(path) or path.dim() != 3 or path.shape[2] != 2 or path.dtype != torch.int32 or not path.is_contiguous():
-        raise ValueError("f0_path_stats: path must be a contiguous int32 (B, P, 2) tensor")
-    if path.device.type != "cuda":
-        raise ValueError(f"f0_path_stats: path must be on the GPU, got {path.device}")
-    B, P, _ = path.shape
-    if B < 1 or B > 65535 or P < 1:
-        raise ValueError(f"f0_path_stats: path of shape {tuple(path.shape)}: need 1 .. 65535 pairs and P >= 1")
-    if not torch.is_tensor(path_len) or path_len.dtype != torch.int32 or path_len.device != path.device or path_len.shape != (B,):
-        raise ValueError(f"f0_path_stats: path_len must be {B} int32 on {path.device}")
-    for name, x in (("f0_a", f0_a), ("f0_b", f0_b)):
-        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device != path.device or x.shape[0] != B \
-                or x.shape[1] < 1 or not x.is_contiguous():
-            raise ValueError(f"f0_path_stats: {name} must be a contiguous float32 ({B}, T >= 1) tensor on {path.device}")
-    for name, val in (("hop", hop), ("span", span)):
-        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
-            raise ValueError(f"f0_path_stats: {name} must be an integer >= 1, got {val!r}")
-    na64 = _check_lengths("f0_path_stats", n_a, B, path.device)
-    nb64 = _check_lengths("f0_path_stats", n_b, B, path.device)
-    with torch.cuda.device(path.device):
-        out = torch.empty(B, F0_NSTAT, dtype=torch.float64, device=path.device)
-        a = make("T2F0PathStats", path=path, path_len=path_len.contiguous(), f0_a=f0_a, f0_b=f0_b, n_a=na64, n_b=nb64, B=B, P=P,
-                 Ta=f0_a.shape[1], Tb=f0_b.shape[1], hop=hop, S=span, out=out)
-        call("t2_f0_path_stats", a, _stream())
-    return out
-
-
-def f0_figures(row) -> dict:
-    """The figures of one f0_path_stats row (12 numbers): n_pairs, n_voiced_both, f0_rmse_cents, f0_bias_cents (a minus b), f0_corr
-    (Pearson of log2 f0; None with fewer than 2 both-voiced cells or a column without variance), vuv_error = (only a + only b) /
-    scored.  None where undefined."""
-    n, nb = int(row[0]), int(row[1])
-    out = dict(n_pairs=n, n_voiced_both=nb, f0_rmse_cents=None, f0_bias_cents=None, f0_corr=None, vuv_error=None)
-    if n > 0:
-        out["vuv_error"] = (row[2] + row[3]) / n
-    if nb > 0:
-        out["f0_rmse_cents"] = math.sqrt(max(row[5], 0.0) / nb)
-        out["f0_bias_cents"] = row[4] / nb
-    if nb >= 2:
-        va, vb = row[8] - row[6] * row[6] / nb, row[9] - row[7] * row[7] / nb
-        if va > 1e-12 * row[8] and vb > 1e-12 * row[9]:      # (a constant column leaves rounding noise, not variance)
-            out["f0_corr"] = (row[10] - row[6] * row[7] / nb) / math.sqrt(va * vb)
-    return out
-
-
-def resample(wav, n, sr_in: int, sr_out: int):
-    """A padded batch brought from sr_in to sr_out Hz (C-ABI t2_resample): wav (B, ld) float32 on the GPU, n the B sample
-    counts (host integers, or an integer tensor, which is read back).  Returns (out (B, ld') float32, zeros behind each row, and the
-    output counts ceil(n sr_out / sr_in) as host integers).  The Kaiser-windowed sinc of datasets/resample.py, designed once per
-    rate pair; sr_in == sr_out returns the input.  Needs no model."""
-    from .datasets.resample import Resampler
-    if not torch.is_tensor(wav) or wav.device.type != "cuda":
-        raise ValueError("resample: wav must be a float32 (B, samples) tensor on the GPU")
-    key = (int(sr_out), wav.device)
-    rs = _RESAMPLERS.get(key)
-    if rs is None:
-        rs = _RESAMPLERS.setdefault(key, Resampler(int(sr_out), wav.device))
-    return rs.batch(wav, n.tolist() if torch.is_tensor(n) else n, int(sr_in))
-
-
-_RESAMPLERS: dict = {}
 
 
 def fill_splits(M: int, N: int, K: int) -> bool:
@@ -2118,26 +1806,19 @@ class Engine:
         steps than characters has no monotonic path: it gets the argmax counts and feasible = 0."""
         if mode not in self.DURATION_MODES:
             raise ValueError(f"durations: mode must be one of {sorted(self.DURATION_MODES)}, got {mode!r}")
-        if not torch.is_tensor(align) or align.dim() != 3 or align.dtype != torch.float32:
-            raise ValueError("durations: the alignments must be a float32 (B, S, L) tensor")
+        _args.tensor_arg("durations", "the alignments", align, 3, "(B, S, L)")
         B, S, L = align.shape
         if B < 1 or S < 1 or L < 1:
             raise ValueError(f"durations: empty alignments {tuple(align.shape)}")
         if L > self.ALIGN_MAX_L:
             raise ValueError(f"durations: L = {L} is above the limit of {self.ALIGN_MAX_L} text positions")
-        if align.stride(2) != 1 and L > 1:
-            raise ValueError("durations: the last dimension of the alignments must be contiguous")
+        _args.last_contiguous("durations", "the alignments", align)
         dev = self.ps.flat.device          # (the parameters' device with its index: self.dev may be a bare "cuda")
         for name, t in (("align", align), ("chars_len", chars_len), ("frames_len", frames_len)):
-            if not torch.is_tensor(t) or t.device != dev:
-                raise ValueError(f"durations: {name} must be a tensor on the engine's device {dev}")
-        for name, t in (("chars_len", chars_len), ("frames_len", frames_len)):
-            if t.dim() != 1 or t.shape[0] != B or t.is_floating_point() or t.dtype == torch.bool:
-                raise ValueError(f"durations: {name} must be {B} integers")
-        ld_s = align.stride(1) if S > 1 else L
-        ld_b = align.stride(0) if B > 1 else S * ld_s
-        if ld_s < L or (B > 1 and ld_b < (S - 1) * ld_s + L):
-            raise ValueError(f"durations: overlapping alignment rows (strides {tuple(align.stride())})")
+            _args.on_device("durations", name, t, dev, engine=True)
+        _args.int_vector("durations", "chars_len", chars_len, B)
+        _args.int_vector("durations", "frames_len", frames_len, B)
+        ld_b, ld_s = _args.strided_3d("durations", "the alignments", align)
         m = self.DURATION_MODES[mode]
         clen32 = chars_len.to(torch.int32).contiguous()
         flen32 = frames_len.to(torch.int32).contiguous()
@@ -2161,25 +1842,15 @@ class Engine:
     def _check_seq(self, fn: str, name: str, x, lname: str, lens, last: str):
         """The up-front checks of a (B, T, C) float32 sequence tensor and its B integer lengths: ValueError, never a device fault."""
         dev = self.ps.flat.device
-        if not torch.is_tensor(x) or x.dim() != 3 or x.dtype != torch.float32:
-            raise ValueError(f"{fn}: {name} must be a float32 (B, T, {last}) tensor")
-        if x.device != dev:
-            raise ValueError(f"{fn}: {name} must be a tensor on the engine's device {dev}")
+        _args.tensor_arg(fn, name, x, 3, f"(B, T, {last})")
+        _args.on_device(fn, name, x, dev, engine=True)
         B, T, C = x.shape
         if B < 1 or T < 1 or C < 1:
             raise ValueError(f"{fn}: empty {name} {tuple(x.shape)}")
         if T > self.DTW_MAX_T:
             raise ValueError(f"{fn}: {name} has {T} frames, above the limit of {self.DTW_MAX_T} (T2_DTW_MAX_T)")
-        if x.stride(2) != 1 and C > 1:
-            raise ValueError(f"{fn}: the last dimension of {name} must be contiguous")
-        ld_t = x.stride(1) if T > 1 else C
-        ld_b = x.stride(0) if B > 1 else T * ld_t
-        if ld_t < C or (B > 1 and ld_b < (T - 1) * ld_t + C):
-            raise ValueError(f"{fn}: overlapping rows of {name} (strides {tuple(x.stride())})")
-        if not torch.is_tensor(lens) or lens.device != dev:
-            raise ValueError(f"{fn}: {lname} must be a tensor on the engine's device {dev}")
-        if lens.dim() != 1 or lens.shape[0] != B or lens.is_floating_point() or lens.dtype == torch.bool:
-            raise ValueError(f"{fn}: {lname} must be {B} integers")
+        ld_b, ld_t = _args.strided_3d(fn, name, x)
+        _args.lengths(fn, lname, lens, B, dev, engine=True)
         return ld_b, ld_t
 
     def _ceps_basis(self, M: int, K: int) -> torch.Tensor:
@@ -2192,8 +1863,7 @@ class Engine:
         return self._ceps_bases[key]
 
     def _mel_cepstra(self, fn: str, name: str, mel, lname: str, lens, n_ceps, ws: str) -> torch.Tensor:
-        if isinstance(n_ceps, bool) or not isinstance(n_ceps, int) or not 1 <= n_ceps <= self.DTW_MAX_K:
-            raise ValueError(f"{fn}: n_ceps must be an integer in 1 .. {self.DTW_MAX_K}, got {n_ceps!r}")
+        _args.int_arg(fn, "n_ceps", n_ceps, 1, self.DTW_MAX_K)
         ld_b, ld_t = self._check_seq(fn, name, mel, lname, lens, "num_mels")
         B, T, M = mel.shape
         if n_ceps >= M:

@@ -1,10 +1,10 @@
 """What came out of a synthesis, measured on the GPU: pitch level and range, intensity, noisiness and speaking rate of a batch of
-waveforms.  The YIN pitch tracker (engine.yin, C-ABI t2_yin) analyses frames on the mel grid - hop 256, frame t
-centred on sample 256 t - and engine.prosody_stats (t2_prosody_stats) reduces every track to one row; this module only packs the
+waveforms.  The YIN pitch tracker (analysis.yin, C-ABI t2_yin) analyses frames on the mel grid - hop 256, frame t
+centred on sample 256 t - and analysis.prosody_stats (t2_prosody_stats) reduces every track to one row; this module only packs the
 batch and names the fields.  No parity with Praat's absolute values: the numbers are for correlating with the requested controls
 (run/correlation.py).  ProsodyMeter.features adds jitter, shimmer and a noise-to-harmonics ratio by cycle matching
-(engine.voice_quality) and returns the reference's FEATURES_ALL columns: what `main.py prosody-export` writes.  ProsodyMeter(smooth=True) decodes the track with engine.pitch_viterbi, and
-f0_scores compares the tracks of two batches along a warping path (engine.f0_path_stats): what `test --score --f0` reports."""
+(analysis.voice_quality) and returns the reference's FEATURES_ALL columns: what `main.py prosody-export` writes.  ProsodyMeter(smooth=True) decodes the track with analysis.pitch_viterbi, and
+f0_scores compares the tracks of two batches along a warping path (analysis.f0_path_stats): what `test --score --f0` reports."""
 from __future__ import annotations
 
 import math
@@ -12,7 +12,7 @@ from typing import List, Sequence
 
 import torch
 
-from . import engine
+from . import analysis
 
 MEASURES = ["pitch_mean_log", "pitch_range_log", "intensity_mean_db", "aperiodicity_mean", "rate"]
 # the reference's feature columns (preprocessing/preprocessing_split/normalize.py: FEATURES_ALL), in its order
@@ -22,23 +22,23 @@ FEATURES = ["duration", "duration_vcd", "pitch_mean", "pitch_5", "pitch_95", "pi
 
 
 class ProsodyMeter:
-    """measure() of a list of waveforms in one launch of each kernel.  The settings are engine.yin's (engine.YIN_DEFAULTS).
-    smooth=True decodes the track with engine.pitch_viterbi before the statistics: further settings are then
-    engine.VITERBI_DEFAULTS' (w, max_jump, u - default: this meter's vthr -, c_sw)."""
+    """measure() of a list of waveforms in one launch of each kernel.  The settings are analysis.yin's (analysis.YIN_DEFAULTS).
+    smooth=True decodes the track with analysis.pitch_viterbi before the statistics: further settings are then
+    analysis.VITERBI_DEFAULTS' (w, max_jump, u - default: this meter's vthr -, c_sw)."""
 
     def __init__(self, sample_rate: int = 22050, device=None, smooth: bool = False, **settings):
-        yin_keys, vit_keys = set(engine.YIN_DEFAULTS) - {"sr"}, set(engine.VITERBI_DEFAULTS)
+        yin_keys, vit_keys = set(analysis.YIN_DEFAULTS) - {"sr"}, set(analysis.VITERBI_DEFAULTS)
         unknown = set(settings) - yin_keys - (vit_keys if smooth else set())
         if unknown:
             raise ValueError(f"ProsodyMeter: unknown YIN settings {sorted(unknown)}")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.smooth = bool(smooth)
-        self.settings = dict(engine.YIN_DEFAULTS, sr=int(sample_rate), **{k: v for k, v in settings.items() if k in yin_keys})
+        self.settings = dict(analysis.YIN_DEFAULTS, sr=int(sample_rate), **{k: v for k, v in settings.items() if k in yin_keys})
         self.viterbi = None
         if self.smooth:
-            self.viterbi = dict(engine.VITERBI_DEFAULTS, u=self.settings["vthr"])
+            self.viterbi = dict(analysis.VITERBI_DEFAULTS, u=self.settings["vthr"])
             self.viterbi.update({k: v for k, v in settings.items() if k in vit_keys})
-        self.tau_min, self.tau_max = engine.yin_lags(self.settings["sr"], self.settings["fmin"], self.settings["fmax"])
+        self.tau_min, self.tau_max = analysis.yin_lags(self.settings["sr"], self.settings["fmin"], self.settings["fmax"])
         self.span = self.settings["W"] + self.tau_max
 
     def describe(self) -> dict:
@@ -55,8 +55,8 @@ class ProsodyMeter:
         lens = [int(w.shape[0]) for w in wavs]
         n_max = max(lens)
         s = self.settings
-        if 1 + n_max // s["hop"] > engine.PROSODY_MAX_T:
-            raise ValueError(f"{fn}: a waveform of {n_max} samples has more than {engine.PROSODY_MAX_T} frames (T2_PROSODY_MAX_T)")
+        if 1 + n_max // s["hop"] > analysis.PROSODY_MAX_T:
+            raise ValueError(f"{fn}: a waveform of {n_max} samples has more than {analysis.PROSODY_MAX_T} frames (T2_PROSODY_MAX_T)")
         batch = torch.zeros(len(wavs), max(n_max, 1), dtype=torch.float32, device=self.device)
         for k, w in enumerate(wavs):
             batch[k, :lens[k]] = w
@@ -66,9 +66,9 @@ class ProsodyMeter:
         """(f0, aper, power) of a packed batch: yin's own pick, or with smooth the Viterbi decode of its cmnd."""
         s = self.settings
         if not self.smooth:
-            return engine.yin(batch, n, n_max=n_max, **s)
-        _, _, power, cmnd = engine.yin(batch, n, n_max=n_max, return_cmnd=True, **s)
-        f0, aper, _, _ = engine.pitch_viterbi(cmnd, power, n, sr=s["sr"], hop=s["hop"], fmin=s["fmin"], fmax=s["fmax"],
+            return analysis.yin(batch, n, n_max=n_max, **s)
+        _, _, power, cmnd = analysis.yin(batch, n, n_max=n_max, return_cmnd=True, **s)
+        f0, aper, _, _ = analysis.pitch_viterbi(cmnd, power, n, sr=s["sr"], hop=s["hop"], fmin=s["fmin"], fmax=s["fmax"],
                                               power_floor=s["power_floor"], **self.viterbi)
         return f0, aper, power
 
@@ -92,7 +92,7 @@ class ProsodyMeter:
         batch, lens, n_max, n = self._pack("measure", wavs)
         s = self.settings
         f0, aper, power = self._track(batch, n, n_max)
-        st = engine.prosody_stats(f0, aper, power, n, hop=s["hop"], span=self.span).cpu().tolist()
+        st = analysis.prosody_stats(f0, aper, power, n, hop=s["hop"], span=self.span).cpu().tolist()
         out = []
         for k, row in enumerate(st):
             voiced = int(row[1]) > 0
@@ -113,7 +113,7 @@ class ProsodyMeter:
         pitch_5, and their _log twins - pitch_mean_log = mean ln f0 and pitch_range_log = ln p95 - ln p5, exactly measure()'s,
         pitch_5_log = ln p5, pitch_95_log = ln p95; intensity_mean = mean 10 log10 of the frame power over the loud frames (power >
         power_floor), intensity_mean_vcd over the voiced frames (measure()'s intensity_mean_db); jitter, shimmer, nhr = means over
-        the measured frames (engine.voice_quality); rate = n_chars / duration, rate_vcd = n_chars / duration_vcd.  nhr_vcd is a COPY
+        the measured frames (analysis.voice_quality); rate = n_chars / duration, rate_vcd = n_chars / duration_vcd.  nhr_vcd is a COPY
         of nhr: every period-based measure here is taken on voiced frames by construction, there is no other kind of nhr.  None where
         undefined: no voiced frame (pitch_*, intensity_mean_vcd, rate_vcd), no measured frame (jitter, shimmer, nhr, nhr_vcd), no loud
         frame (intensity_mean), an empty waveform (rate)."""
@@ -124,9 +124,9 @@ class ProsodyMeter:
         batch, lens, n_max, n = self._pack("features", wavs)
         s = self.settings
         f0, aper, power = self._track(batch, n, n_max)
-        st = engine.prosody_stats(f0, aper, power, n, hop=s["hop"], span=self.span)
-        vq = engine.voice_quality(batch, n, f0, sr=s["sr"], hop=s["hop"], W=s["W"], fmin=s["fmin"], fmax=s["fmax"], n_max=n_max)
-        cs = engine.corpus_stats(f0, power, *vq, n, hop=s["hop"], span=self.span, power_floor=s["power_floor"])
+        st = analysis.prosody_stats(f0, aper, power, n, hop=s["hop"], span=self.span)
+        vq = analysis.voice_quality(batch, n, f0, sr=s["sr"], hop=s["hop"], W=s["W"], fmin=s["fmin"], fmax=s["fmax"], n_max=n_max)
+        cs = analysis.corpus_stats(f0, power, *vq, n, hop=s["hop"], span=self.span, power_floor=s["power_floor"])
         st, cs = st.cpu().tolist(), cs.cpu().tolist()
         out = []
         for k, (row, c) in enumerate(zip(st, cs)):
@@ -153,7 +153,7 @@ F0_MEASURES = ["f0_rmse_cents", "f0_bias_cents", "f0_corr", "vuv_error"]
 
 
 def f0_scores(meter: ProsodyMeter, syn_wavs: Sequence[torch.Tensor], ref_wavs: Sequence[torch.Tensor], path, path_len) -> List[dict]:
-    """One dict per pair (engine.f0_figures: n_pairs, n_voiced_both and the F0_MEASURES, None where undefined): the meter's tracks of
+    """One dict per pair (analysis.f0_figures: n_pairs, n_voiced_both and the F0_MEASURES, None where undefined): the meter's tracks of
     syn_wavs[k] and ref_wavs[k] compared along the first path_len[k] cells (i = frame of the synthesis, j = frame of the recording)
     of path (B, P, 2) int32 - Tacotron2.score_decode(return_path=True) - whose frames lie on the meter's hop."""
     if len(syn_wavs) != len(ref_wavs):
@@ -162,5 +162,5 @@ def f0_scores(meter: ProsodyMeter, syn_wavs: Sequence[torch.Tensor], ref_wavs: S
         return []
     f0_a, n_a = meter.tracks(syn_wavs)
     f0_b, n_b = meter.tracks(ref_wavs)
-    st = engine.f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=meter.settings["hop"], span=meter.span)
-    return [engine.f0_figures(row) for row in st.cpu().tolist()]
+    st = analysis.f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=meter.settings["hop"], span=meter.span)
+    return [analysis.f0_figures(row) for row in st.cpu().tolist()]

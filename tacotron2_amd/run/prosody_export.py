@@ -157,7 +157,7 @@ def do_prosody_export(dataset_config: dict, extensions_config: dict, device: int
     import pandas as pd
     import torch
 
-    from .. import engine
+    from .. import analysis
     from ..datasets.tts_dataset import TTSDataset
     from ..prosody import ProsodyMeter
     paths = {k: dataset_config[k] for k in SPLITS if dataset_config.get(k)}
@@ -185,9 +185,9 @@ def do_prosody_export(dataset_config: dict, extensions_config: dict, device: int
             df = pd.read_csv(p, delimiter="|", quoting=csv.QUOTE_NONE, engine="c")
             ds = TTSDataset(filenames=list(df.wav), texts=list(df.text), base_dir=speech_dir, device=dev, **pre)
             n_chars = [len(i) for i in ds.ids]
-            fs, ns = measure_manifest(ds, meter, n_chars, batch_size, pool, engine.PROSODY_MAX_T)
+            fs, ns = measure_manifest(ds, meter, n_chars, batch_size, pool, analysis.PROSODY_MAX_T)
             frames[k], feats[k] = df, fs
-            reasons[k] = [drop_reason(n, f, engine.PROSODY_MAX_T, meter.settings["hop"]) for n, f in zip(ns, fs)]
+            reasons[k] = [drop_reason(n, f, analysis.PROSODY_MAX_T, meter.settings["hop"]) for n, f in zip(ns, fs)]
             n_utts += len(df)
     finally:
         pool.shutdown(wait=True)

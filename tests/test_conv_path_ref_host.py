@@ -81,6 +81,9 @@ def test_bilstm_equals_nn_lstm_on_a_packed_sequence():
     I = 8 * H                                   # square stacked W_ih: dx = dpre . W_ih determines dpre
     g = torch.Generator().manual_seed(3)
     m = torch.nn.LSTM(I, H, batch_first=True, bidirectional=True).double()
+    with torch.no_grad():                       # nn.LSTM's own init, U(-1/sqrt(H), 1/sqrt(H)), drawn from g and not from the global
+        for p in m.parameters():                # generator: the weights, and with them the condition of W_ih, are the same in every run
+            p.uniform_(-H ** -0.5, H ** -0.5, generator=g)
     x = torch.randn(B, L, I, generator=g, dtype=F64).requires_grad_(True)
     lens = torch.tensor([L, 1, 3, L, 2])
     denc = torch.randn(B, L, 2 * H, generator=g, dtype=F64)

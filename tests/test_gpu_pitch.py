@@ -365,3 +365,22 @@ def test_engine_functions_and_their_argument_checks():
         with pytest.raises(ValueError) as e:
             engine.f0_path_stats(**kw)
         assert str(e.value).startswith("f0_path_stats:"), (bad, str(e.value))
+
+
+def test_engine_pitch_viterbi_of_a_cut_of_a_larger_allocation():
+    """The accepted strided path of the shared check: cmnd as a view (2, 63, tau_max + 1) into a (2, 70, tau_max + 6) buffer - rows
+    and utterances further apart than the view is wide, NaN between them - decodes to what the contiguous tensor gives, bit for bit."""
+    from tacotron2_amd import engine
+    dev = torch.device("cuda:0")
+    cm, power, _, cfg, _ = signal_case("default")
+    NT = cfg["tau_max"] + 1
+    n = torch.tensor([16000, 50 * 256 - 1], device=dev)   # 63 and 50 frames
+    cm_d, pw_d = torch.from_numpy(np.nan_to_num(cm, nan=1.0)).to(dev), torch.from_numpy(np.nan_to_num(power, nan=0.0)).to(dev)
+    big = torch.full((2, 70, NT + 5), float("nan"), device=dev)
+    view = big[:, :63, :NT]
+    view.copy_(cm_d)
+    assert not view.is_contiguous() and view.stride() == (70 * (NT + 5), NT + 5, 1)
+    dense = engine.pitch_viterbi(cm_d, pw_d, n)
+    assert int((dense[2] > 0).sum()) > 50                  # (voiced frames: the comparison is not one of zeros)
+    for got, want in zip(engine.pitch_viterbi(view, pw_d, n), dense):
+        assert torch.equal(got, want)

@@ -28,7 +28,7 @@ def main():
 
     import torch
     import prosody_ref as R
-    from tacotron2_amd import _lib, engine
+    from tacotron2_amd import _lib, analysis
     from tacotron2_amd.prosody import ProsodyMeter
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -77,7 +77,7 @@ def main():
         case["t2_yin_with_cmnd"], _ = series(lambda: _lib.call("t2_yin", y, st))
         case["t2_pitch_viterbi"], _ = series(lambda: _lib.call("t2_pitch_viterbi", p, st))
         path = torch.arange(T, dtype=torch.int32, device=dev)[None, :, None].expand(B, T, 2).contiguous()
-        stats = torch.empty(B, engine.F0_NSTAT, dtype=torch.float64, device=dev)
+        stats = torch.empty(B, analysis.F0_NSTAT, dtype=torch.float64, device=dev)
         q = _lib.make("T2F0PathStats", path=path, path_len=torch.full((B,), T, dtype=torch.int32, device=dev), f0_a=f0v,
                       f0_b=(f0v * 2.0 ** (1 / 12)).contiguous(), n_a=nd, n_b=nd, B=B, P=T, Ta=T, Tb=T, hop=s["hop"], S=raw.span, out=stats)
         case["t2_f0_path_stats"], _ = series(lambda: _lib.call("t2_f0_path_stats", q, st))

@@ -31,7 +31,7 @@ def main():
 
     import torch
     import prosody_ref as R
-    from tacotron2_amd import _lib, engine
+    from tacotron2_amd import _lib, analysis
     from tacotron2_amd.prosody import ProsodyMeter
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -42,7 +42,7 @@ def main():
     nd = torch.full((B,), n, dtype=torch.int64, device=dev)
     T = 1 + n // 256
     f0, aper, power = (torch.empty(B, T, device=dev) for _ in range(3))
-    stats = torch.empty(B, engine.PROSODY_NSTAT, device=dev)
+    stats = torch.empty(B, analysis.PROSODY_NSTAT, device=dev)
     s = meter.settings
     y = _lib.make("T2Yin", wav=batch, ld_wav=n, n=nd, B=B, n_max=n, sr=sr, hop=s["hop"], W=s["W"], tau_min=meter.tau_min,
                   tau_max=meter.tau_max, thr=s["thr"], vthr=s["vthr"], power_floor=s["power_floor"], f0=f0, aper=aper, power=power,

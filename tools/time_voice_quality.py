@@ -41,7 +41,7 @@ def main():
     import prosody_ref as R
     from bench_frontend import make_manifest
     from concurrent.futures import ThreadPoolExecutor
-    from tacotron2_amd import _lib, engine
+    from tacotron2_amd import _lib, analysis
     from tacotron2_amd.datasets.tts_dataset import DeviceBatchLoader, DevicePrefetcher, TTSDataset
     from tacotron2_amd.prosody import ProsodyMeter
     from tacotron2_amd.run.prosody_export import host_threads, measure_manifest
@@ -85,8 +85,8 @@ def main():
                   tau_max=meter.tau_max, thr=s["thr"], vthr=s["vthr"], power_floor=s["power_floor"], f0=y_out[0], aper=y_out[1],
                   power=y_out[2], cmnd=None)
     out["t2_yin"], _ = series(lambda: _lib.call("t2_yin", y, st))
-    out["t2_yin_with_cmnd"], (_, _, power, cmnd) = series(lambda: engine.yin(batch, nd, n_max=n, return_cmnd=True, **s))
-    out["t2_pitch_viterbi"], (f0, aper, _, _) = series(lambda: engine.pitch_viterbi(
+    out["t2_yin_with_cmnd"], (_, _, power, cmnd) = series(lambda: analysis.yin(batch, nd, n_max=n, return_cmnd=True, **s))
+    out["t2_pitch_viterbi"], (f0, aper, _, _) = series(lambda: analysis.pitch_viterbi(
         cmnd, power, nd, sr=sr, hop=s["hop"], fmin=s["fmin"], fmax=s["fmax"], power_floor=s["power_floor"], **meter.viterbi))
     outs = [torch.empty(B, T, device=dev) for _ in range(4)] + [torch.empty(B, T, dtype=torch.int32, device=dev)]
     v = _lib.make("T2VoiceQuality", wav=batch, ld_wav=n, n=nd, B=B, n_max=n, sr=sr, hop=s["hop"], W=s["W"], tau_min=meter.tau_min,
@@ -94,8 +94,8 @@ def main():
     out["t2_voice_quality"], _ = series(lambda: _lib.call("t2_voice_quality", v, st))
     out["measured_frames"] = int((outs[4] > 0).sum())
     out["cycles_matched"] = int(outs[4].sum())
-    out["t2_prosody_stats"], _ = series(lambda: engine.prosody_stats(f0, aper, power, nd, hop=s["hop"], span=meter.span))
-    out["t2_corpus_stats"], _ = series(lambda: engine.corpus_stats(f0, power, *outs, nd, hop=s["hop"], span=meter.span))
+    out["t2_prosody_stats"], _ = series(lambda: analysis.prosody_stats(f0, aper, power, nd, hop=s["hop"], span=meter.span))
+    out["t2_corpus_stats"], _ = series(lambda: analysis.corpus_stats(f0, power, *outs, nd, hop=s["hop"], span=meter.span))
     out["meter_features"], rows = series(lambda: meter.features(wavs, [100] * B))
     out["meter_measure"], _ = series(lambda: meter.measure(wavs, [100] * B))
     out["voice_quality_over_yin"] = round(out["t2_voice_quality"]["ms_median"] / out["t2_yin"]["ms_median"], 4)
@@ -121,7 +121,7 @@ def main():
         def export_rate(dataset):
             with ThreadPoolExecutor(max_workers=threads) as pool:
                 torch.cuda.synchronize(); t0 = time.perf_counter()
-                feats, _ = measure_manifest(dataset, meter, n_chars, B, pool, engine.PROSODY_MAX_T)
+                feats, _ = measure_manifest(dataset, meter, n_chars, B, pool, analysis.PROSODY_MAX_T)
                 torch.cuda.synchronize(); dt = time.perf_counter() - t0
             return round(len(dataset) / dt, 1), sum(1 for f in feats if f is not None and f["n_measured"] > 0)
 
