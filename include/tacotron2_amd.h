@@ -674,6 +674,54 @@ typedef struct {
 int t2_align_durations(const T2AlignDur* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-character pitch and energy on the grid of t2_align_durations (no reference counterpart; the two further targets FastSpeech 2
+ * and FastPitch train on, csrc/t2_variance.hip, DESIGN 5.15, restated in float64 in tests/variance_ref.py): a pitch track and a
+ * log-mel are cut at the character boundaries and averaged, and the sums a normalisation needs are collected.  ONE launch, one
+ * 256-thread workgroup per utterance; no cross-workgroup synchronisation, no global atomics; every sum is taken in a fixed order,
+ * so two calls are bit-identical.
+ *   Inputs: f0[b*ld_f0 + t] in Hz (t2_yin's track or t2_pitch_viterbi's: frame t centred on sample hop*t, as the mel frame is);
+ *   the log-mel mel[b*ld_b + t*ld_t + m], M bins, m contiguous (the natural log of a magnitude); dur[b*ld_dur + n] int32.
+ *   N_b = clip(chars_len[b], 0, L) characters, F_b = clip(frames_len[b], 0, T) frames.
+ *   Frame t is VOICED iff t < F_b and f0 > 0 (a NaN is unvoiced); p(t) = log((double)f0) with log_pitch, else (double)f0.
+ *   Energy e(t) = sqrt(sum_m exp(2.0 * (double)mel[t][m])): the L2 norm of the mel magnitudes, in fp64.
+ *   Filled pitch q(t), t < F_b.  interpolate = 0: q = p on the voiced frames, 0 elsewhere.  interpolate = 1, with u0 / u1 the first /
+ *     last voiced frame: q(t) = p(u0) before u0 and p(u1) behind u1; between neighbouring voiced frames a < t < c
+ *       q(t) = p(a) + (p(c) - p(a)) * ((double)(t - a) / (double)(c - a));   q = 0 everywhere without a voiced frame.
+ *   Character n < N_b covers the frames [s_n, s_n + max(dur[n], 0)), s_n the prefix sum (int64), clipped to F_b;
+ *     consistent = (sum_{n < N_b} max(dur[n], 0) == F_b).
+ *   char_pitch [B][L]: interpolate = 0: the mean of p over the VOICED frames of the span, 0 without one (FastPitch's rule);
+ *     interpolate = 1: the mean of q over ALL frames of the span, 0 for an empty span (FastSpeech 2's rule).
+ *   char_energy [B][L]: the mean of e over the span, 0 for an empty span.  char_voiced [B][L] int32: the span's voiced frames.
+ *   Entries n >= N_b of the three are written as 0.  frame_pitch / frame_energy [B][T] (either may be NULL): q and e as float;
+ *   entries t >= F_b are not written.
+ *   stats [B][T2_VAR_NSTAT] doubles: [0] F_b  [1] voiced frames  [2] sum p, [3] sum p^2 over the voiced frames  [4] sum q, [5] sum q^2,
+ *     [6] sum e, [7] sum e^2 over all frames  [8] consistent  [9] the characters n < N_b without a voiced frame.
+ *   Every mean and sum is fp64 (the tolerance of the tests then follows from the formats, not from a measurement); a character's
+ *   sums run in frame order.  N_b == 0 or F_b == 0: the three character rows are 0, the frame outputs are 0 for t < F_b, the stats
+ *   are 0 except [8], and nothing of f0 or mel is read.  Nothing at t >= F_b is ever read, nor dur at n >= N_b.
+ *   q and e stay in LDS as doubles with the span starts: 16 T + 4 (L + 1) bytes = 80 KB at both caps (plus 4.8 KB of partials).
+ *   T2_ERR_ARG before any launch: a null pointer (the two frame outputs excepted), B, T, L or M < 1, T > T2_VAR_MAX_T,
+ *   L > T2_VAR_MAX_L, a flag other than 0 / 1, ld_f0 < T, ld_dur < L, ld_t < M, ld_b < (T-1)*ld_t + M. */
+#define T2_VAR_MAX_T 4096
+#define T2_VAR_MAX_L 4096
+#define T2_VAR_NSTAT 10
+typedef struct {
+    const float* f0; int64_t ld_f0;           /* f0[b*ld_f0 + t], Hz; not > 0 = unvoiced */
+    const float* mel; int64_t ld_b, ld_t;     /* mel[b*ld_b + t*ld_t + m], m contiguous */
+    const int32_t* dur; int64_t ld_dur;       /* [B][ld_dur >= L]: frames per character (t2_align_durations) */
+    int B, T, L, M, log_pitch, interpolate;
+    const int32_t* chars_len;                 /* [B] device; N_b = clip(., 0, L) */
+    const int32_t* frames_len;                /* [B] device; F_b = clip(., 0, T) */
+    float* char_pitch;                        /* [B][L] */
+    float* char_energy;                       /* [B][L] */
+    int32_t* char_voiced;                     /* [B][L] */
+    float* frame_pitch;                       /* optional [B][T]: q */
+    float* frame_energy;                      /* optional [B][T]: e */
+    double* stats;                            /* [B][T2_VAR_NSTAT] */
+} T2CharVariance;
+int t2_char_variance(const T2CharVariance* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Objective scoring of a free-running decode against the recording: mel-cepstral distortion under dynamic time warping
  * (MCD-DTW; no reference counterpart - the reference's `test` decodes the recordings and drops them).  Two entries
  * (csrc/t2_dtw.hip), the rule in DESIGN 5.9, restated in float64 in tests/mcd_dtw_ref.py.

@@ -14,6 +14,8 @@
     (say, test and test-correlation also take --stop-threshold P)
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
     python main.py --config C --device N duration-export --speech-dir S --checkpoint K [--results-dir R] [--mode monotonic|argmax]
+                                                  [--variances [--pitch-domain log|hz] [--interpolate-pitch] [--frame-level]
+                                                   [--no-smooth-pitch]]
     python main.py --config C --device N prosody-export --speech-dir S [--results-dir R] [--no-smooth-pitch] [--batch-size 64]
 
 Other reference sub-commands (preprocess, server) are data preparation / demo tooling outside the hot-path scope
@@ -329,15 +331,36 @@ def train_mel_export(ctx, speech_dir, checkpoint, results_dir=None):
 @click.option("--mode", required=False, type=click.Choice(["monotonic", "argmax"]), default="monotonic",
               help="monotonic: the best monotonic path through the alignment (first character to last, stay or advance by one per "
                    "decoder step); argmax: each decoder step's attention peak. Default: monotonic.")
-def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monotonic"):
-    """Per-character durations (mel frames) of the train + val manifests from teacher-forced alignments, plus durations.csv."""
+@click.option("--variances", is_flag=True, default=False,
+              help="Also write per-character pitch and energy targets (<name>.pitch.npy, <name>.energy.npy) beside every .dur.npy, "
+                   "with variances.csv, variance_stats.json (the train set's normalisation constants) and variances_dropped.csv. "
+                   "Default: off.")
+@click.option("--pitch-domain", required=False, type=click.Choice(["log", "hz"]), default=None,
+              help="With --variances: the pitch in ln Hz or in Hz. Default: log.")
+@click.option("--interpolate-pitch", is_flag=True, default=False,
+              help="With --variances: interpolate the pitch across the unvoiced frames and average over all frames of a character "
+                   "(FastSpeech 2). Default: the mean over its voiced frames, 0 without one (FastPitch).")
+@click.option("--frame-level", is_flag=True, default=False,
+              help="With --variances: also write <name>.pitch_frames.npy and <name>.energy_frames.npy, one value per mel frame.")
+@click.option("--no-smooth-pitch", is_flag=True, default=False,
+              help="With --variances: the raw YIN track instead of the Viterbi-smoothed one. Default: smoothed.")
+def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monotonic", variances=False, pitch_domain=None,
+                    interpolate_pitch=False, frame_level=False, no_smooth_pitch=False):
+    """Per-character durations (mel frames) of the train + val manifests from teacher-forced alignments, plus durations.csv; with
+    --variances also per-character pitch and energy."""
+    if not variances:
+        given = [flag for flag, on in (("--pitch-domain", pitch_domain is not None), ("--interpolate-pitch", interpolate_pitch),
+                                       ("--frame-level", frame_level), ("--no-smooth-pitch", no_smooth_pitch)) if on]
+        if given:
+            raise click.UsageError(f"{', '.join(given)} need{'s' if len(given) == 1 else ''} --variances")
     if ctx.obj["config"] is None:
         raise Exception("Configuration required!")
     from tacotron2_amd.run.duration_export import do_duration_export
     c = ctx.obj["config"]
     do_duration_export(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
                        extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
-                       results_dir=results_dir, mode=mode)
+                       results_dir=results_dir, mode=mode, variances=variances, pitch_domain=pitch_domain or "log",
+                       interpolate_pitch=interpolate_pitch, frame_level=frame_level, smooth_pitch=not no_smooth_pitch)
 
 
 @main.command()

@@ -69,7 +69,7 @@ class TTSDataset(torch.utils.data.Dataset):
                  trim: bool = True, trim_top_db: int = 60, trim_frame_length: int = 2048, expand_abbreviations=False,
                  include_text=False, include_filename=False, num_mels: int = 80, cache=False, cache_dir=None,
                  description_embeddings: Optional[List[Optional[str]]] = None, description_embeddings_dim: int = 768,
-                 sample_rate: int = 22050, resample: bool = True, device="cuda:0", **_ignored):
+                 sample_rate: int = 22050, resample: bool = True, device="cuda:0", include_audio: bool = False, **_ignored):
         assert (cache and cache_dir is not None) or not cache, "If caching spectrograms, a cache directory is required"
         if cache and not os.path.exists(cache_dir):
             os.makedirs(cache_dir, exist_ok=True)
@@ -82,6 +82,8 @@ class TTSDataset(torch.utils.data.Dataset):
         self.cache, self.cache_dir = cache, cache_dir
         self.description_embeddings, self.description_embeddings_dim = description_embeddings, description_embeddings_dim
         self.include_text, self.include_filename = include_text, include_filename
+        # opt-in: the item also carries load_audio(i), the signal its mel came from, as extra["audio"] (run/duration_export.py)
+        self.include_audio = bool(include_audio)
         self.melspectrogram = TacotronMelSpectrogram(n_mels=num_mels, sample_rate=sample_rate, device=device)
         # files at another rate than the model's: trimmed at their own rate, then resampled on the device
         self.sample_rate, self.resample = int(sample_rate), bool(resample)
@@ -161,6 +163,7 @@ class TTSDataset(torch.utils.data.Dataset):
                     mel = torch.load(cache_path, weights_only=True).to(self.melspectrogram.device)
                 except Exception:       # unreadable entry (e.g. left by a killed run): a cache miss, recomputed below
                     mel = None
+        wav = None
         if mel is None:
             wav = self.load_audio(i)
             # (the item's mel is computed on the device and stays there: collate pads device tensors, nothing is copied back)
@@ -177,6 +180,8 @@ class TTSDataset(torch.utils.data.Dataset):
             extra["text"] = self.texts[i]
         if self.include_filename:
             extra["filename"] = fn
+        if self.include_audio:
+            extra["audio"] = wav if wav is not None else self.load_audio(i)        # (a cache hit decoded nothing)
         if self.speaker_ids is not None:
             meta["speaker_id"] = torch.IntTensor([self.speaker_ids[i]])
         if self.description_embeddings is not None:

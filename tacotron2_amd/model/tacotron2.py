@@ -261,6 +261,23 @@ class Tacotron2(nn.Module):
             self.train(was_training)
         return dur, stats, align
 
+    def variances(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor, wavs, meter,
+                  mode: str = "monotonic", log_pitch: bool = True, interpolate: bool = False, return_frames: bool = False, **kw):
+        """Per-character durations, pitch and energy of a batch - the three targets of a duration-based student: durations(...) with
+        the same arguments, then prosody.char_variances on its durations with `wavs` (the signals the mels came from, 1-D float32 on
+        the meter's device) and `meter` (a ProsodyMeter; its track is the pitch).  Returns (durations, variances, stats): int32
+        (B, L); the dict of analysis.char_variance - pitch, energy float32 (B, L), voiced int32 (B, L), with return_frames also
+        pitch_frames and energy_frames (B, T) - plus alignment_stats = durations' float32 (B, 4); and its float64 (B, 10) sums
+        (analysis.VAR_STATS).  The energy is taken on `mel_spectrogram`, the recording's log-mel."""
+        from .. import prosody
+        dur, dstats, _ = self.durations(chars_idx, chars_idx_len, mel_spectrogram, mel_spectrogram_len, mode=mode, **kw)
+        dev = dur.device
+        out, stats = prosody.char_variances(meter, wavs, mel_spectrogram.to(dev).float(), mel_spectrogram_len.to(dev), dur,
+                                            chars_idx_len.to(dev), log_pitch=log_pitch, interpolate=interpolate,
+                                            return_frames=return_frames)
+        out["alignment_stats"] = dstats
+        return dur, out, stats
+
     def score(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
               max_len_override: int = 5000, n_ceps: int = 13, **kw):
         """Objective score of a free-running decode against the recording: an EVAL-mode forward(teacher_forcing=False, ...) with the

@@ -173,6 +173,18 @@ class TTSModel(nn.Module):
                                         description_embeddings=description_embeddings,
                                         train_forward_attention=train_forward_attention)
 
+    def variances(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor, wavs, meter,
+                  mode: str = "monotonic", log_pitch: bool = True, interpolate: bool = False, return_frames: bool = False,
+                  speaker_id: Optional[Tensor] = None, controls: Optional[Tensor] = None, max_len_override: Optional[int] = None,
+                  description_embeddings: Optional[Tensor] = None, train_forward_attention: bool = False):
+        """(durations, variances, stats) - per-character durations, pitch and energy - of an eval-mode teacher-forced forward and the
+        meter's pitch track of `wavs`: Tacotron2.variances."""
+        return self.tacotron2.variances(chars_idx, chars_idx_len, mel_spectrogram, mel_spectrogram_len, wavs, meter, mode=mode,
+                                        log_pitch=log_pitch, interpolate=interpolate, return_frames=return_frames,
+                                        speaker_id=speaker_id, controls=controls, max_len_override=max_len_override,
+                                        description_embeddings=description_embeddings,
+                                        train_forward_attention=train_forward_attention)
+
     def score(self, chars_idx: Tensor, chars_idx_len: Tensor, mel_spectrogram: Tensor, mel_spectrogram_len: Tensor,
               max_len_override: Optional[int] = None, n_ceps: int = 13, speaker_id: Optional[Tensor] = None,
               controls: Optional[Tensor] = None, description_embeddings: Optional[Tensor] = None,

@@ -149,6 +149,30 @@ class ProsodyMeter:
         return out
 
 
+def char_variances(meter: ProsodyMeter, wavs: Sequence[torch.Tensor], mel, mel_len, dur, chars_len, log_pitch: bool = True,
+                   interpolate: bool = False, return_frames: bool = False):
+    """Per-character pitch and energy targets of a batch (analysis.char_variance) from the meter's own track: wavs[k] the
+    signal the log-mel mel[k] (B, T, M) came from (TTSDataset.load_audio), mel_len (B,) its frames, dur (B, L) int32 the durations
+    of Engine.durations and chars_len (B,) the text lengths.  The track's frame t is centred on sample hop * t, as the mel frame is:
+    the track of utterance k must have 1 + len(wavs[k]) // hop == mel_len[k] frames, anything else is a ValueError.  Returns
+    analysis.char_variance's (out, stats)."""
+    if not torch.is_tensor(mel) or mel.dim() != 3 or len(wavs) != mel.shape[0]:
+        raise ValueError(f"char_variances: {len(wavs)} waveforms, mel must be a ({len(wavs)}, T, M) tensor")
+    f0, n = meter.tracks(wavs)
+    hop = meter.settings["hop"]
+    frames = [1 + int(w.shape[0]) // hop for w in wavs]
+    want = [int(v) for v in mel_len.reshape(-1).tolist()]
+    if frames != want:
+        k = next(i for i, (x, y) in enumerate(zip(frames, want)) if x != y) if len(frames) == len(want) else 0
+        raise ValueError(f"char_variances: the track of utterance {k} has {frames[k]} frames (1 + {int(wavs[k].shape[0])} // {hop}), "
+                         f"its mel {want[k] if k < len(want) else 'none'}: the waveforms are not the signals the mels came from")
+    T = f0.shape[1]
+    if mel.shape[1] < T:
+        raise ValueError(f"char_variances: mel has {mel.shape[1]} frames, the longest utterance {T}")
+    return analysis.char_variance(dur, chars_len, mel_len.reshape(-1).to(f0.device), f0, mel[:, :T], log_pitch=log_pitch,
+                                  interpolate=interpolate, return_frames=return_frames)
+
+
 F0_MEASURES = ["f0_rmse_cents", "f0_bias_cents", "f0_corr", "vuv_error"]
 
 
