@@ -973,6 +973,54 @@ typedef struct {
 int t2_resample(const T2Resample* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Joining synthesised pieces into one waveform (no reference counterpart: its `say` speaks one text; csrc/t2_join.hip, the rule in
+ * DESIGN 5.16, restated in numpy in tests/join_ref.py).
+ *
+ * t2_join: x[b*ldx + i] float32 is a padded batch of B waveforms, n[b] (DEVICE int32, 0 <= n[b] <= n_max <= ldx) their sample
+ *   counts, pause[b] (DEVICE int32, >= 0) the samples of silence behind piece b.  Nothing is read from a row at or behind n[b].
+ *   SPAN of row b - the rule of trim_silence (datasets/tts_dataset.py), the ruler the corpus was trimmed on.  With trim = 0 or n[b] < F
+ *   it is [0, n[b]).  Otherwise frame f = 0 .. n[b] / H is centred on sample f H (zero padded, F even):
+ *     e_f = the fp64 sum of x[i]^2 over [f H - F/2, f H + F/2) within [0, n[b]);   e_max = max_f e_f;
+ *     frame f is active iff e_f > e_max * 10^(-top_db / 10)  (the factor is formed once, by the host, in fp64);
+ *     with the first and last active frames f0, f1:  s0 = max(0, f0 H - keep),  s1 = min(n[b], (f1 + 1) H + keep).
+ *   A row without an active frame - e_max == 0, or top_db == 0 - has the EMPTY span s0 = s1 = 0 and contributes its pause alone.
+ *   (trim_silence floors both levels at 1e-10 and so keeps an all-zero signal whole; a synthesised piece of silence is dropped.)
+ *   Over the span: sumsq_b (fp64) and peak_b = max |x|.
+ *   PLAN, in fp64:  len_b = s1 - s0,  rms_b = sqrt(sumsq_b / len_b).  gain_b = 1 with level = 0; with level = 1
+ *     rms_doc = sqrt(sum_b sumsq_b / sum_b len_b),  gain_b = clamp(rms_doc / rms_b, 1 / max_gain, max_gain),  1 where len_b == 0 or
+ *     rms_b == 0.  If ceiling > 0 and pk = max_b gain_b peak_b > ceiling, every gain is multiplied by ceiling / pk.  One cast to
+ *     float32.  off_b = the exclusive int64 scan of len_b + pause_b, total = off_B.  Written: off, s0, len, gain [B] each, total [1].
+ *   WRITE, with fl_b = min(fade, len_b / 2) (integer division), for i < len_b:
+ *     y[off_b + i] = x[b*ldx + s0 + i] * (gain_b * e)   - two float32 multiplications in this order, nothing fused -
+ *     e = w_b(i) for i < fl_b,  w_b(len_b - 1 - i) for i >= len_b - fl_b,  1.0f elsewhere;   w_b(i) = w[(2 i + 1) fade / (2 fl_b)]
+ *     in integer arithmetic, so that a shortened fade samples the same table;  y[off_b + len_b + j] = 0.0f for j < pause_b.
+ *   w [fade] float32 is built by the HOST: w[k] = float32(0.5 - 0.5 cos(pi (k + 0.5) / fade)) formed in fp64; fade = 0: no table,
+ *   no fades.  y holds cap floats, the caller's bound sum n + sum pause; nothing at or behind total is written.
+ *   REFUSED on the device, not clamped: an n[b] outside 0 .. n_max, a negative pause[b] or total > cap give total = -1 and all
+ *   off = 0; such rows are never read and nothing is written to y.
+ *   Workspaces: energy [B][lde] fp64 with lde >= n_max / H + 1 (may be NULL with trim = 0), stat [B][2] fp64 (sumsq, peak).
+ *   Four launches on one stream: frame energies (one wave per frame, grid frames / 4 x B), spans and sums (one 1024-thread
+ *   workgroup per row), the plan (one workgroup), the write (grid chunks x B).  No cross-workgroup synchronisation, no atomics,
+ *   every sum in a fixed order: two calls give bit-identical outputs, and a row's span does not depend on B, ldx or the other rows.
+ *   T2_ERR_ARG before any launch: a null pointer (x only when n_max > 0, w only when fade > 0, y only when cap > 0, energy only
+ *   when trim = 1), B < 1 or > 65535, F < 2 or odd, H < 1, keep < 0, fade < 0, top_db not finite or < 0, max_gain not finite or
+ *   < 1, ceiling not finite or < 0, n_max < 0, ldx < n_max, lde < n_max / H + 1 with trim = 1, cap < 0, a trim or level other than
+ *   0 / 1. */
+typedef struct {
+    const float* x; int64_t ldx;                        /* rows are read only inside [0, n[b]) */
+    const int32_t* n; const int32_t* pause;             /* [B] device each */
+    const float* w;                                     /* [fade] fp32, host-made; NULL with fade = 0 */
+    int B, n_max, trim, F, H, keep, fade, level;
+    double top_db, max_gain, ceiling;
+    double* energy; int64_t lde;                        /* workspace [B][lde] */
+    double* stat;                                       /* workspace [B][2] */
+    int64_t* off; int32_t* s0; int32_t* len; float* gain;   /* the plan, [B] each */
+    int64_t* total;                                     /* [1]; -1: refused */
+    float* y; int64_t cap;
+} T2Join;
+int t2_join(const T2Join* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

@@ -5,6 +5,7 @@
                                                   [--guided-attention SIGMA,ALPHA]
                                                   [--mel-loss l2|l1|l1+l2] [--masked-loss | --no-masked-loss] [--stop-weight W]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
+    python main.py --config C --device N say --checkpoint K --text-file chapter.txt --out chapter.wav [--expand-numbers] [--level]
                                                   [--attention-window BACK,FWD | --forward-attention] [--durations-out PATH]
     python main.py --config C --device N test --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention] [--score [--no-audio | --f0]]
@@ -160,7 +161,30 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @main.command()
 @click.pass_context
 @click.option("--checkpoint", required=True, type=str, help="A trained Tacotron model checkpoint")
-@click.option("--text", required=True, type=str, help="Text to speak")
+@click.option("--text", required=False, type=str, default=None, help="Text to speak (or --text-file)")
+@click.option("--text-file", required=False, type=click.Path(exists=True, dir_okay=False), default=None, metavar="PATH",
+              help="A document to read: split into sentences of at most --max-chars characters, decoded side by side in chunks of "
+                   "--batch-size, trimmed, faded and joined on the GPU with --pause between them, written as ONE .wav. Exclusive "
+                   "with --text; needs a .wav target or a HiFi-GAN checkpoint.")
+@click.option("--max-chars", required=False, type=click.IntRange(min=1), default=None, metavar="N",
+              help="With --text-file: the longest piece, in characters of the cleaned text; a longer sentence is cut at its last "
+                   "';', ':' or ',', else at a space. Default: 190.")
+@click.option("--expand-numbers", is_flag=True, default=False,
+              help="With --text-file: English number words for integers, decimals, ordinals, -5 and 50%% before the text is cleaned "
+                   "(which deletes every digit). No years, currency, times or Roman numerals.")
+@click.option("--pause", required=False, type=str, default=None, metavar="SENT,CLAUSE,PARA",
+              help="With --text-file: seconds of silence behind a sentence, a cut inside a sentence and a paragraph. Default: 0.25,0.12,0.60.")
+@click.option("--no-trim", is_flag=True, default=False,
+              help="With --text-file: keep each piece's leading and trailing silence (default: trimmed by the dataset's rule, "
+                   "preprocessing.trim_top_db over trim_frame_length, 20 ms kept).")
+@click.option("--level", is_flag=True, default=False,
+              help="With --text-file: bring every piece towards the document's RMS (by at most 6 dB either way) and keep the peak at or below 1.")
+@click.option("--fade-ms", required=False, type=click.FloatRange(min=0), default=None, metavar="X",
+              help="With --text-file: half-Hann fade at both ends of every piece, in ms. Default: 5.")
+@click.option("--batch-size", required=False, type=click.IntRange(min=1, max=64), default=None, metavar="N",
+              help="With --text-file: pieces decoded together, 1 to 64. Default: 64.")
+@click.option("--max-len", required=False, type=click.IntRange(min=1), default=5000, metavar="FRAMES",
+              help="The decode stops a text that has not stopped by itself after FRAMES mel frames. Default: 5000.")
 @click.option("--out", required=False, type=str, default="out.npy", help="Output file (log-mel .npy). Default: out.npy")
 @click.option("--hifi-gan-checkpoint", required=False, type=str, default=None, help="HiFi-GAN generator checkpoint (config.json next to it, UNIVERSAL_V1 values when absent)")
 @click.option("--random-seed", required=False, type=int, default=None, help="A random seed to use in generation.")
@@ -177,17 +201,39 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
               help="Write the audio at R Hz (48000, 44100, 16000, 8000, ...) instead of the model's rate: the vocoded waveform is "
                    "resampled on the GPU. Needs a .wav target; --durations-out times stay in model frames. Default: the model's rate.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
-        forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None):
+        forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
+        expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000):
+    if (text is None) == (text_file is None):
+        raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
+    if text_file is None:
+        given = [name for name, v in (("--max-chars", max_chars), ("--expand-numbers", expand_numbers or None), ("--pause", pause),
+                                      ("--no-trim", no_trim or None), ("--level", level or None), ("--fade-ms", fade_ms),
+                                      ("--batch-size", batch_size)) if v is not None]
+        if given:
+            raise click.UsageError(f"{', '.join(given)} only with --text-file")
+    elif hifi_gan_checkpoint is None and not out.endswith(".wav"):
+        raise click.UsageError(f"--text-file needs a .wav target (--out) or --hifi-gan-checkpoint, got --out {out}: a document has no single log-mel")
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if ctx.obj["config"] is None:
         raise Exception("Configuration required for speech!")
-    from tacotron2_amd.run.say import do_say
     c = ctx.obj["config"]
-    do_say(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
-           extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, text=text, output=out,
-           speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
-           description=description, attention_window=attention_window, forward_attention=forward_attention,
-           durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate)
+    common = dict(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
+                  extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, output=out,
+                  speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
+                  description=description, attention_window=attention_window, forward_attention=forward_attention,
+                  durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len)
+    if text_file is None:
+        from tacotron2_amd.run.say import do_say
+        do_say(text=text, **common)
+        return
+    from tacotron2_amd.run.say import do_say_document, parse_pauses
+    try:
+        parse_pauses(pause)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    do_say_document(text_file=text_file, max_chars=190 if max_chars is None else max_chars, expand_numbers=expand_numbers, pause=pause,
+                    trim=not no_trim, level=level, fade_ms=5.0 if fade_ms is None else fade_ms,
+                    batch_size=64 if batch_size is None else batch_size, **common)
 
 
 @main.command()

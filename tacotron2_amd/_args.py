@@ -138,3 +138,28 @@ def strided_3d(fn: str, name: str, x):
     if ld_t < C or (B > 1 and ld_b < (T - 1) * ld_t + C):
         raise ValueError(f"{fn}: overlapping rows of {name} (strides {tuple(x.stride())})")
     return ld_b, ld_t
+
+
+def flag_arg(fn: str, name: str, v) -> int:
+    """v a bool, or the integer 0 or 1."""
+    if not isinstance(v, (bool, int)) or v not in (0, 1):
+        raise ValueError(f"{fn}: {name} must be a flag (a bool, 0 or 1), got {v!r}")
+    return int(v)
+
+
+def counts32(fn: str, name: str, v, B: int, dev, hi=None):
+    """B integer counts for a kernel that takes them as int32 on dev.  Host integers (a sequence, a numpy array, a CPU tensor) are
+    checked here, 0 <= v[b] <= hi, and their sum is known without a read; a tensor on dev is checked for type and shape alone
+    (int_vector) - its values are the kernel's to refuse.  Returns (the int32 tensor on dev, the host's sum or None)."""
+    if torch.is_tensor(v) and v.device.type == "cuda":
+        lengths(fn, name, v, B, dev)
+        return v.to(torch.int32).contiguous(), None
+    try:
+        t = torch.as_tensor(v)
+    except Exception:
+        raise ValueError(f"{fn}: {name} must be {B} integers") from None
+    int_vector(fn, name, t, B)
+    t = t.to(torch.int64)
+    if int(t.min()) < 0 or (hi is not None and int(t.max()) > hi):
+        raise ValueError(f"{fn}: {name} must lie in 0 .. {'' if hi is None else hi}, got {int(t.min())} .. {int(t.max())}")
+    return t.to(torch.int32).to(dev), int(t.sum())

@@ -11,6 +11,7 @@ from . import _args
 from ._args import YIN_MAX_SPAN
 from ._lib import call, make
 # per-character pitch and energy on the duration grid: analysis.char_variance, written in variance.py
+from .join import fade_table, join_audio  # noqa: F401  (pieces joined into one waveform, DESIGN 5.16: analysis.join_audio, in join.py)
 from .variance import VAR_MAX_L, VAR_MAX_T, VAR_NSTAT, VAR_STATS, char_variance  # noqa: F401
 
 PROSODY_MAX_T = 4096        # T2_PROSODY_MAX_T: frames of one utterance in t2_prosody_stats

@@ -28,8 +28,8 @@ from . import _args
 from ._lib import call, make
 # the documented module API: the model-free measurements live in analysis, and engine.<name> is the same object
 from .analysis import (CORPUS_NSTAT, F0_NSTAT, PITCH_MAX_STATES, PROSODY_MAX_T, PROSODY_NSTAT, VITERBI_DEFAULTS, VQ_MAX_CYCLES,  # noqa: F401
-                       YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, f0_figures, f0_path_stats, pitch_viterbi, prosody_stats,
-                       resample, voice_quality, yin, yin_lags)
+                       YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, f0_figures, f0_path_stats, fade_table, join_audio,
+                       pitch_viterbi, prosody_stats, resample, voice_quality, yin, yin_lags)
 from .params import ParamStore, reduction_factor
 
 KL, KPAD = 31, 15

@@ -197,6 +197,19 @@ class TTSModel(nn.Module):
                                     attention_window=attention_window, forward_attention=forward_attention,
                                     stop_threshold=stop_threshold)
 
+    def say_document(self, pieces, encoder, preprocessing: Optional[dict] = None, vocoder=None, **options):
+        """A document spoken as one waveform: run.say.say_document on this model - pieces (datasets.document.Piece, or a text, which
+        is split), the TextEncoder of the model's alphabet, the dataset's `preprocessing` settings (sample_rate, trim_top_db,
+        trim_frame_length; None: the defaults) and a loaded vocoder object (hifigan.Generator or vocoder.GriffinLim; None: a
+        Griffin-Lim for this model's mel bands).  Loads no checkpoint.  Returns (waveform, plan, per-piece dict)."""
+        from ..run.say import say_document
+        pre = dict(preprocessing or {})
+        if vocoder is None:
+            from ..vocoder import GriffinLim
+            vocoder = GriffinLim(n_mels=int(self.hparams["num_mels"]), sample_rate=int(pre.get("sample_rate", 22050)),
+                                 device=next(self.parameters()).device)
+        return say_document(self, pieces, encoder, pre, vocoder, **options)
+
     def _args(self, meta):
         args = {}
         if self.speaker_tokens:
