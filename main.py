@@ -26,7 +26,7 @@ import re
 
 import click
 
-from tacotron2_amd.run.common import load_config
+from tacotron2_amd.run.common import load_config, sample_rate
 
 
 def parse_attention_window(ctx, param, value):
@@ -43,7 +43,7 @@ def parse_guided_attention(ctx, param, value):
     """--guided-attention SIGMA,ALPHA -> (sigma, alpha): two numbers, sigma > 0 and alpha >= 0, anything else a usage error."""
     if value is None:
         return None
-    from tacotron2_amd.engine import check_guided_attention
+    from tacotron2_amd.options import check_guided_attention
     parts = [p.strip() for p in value.split(",")]
     try:
         if len(parts) != 2:
@@ -72,7 +72,7 @@ def parse_stop_threshold(ctx, param, value):
     """--stop-threshold P -> a float with 0 < P < 1, anything else a usage error."""
     if value is None:
         return None
-    from tacotron2_amd.engine import check_stop_threshold
+    from tacotron2_amd.options import check_stop_threshold
     try:
         return check_stop_threshold(float(value))
     except ValueError:
@@ -85,11 +85,19 @@ stop_threshold_option = click.option(
          "Wins over model.stop_threshold of the config. Default: 0.5, the reference's rule.")
 
 
+def decode_options(f):
+    """--attention-window, --forward-attention and --stop-threshold, in this order: the decode settings that say, test and
+    test-correlation share."""
+    for option in (stop_threshold_option, forward_attention_option, attention_window_option):
+        f = option(f)
+    return f
+
+
 def parse_stop_weight(ctx, param, value):
     """--stop-weight W -> a finite float > 0, anything else a usage error."""
     if value is None:
         return None
-    from tacotron2_amd.engine import check_loss_options
+    from tacotron2_amd.options import check_loss_options
     try:
         return check_loss_options({"stop_weight": float(value)})[2]
     except ValueError:
@@ -102,6 +110,15 @@ def forward_attention_arg(forward_attention, attention_window):
     if forward_attention and attention_window is not None:
         raise click.UsageError("--forward-attention and --attention-window do not combine: use one of the two")
     return True if forward_attention else None
+
+
+def config_args(ctx, missing: str) -> dict:
+    """The four sections of --config and --device as the drivers' keyword arguments; without --config an Exception saying `missing`."""
+    c = ctx.obj["config"]
+    if c is None:
+        raise Exception(missing)
+    return dict(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
+                extensions_config=c["extensions"], device=ctx.obj["device"])
 
 
 @click.group()
@@ -145,17 +162,13 @@ def main(ctx, config, device):
 def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_checkpoint=None, finetune=False,
           finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None, forward_attention=False, mel_loss=None,
           masked_loss=None, stop_weight=None):
-    if ctx.obj["config"] is None:
-        raise Exception("Configuration required for training!")
+    cfg = config_args(ctx, "Configuration required for training!")
     if finetune and finetune_steps is None:
         raise Exception("If finetuning, --finetune-steps is required!")
     from tacotron2_amd.run.train import do_train
-    c = ctx.obj["config"]
-    do_train(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
-             extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, results_dir=results_dir,
-             resume_ckpt=resume_ckpt, finetune=finetune, finetune_steps=finetune_steps, max_steps_override=max_steps,
-             synthetic=synthetic, guided_attention=guided_attention, forward_attention=True if forward_attention else None,
-             mel_loss=mel_loss, masked_loss=masked_loss, stop_weight=stop_weight)
+    do_train(**cfg, speech_dir=speech_dir, results_dir=results_dir, resume_ckpt=resume_ckpt, finetune=finetune,
+             finetune_steps=finetune_steps, max_steps_override=max_steps, synthetic=synthetic, guided_attention=guided_attention,
+             forward_attention=True if forward_attention else None, mel_loss=mel_loss, masked_loss=masked_loss, stop_weight=stop_weight)
 
 
 @main.command()
@@ -191,12 +204,10 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--speaker-id", required=False, type=int, default=None, help="Speaker ID for a multi-speaker model")
 @click.option("--controls", required=False, type=str, default=None, help="If controls are enabled, a comma-separated list of values to pass into the model. Defaults to all 0 values.")
 @click.option("--description", required=False, type=str, default=None, help="Path of a precomputed description embedding (.pt / .npy, pooler_output of bert-base-uncased); raw text needs the BERT weights (unavailable offline)")
-@attention_window_option
-@forward_attention_option
+@decode_options
 @click.option("--durations-out", required=False, type=str, default=None, metavar="PATH",
               help="Write character timestamps as JSON: per text the encoded symbols, the mel frames each one lasts (the best "
                    "monotonic path through the decode's own alignments), start_s / end_s, focus_rate and feasible. Default: off.")
-@stop_threshold_option
 @click.option("--out-sample-rate", required=False, type=click.IntRange(min=1), default=None, metavar="R",
               help="Write the audio at R Hz (48000, 44100, 16000, 8000, ...) instead of the model's rate: the vocoded waveform is "
                    "resampled on the GPU. Needs a .wav target; --durations-out times stay in model frames. Default: the model's rate.")
@@ -214,12 +225,8 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
     elif hifi_gan_checkpoint is None and not out.endswith(".wav"):
         raise click.UsageError(f"--text-file needs a .wav target (--out) or --hifi-gan-checkpoint, got --out {out}: a document has no single log-mel")
     forward_attention = forward_attention_arg(forward_attention, attention_window)
-    if ctx.obj["config"] is None:
-        raise Exception("Configuration required for speech!")
-    c = ctx.obj["config"]
-    common = dict(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
-                  extensions_config=c["extensions"], device=ctx.obj["device"], checkpoint=checkpoint, output=out,
-                  speaker_id=speaker_id, hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
+    common = dict(config_args(ctx, "Configuration required for speech!"), checkpoint=checkpoint, output=out, speaker_id=speaker_id,
+                  hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
                   durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len)
     if text_file is None:
@@ -245,9 +252,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
 @click.option("--batch-size", required=False, type=int, default=8, help="Utterances decoded together (reference: 8; up to 64 per decode group).")
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit", required=False, type=int, default=None, help="Only the first n utterances of the test manifest.")
-@attention_window_option
-@forward_attention_option
-@stop_threshold_option
+@decode_options
 @click.option("--score", is_flag=True, default=False,
               help="Also score every decode against its recording (the manifest's wav column under --speech-dir): mel-cepstral "
                    "distortion under dynamic time warping (MCD-DTW, 13 coefficients, dB), duration ratio, stop failures and "
@@ -268,15 +273,11 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
         raise click.UsageError("--f0 needs --score: the tracks are compared along the path of the MCD score")
     if f0 and no_audio:
         raise click.UsageError("--f0 cannot go with --no-audio: there would be no waveform to track")
-    if ctx.obj["config"] is None:
-        raise Exception("Configuration required for testing!")
+    cfg = config_args(ctx, "Configuration required for testing!")
     from tacotron2_amd.run.test import do_test
-    c = ctx.obj["config"]
-    do_test(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
-            extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
-            hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, batch_size=batch_size, max_len=max_len, limit=limit,
-            attention_window=attention_window, forward_attention=forward_attention, stop_threshold=stop_threshold, score=score,
-            audio=not no_audio, **({"f0": True} if f0 else {}))
+    do_test(**cfg, speech_dir=speech_dir, checkpoint=checkpoint, hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir,
+            batch_size=batch_size, max_len=max_len, limit=limit, attention_window=attention_window,
+            forward_attention=forward_attention, stop_threshold=stop_threshold, score=score, audio=not no_audio, **({"f0": True} if f0 else {}))
 
 
 @main.command()
@@ -288,9 +289,7 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
 @click.option("--samples-per-speaker", required=False, type=int, default=200, help="Utterances drawn per speaker (reference: 200).")
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit-overrides", required=False, type=int, default=None, help="Only the first n of the 51 control overrides.")
-@attention_window_option
-@forward_attention_option
-@stop_threshold_option
+@decode_options
 @click.option("--measure", is_flag=True, default=False,
               help="Also measure what comes out, on the GPU: pitch level and range (YIN), intensity, aperiodicity and speaking rate "
                    "of every waveform as prosody.csv in each override directory, and the correlation of every requested control "
@@ -305,29 +304,24 @@ def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_d
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if smooth_pitch and not measure:
         raise click.UsageError("--smooth-pitch needs --measure: without it no pitch is tracked")
-    if ctx.obj["config"] is None:
-        raise Exception("Configuration required for testing!")
+    cfg = config_args(ctx, "Configuration required for testing!")
     from tacotron2_amd.run.test_correlation import do_test_correlation
-    c = ctx.obj["config"]
-    model_config = c["model"] if attention_window is None else dict(c["model"], attention_window=list(attention_window))
-    if forward_attention:      # load_test_model reads it from the model config, as it does the window
-        model_config = dict(model_config, forward_attention=True)
-    if stop_threshold is not None:
-        model_config = dict(model_config, stop_threshold=stop_threshold)
+    given = dict(attention_window=None if attention_window is None else list(attention_window), forward_attention=forward_attention,
+                 stop_threshold=stop_threshold)
+    model_config = dict(cfg["model_config"], **{k: v for k, v in given.items() if v is not None})      # load_test_model reads them there
     if measure:                # the meter travels with the model (load_test_model), the tables need the directory's name afterwards
         import datetime
         model_config = dict(model_config, measure_prosody=True, **({"smooth_pitch": True} if smooth_pitch else {}))
         if results_dir is None:
-            results_dir = f"results_{c['training']['name']}_test_correlation {datetime.datetime.now()}"
-    do_test_correlation(dataset_config=c["dataset"], training_config=c["training"], model_config=model_config,
-                        extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
+            results_dir = f"results_{cfg['training_config']['name']}_test_correlation {datetime.datetime.now()}"
+    do_test_correlation(**dict(cfg, model_config=model_config), speech_dir=speech_dir, checkpoint=checkpoint,
                         hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir, samples_per_speaker=samples_per_speaker,
                         max_len=max_len, limit_overrides=limit_overrides)
     if measure:
         from tacotron2_amd.prosody import ProsodyMeter
         from tacotron2_amd.run.correlation import correlate_tree
-        sr = int(c["dataset"].get("preprocessing", {}).get("sample_rate", 22050))
-        correlate_tree(results_dir, c["extensions"]["controls"]["features"], ProsodyMeter(sr, f"cuda:{ctx.obj['device']}", smooth=smooth_pitch).describe())
+        meter = ProsodyMeter(sample_rate(cfg["dataset_config"].get("preprocessing", {})), f"cuda:{cfg['device']}", smooth=smooth_pitch)
+        correlate_tree(results_dir, cfg["extensions_config"]["controls"]["features"], meter.describe())
 
 
 @main.command()
@@ -360,13 +354,9 @@ def measure_correlation(ctx, results_dir, features=None):
 @click.option("--results-dir", required=False, type=str, default=None, help="The directory to save results. Defaults to the model configuration name with a timestamp.")
 def train_mel_export(ctx, speech_dir, checkpoint, results_dir=None):
     """Teacher-forced post-net mels of the train + val manifests (run/train_mel_export.py of the reference)."""
-    if ctx.obj["config"] is None:
-        raise Exception("Configuration required!")
+    cfg = config_args(ctx, "Configuration required!")
     from tacotron2_amd.run.train_mel_export import do_train_mel_export
-    c = ctx.obj["config"]
-    do_train_mel_export(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
-                        extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
-                        results_dir=results_dir)
+    do_train_mel_export(**cfg, speech_dir=speech_dir, checkpoint=checkpoint, results_dir=results_dir)
 
 
 @main.command()
@@ -399,13 +389,9 @@ def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monoton
                                        ("--frame-level", frame_level), ("--no-smooth-pitch", no_smooth_pitch)) if on]
         if given:
             raise click.UsageError(f"{', '.join(given)} need{'s' if len(given) == 1 else ''} --variances")
-    if ctx.obj["config"] is None:
-        raise Exception("Configuration required!")
+    cfg = config_args(ctx, "Configuration required!")
     from tacotron2_amd.run.duration_export import do_duration_export
-    c = ctx.obj["config"]
-    do_duration_export(dataset_config=c["dataset"], training_config=c["training"], model_config=c["model"],
-                       extensions_config=c["extensions"], device=ctx.obj["device"], speech_dir=speech_dir, checkpoint=checkpoint,
-                       results_dir=results_dir, mode=mode, variances=variances, pitch_domain=pitch_domain or "log",
+    do_duration_export(**cfg, speech_dir=speech_dir, checkpoint=checkpoint, results_dir=results_dir, mode=mode, variances=variances, pitch_domain=pitch_domain or "log",
                        interpolate_pitch=interpolate_pitch, frame_level=frame_level, smooth_pitch=not no_smooth_pitch)
 
 

@@ -14,9 +14,7 @@ the hardware:
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import math
-import numbers
 import threading as _threading
 from typing import Dict, NamedTuple, Optional
 
@@ -30,6 +28,9 @@ from ._lib import call, make
 from .analysis import (CORPUS_NSTAT, F0_NSTAT, PITCH_MAX_STATES, PROSODY_MAX_T, PROSODY_NSTAT, VITERBI_DEFAULTS, VQ_MAX_CYCLES,  # noqa: F401
                        YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, f0_figures, f0_path_stats, fade_table, join_audio,
                        pitch_viterbi, prosody_stats, resample, voice_quality, yin, yin_lags)
+# likewise the option checks, which live in options (no torch, no library) and are served from here as before
+from .options import (LOSS_DEFAULTS, MEL_LOSSES, check_attention_window, check_forward_attention, check_guided_attention,  # noqa: F401
+                      check_loss_options, check_rate, check_stop_threshold, stop_logit)
 from .params import ParamStore, reduction_factor
 
 KL, KPAD = 31, 15
@@ -91,109 +92,15 @@ def chunk_splits(frames: int, B: int, D: int) -> int:
     return max(1, min(4, 256 // max(tiles, 1)))
 
 
-def check_attention_window(window):
-    """None, or (back, fwd) as two integers >= 0 -> the same as a tuple of ints; anything else raises ValueError."""
-    if window is None:
-        return None
-    try:
-        back, fwd = window
-    except (TypeError, ValueError):
-        raise ValueError(f"attention_window must be (back, fwd), got {window!r}") from None
-    for v in (back, fwd):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0:
-            raise ValueError(f"attention_window must be two integers >= 0, got {window!r}")
-    return int(back), int(fwd)
-
-
-def check_forward_attention(forward, window=None):
-    """True or False -> the same; anything else, or True together with an attention window, raises ValueError."""
-    if not isinstance(forward, bool):
-        raise ValueError(f"forward_attention must be True or False, got {forward!r}")
-    if forward and window is not None:
-        raise ValueError("forward_attention does not compose with attention_window: use one of the two")
-    return forward
-
-
-def check_rate(p, name: str, closed: bool = False) -> float:
-    """A probability in [0, 1) - or [0, 1] with closed=True - as a float; anything else is a ValueError that names the option."""
-    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0 or (closed and float(p) == 1.0)):
-        raise ValueError(f"{name} must be a number in [0, 1{']' if closed else ')'}, got {p!r}")
-    return float(p)
-
-
 def zone_stride(z, n: int) -> int:
     """Per-step element increment of a zone mask [S][B][H]: 0 for ONE (B, H) block that serves every step (eval: filled with the rate)."""
     return 0 if z is None or z.shape[0] == 1 else n
-
-
-def check_guided_attention(guided):
-    """None, or (sigma, alpha) of the guided-attention loss as two real numbers, sigma > 0 and alpha >= 0 -> a tuple of floats;
-    anything else raises ValueError."""
-    if guided is None:
-        return None
-    try:
-        sigma, alpha = guided
-    except (TypeError, ValueError):
-        raise ValueError(f"guided_attention must be (sigma, alpha), got {guided!r}") from None
-    for v in (sigma, alpha):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or abs(v) == float("inf"):
-            raise ValueError(f"guided_attention must be two finite numbers (sigma, alpha), got {guided!r}")
-    if sigma <= 0 or alpha < 0:
-        raise ValueError(f"guided_attention needs sigma > 0 and alpha >= 0, got {guided!r}")
-    return float(sigma), float(alpha)
-
-
-MEL_LOSSES = ("l2", "l1", "l1+l2")       # T2LossOpts.mel_loss = the index
-LOSS_DEFAULTS = ("l2", False, 1.0)
-
-
-def check_loss_options(loss):
-    """None, a dict with any of the keys "mel" / "masked" / "stop_weight", or a 3-tuple (mel, masked, stop_weight) -> the tuple
-    (mel in MEL_LOSSES, masked bool, stop_weight float > 0), missing keys at their defaults ("l2", False, 1.0: the reference's loss);
-    anything else raises ValueError naming the offending value."""
-    if loss is None:
-        return LOSS_DEFAULTS
-    if isinstance(loss, dict):
-        unknown = sorted(set(loss) - {"mel", "masked", "stop_weight"})
-        if unknown:
-            raise ValueError(f"loss options: unknown key {unknown[0]!r} (known: mel, masked, stop_weight)")
-        mel, masked, w = (loss.get(k, dflt) for k, dflt in zip(("mel", "masked", "stop_weight"), LOSS_DEFAULTS))
-    else:
-        try:
-            mel, masked, w = loss
-        except (TypeError, ValueError):
-            raise ValueError(f"loss options must be a dict or (mel, masked, stop_weight), got {loss!r}") from None
-    if not isinstance(mel, str) or mel not in MEL_LOSSES:
-        raise ValueError(f"loss options: mel must be one of {', '.join(MEL_LOSSES)}, got {mel!r}")
-    if not isinstance(masked, bool):
-        raise ValueError(f"loss options: masked must be True or False, got {masked!r}")
-    if isinstance(w, bool) or not isinstance(w, numbers.Real) or w != w or abs(w) == float("inf") or w <= 0:
-        raise ValueError(f"loss options: stop_weight must be a finite number > 0, got {w!r}")
-    if not 0.0 < float(ctypes.c_float(float(w)).value) < float("inf"):
-        raise ValueError(f"loss options: stop_weight must be a finite float32 > 0, got {w!r}")
-    return mel, masked, float(w)
 
 
 def loss_opts_struct(loss):
     """The T2LossOpts block of checked options."""
     mel, masked, w = loss
     return make("T2LossOpts", mel_loss=MEL_LOSSES.index(mel), masked=int(masked), stop_weight=w)
-
-
-def check_stop_threshold(tau) -> float:
-    """A stop threshold 0 < tau < 1 as a float (0.5: the reference's rule); anything else raises ValueError."""
-    if isinstance(tau, bool) or not isinstance(tau, numbers.Real) or not 0.0 < float(tau) < 1.0:
-        raise ValueError(f"stop_threshold must be a number with 0 < threshold < 1, got {tau!r}")
-    return float(tau)
-
-
-def stop_logit(tau: float) -> float:
-    """logit(tau) = log(tau / (1 - tau)) formed in double and rounded to float32: the ONE value the decode loop's flags, the scan
-    and the drivers' length rule compare against.  0.5 gives 0.0, the reference's comparison."""
-    v = float(ctypes.c_float(math.log(tau / (1.0 - tau))).value)
-    if v != v or abs(v) == float("inf"):
-        raise ValueError(f"stop_threshold {tau!r} has no finite float32 logit")
-    return v
 
 
 def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:

@@ -1,8 +1,13 @@
-"""Config handling shared by train/say: the reference's four-section JSON (main.py:95-99) with the staleness rules of
-SURVEY.md section 5: `char_embedding_dim` is an alias of `encoded_dim`; missing `extensions.*` sections are inactive."""
+"""Config handling shared by the drivers: the reference's four-section JSON (main.py:95-99) with the staleness rules of
+SURVEY.md section 5: `char_embedding_dim` is an alias of `encoded_dim`; missing `extensions.*` sections are inactive.  And what
+the decoding drivers (say, test, test-correlation) share: the loader, the text encoding, the free-running call, `say`'s frame rule."""
 from __future__ import annotations
 
 import json
+
+# the resolvers of an option against its config key live in options; run.common.<name> is the same object
+from ..options import (decode_settings, decode_settings_of, guided_attention_setting, loss_options_setting,  # noqa: F401
+                       stop_threshold_setting, train_forward_attention_setting)
 
 
 def load_config(path: str) -> dict:
@@ -34,53 +39,54 @@ def model_kwargs(cfg: dict) -> dict:
                 scheduler_milestones=[int(x * max_steps) for x in md.get("scheduler_milestones", [])], **args)
 
 
-def train_forward_attention_setting(training_config: dict, override=None) -> bool:
-    """Forward attention under teacher forcing (training, validation, train-mel-export): `override` (True for the
-    `--forward-attention` flag of `main.py train`, None without it) wins over `"training": {"forward_attention": true}`; default off.
-    A value that is not a bool raises ValueError."""
-    from ..engine import check_forward_attention
-    if override is not None:
-        return check_forward_attention(override)
-    return check_forward_attention(training_config.get("forward_attention", False))
+# (torch is imported where it is used: main.py imports this module, and a usage error must not wait for it)
+def sample_rate(pre: dict) -> int:
+    """The sample rate of a `dataset.preprocessing` section."""
+    return int(pre.get("sample_rate", 22050))
 
 
-def loss_options_setting(training_config: dict, mel=None, masked=None, stop_weight=None):
-    """(mel, masked, stop_weight) of the training loss (engine.check_loss_options): each of `mel` (--mel-loss), `masked` (True / False for
-    --masked-loss / --no-masked-loss) and `stop_weight` (--stop-weight) wins, when it is not None, over its key of
-    `"training": {"loss": {"mel": "l1+l2", "masked": true, "stop_weight": 8.0}}`; any key may be left out ("l2", false, 1.0: the
-    reference's loss).  A section of another form or a bad value raises ValueError naming it."""
-    from ..engine import check_loss_options
-    sec = training_config.get("loss")
-    if sec is None:
-        sec = {}
-    if not isinstance(sec, dict):
-        raise ValueError('training.loss must be an object with the keys "mel", "masked" and "stop_weight" '
-                         f'(e.g. {{"mel": "l1+l2", "masked": true, "stop_weight": 8.0}}), got {sec!r}')
-    sec = dict(sec)
-    for key, v in (("mel", mel), ("masked", masked), ("stop_weight", stop_weight)):
-        if v is not None:
-            sec[key] = v
-    return check_loss_options(sec)
+def load_decode_model(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, checkpoint: str, dev,
+                      random_seed=None, attention_window=None, forward_attention=None, stop_threshold=None, **model_overrides):
+    """The checkpoint as a TTSModel in eval mode, built with model_kwargs of the config (model_overrides on top), seeded with
+    random_seed if there is one, and with decode_settings of the three options on the three attributes free_run reads them from."""
+    from ..model.tts_model import TTSModel
+    cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
+    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **dict(model_kwargs(cfg), **model_overrides))
+    model.eval()
+    if random_seed is not None:
+        model.tacotron2._seed = int(random_seed)
+    model.attention_window, model.forward_attention, model.stop_threshold = decode_settings(
+        model_config, attention_window, forward_attention, stop_threshold)
+    return model
 
 
-def stop_threshold_setting(model_config: dict, override=None) -> float:
-    """The decode stop threshold 0 < tau < 1: `override` (the --stop-threshold option) wins over `"model": {"stop_threshold": 0.4}`;
-    default 0.5, the reference's rule.  Anything else raises ValueError."""
-    from ..engine import check_stop_threshold
-    return check_stop_threshold(override if override is not None else model_config.get("stop_threshold", 0.5))
+def pad_ids(ids: list, dev):
+    """Encoded texts -> (chars (B, longest) int64, zero-padded; lens (B,) int64), both on dev."""
+    import torch
+    return torch.nn.utils.rnn.pad_sequence(ids, batch_first=True).to(dev), torch.tensor([len(i) for i in ids], dtype=torch.int64, device=dev)
 
 
-def guided_attention_setting(training_config: dict, override=None):
-    """(sigma, alpha) of the guided-attention loss, or None when it is off: `override` (the --guided-attention option) wins over
-    `"training": {"guided_attention": {"sigma": 0.4, "alpha": 1.0}}` (either key may be left out: 0.4 and 1.0).  A section of
-    another form, sigma <= 0 or alpha < 0 raises ValueError."""
-    from ..engine import check_guided_attention
-    if override is not None:
-        return check_guided_attention(override)
-    sec = training_config.get("guided_attention")
-    if sec is None or sec is False:
-        return None
-    if not isinstance(sec, dict) or set(sec) - {"sigma", "alpha"}:
-        raise ValueError('training.guided_attention must be an object with the keys "sigma" and "alpha" '
-                         f'(e.g. {{"sigma": 0.4, "alpha": 1.0}}), got {sec!r}')
-    return check_guided_attention((sec.get("sigma", 0.4), sec.get("alpha", 1.0)))
+def encode_texts(enc, texts, dev=None):
+    """(ids - one int64 host tensor per text, enc.encode of it -, chars, lens): pad_ids of all of them as one batch, or None and
+    None without a device, for a driver that pads batch by batch."""
+    import torch
+    ids = [torch.tensor(enc.encode(t), dtype=torch.int64) for t in texts]
+    return (ids, *(pad_ids(ids, dev) if dev is not None else (None, None)))
+
+
+def free_run(model, chars, lens, max_len: int, **conditioning):
+    """The free-running decode of a padded batch under the settings that are on the model -> (post, gates, align)."""
+    import torch
+    with torch.no_grad():
+        return model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
+                     **decode_settings_of(model).kwargs(), **conditioning)[1:]
+
+
+def emitted_frames(gates, n_emitted: int):
+    """(frames: List[int], stopped: List[bool]): `say`'s frames per utterance of a decode with n_emitted frames, and whether it stopped.
+    run/say.py:155,161 keeps mel_spectrogram_post[:, :-1]: all emitted frames but the last.  The stop frame itself is already
+    masked (gate -1000 from `lengths` on), so an utterance that stopped keeps its `lengths` = n - 1 frames; one that ran into
+    max_len without stopping has n unmasked frames and loses the last one, as in the reference.  (A stop threshold changes
+    `lengths`, not this rule: it reads the mask, never a logit's sign.)  Counted where gates (B, n, 1) lives; one vector is read."""
+    valid = (gates[:, :, 0] != -1000.0).sum(1).cpu().tolist()
+    return [max(min(v, n_emitted - 1), 1) for v in valid], [v < n_emitted for v in valid]

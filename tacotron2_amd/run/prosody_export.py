@@ -23,6 +23,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from ..prosody import FEATURES
+from .common import sample_rate
 
 SPLITS = ("train", "val", "test")
 DROPPED_HEADER = ["manifest", "wav", "reason"]
@@ -175,7 +176,7 @@ def do_prosody_export(dataset_config: dict, extensions_config: dict, device: int
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = {k: v for k, v in dataset_config.get("preprocessing", {}).items() if k not in ("cache", "cache_dir")}
-    sr = int(pre.get("sample_rate", 22050))
+    sr = sample_rate(pre)
     meter = ProsodyMeter(sr, dev, smooth=smooth_pitch)
     pool = ThreadPoolExecutor(max_workers=host_threads())
     frames, feats, reasons, n_utts = {}, {}, {}, 0

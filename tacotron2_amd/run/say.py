@@ -5,15 +5,15 @@ run/say.py:161-171 takes without a HiFi-GAN checkpoint), or HiFi-GAN audio with 
 run/say.py:66-86,153-159)."""
 from __future__ import annotations
 
+import json
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
-from ..engine import check_attention_window, check_forward_attention
-from ..model.tts_model import TTSModel
-from .common import model_kwargs, stop_threshold_setting
+from .common import emitted_frames, encode_texts, free_run, load_decode_model, pad_ids, sample_rate
+from .test import make_vocoders
 
 
 def load_description(description: Optional[str], dim: int, n: int, dev) -> torch.Tensor:
@@ -56,35 +56,6 @@ def duration_records(model, enc: TextEncoder, texts: List[str], align: torch.Ten
     return out
 
 
-def write_durations(path: str, model, enc: TextEncoder, texts: List[str], align: torch.Tensor, lens: torch.Tensor,
-                    frames: List[int], sample_rate: int, hop: int = 256) -> list:
-    """`say --durations-out`: duration_records of the decode, as a JSON list."""
-    import json
-    out = duration_records(model, enc, texts, align, lens, frames, sample_rate, hop)
-    with open(path, "w") as f:
-        json.dump(out, f)
-    return out
-
-
-def load_say_model(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, dev, checkpoint: str,
-                   random_seed: Optional[int], attention_window, forward_attention: Optional[bool], stop_threshold: Optional[float]):
-    """The checkpoint in eval mode with the decode settings of `say` on it (seed, attention window, forward attention, stop
-    threshold; None takes the config's): what do_say and do_say_document share."""
-    cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
-    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **model_kwargs(cfg))
-    model.eval()
-    if random_seed is not None:
-        model.tacotron2._seed = int(random_seed)
-    if attention_window is None:       # the config's model.attention_window, if any (as load_test_model does)
-        attention_window = model_config.get("attention_window")
-    model.attention_window = check_attention_window(attention_window)
-    if forward_attention is None:      # likewise the config's model.forward_attention (a bool)
-        forward_attention = model_config.get("forward_attention", False)
-    model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
-    model.stop_threshold = stop_threshold_setting(model_config, stop_threshold)
-    return model
-
-
 def conditioning(model, n: int, dev, speaker_id: Optional[int], controls: Optional[str], description: Optional[str]) -> dict:
     """The speaker, description and control inputs of n texts, as the model's keyword arguments."""
     kw = {}
@@ -99,6 +70,15 @@ def conditioning(model, n: int, dev, speaker_id: Optional[int], controls: Option
         assert len(vals) == n_ctl, f"--controls needs {n_ctl} comma-separated values"
         kw["controls"] = torch.tensor([vals] * n, dtype=torch.float32, device=dev)
     return kw
+
+
+def output_resampler(pre: dict, out_sample_rate: Optional[int], dev):
+    """The datasets.resample.Resampler of --out-sample-rate, None without one; a bad rate is refused here, before anything is decoded."""
+    if out_sample_rate is None:
+        return None
+    from ..datasets.resample import Resampler, plan
+    plan(sample_rate(pre), int(out_sample_rate))
+    return Resampler(int(out_sample_rate), dev)
 
 
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
@@ -119,63 +99,39 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
-    to_rate = None
-    if out_sample_rate is not None:
-        if hifi_gan_checkpoint is None and not output.endswith(".wav"):
-            raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
-        from ..datasets.resample import Resampler, plan
-        plan(int(pre.get("sample_rate", 22050)), int(out_sample_rate))      # (refuses a bad rate before anything is decoded)
-        resampler = Resampler(int(out_sample_rate), dev)
-        to_rate = lambda wav, sr: torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
+    if out_sample_rate is not None and hifi_gan_checkpoint is None and not output.endswith(".wav"):
+        raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
+    resampler = output_resampler(pre, out_sample_rate, dev)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
-    ids = [torch.tensor(enc.encode(t), dtype=torch.int64) for t in texts]
-    chars = torch.nn.utils.rnn.pad_sequence(ids, batch_first=True).to(dev)
-    lens = torch.tensor([len(i) for i in ids], dtype=torch.int64, device=dev)
-    model = load_say_model(dataset_config, training_config, model_config, extensions_config, dev, checkpoint, random_seed,
-                           attention_window, forward_attention, stop_threshold)
-    kw = conditioning(model, len(texts), dev, speaker_id, controls, description)
-    with torch.no_grad():
-        _, post, gates, align = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                      attention_window=model.attention_window, forward_attention=model.forward_attention,
-                                      stop_threshold=model.stop_threshold, **kw)
-    post = post.cpu().numpy()
-    # run/say.py:155,161 keeps mel_spectrogram_post[:, :-1]: all emitted frames but the last.  The stop frame itself is already
-    # masked (gate -1000 from `lengths` on), so an utterance that stopped keeps its `lengths` = n - 1 frames; one that ran into
-    # max_len without stopping has n unmasked frames and loses the last one, as in the reference.  (A stop threshold changes
-    # `lengths`, not this rule: it reads the mask, never a logit's sign.)
-    valid = (gates.cpu().numpy()[:, :, 0] != -1000.0).sum(1)
-    n_emitted = post.shape[1]
-    mels = [post[b, :max(min(int(valid[b]), n_emitted - 1), 1)] for b in range(len(texts))]
+    _, chars, lens = encode_texts(enc, texts, dev)
+    model = load_decode_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
+                              attention_window, forward_attention, stop_threshold)
+    post, gates, align = free_run(model, chars, lens, max_len, **conditioning(model, len(texts), dev, speaker_id, controls, description))
+    frames, _ = emitted_frames(gates, post.shape[1])
+    mels = [m[:n] for m, n in zip(post.cpu().numpy(), frames)]
+    sr = sample_rate(pre)
     if durations_out is not None:
-        write_durations(durations_out, model, enc, texts, align, lens, [len(m) for m in mels], int(pre.get("sample_rate", 22050)))
-    if hifi_gan_checkpoint is not None:
+        with open(durations_out, "w") as f:
+            json.dump(duration_records(model, enc, texts, align, lens, frames, sr), f)
+    if hifi_gan_checkpoint is None and not output.endswith(".wav"):
+        np.save(output, mels[0] if isinstance(text, str) else np.array(mels, dtype=object), allow_pickle=not isinstance(text, str))
+        return mels
+    from ..vocoder import write_wav
+    gen, gl, _ = make_vocoders(hifi_gan_checkpoint, dict(pre, num_mels=post.shape[2]), dev)
+    if gen is not None:
         # run/say.py:66-86,153-159: generator(mel_post[:, :-1].swapaxes(1, 2)) -> waveform, written as audio whatever the name
-        from ..hifigan import Generator
-        from ..vocoder import write_wav
-        sr = int(pre.get("sample_rate", 22050))
-        gen = Generator.from_checkpoint(hifi_gan_checkpoint, device=dev)
-        for i, m in enumerate(mels):
-            wav = gen(torch.from_numpy(np.ascontiguousarray(m.T)).to(dev))[0, 0].cpu()
-            name = output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav"
-            if to_rate is not None:
-                write_wav(name, to_rate(wav, sr), int(out_sample_rate))
-            else:
-                write_wav(name, wav, sr)
-        return mels
-    if output.endswith(".wav"):
-        from ..vocoder import GriffinLim, write_wav
-        sr = int(pre.get("sample_rate", 22050))
-        gl = GriffinLim(n_mels=post.shape[2], sample_rate=sr, device=dev)
-        for i, m in enumerate(mels):
-            name = output if isinstance(text, str) else f"{output[:-4]}_{i}.wav"
-            wav = gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0))
-            if to_rate is not None:
-                write_wav(name, to_rate(wav, sr), int(out_sample_rate))
-            else:
-                write_wav(name, wav, sr)
-        return mels
-    np.save(output, mels[0] if isinstance(text, str) else np.array(mels, dtype=object), allow_pickle=not isinstance(text, str))
+        vocode = lambda m: gen(torch.from_numpy(np.ascontiguousarray(m.T)).to(dev))[0, 0].cpu()
+    else:
+        vocode = lambda m: gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0))
+    for i, m in enumerate(mels):
+        # several texts: `<output without its extension>_<i>.wav`.  Griffin-Lim is reached with a name that ends in ".wav" only, whose
+        # last dot is that extension's, so this is the `output[:-4]` of the reference's branch as well
+        name = output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav"
+        wav = vocode(m)
+        if resampler is not None:
+            wav = torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
+        write_wav(name, wav, sr if resampler is None else int(out_sample_rate))
     return mels
 
 
@@ -190,11 +146,10 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                  durations: bool = False):
     """Pieces (datasets.document.Piece, or a text, which is split at the defaults) -> one waveform on the model's device.
     The pieces are sorted by encoded length and decoded in chunks of batch_size through the model's free-running forward, with the
-    decode settings that are on the model (attention_window, forward_attention, stop_threshold; none, off and 0.5 where it has
-    none).  `vocoder` is a loaded
-    hifigan.Generator - each chunk's PADDED batch is vocoded in one call and cut at frames * 256, as `test` does, so a row's last
-    samples see the padding inside the generator's receptive field, which `say --text` of one piece does not - or a
-    vocoder.GriffinLim, which runs per piece.  The rows go back into document order in one padded buffer, and one
+    decode settings that are on the model (common.free_run).  `vocoder` is a loaded hifigan.Generator - each chunk's PADDED batch
+    is vocoded in one call and cut at frames * 256, as `test` does, so a row's last samples see the padding inside the generator's
+    receptive field, which `say --text` of one piece does not - or a vocoder.GriffinLim, which runs per piece.  The rows go back
+    into document order in one padded buffer, and one
     analysis.join_audio call trims (dataset.preprocessing's trim_top_db and trim_frame_length, the hop a quarter of it, 20 ms kept
     at both ends), levels, fades and joins them, with pauses[break_after] seconds behind each piece.
     A piece that ran into max_len without stopping is kept, cut there, and marked stopped=False.
@@ -212,25 +167,17 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     if isinstance(batch_size, bool) or not isinstance(batch_size, int) or not 1 <= batch_size <= 64:
         raise ValueError(f"say_document: batch_size must be an integer in 1 .. 64, got {batch_size!r}")
     dev = next(model.parameters()).device
-    sr = int(pre.get("sample_rate", 22050))
+    sr = sample_rate(pre)
     texts = [p.text for p in pieces]
-    ids = [torch.tensor(enc.encode(t), dtype=torch.int64) for t in texts]
+    ids, _, _ = encode_texts(enc, texts)
     order = sorted(range(len(ids)), key=lambda i: (len(ids[i]), i))
     chunks = [order[k:k + batch_size] for k in range(0, len(order), batch_size)]
     P = len(pieces)
     waves, frames, stopped, records = [None] * P, [0] * P, [False] * P, [None] * P
     for ch in chunks:
-        chars = torch.nn.utils.rnn.pad_sequence([ids[i] for i in ch], batch_first=True).to(dev)
-        lens = torch.tensor([len(ids[i]) for i in ch], dtype=torch.int64, device=dev)
-        kw = conditioning(model, len(ch), dev, speaker_id, controls, description)
-        with torch.no_grad():
-            _, post, gates, align = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                          attention_window=getattr(model, "attention_window", None),
-                                          forward_attention=getattr(model, "forward_attention", False),
-                                          stop_threshold=getattr(model, "stop_threshold", 0.5), **kw)
-        n_emitted = post.shape[1]
-        valid = (gates[:, :, 0] != -1000.0).sum(1).cpu().tolist()             # (do_say's rule: all emitted frames but the last)
-        fr = [max(min(int(v), n_emitted - 1), 1) for v in valid]
+        chars, lens = pad_ids([ids[i] for i in ch], dev)
+        post, gates, align = free_run(model, chars, lens, max_len, **conditioning(model, len(ch), dev, speaker_id, controls, description))
+        fr, stop = emitted_frames(gates, post.shape[1])
         if durations:
             for i, rec in zip(ch, duration_records(model, enc, [texts[i] for i in ch], align, lens, fr, sr)):
                 records[i] = rec
@@ -241,7 +188,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
             out = [torch.as_tensor(vocoder.mel_to_audio(post[k, :fr[k]], seed=int(random_seed or 0))).float().reshape(-1).to(dev)
                    for k in range(len(ch))]
         for k, i in enumerate(ch):
-            waves[i], frames[i], stopped[i] = out[k], fr[k], valid[k] < n_emitted
+            waves[i], frames[i], stopped[i] = out[k], fr[k], stop[k]
     n = [int(w.numel()) for w in waves]
     buf = torch.zeros(P, max(max(n), 1), dtype=torch.float32, device=dev)
     for i, w in enumerate(waves):
@@ -298,12 +245,10 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     the joined waveform is resampled to out_sample_rate if given (one Resampler call) and written by ONE write_wav call.
     durations_out: document_records as a JSON list.  A piece that did not stop is reported on stderr; the exit status stays 0.
     Returns say_document's (y, plan, info), y as written (after resampling)."""
-    import json
     import sys
     import time
     from .. import vocoder as V
     from ..datasets.document import expand_numbers as expand, split_document
-    from .test import make_vocoders
     if hifi_gan_checkpoint is None and not output.endswith(".wav"):
         raise ValueError(f"--text-file needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a document has no single log-mel")
     if fade_ms < 0:
@@ -313,12 +258,8 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
-    sr = int(pre.get("sample_rate", 22050))
-    resampler = None
-    if out_sample_rate is not None:
-        from ..datasets.resample import Resampler, plan
-        plan(sr, int(out_sample_rate))                                      # (refuses a bad rate before anything is decoded)
-        resampler = Resampler(int(out_sample_rate), dev)
+    sr = sample_rate(pre)
+    resampler = output_resampler(pre, out_sample_rate, dev)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     with open(text_file, encoding="utf-8") as f:
         text = f.read()
@@ -328,8 +269,8 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     pieces = split_document(text, max_chars=max_chars, clean=lambda t: enc.clean(t)[:len(enc.clean(t)) - n_end])
     if not pieces:
         raise ValueError(f"--text-file {text_file!r}: nothing to say - no piece of the text survives cleaning")
-    model = load_say_model(dataset_config, training_config, model_config, extensions_config, dev, checkpoint, random_seed,
-                           attention_window, forward_attention, stop_threshold)
+    model = load_decode_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
+                              attention_window, forward_attention, stop_threshold)
     gen, gl, _ = make_vocoders(hifi_gan_checkpoint, dict(pre, num_mels=int(model.hparams.get("num_mels", pre.get("num_mels", 80)))), dev)
     y, plan_, info = say_document(model, pieces, enc, pre, gen if gen is not None else gl, max_len=max_len, batch_size=batch_size,
                                   pauses=pauses, trim=trim, level=level, fade_ms=fade_ms, speaker_id=speaker_id, controls=controls,

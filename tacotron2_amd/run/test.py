@@ -38,42 +38,26 @@ import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
-from ..engine import check_attention_window, check_forward_attention, stop_logit
-from ..model.tts_model import TTSModel
-from .common import model_kwargs, stop_threshold_setting
+from ..model.tts_model import TTSModel      # noqa: F401  (load_decode_model's class, under the name it always had here)
+from ..options import decode_settings_of, stop_logit
+from .common import encode_texts, free_run, load_decode_model, pad_ids, sample_rate
 
 
 def load_test_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed=None,
                     attention_window=None, forward_attention=None, stop_threshold=None):
-    """TTSModel.load_from_checkpoint as run/test.py:116-130 calls it (max_len_override 5000, no scheduler), in eval mode.
-    attention_window: (back, fwd) of the windowed attention the model decodes with (TTSModel.attention_window); None takes the
-    config's `model.attention_window` if there is one (`main.py --attention-window` puts it there for test-correlation), else off.
-    forward_attention: True decodes with forward attention (TTSModel.forward_attention); None takes the config's
-    `model.forward_attention` (a bool; `main.py --forward-attention` puts it there for test-correlation), else off.  Forward
-    attention together with a window is refused.
-    stop_threshold: 0 < tau < 1 of the decode's stop rule (TTSModel.stop_threshold); None takes the config's `model.stop_threshold`
-    (`main.py --stop-threshold` puts it there for test-correlation), else 0.5.
+    """TTSModel.load_from_checkpoint as run/test.py:116-130 calls it (max_len_override 5000, no scheduler), in eval mode
+    (load_decode_model).  attention_window (back, fwd), forward_attention (a bool) and stop_threshold (0 < tau < 1) are what the
+    model decodes with (TTSModel's attributes of these names); None takes the config's `model.<name>` if there is one (`main.py`
+    puts its options there for test-correlation), else off, off and 0.5 (options.decode_settings).  Forward attention together
+    with a window is refused.
     The config's `model.measure_prosody` (a bool; `main.py test-correlation --measure` puts it there, as it does the settings above)
     gives the model a prosody.ProsodyMeter as `model.prosody_meter`, which synthesize_manifest then measures with; the config's
     `model.smooth_pitch` (`--smooth-pitch`) builds it with smooth=True."""
-    cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
-    kw = model_kwargs(cfg)
-    kw["scheduler_milestones"] = []
-    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **kw)
-    model.eval()
-    if random_seed is not None:
-        model.tacotron2._seed = int(random_seed)
-    if attention_window is None:
-        attention_window = model_config.get("attention_window")
-    model.attention_window = check_attention_window(attention_window)
-    if forward_attention is None:
-        forward_attention = model_config.get("forward_attention", False)
-    model.forward_attention = check_forward_attention(forward_attention, model.attention_window)
-    model.stop_threshold = stop_threshold_setting(model_config, stop_threshold)
+    model = load_decode_model(dataset_config, training_config, model_config, extensions_config, checkpoint, dev, random_seed,
+                              attention_window, forward_attention, stop_threshold, scheduler_milestones=[])
     if model_config.get("measure_prosody", False):
         from ..prosody import ProsodyMeter
-        model.prosody_meter = ProsodyMeter(int(dataset_config["preprocessing"].get("sample_rate", 22050)), dev,
-                                           smooth=bool(model_config.get("smooth_pitch", False)))
+        model.prosody_meter = ProsodyMeter(sample_rate(dataset_config["preprocessing"]), dev, smooth=bool(model_config.get("smooth_pitch", False)))
     return model
 
 
@@ -92,7 +76,7 @@ def check_force_speaker(extensions_config: dict):
 def make_vocoders(hifi_gan_checkpoint, pre, dev):
     """(HiFi-GAN generator or None, Griffin-Lim or None, sample rate)."""
     from ..vocoder import GriffinLim
-    sr = int(pre.get("sample_rate", 22050))
+    sr = sample_rate(pre)
     if hifi_gan_checkpoint is not None:
         from ..hifigan import Generator
         return Generator.from_checkpoint(hifi_gan_checkpoint, device=dev), None, sr
@@ -203,9 +187,10 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     if f0 and not (score and audio):
         raise ValueError("test: f0=True (--f0) needs score=True (--score) and audio (no --no-audio): it tracks the waveforms")
     dev = model.tacotron2.store.device
+    s = decode_settings_of(model)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), bool(pre.get("expand_abbreviations", False)))
     texts = [enc.clean(t) for t in df.text]
-    ids = [torch.tensor(enc.encode(t), dtype=torch.int64) for t in df.text]
+    ids, _, _ = encode_texts(enc, df.text)
     desc_paths = None
     if model.description_embeddings:
         desc_paths = [None if isinstance(x, float) else x for x in df.description_embedding] \
@@ -214,8 +199,8 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     speaker_ids = list(df.speaker_id) if model.speaker_tokens else None
     written: List[str] = []
     recordings, score_rows, prosody_rows, f0_rows, f0_meter = None, [], [], [], None
-    if meter is None:
-        meter = getattr(model, "prosody_meter", None)
+    if meter is None and hasattr(model, "prosody_meter"):
+        meter = model.prosody_meter
     if score:
         from ..datasets.tts_dataset import TTSDataset
         check_recordings(df, speech_dir)
@@ -233,8 +218,7 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     i = 0
     for b0 in range(0, len(df), batch_size):
         sel = list(range(b0, min(len(df), b0 + batch_size)))
-        chars = torch.nn.utils.rnn.pad_sequence([ids[j] for j in sel], batch_first=True).to(dev)
-        lens = torch.tensor([len(ids[j]) for j in sel], dtype=torch.int64, device=dev)
+        chars, lens = pad_ids([ids[j] for j in sel], dev)
         args = {}
         if speaker_ids is not None:
             args["speaker_id"] = torch.tensor([int(speaker_ids[j]) for j in sel], dtype=torch.int32, device=dev)
@@ -245,18 +229,13 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
             rows = [torch.load(os.path.join(speech_dir, desc_paths[j]), map_location="cpu", weights_only=True).reshape(-1)
                     if desc_paths[j] is not None else torch.zeros(dim) for j in sel]
             args["description_embeddings"] = torch.stack(rows).to(dev)
-        with torch.no_grad():
-            _, post, gate, align = model(chars_idx=chars, chars_idx_len=lens, teacher_forcing=False, max_len_override=max_len,
-                                     attention_window=model.attention_window,
-                                     forward_attention=getattr(model, "forward_attention", False),
-                                     stop_threshold=getattr(model, "stop_threshold", 0.5), **args)
-        mel_lengths = mel_lengths_of(gate, getattr(model, "stop_threshold", 0.5)).cpu().tolist()
+        post, gate, align = free_run(model, chars, lens, max_len, **args)
+        mel_lengths = mel_lengths_of(gate, s.stop_threshold).cpu().tolist()
         if score:
             refs = [recordings[j][0]["mel_spectrogram"] for j in sel]
             sc = model.tacotron2.score_decode(post, gate, align, lens, torch.nn.utils.rnn.pad_sequence(refs, batch_first=True),
                                               torch.tensor([len(m) for m in refs], dtype=torch.int64, device=dev),
-                                              stop_threshold=getattr(model, "stop_threshold", 0.5), n_ceps=n_ceps,
-                                              return_path=f0)
+                                              stop_threshold=s.stop_threshold, n_ceps=n_ceps, return_path=f0)
             warp = (sc.pop("path"), sc["path_len"]) if f0 else None
             sc = {k: v.cpu().tolist() for k, v in sc.items()}
             assert sc["syn_frames"] == [int(n) for n in mel_lengths]
@@ -313,10 +292,10 @@ def synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, fe
     if score:
         f0_means = write_f0_scores(results_dir, f0_rows) if f0 else None
         write_scores(results_dir, score_rows, {
-            **({"f0": f0_meter.describe()} if f0 else {}), "n_ceps": n_ceps, "attention_window": list(model.attention_window) if model.attention_window is not None else None,
-            "forward_attention": bool(getattr(model, "forward_attention", False)),
-            "stop_threshold": float(getattr(model, "stop_threshold", 0.5)), "r": int(model.tacotron2.reduction_factor),
-            "max_len": int(max_len)}, f0_means)
+            **({"f0": f0_meter.describe()} if f0 else {}), "n_ceps": n_ceps,
+            "attention_window": list(s.attention_window) if s.attention_window is not None else None,
+            "forward_attention": bool(s.forward_attention), "stop_threshold": float(s.stop_threshold),
+            "r": int(model.tacotron2.reduction_factor), "max_len": int(max_len)}, f0_means)
     return written
 
 
@@ -347,7 +326,7 @@ def do_test(dataset_config: dict, training_config: dict, model_config: dict, ext
     feats = df[ctl_cfg["features"]].values.tolist() if model.controls else None
     if results_dir is None:
         results_dir = f"results_{training_config['name']}_test {datetime.datetime.now()}"
-    gen, gl, sr = make_vocoders(hifi_gan_checkpoint, pre, dev) if audio else (None, None, int(pre.get("sample_rate", 22050)))
+    gen, gl, sr = make_vocoders(hifi_gan_checkpoint, pre, dev) if audio else (None, None, sample_rate(pre))
     return synthesize_manifest(model, df, pre, speech_dir, results_dir, gen, gl, sr, feats, batch_size=batch_size,
                                max_len=max_len, random_seed=random_seed, zero_length="test", score=score, audio=audio,
                                n_ceps=n_ceps, f0=f0)

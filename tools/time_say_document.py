@@ -39,6 +39,7 @@ def main():
     from tacotron2_amd.datasets.text import TextEncoder
     from tacotron2_amd.hifigan import Generator
     from tacotron2_amd.model.tts_model import TTSModel
+    from tacotron2_amd.run.common import emitted_frames
     from tacotron2_amd.run.say import say_document
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -85,7 +86,7 @@ def main():
     out = dict(gpu=torch.cuda.get_device_name(0), pieces=P, max_len=a.max_len, reps=a.reps, warmup=a.warmup,
                chars_mean=round(float(lengths.mean()), 1), generator="V1 shapes, synthetic weights")
     out["decode"], (_, post, gates, _) = series(decode)
-    frames = (gates[:, :, 0] != -1000.0).sum(1).clamp(max=post.shape[1] - 1).clamp(min=1).cpu().tolist()
+    frames, _ = emitted_frames(gates, post.shape[1])
     assert frames == [a.max_len - 1] * P, frames
     out["frames"] = a.max_len - 1
     out["vocode_batched"], rows = series(lambda: gen(post.transpose(1, 2))[:, 0])
