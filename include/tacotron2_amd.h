@@ -1021,6 +1021,50 @@ typedef struct {
 int t2_join(const T2Join* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Time stretching of a waveform: WSOLA (Verhelst & Roelands 1993; the rule as in Driedger & Mueller 2014; no reference counterpart;
+ * csrc/t2_stretch.hip, the rule in DESIGN 5.17, restated in numpy in tests/stretch_ref.py).
+ *
+ * t2_stretch: x[b*ldx + i] float32 is a padded batch of B waveforms of finite samples, n[b] (DEVICE int32, 0 <= n[b] <= n_max <= ldx)
+ *   their sample counts.  Nothing is read from a row at or behind n[b]; x~ is x with zeros outside [0, n[b]).  The tempo is the
+ *   rational P / Q, the window N (even, 4 .. T2_STRETCH_MAX_N) with Hs = N / 2, the tolerance D (0 .. T2_STRETCH_MAX_D).  Every
+ *   position is an integer formed in integer arithmetic; no float decides anything.
+ *   LENGTHS  n_out = ceil(n Q / P);  frames m = 0 .. M - 1,  M = ceil(n_out / Hs) + 1;  the nominal input centre of frame m is
+ *     a_m = (m Hs P + Q / 2) div Q  in int64.
+ *   SEARCH SIGNAL  peak = max |x[i]| over i < n[b];  q[i] = (int) rint((double) x[i] * 1023.0 / (double) peak), an IEEE fp64
+ *     division, ties to even;  q = 0 everywhere when peak == 0.  |q| <= 1023 and N <= 2048 keep every score below 2^31
+ *     (1023^2 * 2048 = 2143291392): int32 sums are exact in any order.
+ *   OFFSETS  delta_0 = 0,  p_m = a_m + delta_m.  For m >= 1, with c = p_{m-1} + Hs, the natural continuation of the frame before:
+ *     score(d) = sum_{k = -Hs .. Hs - 1} q~[a_m + d + k] * q~[c + k]   for d in [-D, D];
+ *     delta_m = the d of the largest score; ties go to the smaller |d|, then to the negative one.
+ *   OVERLAP-ADD  w [N] float32 is the periodic Hann window built by the HOST: w[k] = float32(0.5 - 0.5 cos(2 pi k / N)) formed in
+ *     fp64; w[k] + w[k + Hs] = 1, so nothing is normalised.  For j = m Hs + i, 0 <= i < Hs, j < n_out:
+ *       y[b*ldy + j] = w[Hs + i] * x~[p_m + i] + w[i] * x~[p_{m+1} - Hs + i]   - two float32 products and one sum, nothing fused -
+ *     and y[b*ldy + j] = 0.0f for n_out <= j < ldy.
+ *   Written besides y: pos[b*ldp + m] = p_m (int32) for m < M and 0 for M <= m < ldp;  n_out[b] (int32).
+ *   REFUSED on the device, not clamped: a row with n[b] outside 0 .. n_max gets n_out[b] = -1; nothing else is read or written for it.
+ *   P == Q is NOT an identity (the correlation is not normalised); a caller that wants one launches nothing.
+ *   One launch, one 1024-thread workgroup per row, three phases: the peak; the chain of frames - template (N int16) and search
+ *   region (N + 2D int16) in LDS, a thread scores four adjacent offsets over a slice of the template, one workgroup-wide argmax
+ *   per frame -; a parallel sweep that writes y.  No atomics and integer decisions: two calls give bit-identical outputs, and
+ *   a row's outputs do not depend on B, ldx, ldy, ldp or the other rows.
+ *   T2_ERR_ARG before any launch: a null pointer (x only when n_max > 0, y only when ldy > 0), B < 1 or > 65535, N outside
+ *   4 .. 2048 or odd, D outside 0 .. 1024, P or Q outside 1 .. 2^20 or P / Q outside 1/8 .. 8, n_max outside 0 .. 2^27
+ *   (so that n_out <= 2^30 and every position fits int32),
+ *   ldx < n_max, ldy < ceil(n_max Q / P), ldp < ceil(ceil(n_max Q / P) / Hs) + 1. */
+#define T2_STRETCH_MAX_N 2048
+#define T2_STRETCH_MAX_D 1024
+typedef struct {
+    const float* x; int64_t ldx;                        /* rows are read only inside [0, n[b]) */
+    const int32_t* n;                                   /* [B] device */
+    const float* w;                                     /* [N] fp32, host-made periodic Hann */
+    int B, n_max, N, D, P, Q;
+    float* y; int64_t ldy;                              /* y[b][j] for j < ldy */
+    int32_t* pos; int64_t ldp;                          /* pos[b][m] = p_m */
+    int32_t* n_out;                                     /* [B]; -1: refused */
+} T2Stretch;
+int t2_stretch(const T2Stretch* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

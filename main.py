@@ -211,9 +211,17 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--out-sample-rate", required=False, type=click.IntRange(min=1), default=None, metavar="R",
               help="Write the audio at R Hz (48000, 44100, 16000, 8000, ...) instead of the model's rate: the vocoded waveform is "
                    "resampled on the GPU. Needs a .wav target; --durations-out times stay in model frames. Default: the model's rate.")
+@click.option("--tempo", required=False, type=float, default=None, metavar="T",
+              help="Speak T times as fast, 0.5 to 2.0, at the same pitch: the vocoded waveform is time-stretched on the GPU (WSOLA), the "
+                   "model's output stays as decoded. Needs a .wav target; --durations-out times and --text-file pauses are divided by "
+                   "the tempo. Default: off.")
+@click.option("--pitch-shift", required=False, type=float, default=None, metavar="SEMITONES",
+              help="Raise the voice by SEMITONES, -12 to 12, at the same tempo: a time stretch and a resampling on the GPU (formants "
+                   "move with the pitch). Needs a .wav target. Default: off.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
         forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
-        expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000):
+        expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000, tempo=None,
+        pitch_shift=None):
     if (text is None) == (text_file is None):
         raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
     if text_file is None:
@@ -224,11 +232,20 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
             raise click.UsageError(f"{', '.join(given)} only with --text-file")
     elif hifi_gan_checkpoint is None and not out.endswith(".wav"):
         raise click.UsageError(f"--text-file needs a .wav target (--out) or --hifi-gan-checkpoint, got --out {out}: a document has no single log-mel")
+    if tempo is not None or pitch_shift is not None:
+        from tacotron2_amd.run.common import sample_rate
+        from tacotron2_amd.run.say import voice_settings
+        try:
+            voice_settings(tempo, pitch_shift, sample_rate(config_args(ctx, "Configuration required for speech!")["dataset_config"]["preprocessing"]),
+                           hifi_gan_checkpoint is not None or out.endswith(".wav"))
+        except ValueError as e:
+            raise click.UsageError(str(e))
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     common = dict(config_args(ctx, "Configuration required for speech!"), checkpoint=checkpoint, output=out, speaker_id=speaker_id,
                   hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
-                  durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len)
+                  durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len,
+                  tempo=tempo, pitch_shift=pitch_shift)
     if text_file is None:
         from tacotron2_amd.run.say import do_say
         do_say(text=text, **common)

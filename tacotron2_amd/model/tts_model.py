@@ -201,7 +201,9 @@ class TTSModel(nn.Module):
         """A document spoken as one waveform: run.say.say_document on this model - pieces (datasets.document.Piece, or a text, which
         is split), the TextEncoder of the model's alphabet, the dataset's `preprocessing` settings (sample_rate, trim_top_db,
         trim_frame_length; None: the defaults) and a loaded vocoder object (hifigan.Generator or vocoder.GriffinLim; None: a
-        Griffin-Lim for this model's mel bands).  Loads no checkpoint.  Returns (waveform, plan, per-piece dict)."""
+        Griffin-Lim for this model's mel bands).  Among the options: tempo=T (0.5 .. 2.0) and pitch_shift=SEMITONES (-12 .. 12), a
+        WSOLA stretch of all pieces in one launch in front of the join.  Loads no checkpoint.  Returns (waveform, plan, per-piece
+        dict)."""
         from ..run.say import say_document
         pre = dict(preprocessing or {})
         if vocoder is None:

@@ -81,13 +81,77 @@ def output_resampler(pre: dict, out_sample_rate: Optional[int], dev):
     return Resampler(int(out_sample_rate), dev)
 
 
+TEMPO_LIMITS, PITCH_LIMITS = (0.5, 2.0), (-12.0, 12.0)                  # what `say` offers of analysis.time_stretch / pitch_shift
+
+
+def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True) -> Optional[dict]:
+    """--tempo T and --pitch-shift SEMITONES of `say`, checked before anything is decoded: None when neither is given,
+    else dict(tempo - the EFFECTIVE tempo, what the times of --durations-out and the pauses are divided by -, requested_tempo,
+    semitones, ratio - the (P, 1000) the stretch runs at, which a pitch shift may take to 1/8 .. 8 -, sr_mid, frame, tolerance,
+    active - False when nothing would change, and nothing is then launched).  The window is 1024 samples and the tolerance 256 at 22 050 Hz, scaled with the rate, rounded to even and kept
+    within the kernel's limits: product defaults, not measurements."""
+    import math
+    from ..stretch import MAX_FRAME, MAX_TOLERANCE, pitch_plan
+    if tempo is None and pitch_shift is None:
+        return None
+    for name, v, (lo, hi) in (("--tempo", tempo, TEMPO_LIMITS), ("--pitch-shift", pitch_shift, PITCH_LIMITS)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not lo <= v <= hi):
+            raise ValueError(f"{name} must lie in {lo:g} .. {hi:g}, got {v!r}")
+    if not wav_target:
+        raise ValueError("--tempo and --pitch-shift need a .wav target or a HiFi-GAN checkpoint: a log-mel is not stretched")
+    tempo, semitones = 1.0 if tempo is None else float(tempo), 0.0 if pitch_shift is None else float(pitch_shift)
+    even = lambda v, lo, hi: min(max(2 * int(round(v * sample_rate / 22050.0 / 2.0)), lo), hi)
+    if semitones == 0.0:
+        P = int(round(tempo * 1000.0))
+        sr_mid, eff, ratio = int(sample_rate), P / 1000.0, (P, 1000)
+    else:                                          # (what analysis.pitch_shift will do, checked here: its ratio and its resampling plan)
+        from ..datasets.resample import plan
+        sr_mid, eff, ratio = pitch_plan("say", semitones, int(sample_rate), tempo)
+        plan(sr_mid, int(sample_rate))
+    return dict(tempo=eff, requested_tempo=tempo, semitones=semitones, ratio=ratio, sr_mid=sr_mid, frame=even(1024, 4, MAX_FRAME),
+                tolerance=even(256, 0, MAX_TOLERANCE), active=ratio[0] != ratio[1] or sr_mid != int(sample_rate))
+
+
+def apply_voice(buf: torch.Tensor, n: List[int], voice: Optional[dict], sample_rate: int):
+    """A padded batch (B, ld) on the device with its counts through analysis.time_stretch - or, for a pitch shift, through
+    analysis.pitch_shift, which is the stretch and the resampling behind it - with voice_settings' window: ONE t2_stretch launch for
+    all rows.  (buf', n'); the arguments themselves when nothing is active."""
+    if voice is None or not voice["active"]:
+        return buf, n
+    from .. import analysis
+    if voice["semitones"] == 0.0:
+        y, n_out, _ = analysis.time_stretch(buf, n, voice["ratio"], voice["frame"], voice["tolerance"])
+    else:
+        y, n_out, eff, sr_mid = analysis.pitch_shift(buf, n, voice["semitones"], int(sample_rate), voice["requested_tempo"], voice["frame"],
+                                                     voice["tolerance"])
+        if (eff, sr_mid) != (voice["tempo"], voice["sr_mid"]):          # (one plan: the times were scaled by this tempo)
+            raise RuntimeError(f"say: pitch_shift ran at tempo {eff!r} through {sr_mid} Hz, the settings say {voice['tempo']!r}, {voice['sr_mid']}")
+    return y, [int(v) for v in n_out]
+
+
+def scale_records(records: list, voice: Optional[dict]) -> list:
+    """duration_records behind voice_settings: start_s / end_s divided by the effective tempo - the NOMINAL time map; a frame's
+    offset moves a sample by at most the tolerance - and the fields `tempo` and `pitch_shift_semitones` added."""
+    if voice is None:
+        return records
+    for r in records:
+        r["start_s"], r["end_s"] = [t / voice["tempo"] for t in r["start_s"]], [t / voice["tempo"] for t in r["end_s"]]
+        r["tempo"], r["pitch_shift_semitones"] = voice["tempo"], voice["semitones"]
+    return records
+
+
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
            description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
            forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
-           stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None):
-    """out_sample_rate: R Hz - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is resampled from the model's
+           stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, tempo: Optional[float] = None,
+           pitch_shift: Optional[float] = None):
+    """tempo: 0.5 .. 2.0, pitch_shift: -12 .. 12 semitones - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is
+    time-stretched by WSOLA on the device (analysis.time_stretch / pitch_shift) before out_sample_rate applies; the
+    model's output itself is as decoded.  `durations_out` times are divided by the effective tempo and each object gains `tempo`
+    and `pitch_shift_semitones`.  None: nothing of this runs; tempo 1 with pitch_shift 0 launches nothing either.
+    out_sample_rate: R Hz - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is resampled from the model's
     rate to R on the device (datasets/resample.py) before it is written, and the header carries R; `durations_out`
     times stay in model frames.  None: the model's rate, nothing changes.
     stop_threshold: 0 < tau < 1, the stop probability below which an utterance ends (Tacotron2.forward); None takes the config's
@@ -102,6 +166,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     if out_sample_rate is not None and hifi_gan_checkpoint is None and not output.endswith(".wav"):
         raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
     resampler = output_resampler(pre, out_sample_rate, dev)
+    voice = voice_settings(tempo, pitch_shift, sample_rate(pre), hifi_gan_checkpoint is not None or output.endswith(".wav"))
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     _, chars, lens = encode_texts(enc, texts, dev)
@@ -113,7 +178,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     sr = sample_rate(pre)
     if durations_out is not None:
         with open(durations_out, "w") as f:
-            json.dump(duration_records(model, enc, texts, align, lens, frames, sr), f)
+            json.dump(scale_records(duration_records(model, enc, texts, align, lens, frames, sr), voice), f)
     if hifi_gan_checkpoint is None and not output.endswith(".wav"):
         np.save(output, mels[0] if isinstance(text, str) else np.array(mels, dtype=object), allow_pickle=not isinstance(text, str))
         return mels
@@ -124,11 +189,20 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         vocode = lambda m: gen(torch.from_numpy(np.ascontiguousarray(m.T)).to(dev))[0, 0].cpu()
     else:
         vocode = lambda m: gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0))
+    stretched = None
+    if voice is not None and voice["active"]:             # every text's waveform in one padded batch: ONE stretch launch
+        raw = [torch.as_tensor(vocode(m)).detach().float().reshape(-1) for m in mels]
+        n = [int(w.numel()) for w in raw]
+        buf = torch.zeros(len(raw), max(max(n), 1), dtype=torch.float32, device=dev)
+        for i, w in enumerate(raw):
+            buf[i, :n[i]] = w
+        rows, n_out = apply_voice(buf, n, voice, sr)
+        stretched = [rows[i, :n_out[i]].cpu() for i in range(len(raw))]
     for i, m in enumerate(mels):
         # several texts: `<output without its extension>_<i>.wav`.  Griffin-Lim is reached with a name that ends in ".wav" only, whose
         # last dot is that extension's, so this is the `output[:-4]` of the reference's branch as well
         name = output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav"
-        wav = vocode(m)
+        wav = vocode(m) if stretched is None else stretched[i]
         if resampler is not None:
             wav = torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
         write_wav(name, wav, sr if resampler is None else int(out_sample_rate))
@@ -143,7 +217,7 @@ KEEP_S = 0.020                                                          # audio 
 def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: int = 5000, batch_size: int = 64, pauses: dict = PAUSES,
                  trim: bool = True, level: bool = False, fade_ms: float = 5.0, speaker_id: Optional[int] = None,
                  controls: Optional[str] = None, description: Optional[str] = None, random_seed: Optional[int] = None,
-                 durations: bool = False):
+                 durations: bool = False, tempo: Optional[float] = None, pitch_shift: Optional[float] = None):
     """Pieces (datasets.document.Piece, or a text, which is split at the defaults) -> one waveform on the model's device.
     The pieces are sorted by encoded length and decoded in chunks of batch_size through the model's free-running forward, with the
     decode settings that are on the model (common.free_run).  `vocoder` is a loaded hifigan.Generator - each chunk's PADDED batch
@@ -152,10 +226,13 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     into document order in one padded buffer, and one
     analysis.join_audio call trims (dataset.preprocessing's trim_top_db and trim_frame_length, the hop a quarter of it, 20 ms kept
     at both ends), levels, fades and joins them, with pauses[break_after] seconds behind each piece.
+    tempo (0.5 .. 2.0) and pitch_shift (-12 .. 12 semitones): the whole padded buffer goes through voice_settings' stretch in ONE
+    launch in front of the join, the pieces side by side; the pauses and the piece-local times of `durations` are divided by the
+    effective tempo.
     A piece that ran into max_len without stopping is kept, cut there, and marked stopped=False.
     Returns (y (total,) float32, plan - join_audio's, device tensors -, info): info = dict(pieces, frames, stopped, n, pause,
     waveforms - the per-piece device tensors that went into the join -, chunks, join - the keyword arguments of the join_audio
-    call -, durations - duration_records per piece, or None)."""
+    call -, durations - duration_records per piece, or None -, voice - voice_settings, or None)."""
     from .. import analysis
     from ..datasets.document import split_document
     from ..hifigan import Generator
@@ -168,6 +245,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
         raise ValueError(f"say_document: batch_size must be an integer in 1 .. 64, got {batch_size!r}")
     dev = next(model.parameters()).device
     sr = sample_rate(pre)
+    voice = voice_settings(tempo, pitch_shift, sr)
     texts = [p.text for p in pieces]
     ids, _, _ = encode_texts(enc, texts)
     order = sorted(range(len(ids)), key=lambda i: (len(ids[i]), i))
@@ -179,7 +257,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
         post, gates, align = free_run(model, chars, lens, max_len, **conditioning(model, len(ch), dev, speaker_id, controls, description))
         fr, stop = emitted_frames(gates, post.shape[1])
         if durations:
-            for i, rec in zip(ch, duration_records(model, enc, [texts[i] for i in ch], align, lens, fr, sr)):
+            for i, rec in zip(ch, scale_records(duration_records(model, enc, [texts[i] for i in ch], align, lens, fr, sr), voice)):
                 records[i] = rec
         if isinstance(vocoder, Generator):
             rows = vocoder(post.transpose(1, 2))[:, 0]                        # the padded batch in one call
@@ -193,21 +271,25 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     buf = torch.zeros(P, max(max(n), 1), dtype=torch.float32, device=dev)
     for i, w in enumerate(waves):
         buf[i, :n[i]] = w
-    pause = [int(round(float(pauses[p.break_after]) * sr)) for p in pieces]
+    if voice is not None and voice["active"]:
+        buf, n = apply_voice(buf, n, voice, sr)
+        waves = [buf[i, :n[i]] for i in range(P)]
+    pause = [int(round(float(pauses[p.break_after]) * sr / (voice["tempo"] if voice else 1.0))) for p in pieces]
     F = int(pre.get("trim_frame_length", 2048))
     join = dict(trim=bool(trim), top_db=float(pre.get("trim_top_db", 60)), frame_length=F, hop_length=max(F // 4, 1),
                 keep=int(round(KEEP_S * sr)), fade=int(round(float(fade_ms) * sr / 1000.0)), level=bool(level),
                 ceiling=1.0 if level else 0.0)
     y, _, plan = analysis.join_audio(buf, n, pause, **join)
     return y, plan, dict(pieces=pieces, frames=frames, stopped=stopped, n=n, pause=pause, waveforms=waves, chunks=len(chunks),
-                         join=join, durations=records if durations else None)
+                         join=join, durations=records if durations else None, voice=voice)
 
 
 def document_records(info: dict, plan: dict, sample_rate: int) -> list:
     """`say --text-file --durations-out`: one object per piece in document order - piece, paragraph, text; symbols, frames,
     focus_rate, feasible as duration_records gives them; stopped; offset_s, trim_start_s, length_s, pause_s and gain of the join's
     plan; start_s / end_s per symbol in DOCUMENT time: a piece-local time t lies at offset_s + clip(t - trim_start_s, 0, length_s),
-    still at the model's rate and its hop of 256."""
+    still at the model's rate and its hop of 256.  With --tempo / --pitch-shift the piece-local times arrive divided by the effective
+    tempo (scale_records), and `tempo` and `pitch_shift_semitones` are passed on."""
     off, s0, length, gain = (plan[k].cpu().tolist() for k in ("off", "s0", "len", "gain"))
     out = []
     for i, (p, rec) in enumerate(zip(info["pieces"], info["durations"])):
@@ -216,7 +298,8 @@ def document_records(info: dict, plan: dict, sample_rate: int) -> list:
         out.append(dict(piece=i, paragraph=p.paragraph_index, text=p.text, symbols=rec["symbols"], frames=rec["frames"],
                         focus_rate=rec["focus_rate"], feasible=rec["feasible"], stopped=bool(info["stopped"][i]), offset_s=o,
                         trim_start_s=t0, length_s=ln, pause_s=info["pause"][i] / sample_rate, gain=float(gain[i]),
-                        start_s=[doc(t) for t in rec["start_s"]], end_s=[doc(t) for t in rec["end_s"]]))
+                        start_s=[doc(t) for t in rec["start_s"]], end_s=[doc(t) for t in rec["end_s"]],
+                        **{k: rec[k] for k in ("tempo", "pitch_shift_semitones") if k in rec}))
     return out
 
 
@@ -240,9 +323,10 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
                     forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
                     stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, max_chars: int = 190,
                     expand_numbers: bool = False, pause=None, trim: bool = True, level: bool = False, fade_ms: float = 5.0,
-                    batch_size: int = 64):
+                    batch_size: int = 64, tempo: Optional[float] = None, pitch_shift: Optional[float] = None):
     """`say --text-file`: the file is read, its numbers expanded if asked, split (datasets/document.py) and spoken by say_document;
     the joined waveform is resampled to out_sample_rate if given (one Resampler call) and written by ONE write_wav call.
+    tempo, pitch_shift: say_document's, in front of the join.
     durations_out: document_records as a JSON list.  A piece that did not stop is reported on stderr; the exit status stays 0.
     Returns say_document's (y, plan, info), y as written (after resampling)."""
     import sys
@@ -260,6 +344,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     pre = dataset_config["preprocessing"]
     sr = sample_rate(pre)
     resampler = output_resampler(pre, out_sample_rate, dev)
+    voice_settings(tempo, pitch_shift, sr)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     with open(text_file, encoding="utf-8") as f:
         text = f.read()
@@ -274,7 +359,8 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     gen, gl, _ = make_vocoders(hifi_gan_checkpoint, dict(pre, num_mels=int(model.hparams.get("num_mels", pre.get("num_mels", 80)))), dev)
     y, plan_, info = say_document(model, pieces, enc, pre, gen if gen is not None else gl, max_len=max_len, batch_size=batch_size,
                                   pauses=pauses, trim=trim, level=level, fade_ms=fade_ms, speaker_id=speaker_id, controls=controls,
-                                  description=description, random_seed=random_seed, durations=durations_out is not None)
+                                  description=description, random_seed=random_seed, durations=durations_out is not None, tempo=tempo,
+                                  pitch_shift=pitch_shift)
     for i, ok in enumerate(info["stopped"]):
         if not ok:
             print(f"say: piece {i} did not stop within --max-len {max_len} frames and is cut there: {pieces[i].text[:40]!r}", file=sys.stderr)
