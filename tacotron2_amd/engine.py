@@ -72,12 +72,15 @@ def set_float32_matmul_precision(name: str) -> None:
 
 
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_k=1, b_k=1, alpha=1.0, bias=None, bias2=None, mulmask=None, ldmask=0,
-         relu=0, accumulate=0, splitk=1, batch=1, sA=0, sB=0, sC=0, a_tap_len=0, a_tap_stride=0, stat_out=None, stat_Lp=0, stat_L=0):
-    """C-ABI t2_gemm on raw pointers (ints) or tensors."""
+         relu=0, accumulate=0, splitk=1, batch=1, sA=0, sB=0, sC=0, a_tap_len=0, a_tap_stride=0, stat_out=None, stat_Lp=0, stat_L=0,
+         precision=None):
+    """C-ABI t2_gemm on raw pointers (ints) or tensors.  precision: None = the process-wide GEMM_PRECISION (the training path);
+    the vocoders pass 0, as the reference's matmul precision setting touches torch.matmul only."""
     g = make("T2Gemm", A=A, B=B, C=C, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, a_kmajor=a_k, b_kmajor=b_k,
              alpha=alpha, bias=bias, bias2=bias2, mulmask=mulmask, ldmask=ldmask, relu=relu, accumulate=accumulate,
              splitk=splitk, batch=batch, sA=sA, sB=sB, sC=sC, share_cu=getattr(_TLS, "share_cu", 0), native_fp32=GEMM_NATIVE_FP32[0],
-             precision=GEMM_PRECISION[0], a_tap_len=a_tap_len, a_tap_stride=a_tap_stride, stat_out=stat_out, stat_Lp=stat_Lp, stat_L=stat_L)
+             precision=GEMM_PRECISION[0] if precision is None else precision, a_tap_len=a_tap_len, a_tap_stride=a_tap_stride,
+             stat_out=stat_out, stat_Lp=stat_Lp, stat_L=stat_L)
     call("t2_gemm", g, _stream())
 
 

@@ -61,15 +61,16 @@ class _Conv:
         Ci, Co, k = self.Ci, self.Co, self.k
         yo = _ptr(y, PAD * Co)
         if self.d == 1:
-            gemm(_ptr(x, (PAD - self.p) * Ci), self.wp, yo, L, Co, k * Ci, Ci, k * Ci, Co, bias=self.b, accumulate=1 if accumulate else 0)
+            gemm(_ptr(x, (PAD - self.p) * Ci), self.wp, yo, L, Co, k * Ci, Ci, k * Ci, Co, bias=self.b, accumulate=1 if accumulate else 0,
+                 precision=0)
             return
         if Ci % 32 == 0:     # dilated: still ONE GEMM - the A row's K axis is k blocks of Ci channels, d rows apart (T2Gemm.a_tap_len)
             gemm(_ptr(x, (PAD - self.p) * Ci), self.wp, yo, L, Co, k * Ci, Ci, k * Ci, Co, bias=self.b,
-                 accumulate=1 if accumulate else 0, a_tap_len=Ci, a_tap_stride=self.d * Ci)
+                 accumulate=1 if accumulate else 0, a_tap_len=Ci, a_tap_stride=self.d * Ci, precision=0)
             return
         for j in range(k):
             gemm(_ptr(x, (PAD + j * self.d - self.p) * Ci), _ptr(self.wp, j * Ci), yo, L, Co, Ci, Ci, k * Ci, Co,
-                 bias=self.b if j == 0 else None, accumulate=1 if (accumulate or j > 0) else 0)
+                 bias=self.b if j == 0 else None, accumulate=1 if (accumulate or j > 0) else 0, precision=0)
 
 
 class _Up:
@@ -80,6 +81,8 @@ class _Up:
         if k != 2 * u or u % 2:
             raise NotImplementedError(f"ConvTranspose1d with kernel {k}, stride {u}: only k = 2*stride with even stride (every "
                                       "published HiFi-GAN configuration) is laid out as one GEMM")
+        if u // 2 > PAD:        # rows q = 0 and q = L spill u/2 rows into the margins: a larger stride would write in front of the buffer
+            raise NotImplementedError(f"ConvTranspose1d with stride {u}: the margin layout holds strides up to {2 * PAD}")
         self.u = u
         wt = torch.empty(u, self.Co, 2, self.Ci)
         wt[:, :, 0, :] = w[:, :, u:].permute(2, 1, 0)          # x[q-1] meets tap r + u
@@ -91,7 +94,7 @@ class _Up:
         """x (L + 2*PAD, Ci) -> y (L*u + 2*PAD, Co); y's margins are re-zeroed (rows q = 0 and q = L spill u/2 rows into them)."""
         Ci, Co, u = self.Ci, self.Co, self.u
         p = u // 2
-        gemm(_ptr(x, (PAD - 1) * Ci), self.wt, _ptr(y, (PAD - p) * Co), L + 1, u * Co, 2 * Ci, Ci, 2 * Ci, u * Co, bias=self.b)
+        gemm(_ptr(x, (PAD - 1) * Ci), self.wt, _ptr(y, (PAD - p) * Co), L + 1, u * Co, 2 * Ci, Ci, 2 * Ci, u * Co, bias=self.b, precision=0)
         y[:PAD].zero_(); y[PAD + L * u:].zero_()
 
 

@@ -6,8 +6,11 @@ Both transforms of the iteration are dense contractions with a fixed DFT basis, 
 (t2_gemm): the analysis reads the padded signal as overlapping rows (lda = hop), the synthesis multiplies by the
 window-folded inverse basis and overlap-adds.  Elementwise phase updates are torch glue.
 
-PARITY UNPINNED: librosa is not importable here and the reference holds no audio fixture; Griffin-Lim starts from random
-phases, so only properties are tested (exact STFT -> ISTFT round trip, spectral convergence).  The mel -> linear step uses the
+PARITY WITH LIBROSA UNPINNED: librosa is not importable here and the reference holds no audio fixture.  This file's own
+definition is pinned against float64: STFT, ISTFT of inconsistent spectrograms, the mel inversion and the first iterations of
+the recursion from its seeded phases (tests/test_gpu_audio_chain.py), beside the property tests (exact STFT -> ISTFT round trip,
+spectral convergence).  The GEMMs run at full float32 accuracy whatever set_float32_matmul_precision says (the reference's
+setting touches the model's matmuls only).  The mel -> linear step uses the
 clamped minimum-norm solution (pseudo-inverse of the slaney filterbank) where librosa solves a non-negative least squares
 problem per frame.
 """
@@ -48,14 +51,14 @@ class GriffinLim:
         frames = 1 + n // self.hop
         padded = torch.nn.functional.pad(y.view(1, 1, -1), (self.n_fft // 2, self.n_fft // 2), mode="reflect").view(-1).contiguous()
         spec = torch.empty(frames, 2 * self.nb, device=self.device)
-        gemm(padded, self.front.basis, spec, frames, 2 * self.nb, self.n_fft, self.hop, self.n_fft, 2 * self.nb)
+        gemm(padded, self.front.basis, spec, frames, 2 * self.nb, self.n_fft, self.hop, self.n_fft, 2 * self.nb, precision=0)
         return spec.view(frames, 2, self.nb)
 
     def istft(self, spec: torch.Tensor) -> torch.Tensor:
         """(frames, 2, nb) -> (hop * (frames - 1),) : windowed inverse DFT rows, overlap-add, window-envelope normalisation."""
         frames = spec.shape[0]
         yf = torch.empty(frames, self.n_fft, device=self.device)
-        gemm(spec.contiguous(), self.ibasis, yf, frames, self.n_fft, 2 * self.nb, 2 * self.nb, self.n_fft, self.n_fft, b_k=0)
+        gemm(spec.contiguous(), self.ibasis, yf, frames, self.n_fft, 2 * self.nb, 2 * self.nb, self.n_fft, self.n_fft, b_k=0, precision=0)
         total = self.n_fft + self.hop * (frames - 1)
         fold = lambda cols: torch.nn.functional.fold(cols, (1, total), (1, self.n_fft), stride=(1, self.hop)).view(-1)
         y = fold(yf.t().reshape(1, self.n_fft, frames))
@@ -85,7 +88,7 @@ class GriffinLim:
         """(frames, n_mels) mel magnitude -> (frames, nb) linear magnitude (clamped minimum-norm solution)."""
         m = mel_mag.to(self.device, torch.float32).contiguous()
         out = torch.empty(m.shape[0], self.nb, device=self.device)
-        gemm(m, self.fb_pinv, out, m.shape[0], self.nb, m.shape[1], m.shape[1], m.shape[1], self.nb)
+        gemm(m, self.fb_pinv, out, m.shape[0], self.nb, m.shape[1], m.shape[1], m.shape[1], self.nb, precision=0)
         return torch.clamp_(out, min=0.0)
 
     def mel_to_audio(self, log_mel: torch.Tensor, seed: int = 0) -> torch.Tensor:

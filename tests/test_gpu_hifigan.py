@@ -63,6 +63,21 @@ def test_unsupported_upsampler_shape_fails_loudly():
         Generator(cfg, "cuda:0").load_state_dict(sd)
 
 
+def test_upsampler_stride_beyond_the_margin_fails_loudly():
+    """u / 2 > PAD would put the first output row in front of the buffer: refused at load time, nothing is moved or launched."""
+    from tacotron2_amd import hifigan
+    u = 2 * hifigan.PAD + 2
+    with pytest.raises(NotImplementedError, match="stride"):
+        hifigan._Up(torch.zeros(4, 2, 2 * u), torch.zeros(2), u, "cuda:0")
+    cfg = dict(resblock="2", upsample_rates=[u], upsample_kernel_sizes=[2 * u], upsample_initial_channel=8,
+               resblock_kernel_sizes=[3], resblock_dilation_sizes=[[1, 3]])
+    sd = {"conv_pre.weight": torch.zeros(8, 80, 7), "conv_pre.bias": torch.zeros(8), "ups.0.weight": torch.zeros(8, 4, 2 * u),
+          "ups.0.bias": torch.zeros(4)}
+    with pytest.raises(NotImplementedError, match="stride"):
+        hifigan.Generator(cfg, "cuda:0").load_state_dict(sd)
+    hifigan._Up(torch.zeros(4, 2, 4 * hifigan.PAD), torch.zeros(2), 2 * hifigan.PAD, "cuda:0")       # u / 2 == PAD still fits
+
+
 def test_vocoding_a_padded_row_differs_from_vocoding_the_cut_row_only_in_the_tail():
     """run/test.py:167-181 vocodes the whole padded batch row (masked frames are zeros) and cuts the waveform at
     mel_length * 256.  The generator's receptive field spans many frames, so this is NOT the same as vocoding `mel[:n]`: the
