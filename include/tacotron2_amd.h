@@ -1065,6 +1065,60 @@ typedef struct {
 int t2_stretch(const T2Stretch* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pitch change of a waveform at its own length and with its own formants: TD-PSOLA (Moulines & Charpentier 1990; no reference
+ * counterpart; csrc/t2_psola.hip, the rule in DESIGN 5.18, restated in numpy in tests/psola_ref.py).
+ *
+ * t2_psola: x[b*ldx + i] float32 is a padded batch of B waveforms of finite samples, n[b] (DEVICE int32, 0 <= n[b] <= n_max <= ldx)
+ *   their sample counts; nothing is read from a row at or behind n[b].  lag[b*ldt + t] (int32) is the pitch period in samples at
+ *   frame t, centred on sample t hop, 0 = unvoiced (t2_pitch_viterbi's lag); rho[b*ldt + t] (int32, Q16) the output period over the
+ *   input period there, taken as 65536 where lag == 0.  U is the mark spacing in unvoiced stretches.  All divisions are integer
+ *   divisions; no float decides anything but the comparisons of input samples in the analysis chain.
+ *     Tb = min(T, 1 + n / hop),  t(s) = min((s + hop / 2) / hop, Tb - 1),  per(s) = lag[t(s)].
+ *   ANALYSIS MARKS  a_0 = 0.  Given a_k: step = per(a_k), or U if that is 0;  c = a_k + step.  c >= n: a_{k+1} = n is the terminal
+ *     mark, K = k + 1.  Else, with per(c) > 0: d = min(per(c), step) / 4 and a_{k+1} = the index of the largest x in
+ *     [c - d, min(c + d, n - 1)], the smallest index on a tie; with per(c) == 0: a_{k+1} = c.  Marks before the terminal one are at
+ *     least 12 and at most 5120 samples apart.
+ *   SYNTHESIS MARKS, int64 in 1/256 sample:  s_0 = 0, r_0 = 0, k(0) = 0;  s_{j+1} = s_j + (((a_{k(j)+1} - a_{k(j)}) * rho[t(r_j)]) >> 8);
+ *     r_{j+1} = (s_{j+1} + 128) >> 8.  r_{j+1} >= n: the terminal r_J = n with k(J) = K.  Else k(j+1) = the mark among 0 .. K - 1
+ *     nearest to r_{j+1}, the smaller k on a tie.  With rho == 65536 throughout, r == a.
+ *   OVERLAP-ADD  w [1025] float32 is built by the HOST: w[u] = float32(0.5 - 0.5 cos(pi u / 1024)) formed in fp64.  Grain j = 0 .. J
+ *     copies the analysis grain k = k(j): at output sample i, e = i - r_j, it reads x[a_k + e] with weight 1 at e = 0,
+ *     w[((L + e) * 1024) / L] for -L < e < 0 with L = a_k - a_{k-1} (nothing for k = 0), w[1024 - (e * 1024) / R] for 0 < e < R with
+ *     R = a_{k+1} - a_k (nothing for k = K).  For i < n, over the grains that reach i in ascending j:
+ *       y[b*ldy + i] = (sum_j w_j * x[..]) / max(sum_j w_j, 1)   - float32 products and sums, nothing fused, one IEEE division -
+ *     and y[b*ldy + i] = 0.0f for n <= i < ldy.
+ *   Written besides y: a[b*ldm + k] = a_k for k <= K and 0 behind up to ldm;  r[b*lds + j] = r_j and kmap[b*lds + j] = k(j) for
+ *     j <= J and 0 behind up to lds;  n_marks[b] = K + 1,  n_syn[b] = J + 1.  K + 1 <= n / 12 + 2.  A terminal spacing a_K - a_{K-1} as
+ *     small as one sample makes the synthesis steps of the grains nearest to a_{K-1} as small as rho / 256 of a sample, up to 10250
+ *     of them; every other step is at least 3 samples: J + 1 <= n / 3 + T2_PSOLA_SYN_TAIL.
+ *   REFUSED on the device, not clamped: n[b] outside 0 .. n_max; among the frames t < Tb a lag outside {0} and T2_PSOLA_MIN_LAG ..
+ *     T2_PSOLA_MAX_LAG, or at a voiced frame a rho outside T2_PSOLA_MIN_RHO .. T2_PSOLA_MAX_RHO (1/4 .. 4).  Such a row gets
+ *     n_marks[b] = -1; nothing else is written for it, and x is not read.
+ *   One launch, one 1024-thread workgroup per row: the check; the analysis chain by one wave on pieces of the signal in LDS; the
+ *   synthesis chain by one thread; a sweep in which every thread gathers its samples' grains.  No atomics: two calls give
+ *   bit-identical outputs, and a row's outputs do not depend on B, the leading dimensions or the other rows.
+ *   T2_ERR_ARG before any launch: a null pointer (x only when n_max > 0, y only when ldy > 0), B < 1 or > 65535, n_max outside
+ *   0 .. 2^27, ldx < n_max, T < 1, ldt < T, hop outside 16 .. 2^20, U outside 16 .. 4096, ldy < n_max, ldm < n_max / 12 + 2,
+ *   lds < n_max / 3 + T2_PSOLA_SYN_TAIL. */
+#define T2_PSOLA_MIN_LAG 16
+#define T2_PSOLA_MAX_LAG 4096
+#define T2_PSOLA_MIN_RHO 16384
+#define T2_PSOLA_MAX_RHO 262144
+#define T2_PSOLA_SYN_TAIL 10256
+typedef struct {
+    const float* x; int64_t ldx;                        /* rows are read only inside [0, n[b]) */
+    const int32_t* n;                                   /* [B] device */
+    const int32_t* lag; const int32_t* rho; int64_t ldt;   /* [B][T] each, rows ldt apart */
+    const float* w;                                     /* [1025] fp32, host-made raised cosine */
+    int B, n_max, T, hop, U;
+    float* y; int64_t ldy;                              /* y[b][i] for i < ldy */
+    int32_t* a; int64_t ldm;                            /* a[b][k] = a_k */
+    int32_t* r; int32_t* kmap; int64_t lds;             /* r[b][j] = r_j, kmap[b][j] = k(j) */
+    int32_t* n_marks; int32_t* n_syn;                   /* [B] each; n_marks -1: refused */
+} T2Psola;
+int t2_psola(const T2Psola* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

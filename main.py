@@ -218,10 +218,18 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--pitch-shift", required=False, type=float, default=None, metavar="SEMITONES",
               help="Raise the voice by SEMITONES, -12 to 12, at the same tempo: a time stretch and a resampling on the GPU (formants "
                    "move with the pitch). Needs a .wav target. Default: off.")
+@click.option("--preserve-formants", is_flag=True, default=False,
+              help="With --pitch-shift or --pitch-range: change the pitch by TD-PSOLA on the GPU instead - pitch-synchronous grains are "
+                   "re-spaced, so the formants stay where they are and the length is the tempo's alone. The level falls by up to a "
+                   "third. Default: off.")
+@click.option("--pitch-range", required=False, type=float, default=None, metavar="K",
+              help="Scale the intonation range about the voice's mean pitch by K, 0 to 2: 0 is a monotone voice, 1 unchanged, 2 twice "
+                   "the excursions. Works with any checkpoint; always by TD-PSOLA, so it implies --preserve-formants. Needs a .wav "
+                   "target. Default: off.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
         forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
         expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000, tempo=None,
-        pitch_shift=None):
+        pitch_shift=None, preserve_formants=False, pitch_range=None):
     if (text is None) == (text_file is None):
         raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
     if text_file is None:
@@ -232,12 +240,13 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
             raise click.UsageError(f"{', '.join(given)} only with --text-file")
     elif hifi_gan_checkpoint is None and not out.endswith(".wav"):
         raise click.UsageError(f"--text-file needs a .wav target (--out) or --hifi-gan-checkpoint, got --out {out}: a document has no single log-mel")
-    if tempo is not None or pitch_shift is not None:
+    preserve_formants = True if preserve_formants else None
+    if tempo is not None or pitch_shift is not None or preserve_formants or pitch_range is not None:
         from tacotron2_amd.run.common import sample_rate
         from tacotron2_amd.run.say import voice_settings
         try:
             voice_settings(tempo, pitch_shift, sample_rate(config_args(ctx, "Configuration required for speech!")["dataset_config"]["preprocessing"]),
-                           hifi_gan_checkpoint is not None or out.endswith(".wav"))
+                           hifi_gan_checkpoint is not None or out.endswith(".wav"), preserve_formants, pitch_range)
         except ValueError as e:
             raise click.UsageError(str(e))
     forward_attention = forward_attention_arg(forward_attention, attention_window)
@@ -245,7 +254,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                   hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
                   durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len,
-                  tempo=tempo, pitch_shift=pitch_shift)
+                  tempo=tempo, pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range)
     if text_file is None:
         from tacotron2_amd.run.say import do_say
         do_say(text=text, **common)

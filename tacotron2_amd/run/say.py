@@ -82,25 +82,40 @@ def output_resampler(pre: dict, out_sample_rate: Optional[int], dev):
 
 
 TEMPO_LIMITS, PITCH_LIMITS = (0.5, 2.0), (-12.0, 12.0)                  # what `say` offers of analysis.time_stretch / pitch_shift
+RANGE_LIMITS = (0.0, 2.0)                                               # and of analysis.pitch_shift_psola's pitch_range
 
 
-def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True) -> Optional[dict]:
-    """--tempo T and --pitch-shift SEMITONES of `say`, checked before anything is decoded: None when neither is given,
-    else dict(tempo - the EFFECTIVE tempo, what the times of --durations-out and the pauses are divided by -, requested_tempo,
+def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True, preserve_formants=None, pitch_range=None) -> Optional[dict]:
+    """--tempo T, --pitch-shift SEMITONES, --preserve-formants and --pitch-range K of `say`, checked before anything
+    is decoded: None when none is given, else dict(psola - True with --preserve-formants or --pitch-range: the pitch is changed by
+    analysis.pitch_shift_psola behind a stretch by the tempo alone, nothing is resampled, sr_mid is the sample rate -, pitch_range,
+    tempo - the EFFECTIVE tempo, what the times of --durations-out and the pauses are divided by -, requested_tempo,
     semitones, ratio - the (P, 1000) the stretch runs at, which a pitch shift may take to 1/8 .. 8 -, sr_mid, frame, tolerance,
     active - False when nothing would change, and nothing is then launched).  The window is 1024 samples and the tolerance 256 at 22 050 Hz, scaled with the rate, rounded to even and kept
     within the kernel's limits: product defaults, not measurements."""
     import math
     from ..stretch import MAX_FRAME, MAX_TOLERANCE, pitch_plan
-    if tempo is None and pitch_shift is None:
+    psola = bool(preserve_formants) or pitch_range is not None
+    if tempo is None and pitch_shift is None and not psola:
         return None
-    for name, v, (lo, hi) in (("--tempo", tempo, TEMPO_LIMITS), ("--pitch-shift", pitch_shift, PITCH_LIMITS)):
+    for name, v, (lo, hi) in (("--tempo", tempo, TEMPO_LIMITS), ("--pitch-shift", pitch_shift, PITCH_LIMITS), ("--pitch-range", pitch_range, RANGE_LIMITS)):
         if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not lo <= v <= hi):
             raise ValueError(f"{name} must lie in {lo:g} .. {hi:g}, got {v!r}")
+    if psola and pitch_shift is None and pitch_range is None:
+        raise ValueError("--preserve-formants needs --pitch-shift or --pitch-range: alone it has nothing to change")
+    if not wav_target and psola:
+        raise ValueError("--preserve-formants and --pitch-range need a .wav target or a HiFi-GAN checkpoint: a log-mel has no pitch marks")
     if not wav_target:
         raise ValueError("--tempo and --pitch-shift need a .wav target or a HiFi-GAN checkpoint: a log-mel is not stretched")
     tempo, semitones = 1.0 if tempo is None else float(tempo), 0.0 if pitch_shift is None else float(pitch_shift)
     even = lambda v, lo, hi: min(max(2 * int(round(v * sample_rate / 22050.0 / 2.0)), lo), hi)
+    if psola:                                      # (what analysis.pitch_shift_psola will do, checked here: its meter at this rate)
+        from ..psola import check_rate
+        check_rate("say", int(sample_rate))
+        rng, P = 1.0 if pitch_range is None else float(pitch_range), int(round(tempo * 1000.0))
+        return dict(tempo=P / 1000.0, requested_tempo=tempo, semitones=semitones, ratio=(P, 1000), sr_mid=int(sample_rate),
+                    frame=even(1024, 4, MAX_FRAME), tolerance=even(256, 0, MAX_TOLERANCE), psola=True, pitch_range=rng,
+                    active=P != 1000 or semitones != 0.0 or rng != 1.0)
     if semitones == 0.0:
         P = int(round(tempo * 1000.0))
         sr_mid, eff, ratio = int(sample_rate), P / 1000.0, (P, 1000)
@@ -109,17 +124,24 @@ def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True
         sr_mid, eff, ratio = pitch_plan("say", semitones, int(sample_rate), tempo)
         plan(sr_mid, int(sample_rate))
     return dict(tempo=eff, requested_tempo=tempo, semitones=semitones, ratio=ratio, sr_mid=sr_mid, frame=even(1024, 4, MAX_FRAME),
-                tolerance=even(256, 0, MAX_TOLERANCE), active=ratio[0] != ratio[1] or sr_mid != int(sample_rate))
+                tolerance=even(256, 0, MAX_TOLERANCE), psola=False, pitch_range=1.0,
+                active=ratio[0] != ratio[1] or sr_mid != int(sample_rate))
 
 
 def apply_voice(buf: torch.Tensor, n: List[int], voice: Optional[dict], sample_rate: int):
     """A padded batch (B, ld) on the device with its counts through analysis.time_stretch - or, for a pitch shift, through
-    analysis.pitch_shift, which is the stretch and the resampling behind it - with voice_settings' window: ONE t2_stretch launch for
-    all rows.  (buf', n'); the arguments themselves when nothing is active."""
+    analysis.pitch_shift, which is the stretch and the resampling behind it; with voice["psola"] through analysis.pitch_shift_psola:
+    the stretch, the two pitch-tracking launches and t2_psola - with voice_settings' window: ONE launch of each kernel for all rows.
+    (buf', n'); the arguments themselves when nothing is active."""
     if voice is None or not voice["active"]:
         return buf, n
     from .. import analysis
-    if voice["semitones"] == 0.0:
+    if voice["psola"]:
+        y, n_out, eff = analysis.pitch_shift_psola(buf, n, voice["semitones"], int(sample_rate), voice["pitch_range"], voice["ratio"],
+                                                   frame=voice["frame"], tolerance=voice["tolerance"])
+        if eff != voice["tempo"]:
+            raise RuntimeError(f"say: pitch_shift_psola ran at tempo {eff!r}, the settings say {voice['tempo']!r}")
+    elif voice["semitones"] == 0.0:
         y, n_out, _ = analysis.time_stretch(buf, n, voice["ratio"], voice["frame"], voice["tolerance"])
     else:
         y, n_out, eff, sr_mid = analysis.pitch_shift(buf, n, voice["semitones"], int(sample_rate), voice["requested_tempo"], voice["frame"],
@@ -131,12 +153,15 @@ def apply_voice(buf: torch.Tensor, n: List[int], voice: Optional[dict], sample_r
 
 def scale_records(records: list, voice: Optional[dict]) -> list:
     """duration_records behind voice_settings: start_s / end_s divided by the effective tempo - the NOMINAL time map; a frame's
-    offset moves a sample by at most the tolerance - and the fields `tempo` and `pitch_shift_semitones` added."""
+    offset moves a sample by at most the tolerance - and the fields `tempo` and `pitch_shift_semitones` added; on the PSOLA path, which
+    keeps every sample's time, also `preserve_formants` (true) and `pitch_range`."""
     if voice is None:
         return records
     for r in records:
         r["start_s"], r["end_s"] = [t / voice["tempo"] for t in r["start_s"]], [t / voice["tempo"] for t in r["end_s"]]
         r["tempo"], r["pitch_shift_semitones"] = voice["tempo"], voice["semitones"]
+        if voice["psola"]:
+            r["preserve_formants"], r["pitch_range"] = True, voice["pitch_range"]
     return records
 
 
@@ -146,8 +171,11 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
            description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
            forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
            stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-           pitch_shift: Optional[float] = None):
-    """tempo: 0.5 .. 2.0, pitch_shift: -12 .. 12 semitones - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is
+           pitch_shift: Optional[float] = None, preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None):
+    """preserve_formants (with pitch_shift or pitch_range) and pitch_range: 0 .. 2, the intonation range scaled about the mean pitch -
+    the pitch is then changed by TD-PSOLA on the device (analysis.pitch_shift_psola) behind a stretch by the tempo alone:
+    the sample count is the stretch's and nothing is resampled; `durations_out` objects gain `preserve_formants` and `pitch_range`.
+    tempo: 0.5 .. 2.0, pitch_shift: -12 .. 12 semitones - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is
     time-stretched by WSOLA on the device (analysis.time_stretch / pitch_shift) before out_sample_rate applies; the
     model's output itself is as decoded.  `durations_out` times are divided by the effective tempo and each object gains `tempo`
     and `pitch_shift_semitones`.  None: nothing of this runs; tempo 1 with pitch_shift 0 launches nothing either.
@@ -166,7 +194,8 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     if out_sample_rate is not None and hifi_gan_checkpoint is None and not output.endswith(".wav"):
         raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
     resampler = output_resampler(pre, out_sample_rate, dev)
-    voice = voice_settings(tempo, pitch_shift, sample_rate(pre), hifi_gan_checkpoint is not None or output.endswith(".wav"))
+    voice = voice_settings(tempo, pitch_shift, sample_rate(pre), hifi_gan_checkpoint is not None or output.endswith(".wav"),
+                           preserve_formants, pitch_range)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     _, chars, lens = encode_texts(enc, texts, dev)
@@ -217,7 +246,8 @@ KEEP_S = 0.020                                                          # audio 
 def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: int = 5000, batch_size: int = 64, pauses: dict = PAUSES,
                  trim: bool = True, level: bool = False, fade_ms: float = 5.0, speaker_id: Optional[int] = None,
                  controls: Optional[str] = None, description: Optional[str] = None, random_seed: Optional[int] = None,
-                 durations: bool = False, tempo: Optional[float] = None, pitch_shift: Optional[float] = None):
+                 durations: bool = False, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
+                 preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None):
     """Pieces (datasets.document.Piece, or a text, which is split at the defaults) -> one waveform on the model's device.
     The pieces are sorted by encoded length and decoded in chunks of batch_size through the model's free-running forward, with the
     decode settings that are on the model (common.free_run).  `vocoder` is a loaded hifigan.Generator - each chunk's PADDED batch
@@ -228,7 +258,9 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     at both ends), levels, fades and joins them, with pauses[break_after] seconds behind each piece.
     tempo (0.5 .. 2.0) and pitch_shift (-12 .. 12 semitones): the whole padded buffer goes through voice_settings' stretch in ONE
     launch in front of the join, the pieces side by side; the pauses and the piece-local times of `durations` are divided by the
-    effective tempo.
+    effective tempo.  preserve_formants and pitch_range (0 .. 2): the pitch is changed by TD-PSOLA instead (voice_settings), the whole
+    buffer through ONE launch of t2_stretch, of the two pitch-tracking kernels and of t2_psola; pauses and times are divided by the
+    tempo alone.
     A piece that ran into max_len without stopping is kept, cut there, and marked stopped=False.
     Returns (y (total,) float32, plan - join_audio's, device tensors -, info): info = dict(pieces, frames, stopped, n, pause,
     waveforms - the per-piece device tensors that went into the join -, chunks, join - the keyword arguments of the join_audio
@@ -245,7 +277,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
         raise ValueError(f"say_document: batch_size must be an integer in 1 .. 64, got {batch_size!r}")
     dev = next(model.parameters()).device
     sr = sample_rate(pre)
-    voice = voice_settings(tempo, pitch_shift, sr)
+    voice = voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
     texts = [p.text for p in pieces]
     ids, _, _ = encode_texts(enc, texts)
     order = sorted(range(len(ids)), key=lambda i: (len(ids[i]), i))
@@ -289,7 +321,7 @@ def document_records(info: dict, plan: dict, sample_rate: int) -> list:
     focus_rate, feasible as duration_records gives them; stopped; offset_s, trim_start_s, length_s, pause_s and gain of the join's
     plan; start_s / end_s per symbol in DOCUMENT time: a piece-local time t lies at offset_s + clip(t - trim_start_s, 0, length_s),
     still at the model's rate and its hop of 256.  With --tempo / --pitch-shift the piece-local times arrive divided by the effective
-    tempo (scale_records), and `tempo` and `pitch_shift_semitones` are passed on."""
+    tempo (scale_records), and `tempo`, `pitch_shift_semitones`, `preserve_formants` and `pitch_range` are passed on."""
     off, s0, length, gain = (plan[k].cpu().tolist() for k in ("off", "s0", "len", "gain"))
     out = []
     for i, (p, rec) in enumerate(zip(info["pieces"], info["durations"])):
@@ -299,7 +331,7 @@ def document_records(info: dict, plan: dict, sample_rate: int) -> list:
                         focus_rate=rec["focus_rate"], feasible=rec["feasible"], stopped=bool(info["stopped"][i]), offset_s=o,
                         trim_start_s=t0, length_s=ln, pause_s=info["pause"][i] / sample_rate, gain=float(gain[i]),
                         start_s=[doc(t) for t in rec["start_s"]], end_s=[doc(t) for t in rec["end_s"]],
-                        **{k: rec[k] for k in ("tempo", "pitch_shift_semitones") if k in rec}))
+                        **{k: rec[k] for k in ("tempo", "pitch_shift_semitones", "preserve_formants", "pitch_range") if k in rec}))
     return out
 
 
@@ -323,10 +355,11 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
                     forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
                     stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, max_chars: int = 190,
                     expand_numbers: bool = False, pause=None, trim: bool = True, level: bool = False, fade_ms: float = 5.0,
-                    batch_size: int = 64, tempo: Optional[float] = None, pitch_shift: Optional[float] = None):
+                    batch_size: int = 64, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
+                    preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None):
     """`say --text-file`: the file is read, its numbers expanded if asked, split (datasets/document.py) and spoken by say_document;
     the joined waveform is resampled to out_sample_rate if given (one Resampler call) and written by ONE write_wav call.
-    tempo, pitch_shift: say_document's, in front of the join.
+    tempo, pitch_shift, preserve_formants, pitch_range: say_document's, in front of the join.
     durations_out: document_records as a JSON list.  A piece that did not stop is reported on stderr; the exit status stays 0.
     Returns say_document's (y, plan, info), y as written (after resampling)."""
     import sys
@@ -344,7 +377,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     pre = dataset_config["preprocessing"]
     sr = sample_rate(pre)
     resampler = output_resampler(pre, out_sample_rate, dev)
-    voice_settings(tempo, pitch_shift, sr)
+    voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     with open(text_file, encoding="utf-8") as f:
         text = f.read()
@@ -360,7 +393,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     y, plan_, info = say_document(model, pieces, enc, pre, gen if gen is not None else gl, max_len=max_len, batch_size=batch_size,
                                   pauses=pauses, trim=trim, level=level, fade_ms=fade_ms, speaker_id=speaker_id, controls=controls,
                                   description=description, random_seed=random_seed, durations=durations_out is not None, tempo=tempo,
-                                  pitch_shift=pitch_shift)
+                                  pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range)
     for i, ok in enumerate(info["stopped"]):
         if not ok:
             print(f"say: piece {i} did not stop within --max-len {max_len} frames and is cut there: {pieces[i].text[:40]!r}", file=sys.stderr)
