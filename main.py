@@ -27,6 +27,7 @@ import re
 import click
 
 from tacotron2_amd.run.common import load_config, sample_rate
+from tacotron2_amd.voice import wav_target
 
 
 def parse_attention_window(ctx, param, value):
@@ -238,15 +239,14 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                                       ("--batch-size", batch_size)) if v is not None]
         if given:
             raise click.UsageError(f"{', '.join(given)} only with --text-file")
-    elif hifi_gan_checkpoint is None and not out.endswith(".wav"):
+    elif not wav_target(out, hifi_gan_checkpoint):
         raise click.UsageError(f"--text-file needs a .wav target (--out) or --hifi-gan-checkpoint, got --out {out}: a document has no single log-mel")
     preserve_formants = True if preserve_formants else None
     if tempo is not None or pitch_shift is not None or preserve_formants or pitch_range is not None:
-        from tacotron2_amd.run.common import sample_rate
         from tacotron2_amd.run.say import voice_settings
         try:
             voice_settings(tempo, pitch_shift, sample_rate(config_args(ctx, "Configuration required for speech!")["dataset_config"]["preprocessing"]),
-                           hifi_gan_checkpoint is not None or out.endswith(".wav"), preserve_formants, pitch_range)
+                           wav_target(out, hifi_gan_checkpoint), preserve_formants, pitch_range)
         except ValueError as e:
             raise click.UsageError(str(e))
     forward_attention = forward_attention_arg(forward_attention, attention_window)

@@ -82,6 +82,28 @@ def last_contiguous(fn: str, name: str, x) -> None:
         raise ValueError(f"{fn}: the last dimension of {name} must be contiguous")
 
 
+def row_stride(fn: str, name: str, x, unit: str = "samples") -> int:
+    """The row stride in elements of a (B, ld) view with a contiguous last dimension whose rows do not overlap - a contiguous
+    tensor, or a cut such as big[:, :ld].  One row takes the stride of the contiguous layout, at least 1."""
+    last_contiguous(fn, name, x)
+    B, ld = x.shape
+    ldx = x.stride(0) if B > 1 else max(ld, 1)
+    if ldx < ld:
+        raise ValueError(f"{fn}: overlapping rows of {name} (row stride {ldx}, {ld} {unit})")
+    return ldx
+
+
+def wav_rows(fn: str, name: str, x, max_samples=None):
+    """The front of time_stretch, psola and join_audio: a padded batch x (B, ld) float32 of 1 .. 65535 rows of at most max_samples
+    samples, row_stride's layout.  Returns (B, ld, ldx); the counts and the device are the caller's to check, in its own order."""
+    tensor_arg(fn, name, x, 2, "(B, samples)")
+    B, ld = x.shape
+    batch_arg(fn, B)
+    if max_samples is not None and ld > max_samples:
+        raise ValueError(f"{fn}: rows of {ld} samples, above the limit of {max_samples}")
+    return B, ld, row_stride(fn, name, x)
+
+
 def padded_wav(fn: str, wav, n, n_max, sr, hop, W, fmin, fmax):
     """The front of yin and voice_quality: a padded batch wav (B, ld) float32 on the GPU, its counts n, the largest count n_max
     (None: ld) and the frame geometry.  Returns (B, ld_wav, n_max, n as int64, T = 1 + n_max // hop, tau_min, tau_max)."""

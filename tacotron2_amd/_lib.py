@@ -166,6 +166,18 @@ def make(struct_name: str, **kw):
     return st
 
 
-def current_stream():
+def stream():
+    """The handle of torch's current stream: the last argument of every library call."""
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+_CACHE: dict = {}
+
+
+def cached(key, make, store: dict = _CACHE):
+    """make() once per key: the tables, meters and resamplers that are built once per device.  Keys start with their user's name."""
+    got = store.get(key)
+    if got is None:
+        got = store.setdefault(key, make())
+    return got

@@ -9,7 +9,7 @@ import torch
 
 from . import _args
 from ._args import YIN_MAX_SPAN
-from ._lib import call, make
+from ._lib import cached, call, make, stream
 # per-character pitch and energy on the duration grid: analysis.char_variance, written in variance.py
 from .join import fade_table, join_audio  # noqa: F401  (pieces joined into one waveform, DESIGN 5.16: analysis.join_audio, in join.py)
 from .stretch import hann_table, pitch_shift, time_stretch  # noqa: F401  (WSOLA tempo and pitch, DESIGN 5.17: in stretch.py)
@@ -19,10 +19,6 @@ from .variance import VAR_MAX_L, VAR_MAX_T, VAR_NSTAT, VAR_STATS, char_variance 
 PROSODY_MAX_T = 4096        # T2_PROSODY_MAX_T: frames of one utterance in t2_prosody_stats
 PROSODY_NSTAT = 8           # T2_PROSODY_NSTAT
 YIN_DEFAULTS = dict(sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=0.3, power_floor=1e-10)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _check_frames(fn: str, T: int) -> None:
@@ -49,7 +45,7 @@ def yin(wav, n, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=
         cmnd = torch.empty(B, T, tau_max + 1, dtype=torch.float32, device=wav.device) if return_cmnd else None
         a = make("T2Yin", wav=wav, ld_wav=ld_wav, n=n64, B=B, n_max=n_max, sr=sr, hop=hop, W=W, tau_min=tau_min, tau_max=tau_max,
                  thr=thr, vthr=vthr, power_floor=power_floor, f0=f0, aper=aper, power=power, cmnd=cmnd)
-        call("t2_yin", a, _stream())
+        call("t2_yin", a, stream())
     return (f0, aper, power, cmnd) if return_cmnd else (f0, aper, power)
 
 
@@ -66,7 +62,7 @@ def prosody_stats(f0, aper, power, n, hop=256, span=1024 + 367):
     with torch.cuda.device(f0.device):
         out = torch.empty(B, PROSODY_NSTAT, dtype=torch.float32, device=f0.device)
         a = make("T2ProsodyStats", f0=f0, aper=aper, power=power, n=n64, B=B, T=T, hop=hop, S=span, out=out)
-        call("t2_prosody_stats", a, _stream())
+        call("t2_prosody_stats", a, stream())
     return out
 
 
@@ -89,7 +85,7 @@ def voice_quality(wav, n, f0, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, 
         cyc = torch.empty(B, T, VQ_MAX_CYCLES, 3, dtype=torch.float32, device=wav.device) if return_cycles else None
         a = make("T2VoiceQuality", wav=wav, ld_wav=ld_wav, n=n64, B=B, n_max=n_max, sr=sr, hop=hop, W=W, tau_min=tau_min, tau_max=tau_max,
                  f0=f0, jitter=jitter, shimmer=shimmer, nhr=nhr, hnr_db=hnr_db, cycles=cycles, cyc=cyc)
-        call("t2_voice_quality", a, _stream())
+        call("t2_voice_quality", a, stream())
     return (jitter, shimmer, nhr, hnr_db, cycles, cyc) if return_cycles else (jitter, shimmer, nhr, hnr_db, cycles)
 
 
@@ -110,7 +106,7 @@ def corpus_stats(f0, power, jitter, shimmer, nhr, hnr_db, cycles, n, hop=256, sp
         out = torch.empty(B, CORPUS_NSTAT, dtype=torch.float32, device=f0.device)
         a = make("T2CorpusStats", f0=f0, power=power, jitter=jitter, shimmer=shimmer, nhr=nhr, hnr_db=hnr_db, cycles=cycles, n=n64, B=B,
                  T=T, hop=hop, S=span, power_floor=power_floor, out=out)
-        call("t2_corpus_stats", a, _stream())
+        call("t2_corpus_stats", a, stream())
     return out
 
 
@@ -159,7 +155,7 @@ def pitch_viterbi(cmnd, power, n, sr=22050, hop=256, fmin=60.0, fmax=500.0, powe
         a = make("T2PitchViterbi", cmnd=cmnd, ld_b=ld_b, ld_t=ld_t, power=power, len=frames, lw=lw, B=B, T=T, sr=sr, tau_min=tau_min,
                  tau_max=tau_max, power_floor=power_floor, trans_max=w * max_jump, u=u, c_sw=c_sw,
                  f0=f0, aper=aper, lag=lag, cost=cost, back=back)
-        call("t2_pitch_viterbi", a, _stream())
+        call("t2_pitch_viterbi", a, stream())
     return f0, aper, lag, cost
 
 
@@ -189,7 +185,7 @@ def f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=256, span=1024 + 367
         out = torch.empty(B, F0_NSTAT, dtype=torch.float64, device=path.device)
         a = make("T2F0PathStats", path=path, path_len=path_len.contiguous(), f0_a=f0_a, f0_b=f0_b, n_a=na64, n_b=nb64, B=B, P=P,
                  Ta=f0_a.shape[1], Tb=f0_b.shape[1], hop=hop, S=span, out=out)
-        call("t2_f0_path_stats", a, _stream())
+        call("t2_f0_path_stats", a, stream())
     return out
 
 
@@ -214,16 +210,17 @@ def f0_figures(row) -> dict:
 _RESAMPLERS: dict = {}
 
 
+def _resampler(sr_out: int, dev):
+    """The datasets.resample.Resampler to sr_out on dev, made once: resample's, and voice.run_voice's for a pitch shift."""
+    from .datasets.resample import Resampler
+    return cached((int(sr_out), dev), lambda: Resampler(int(sr_out), dev), _RESAMPLERS)
+
+
 def resample(wav, n, sr_in: int, sr_out: int):
     """A padded batch brought from sr_in to sr_out Hz (C-ABI t2_resample): wav (B, ld) float32 on the GPU, n the B sample
     counts (host integers, or an integer tensor, which is read back).  Returns (out (B, ld') float32, zeros behind each row, and the
     output counts ceil(n sr_out / sr_in) as host integers).  The Kaiser-windowed sinc of datasets/resample.py, designed once per
     rate pair; sr_in == sr_out returns the input.  Needs no model."""
-    from .datasets.resample import Resampler
     if not torch.is_tensor(wav) or wav.device.type != "cuda":
         raise ValueError("resample: wav must be a float32 (B, samples) tensor on the GPU")
-    key = (int(sr_out), wav.device)
-    rs = _RESAMPLERS.get(key)
-    if rs is None:
-        rs = _RESAMPLERS.setdefault(key, Resampler(int(sr_out), wav.device))
-    return rs.batch(wav, n.tolist() if torch.is_tensor(n) else n, int(sr_in))
+    return _resampler(sr_out, wav.device).batch(wav, n.tolist() if torch.is_tensor(n) else n, int(sr_in))

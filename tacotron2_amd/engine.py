@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from . import guard as _guard
 from . import _args
-from ._lib import call, make
+from ._lib import call, make, stream as _stream  # noqa: F401  (hifigan and the model import _stream from here)
 # the documented module API: the model-free measurements live in analysis, and engine.<name> is the same object
 from .analysis import (CORPUS_NSTAT, F0_NSTAT, PITCH_MAX_STATES, PROSODY_MAX_T, PROSODY_NSTAT, VITERBI_DEFAULTS, VQ_MAX_CYCLES,  # noqa: F401
                        YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, f0_figures, f0_path_stats, fade_table, fold_lags, join_audio,
@@ -35,11 +35,6 @@ from .options import (LOSS_DEFAULTS, MEL_LOSSES, check_attention_window, check_f
 from .params import ParamStore, reduction_factor
 
 KL, KPAD = 31, 15
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
 
 _TLS = _threading.local()      # per thread: the share_cu request (below) and the pending zero list (zero_later)
 

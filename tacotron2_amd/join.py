@@ -6,14 +6,7 @@ from __future__ import annotations
 import torch
 
 from . import _args
-from ._lib import call, make
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-_FADES: dict = {}
+from ._lib import cached, call, make, stream
 
 
 def fade_table(fade: int):
@@ -38,12 +31,7 @@ def join_audio(wav, n, pause, trim=True, top_db=60.0, frame_length=2048, hop_len
     fn = "join_audio"
     _args.tensor_arg(fn, "wav", wav, 2, "(B, samples)")
     _args.on_gpu(fn, "wav", wav)
-    B, ld = wav.shape
-    _args.batch_arg(fn, B)
-    _args.last_contiguous(fn, "wav", wav)
-    ldx = wav.stride(0) if B > 1 else max(ld, 1)
-    if ldx < ld:
-        raise ValueError(f"{fn}: overlapping rows of wav (row stride {ldx}, {ld} samples)")
+    B, ld, ldx = _args.wav_rows(fn, "wav", wav)
     trim, level = _args.flag_arg(fn, "trim", trim), _args.flag_arg(fn, "level", level)
     F = _args.int_arg(fn, "frame_length", frame_length, 2)
     if F % 2:
@@ -63,11 +51,7 @@ def join_audio(wav, n, pause, trim=True, top_db=60.0, frame_length=2048, hop_len
             cap = max(int(n32.clamp(0, ld).sum(dtype=torch.int64) + p32.clamp(min=0).sum(dtype=torch.int64)), 0)
         else:
             cap = n_sum + p_sum
-        w = None
-        if fade > 0:
-            w = _FADES.get((fade, dev))
-            if w is None:
-                w = _FADES.setdefault((fade, dev), torch.from_numpy(fade_table(fade)).to(dev))
+        w = cached(("fade", fade, dev), lambda: torch.from_numpy(fade_table(fade)).to(dev)) if fade > 0 else None
         lde = ld // H + 1
         energy = torch.empty(B, lde, dtype=torch.float64, device=dev) if trim else None
         stat = torch.empty(B, 2, dtype=torch.float64, device=dev)
@@ -79,7 +63,7 @@ def join_audio(wav, n, pause, trim=True, top_db=60.0, frame_length=2048, hop_len
         a = make("T2Join", x=wav if ld > 0 else None, ldx=ldx, n=n32, pause=p32, w=w, B=B, n_max=ld, trim=trim, F=F, H=H, keep=keep,
                  fade=fade, level=level, top_db=top_db, max_gain=max_gain, ceiling=ceiling, energy=energy, lde=lde, stat=stat,
                  off=off, s0=s0, len=length, gain=gain, total=total, y=y if cap > 0 else None, cap=cap)
-        call("t2_join", a, _stream())
+        call("t2_join", a, stream())
         t = int(total.item())
     if t < 0:
         raise ValueError(f"{fn}: an n[b] outside 0 .. {ld} or a negative pause[b] (refused on the device; nothing was written)")

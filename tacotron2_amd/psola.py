@@ -4,27 +4,20 @@ analysis.psola, analysis.pitch_ratio and analysis.pitch_shift_psola ARE this mod
 arguments are checked by _args before a pointer reaches a kernel."""
 from __future__ import annotations
 
+import contextlib
 import math
 
 import torch
 
 from . import _args
-from ._lib import call, make
+from ._lib import cached, call, make, stream
+from .stretch import MAX_SAMPLES, SEMITONE_RANGE
 
-MAX_SAMPLES = 1 << 27                       # t2_psola's n_max
 LAG_RANGE = (16, 4096)                      # T2_PSOLA_MIN_LAG, T2_PSOLA_MAX_LAG: voiced lags, and the unvoiced spacing
 RHO_ONE = 65536                             # Q16
 RHO_RANGE = (16384, 262144)                 # T2_PSOLA_MIN_RHO, T2_PSOLA_MAX_RHO: 1/4 .. 4
 SYN_TAIL = 10256                            # T2_PSOLA_SYN_TAIL
-SEMITONE_RANGE = (-24.0, 24.0)
 PITCH_RANGE_RANGE = (0.0, 2.0)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-_TABLES: dict = {}
 
 
 def grain_table():
@@ -40,11 +33,7 @@ def _rows(fn: str, name: str, x, B: int, T, dev):
     _args.on_device(fn, name, x, dev)
     if x.shape[0] != B or x.shape[1] < 1 or (T is not None and x.shape[1] != T):
         raise ValueError(f"{fn}: {name} must be ({B}, {'T >= 1' if T is None else T}), got {tuple(x.shape)}")
-    _args.last_contiguous(fn, name, x)
-    ld = x.stride(0) if B > 1 else x.shape[1]
-    if ld < x.shape[1]:
-        raise ValueError(f"{fn}: overlapping rows of {name} (row stride {ld}, {x.shape[1]} frames)")
-    return x.shape[1], ld
+    return x.shape[1], _args.row_stride(fn, name, x, "frames")
 
 
 def psola(wav, n, lag, rho, hop=256, unvoiced=None):
@@ -61,15 +50,7 @@ def psola(wav, n, lag, rho, hop=256, unvoiced=None):
     n_marks is -1 and nothing else is written for it - with host counts nothing is read back, so look at n_marks when the lags are not
     pitch_viterbi's.  Needs no model."""
     fn = "psola"
-    _args.tensor_arg(fn, "wav", wav, 2, "(B, samples)")
-    B, ld = wav.shape
-    _args.batch_arg(fn, B)
-    if ld > MAX_SAMPLES:
-        raise ValueError(f"{fn}: rows of {ld} samples, above the limit of {MAX_SAMPLES}")
-    _args.last_contiguous(fn, "wav", wav)
-    ldx = wav.stride(0) if B > 1 else max(ld, 1)
-    if ldx < ld:
-        raise ValueError(f"{fn}: overlapping rows of wav (row stride {ldx}, {ld} samples)")
+    B, ld, ldx = _args.wav_rows(fn, "wav", wav, MAX_SAMPLES)
     dev = wav.device
     hop = _args.int_arg(fn, "hop", hop, 16, 1 << 20)
     U = _args.int_arg(fn, "unvoiced", hop // 2 if unvoiced is None else unvoiced, *LAG_RANGE)
@@ -88,16 +69,14 @@ def psola(wav, n, lag, rho, hop=256, unvoiced=None):
     with torch.cuda.device(dev):
         if not torch.is_tensor(rho):
             rho = torch.full((B, ldt), q, dtype=torch.int32, device=dev)
-        w = _TABLES.get(dev)
-        if w is None:
-            w = _TABLES.setdefault(dev, torch.from_numpy(grain_table()).to(dev))
+        w = cached(("grain", dev), lambda: torch.from_numpy(grain_table()).to(dev))
         y = torch.empty(B, ldy, dtype=torch.float32, device=dev)
         a = torch.empty(B, ldm, dtype=torch.int32, device=dev)
         r, kmap = (torch.empty(B, lds, dtype=torch.int32, device=dev) for _ in range(2))
         n_marks, n_syn = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
         args = make("T2Psola", x=wav if ld > 0 else None, ldx=ldx, n=n32, lag=lag, rho=rho, ldt=ldt, w=w, B=B, n_max=n_max, T=T, hop=hop,
                     U=U, y=y if ldy > 0 else None, ldy=ldy, a=a, ldm=ldm, r=r, kmap=kmap, lds=lds, n_marks=n_marks, n_syn=n_syn)
-        call("t2_psola", args, _stream())
+        call("t2_psola", args, stream())
     return y, dict(a=a, r=r, kmap=kmap, n_marks=n_marks, n_syn=n_syn)
 
 
@@ -163,7 +142,7 @@ def fold_lags(cmnd, lag, tau_min, thr=0.1):
     tau_min = _args.int_arg(fn, "tau_min", tau_min, 2, NT - 2)
     thr = _args.real_arg(fn, "thr", thr)
     tau_max = NT - 1
-    with torch.cuda.device(cmnd.device) if cmnd.device.type == "cuda" else _null():
+    with torch.cuda.device(cmnd.device) if cmnd.device.type == "cuda" else contextlib.nullcontext():
         L = lag.to(torch.int64)
         out, done = L.clone(), L <= 0
         big = torch.full((), float("inf"), dtype=cmnd.dtype, device=cmnd.device)
@@ -180,25 +159,10 @@ def fold_lags(cmnd, lag, tau_min, thr=0.1):
         return out.to(torch.int32)
 
 
-class _null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_METERS: dict = {}
-
-
 def default_meter(sample_rate: int, dev):
     """The prosody.ProsodyMeter(sample_rate, dev, smooth=True) pitch_shift_psola tracks with, made once per rate and device."""
     from .prosody import ProsodyMeter
-    key = (int(sample_rate), dev)
-    m = _METERS.get(key)
-    if m is None:
-        m = _METERS.setdefault(key, ProsodyMeter(int(sample_rate), dev, smooth=True))
-    return m
+    return cached(("meter", int(sample_rate), dev), lambda: ProsodyMeter(int(sample_rate), dev, smooth=True))
 
 
 def check_meter(fn: str, meter) -> None:
@@ -246,29 +210,7 @@ def pitch_shift_psola(wav, n, semitones, sample_rate, pitch_range=1.0, tempo=1.0
     the meter refuses it.  The output's RMS is 0.66 .. 0.95 of the input's on synthetic vowels.
     Returns (y (B, ld') float32, n_out host integers, the effective tempo); with semitones == 0 and pitch_range == 1 nothing of the
     PSOLA path is launched and time_stretch's result comes back - at tempo 1, wav itself."""
-    fn = "pitch_shift_psola"
-    from .stretch import _stretch, tempo_ratio, window_args
-    semitones, pitch_range = shift_args(fn, semitones, pitch_range)
-    sr = _args.int_arg(fn, "sample_rate", sample_rate, 1000)
-    ratio = tempo_ratio(fn, tempo)
-    window_args(fn, frame, tolerance)
-    _args.tensor_arg(fn, "wav", wav, 2, "(B, samples)")
-    _args.on_gpu(fn, "wav", wav)
-    meter = default_meter(sr, wav.device) if meter is None else meter
-    check_meter(fn, meter)
-    if meter.settings["sr"] != sr or meter.device != wav.device:
-        raise ValueError(f"{fn}: the meter is for {meter.settings['sr']} Hz on {meter.device}, the signal is {sr} Hz on {wav.device}")
-    y, counts, _ = _stretch(fn, wav, n, ratio, frame, tolerance)
-    counts = [int(v) for v in (counts.tolist() if torch.is_tensor(counts) else counts)]
-    eff = ratio[0] / ratio[1]
-    if semitones == 0.0 and pitch_range == 1.0:
-        return y, counts, eff
-    s = meter.settings
-    n_max = max(counts)
-    check_frames(fn, n_max, s["hop"])
-    with torch.cuda.device(wav.device):
-        n_dev = torch.tensor(counts, dtype=torch.int64, device=wav.device)
-        lag = track_lags(meter, y, n_dev, n_max)
-        rho = pitch_ratio(lag, counts, semitones, pitch_range, s["hop"])
-        out, _ = psola(y, counts, lag, rho, s["hop"])
-    return out, counts, eff
+    from . import voice
+    plan = voice.plan_voice("pitch_shift_psola", sample_rate, tempo, semitones, pitch_range, True, frame, tolerance)
+    y, counts = voice.run_voice(plan, wav, n, meter)
+    return y, counts, plan.tempo

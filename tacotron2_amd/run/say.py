@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from ..datasets.text import TextEncoder
+from ..voice import VoicePlan, run_voice, wav_target
 from .common import emitted_frames, encode_texts, free_run, load_decode_model, pad_ids, sample_rate
 from .test import make_vocoders
 
@@ -85,16 +86,15 @@ TEMPO_LIMITS, PITCH_LIMITS = (0.5, 2.0), (-12.0, 12.0)                  # what `
 RANGE_LIMITS = (0.0, 2.0)                                               # and of analysis.pitch_shift_psola's pitch_range
 
 
-def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True, preserve_formants=None, pitch_range=None) -> Optional[dict]:
+def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True, preserve_formants=None, pitch_range=None) -> Optional[VoicePlan]:
     """--tempo T, --pitch-shift SEMITONES, --preserve-formants and --pitch-range K of `say`, checked before anything
-    is decoded: None when none is given, else dict(psola - True with --preserve-formants or --pitch-range: the pitch is changed by
-    analysis.pitch_shift_psola behind a stretch by the tempo alone, nothing is resampled, sr_mid is the sample rate -, pitch_range,
-    tempo - the EFFECTIVE tempo, what the times of --durations-out and the pauses are divided by -, requested_tempo,
-    semitones, ratio - the (P, 1000) the stretch runs at, which a pitch shift may take to 1/8 .. 8 -, sr_mid, frame, tolerance,
-    active - False when nothing would change, and nothing is then launched).  The window is 1024 samples and the tolerance 256 at 22 050 Hz, scaled with the rate, rounded to even and kept
-    within the kernel's limits: product defaults, not measurements."""
+    is decoded: None when none is given, else the voice.VoicePlan that apply_voice runs - psola with --preserve-formants or
+    --pitch-range; tempo, the EFFECTIVE tempo, is what the times of --durations-out and the pauses are divided by; ratio, the (P, 1000)
+    the stretch runs at, may be taken to 1/8 .. 8 by a pitch shift.  The window is 1024 samples and the tolerance 256 at 22 050 Hz,
+    scaled with the rate, rounded to even and kept within the kernel's limits: product defaults, not measurements."""
     import math
-    from ..stretch import MAX_FRAME, MAX_TOLERANCE, pitch_plan
+    from ..stretch import MAX_FRAME, MAX_TOLERANCE
+    from ..voice import plan_voice
     psola = bool(preserve_formants) or pitch_range is not None
     if tempo is None and pitch_shift is None and not psola:
         return None
@@ -109,59 +109,32 @@ def voice_settings(tempo, pitch_shift, sample_rate: int, wav_target: bool = True
         raise ValueError("--tempo and --pitch-shift need a .wav target or a HiFi-GAN checkpoint: a log-mel is not stretched")
     tempo, semitones = 1.0 if tempo is None else float(tempo), 0.0 if pitch_shift is None else float(pitch_shift)
     even = lambda v, lo, hi: min(max(2 * int(round(v * sample_rate / 22050.0 / 2.0)), lo), hi)
-    if psola:                                      # (what analysis.pitch_shift_psola will do, checked here: its meter at this rate)
+    if psola:                                      # (the default meter of voice.run_voice must be able to follow this rate)
         from ..psola import check_rate
         check_rate("say", int(sample_rate))
-        rng, P = 1.0 if pitch_range is None else float(pitch_range), int(round(tempo * 1000.0))
-        return dict(tempo=P / 1000.0, requested_tempo=tempo, semitones=semitones, ratio=(P, 1000), sr_mid=int(sample_rate),
-                    frame=even(1024, 4, MAX_FRAME), tolerance=even(256, 0, MAX_TOLERANCE), psola=True, pitch_range=rng,
-                    active=P != 1000 or semitones != 0.0 or rng != 1.0)
-    if semitones == 0.0:
-        P = int(round(tempo * 1000.0))
-        sr_mid, eff, ratio = int(sample_rate), P / 1000.0, (P, 1000)
-    else:                                          # (what analysis.pitch_shift will do, checked here: its ratio and its resampling plan)
-        from ..datasets.resample import plan
-        sr_mid, eff, ratio = pitch_plan("say", semitones, int(sample_rate), tempo)
-        plan(sr_mid, int(sample_rate))
-    return dict(tempo=eff, requested_tempo=tempo, semitones=semitones, ratio=ratio, sr_mid=sr_mid, frame=even(1024, 4, MAX_FRAME),
-                tolerance=even(256, 0, MAX_TOLERANCE), psola=False, pitch_range=1.0,
-                active=ratio[0] != ratio[1] or sr_mid != int(sample_rate))
+    return plan_voice("say", int(sample_rate), tempo, semitones, 1.0 if pitch_range is None else float(pitch_range), psola,
+                      even(1024, 4, MAX_FRAME), even(256, 0, MAX_TOLERANCE), pitch=semitones != 0.0)
 
 
-def apply_voice(buf: torch.Tensor, n: List[int], voice: Optional[dict], sample_rate: int):
-    """A padded batch (B, ld) on the device with its counts through analysis.time_stretch - or, for a pitch shift, through
-    analysis.pitch_shift, which is the stretch and the resampling behind it; with voice["psola"] through analysis.pitch_shift_psola:
-    the stretch, the two pitch-tracking launches and t2_psola - with voice_settings' window: ONE launch of each kernel for all rows.
-    (buf', n'); the arguments themselves when nothing is active."""
-    if voice is None or not voice["active"]:
+def apply_voice(buf: torch.Tensor, n: List[int], voice: Optional[VoicePlan]):
+    """A padded batch (B, ld) on the device with its counts through voice.run_voice: ONE launch of each kernel of the plan for all
+    rows.  (buf', n' as host integers); the arguments themselves when nothing is active."""
+    if voice is None or not voice.active:
         return buf, n
-    from .. import analysis
-    if voice["psola"]:
-        y, n_out, eff = analysis.pitch_shift_psola(buf, n, voice["semitones"], int(sample_rate), voice["pitch_range"], voice["ratio"],
-                                                   frame=voice["frame"], tolerance=voice["tolerance"])
-        if eff != voice["tempo"]:
-            raise RuntimeError(f"say: pitch_shift_psola ran at tempo {eff!r}, the settings say {voice['tempo']!r}")
-    elif voice["semitones"] == 0.0:
-        y, n_out, _ = analysis.time_stretch(buf, n, voice["ratio"], voice["frame"], voice["tolerance"])
-    else:
-        y, n_out, eff, sr_mid = analysis.pitch_shift(buf, n, voice["semitones"], int(sample_rate), voice["requested_tempo"], voice["frame"],
-                                                     voice["tolerance"])
-        if (eff, sr_mid) != (voice["tempo"], voice["sr_mid"]):          # (one plan: the times were scaled by this tempo)
-            raise RuntimeError(f"say: pitch_shift ran at tempo {eff!r} through {sr_mid} Hz, the settings say {voice['tempo']!r}, {voice['sr_mid']}")
-    return y, [int(v) for v in n_out]
+    return run_voice(voice, buf, n)
 
 
-def scale_records(records: list, voice: Optional[dict]) -> list:
+def scale_records(records: list, voice: Optional[VoicePlan]) -> list:
     """duration_records behind voice_settings: start_s / end_s divided by the effective tempo - the NOMINAL time map; a frame's
     offset moves a sample by at most the tolerance - and the fields `tempo` and `pitch_shift_semitones` added; on the PSOLA path, which
     keeps every sample's time, also `preserve_formants` (true) and `pitch_range`."""
     if voice is None:
         return records
     for r in records:
-        r["start_s"], r["end_s"] = [t / voice["tempo"] for t in r["start_s"]], [t / voice["tempo"] for t in r["end_s"]]
-        r["tempo"], r["pitch_shift_semitones"] = voice["tempo"], voice["semitones"]
-        if voice["psola"]:
-            r["preserve_formants"], r["pitch_range"] = True, voice["pitch_range"]
+        r["start_s"], r["end_s"] = [t / voice.tempo for t in r["start_s"]], [t / voice.tempo for t in r["end_s"]]
+        r["tempo"], r["pitch_shift_semitones"] = voice.tempo, voice.semitones
+        if voice.psola:
+            r["preserve_formants"], r["pitch_range"] = True, voice.pitch_range
     return records
 
 
@@ -191,11 +164,11 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
     pre = dataset_config["preprocessing"]
-    if out_sample_rate is not None and hifi_gan_checkpoint is None and not output.endswith(".wav"):
+    audio = wav_target(output, hifi_gan_checkpoint)
+    if out_sample_rate is not None and not audio:
         raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
     resampler = output_resampler(pre, out_sample_rate, dev)
-    voice = voice_settings(tempo, pitch_shift, sample_rate(pre), hifi_gan_checkpoint is not None or output.endswith(".wav"),
-                           preserve_formants, pitch_range)
+    voice = voice_settings(tempo, pitch_shift, sample_rate(pre), audio, preserve_formants, pitch_range)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     _, chars, lens = encode_texts(enc, texts, dev)
@@ -208,10 +181,9 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     if durations_out is not None:
         with open(durations_out, "w") as f:
             json.dump(scale_records(duration_records(model, enc, texts, align, lens, frames, sr), voice), f)
-    if hifi_gan_checkpoint is None and not output.endswith(".wav"):
+    if not audio:
         np.save(output, mels[0] if isinstance(text, str) else np.array(mels, dtype=object), allow_pickle=not isinstance(text, str))
         return mels
-    from ..vocoder import write_wav
     gen, gl, _ = make_vocoders(hifi_gan_checkpoint, dict(pre, num_mels=post.shape[2]), dev)
     if gen is not None:
         # run/say.py:66-86,153-159: generator(mel_post[:, :-1].swapaxes(1, 2)) -> waveform, written as audio whatever the name
@@ -219,23 +191,39 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     else:
         vocode = lambda m: gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0))
     stretched = None
-    if voice is not None and voice["active"]:             # every text's waveform in one padded batch: ONE stretch launch
-        raw = [torch.as_tensor(vocode(m)).detach().float().reshape(-1) for m in mels]
-        n = [int(w.numel()) for w in raw]
-        buf = torch.zeros(len(raw), max(max(n), 1), dtype=torch.float32, device=dev)
-        for i, w in enumerate(raw):
-            buf[i, :n[i]] = w
-        rows, n_out = apply_voice(buf, n, voice, sr)
-        stretched = [rows[i, :n_out[i]].cpu() for i in range(len(raw))]
+    if voice is not None and voice.active:                # every text's waveform in one padded batch: ONE stretch launch
+        rows, n_out = apply_voice(*pack_rows([torch.as_tensor(vocode(m)).detach().float().reshape(-1) for m in mels], dev), voice)
+        stretched = [rows[i, :n_out[i]].cpu() for i in range(len(mels))]
     for i, m in enumerate(mels):
         # several texts: `<output without its extension>_<i>.wav`.  Griffin-Lim is reached with a name that ends in ".wav" only, whose
         # last dot is that extension's, so this is the `output[:-4]` of the reference's branch as well
         name = output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav"
-        wav = vocode(m) if stretched is None else stretched[i]
-        if resampler is not None:
-            wav = torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
-        write_wav(name, wav, sr if resampler is None else int(out_sample_rate))
+        write_audio(name, vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
     return mels
+
+
+def pack_rows(waves, dev):
+    """Waveforms of any device -> (one zero-padded float32 buffer (B, max(longest, 1)) on dev, their sample counts)."""
+    n = [int(w.numel()) for w in waves]
+    buf = torch.zeros(len(waves), max(max(n), 1), dtype=torch.float32, device=dev)
+    for i, w in enumerate(waves):
+        buf[i, :n[i]] = w
+    return buf, n
+
+
+def write_audio(name: str, wav, sr: int, resampler, host: bool):
+    """The tail of both drivers: `wav` at sr Hz brought to --out-sample-rate if there is one, then ONE vocoder.write_wav call with the
+    rate the samples then have.  host: do_say's way, which vocodes text by text and writes each text from the host - up and down
+    through Resampler.one; else the document's, whose joined waveform stays on the device through Resampler.batch.  Returns the
+    waveform as written."""
+    from .. import vocoder
+    if resampler is not None and host:
+        wav = torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
+    elif resampler is not None and wav.numel() > 0:
+        out, n_out = resampler.batch(wav[None, :], [int(wav.numel())], sr)
+        wav = out[0, :n_out[0]]
+    vocoder.write_wav(name, wav, sr if resampler is None else resampler.sr_out)
+    return wav
 
 
 # ---- say --text-file: a document split into pieces, decoded side by side, joined on the device (DESIGN 5.16) ----------------------------
@@ -299,14 +287,11 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                    for k in range(len(ch))]
         for k, i in enumerate(ch):
             waves[i], frames[i], stopped[i] = out[k], fr[k], stop[k]
-    n = [int(w.numel()) for w in waves]
-    buf = torch.zeros(P, max(max(n), 1), dtype=torch.float32, device=dev)
-    for i, w in enumerate(waves):
-        buf[i, :n[i]] = w
-    if voice is not None and voice["active"]:
-        buf, n = apply_voice(buf, n, voice, sr)
+    buf, n = pack_rows(waves, dev)
+    if voice is not None and voice.active:
+        buf, n = apply_voice(buf, n, voice)
         waves = [buf[i, :n[i]] for i in range(P)]
-    pause = [int(round(float(pauses[p.break_after]) * sr / (voice["tempo"] if voice else 1.0))) for p in pieces]
+    pause = [int(round(float(pauses[p.break_after]) * sr / (voice.tempo if voice else 1.0))) for p in pieces]
     F = int(pre.get("trim_frame_length", 2048))
     join = dict(trim=bool(trim), top_db=float(pre.get("trim_top_db", 60)), frame_length=F, hop_length=max(F // 4, 1),
                 keep=int(round(KEEP_S * sr)), fade=int(round(float(fade_ms) * sr / 1000.0)), level=bool(level),
@@ -364,9 +349,8 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     Returns say_document's (y, plan, info), y as written (after resampling)."""
     import sys
     import time
-    from .. import vocoder as V
     from ..datasets.document import expand_numbers as expand, split_document
-    if hifi_gan_checkpoint is None and not output.endswith(".wav"):
+    if not wav_target(output, hifi_gan_checkpoint):
         raise ValueError(f"--text-file needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a document has no single log-mel")
     if fade_ms < 0:
         raise ValueError(f"--fade-ms must be >= 0, got {fade_ms!r}")
@@ -401,10 +385,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
         with open(durations_out, "w") as f:
             json.dump(document_records(info, plan_, sr), f)
     seconds = y.numel() / sr
-    if resampler is not None and y.numel() > 0:
-        out, n_out = resampler.batch(y[None, :], [int(y.numel())], sr)
-        y = out[0, :n_out[0]]
-    V.write_wav(output, y, int(out_sample_rate) if out_sample_rate is not None else sr)
+    y = write_audio(output, y, sr, resampler, host=False)
     torch.cuda.synchronize(dev)
     print(f"say: {len(pieces)} pieces in {info['chunks']} chunks, {seconds:.2f} s of audio in {time.perf_counter() - t_start:.2f} s")
     return y, plan_, info

@@ -9,20 +9,13 @@ import math
 import torch
 
 from . import _args
-from ._lib import call, make
+from ._lib import cached, call, make, stream
 
 MAX_FRAME, MAX_TOLERANCE = 2048, 1024       # T2_STRETCH_MAX_N, T2_STRETCH_MAX_D
-MAX_SAMPLES = 1 << 27                       # t2_stretch's n_max
+MAX_SAMPLES = 1 << 27                       # t2_stretch's n_max, and t2_psola's
 TEMPO_RANGE = (0.25, 4.0)
 RATIO_RANGE = (0.125, 8.0)                  # t2_stretch's P / Q: what a pitch shift may ask of the stretch (4 x 2 octaves is refused)
-SEMITONE_RANGE = (-24.0, 24.0)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-_WINDOWS: dict = {}
+SEMITONE_RANGE = (-24.0, 24.0)              # of pitch_shift, and of pitch_shift_psola
 
 
 def hann_table(N: int):
@@ -76,17 +69,9 @@ def time_stretch(wav, n, tempo, frame=1024, tolerance=256):
 
 def _stretch(fn: str, wav, n, ratio, frame, tolerance):
     """time_stretch behind its tempo check, for the caller `fn`: ratio = (P, Q) within t2_stretch's range."""
-    _args.tensor_arg(fn, "wav", wav, 2, "(B, samples)")
     P, Q = ratio
     N, D = window_args(fn, frame, tolerance)
-    B, ld = wav.shape
-    _args.batch_arg(fn, B)
-    if ld > MAX_SAMPLES:
-        raise ValueError(f"{fn}: rows of {ld} samples, above the limit of {MAX_SAMPLES}")
-    _args.last_contiguous(fn, "wav", wav)
-    ldx = wav.stride(0) if B > 1 else max(ld, 1)
-    if ldx < ld:
-        raise ValueError(f"{fn}: overlapping rows of wav (row stride {ldx}, {ld} samples)")
+    B, ld, ldx = _args.wav_rows(fn, "wav", wav, MAX_SAMPLES)
     dev = wav.device
     n32, n_sum = _args.counts32(fn, "n", n, B, dev, hi=ld)
     _args.on_gpu(fn, "wav", wav)
@@ -97,15 +82,13 @@ def _stretch(fn: str, wav, n, ratio, frame, tolerance):
     top = out_len(n_max, P, Q)
     ldy, ldp = (top + 63) // 64 * 64, -(-top // Hs) + 1
     with torch.cuda.device(dev):
-        w = _WINDOWS.get((N, dev))
-        if w is None:
-            w = _WINDOWS.setdefault((N, dev), torch.from_numpy(hann_table(N)).to(dev))
+        w = cached(("hann", N, dev), lambda: torch.from_numpy(hann_table(N)).to(dev))
         y = torch.empty(B, ldy, dtype=torch.float32, device=dev)
         pos = torch.empty(B, ldp, dtype=torch.int32, device=dev)
         n_out = torch.empty(B, dtype=torch.int32, device=dev)
         a = make("T2Stretch", x=wav if ld > 0 else None, ldx=ldx, n=n32, w=w, B=B, n_max=n_max, N=N, D=D, P=P, Q=Q,
                  y=y if ldy > 0 else None, ldy=ldy, pos=pos, ldp=ldp, n_out=n_out)
-        call("t2_stretch", a, _stream())
+        call("t2_stretch", a, stream())
         if n_sum is None:
             counts = n_out.tolist()
             if min(counts) < 0:
@@ -141,20 +124,7 @@ def pitch_shift(wav, n, semitones, sample_rate, tempo=1.0, frame=1024, tolerance
     Hz and brought back to sample_rate.  Formants move with the pitch.  wav and n as time_stretch takes them (a device n is read
     back: the resampler wants host counts).  Returns (y (B, ld') float32, n_out host integers, the effective tempo, sr_mid); with
     semitones so small that sr_mid == sample_rate and a stretch ratio of 1 nothing is launched and wav itself comes back."""
-    fn = "pitch_shift"
-    sr_mid, eff, ratio = pitch_plan(fn, semitones, sample_rate, tempo)
-    window_args(fn, frame, tolerance)
-    from .datasets.resample import Resampler, plan
-    plan(sr_mid, int(sample_rate))
-    y, counts, _ = _stretch(fn, wav, n, ratio, frame, tolerance)
-    if torch.is_tensor(counts):
-        counts = counts.tolist()
-    key = (int(sample_rate), wav.device)
-    rs = _RESAMPLERS.get(key)
-    if rs is None:
-        rs = _RESAMPLERS.setdefault(key, Resampler(int(sample_rate), wav.device))
-    y, counts = rs.batch(y, counts, sr_mid)
-    return y, counts, eff, sr_mid
-
-
-_RESAMPLERS: dict = {}
+    from . import voice
+    plan = voice.plan_voice("pitch_shift", sample_rate, tempo, semitones, frame=frame, tolerance=tolerance)
+    y, counts = voice.run_voice(plan, wav, n, fn="pitch_shift")
+    return y, counts, plan.tempo, plan.sr_mid

@@ -176,6 +176,39 @@ def test_strided_3d_refuses_strided_columns_and_overlapping_rows(fn):
     refused(lambda: A.strided_3d(fn, "mel", flat.as_strided((1, 5, 8), (40, 4, 1))), f"{fn}: overlapping rows of mel (strides (40, 4, 1))")
 
 
+# ---- wav_rows -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fn", FNS)
+def test_wav_rows_messages(fn):
+    x = torch.zeros(2, 100)
+    assert A.wav_rows(fn, "wav", x) == (2, 100, 100) and A.wav_rows(fn, "wav", x, 100) == (2, 100, 100)
+    for bad in (x.double(), x[0], x[None], x.int(), x.numpy(), None):
+        refused(lambda: A.wav_rows(fn, "wav", bad), f"{fn}: wav must be a float32 (B, samples) tensor")
+    refused(lambda: A.wav_rows(fn, "wav", torch.zeros(0, 100)), f"{fn}: batch of 0, outside 1 .. 65535")
+    refused(lambda: A.wav_rows(fn, "wav", torch.zeros(1, 1).expand(65536, 1)), f"{fn}: batch of 65536, outside 1 .. 65535")
+    refused(lambda: A.wav_rows(fn, "wav", x, 99), f"{fn}: rows of 100 samples, above the limit of 99")
+    refused(lambda: A.wav_rows(fn, "wav", torch.zeros(0, 100), 99), f"{fn}: batch of 0, outside 1 .. 65535")       # (the batch first)
+    refused(lambda: A.wav_rows(fn, "wav", torch.zeros(2, 200)[:, ::2]), f"{fn}: the last dimension of wav must be contiguous")
+    refused(lambda: A.wav_rows(fn, "wav", torch.zeros(2, 200)[:, ::2], 99), f"{fn}: rows of 100 samples, above the limit of 99")   # (the limit before the layout)
+    refused(lambda: A.wav_rows(fn, "wav", torch.zeros(200).as_strided((2, 100), (50, 1))), f"{fn}: overlapping rows of wav (row stride 50, 100 samples)")
+    refused(lambda: A.row_stride(fn, "lag", torch.zeros(20, dtype=torch.int32).as_strided((2, 10), (5, 1)), "frames"),
+            f"{fn}: overlapping rows of lag (row stride 5, 10 frames)")
+
+
+def test_wav_rows_stride_rule_on_views():
+    big = torch.zeros(2, 4096)
+    assert A.wav_rows("f", "wav", torch.zeros(1, 0)) == (1, 0, 1)                      # one row without a column: a stride of 1, not 0
+    assert A.wav_rows("f", "wav", big[:, :3000]) == (2, 3000, 4096)                    # a cut of a larger buffer keeps its stride
+    assert A.wav_rows("f", "wav", big[:1, :3000]) == (1, 3000, 3000) and A.wav_rows("f", "wav", big[1:, 5:]) == (1, 4091, 4091)
+    assert A.wav_rows("f", "wav", torch.zeros(3, 1)) == (3, 1, 1) and A.wav_rows("f", "wav", big[:, 7:8]) == (2, 1, 4096)
+    refused(lambda: A.wav_rows("f", "wav", torch.zeros(3000, 2).t()), "f: the last dimension of wav must be contiguous")
+    refused(lambda: A.wav_rows("f", "wav", torch.zeros(1, 1).expand(2, 5)), "f: the last dimension of wav must be contiguous")
+    flat = torch.zeros(300)
+    for stride in (99, 50, 1, 0):
+        refused(lambda: A.wav_rows("f", "wav", flat.as_strided((3, 100), (stride, 1))), f"f: overlapping rows of wav (row stride {stride}, 100 samples)")
+    assert A.wav_rows("f", "wav", flat.as_strided((3, 100), (100, 1))) == (3, 100, 100)
+    assert A.wav_rows("f", "wav", flat.as_strided((1, 100), (0, 1))) == (1, 100, 100)  # (B == 1: the row stride is not used)
+
+
 # ---- the module layout ------------------------------------------------------------------------------------------------------------------
 def test_engine_reexports_the_measurements_as_the_same_objects():
     from tacotron2_amd import analysis, engine

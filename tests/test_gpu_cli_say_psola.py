@@ -101,7 +101,7 @@ def test_a_document_takes_one_launch_of_each_kernel_for_all_pieces(setup, tmp_pa
     assert launches == ["t2_stretch", "t2_yin", "t2_pitch_viterbi", "t2_psola"]                # three pieces, ONE launch each
     assert len(info["pieces"]) == 3 and info["chunks"] == 1
     v = info["voice"]
-    assert (v["psola"], v["tempo"], v["ratio"], v["semitones"], v["pitch_range"]) == (True, 1.25, (1250, 1000), 2.0, 0.5)
+    assert (v.psola, v.tempo, v.ratio, v.semitones, v.pitch_range) == (True, 1.25, (1250, 1000), 2.0, 0.5)
     n0 = base["n"]
     assert info["n"] == [-(-k * 1000 // 1250) for k in n0] and info["frames"] == base["frames"]       # the stretch's counts: no resampling
     buf = torch.zeros(3, max(n0), device=DEV)
@@ -129,7 +129,7 @@ def test_model_say_document_carries_the_two_options(setup, launches):
     model = load_decode_model(cfg["dataset"], cfg["training"], cfg["model"], cfg["extensions"], str(setup["ck"]), torch.device(DEV), 3, None, None, None)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     y, plan, info = model.say_document(DOC, enc, pre, max_len=40, preserve_formants=True, pitch_shift=-3, pitch_range=1.2)
-    assert launches == ["t2_yin", "t2_pitch_viterbi", "t2_psola"] and info["voice"]["psola"] and y.numel() > 0
+    assert launches == ["t2_yin", "t2_pitch_viterbi", "t2_psola"] and info["voice"].psola and y.numel() > 0
 
 
 def test_the_no_op_combination_launches_nothing_and_writes_the_same_bytes(setup, tmp_path, monkeypatch):

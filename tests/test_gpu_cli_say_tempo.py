@@ -155,7 +155,7 @@ def test_a_document_at_tempo_1_25(setup, tmp_path):
     _, plan0, base = do_say_document(output=str(tmp_path / "a.wav"), durations_out=str(tmp_path / "a.json"), **kw)
     y, plan, info = do_say_document(output=str(tmp_path / "b.wav"), durations_out=str(tmp_path / "b.json"), tempo=1.25, **kw)
     assert [p.text for p in info["pieces"]] == ["One came.", "Two stayed, three left!", "It ends here."] and info["chunks"] == 1
-    assert info["voice"]["tempo"] == 1.25 and info["voice"]["ratio"] == (1250, 1000) and base["voice"] is None
+    assert info["voice"].tempo == 1.25 and info["voice"].ratio == (1250, 1000) and base["voice"] is None
     # the pieces: ONE time_stretch call over the padded buffer of the plain run's pieces
     n0 = base["n"]
     assert info["n"] == [-(-k * 1000 // 1250) for k in n0] and info["frames"] == base["frames"]

@@ -166,11 +166,11 @@ def test_say_settings_are_checked_before_anything_is_decoded():
     from tacotron2_amd.run.say import scale_records, voice_settings
     assert voice_settings(None, None, SR) is None and voice_settings(None, None, SR, True, None, None) is None
     plain = voice_settings(0.8, None, SR)
-    assert plain["psola"] is False and plain["ratio"] == (800, 1000)
+    assert plain.psola is False and plain.ratio == (800, 1000)
     v = voice_settings(1.25, 3, SR, True, True, None)
-    assert (v["psola"], v["tempo"], v["ratio"], v["semitones"], v["pitch_range"], v["sr_mid"], v["active"]) == (True, 1.25, (1250, 1000), 3.0, 1.0, SR, True)
-    assert voice_settings(None, None, SR, True, None, 0.5)["psola"] and voice_settings(None, None, SR, True, None, 0.5)["active"]
-    assert voice_settings(None, 0, SR, True, True, 1)["active"] is False and voice_settings(1.0, 0.0, SR, True, True, 1.0)["active"] is False
+    assert (v.psola, v.tempo, v.ratio, v.semitones, v.pitch_range, v.sr_mid, v.active) == (True, 1.25, (1250, 1000), 3.0, 1.0, SR, True)
+    assert voice_settings(None, None, SR, True, None, 0.5).psola and voice_settings(None, None, SR, True, None, 0.5).active
+    assert voice_settings(None, 0, SR, True, True, 1).active is False and voice_settings(1.0, 0.0, SR, True, True, 1.0).active is False
     for args, name in (((None, None, SR, True, True, None), "--preserve-formants needs"), ((None, None, SR, True, None, 2.5), "--pitch-range must lie"),
                        ((None, None, SR, True, None, -0.1), "--pitch-range must lie"), ((None, None, SR, True, None, float("nan")), "--pitch-range"),
                        ((None, None, SR, False, None, 0.5), "--pitch-range need a .wav"), ((None, 2, SR, False, True, None), "--preserve-formants and"),

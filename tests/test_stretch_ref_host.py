@@ -184,17 +184,17 @@ def test_every_corner_of_say_s_ranges_passes_the_checks_the_driver_runs(rate):
         for semitones in (-12, -11.9, -1, 0, 0.01, 5, 12, None):
             voice = voice_settings(tempo, semitones, rate)
             if voice is None:
-                assert tempo is None and semitones is None and apply_voice(x, [1, 2], voice, rate)[0] is x
+                assert tempo is None and semitones is None and apply_voice(x, [1, 2], voice)[0] is x
                 continue
-            assert abs(voice["tempo"] - (tempo or 1.0)) <= 2.1e-3 * (tempo or 1.0) and 125 <= voice["ratio"][0] <= 8000
+            assert abs(voice.tempo - (tempo or 1.0)) <= 2.1e-3 * (tempo or 1.0) and 125 <= voice.ratio[0] <= 8000
             if semitones:
-                assert (voice["sr_mid"], voice["tempo"], voice["ratio"]) == pitch_plan("pitch_shift", semitones, rate, tempo or 1.0)
-            if not voice["active"]:
-                assert apply_voice(x, [1, 2], voice, rate)[0] is x
+                assert (voice.sr_mid, voice.tempo, voice.ratio) == pitch_plan("pitch_shift", semitones, rate, tempo or 1.0)
+            if not voice.active:
+                assert apply_voice(x, [1, 2], voice)[0] is x
             else:
-                _raises("wav must be on the GPU", apply_voice, x, [3000, 2], voice, rate)
+                _raises("wav must be on the GPU", apply_voice, x, [3000, 2], voice)
     # the corner the 50 Hz and 1/1000 roundings push past 4: the stretch of a pitch shift may run at up to 8
-    assert voice_settings(2.0, -12, 22050)["ratio"] == (4009, 1000) and voice_settings(0.5, 12, 22050)["ratio"] == (250, 1000)
+    assert voice_settings(2.0, -12, 22050).ratio == (4009, 1000) and voice_settings(0.5, 12, 22050).ratio == (250, 1000)
     for tempo, semitones, name in ((2.01, 0, "--tempo"), (0.49, None, "--tempo"), (1, 12.01, "--pitch-shift"), (None, -12.5, "--pitch-shift")):
         _raises(name, voice_settings, tempo, semitones, rate)
     _raises("need a .wav target", voice_settings, 1.0, None, rate, False)
