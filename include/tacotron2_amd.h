@@ -1157,6 +1157,29 @@ int t2_sumsq(const float* g, int64_t n, double* out, void* stream);
 int t2_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq, float max_norm, float lr,
                  float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 
+/* t2_adam_step with options: decoupled weight decay (AdamW) and an exponential moving average (EMA) of the parameters, folded
+ * into the same elementwise pass.  The first fourteen fields are t2_adam_step's arguments.  With
+ *   tot  = sqrt(*sumsq) * grad_scale,  clip = min(1, max_norm / (tot + 1e-6)) * grad_scale   (grad_scale alone when sumsq is NULL
+ *   or max_norm <= 0),  bc1 = 1 - beta1^step,  bc2 = 1 - beta2^step                           - all as in t2_adam_step -
+ * per element:
+ *   decoupled = 0:  g' = g * clip + wd * p;  m' = b1 m + (1 - b1) g';  v' = b2 v + (1 - b2) g'^2;
+ *                   p' = p - lr * (m' / bc1) / (sqrtf(v' / bc2) + eps)        exactly t2_adam_step's arithmetic, in its order
+ *   decoupled = 1:  g' = g * clip (no wd * p term);  m', v' as above from g';
+ *                   p1 = p * (1 - lr * wd);  p' = p1 - lr * (m' / bc1) / (sqrtf(v' / bc2) + eps)
+ *                   torch.optim.AdamW's order: the decay first, then the step
+ *   ema != NULL:    ema' = ema + (1 - d) * (p' - ema),  d = ema_decay         the lerp form of torch.optim.swa_utils: ema == p'
+ *                   is a fixed point, so padding and tensors that do not move stay bit-equal to their parameter
+ * A step whose *sumsq is not finite is SKIPPED: p, m, v and ema stay as they are.
+ * With decoupled = 0 and ema = NULL the entry launches the kernel t2_adam_step launches.  T2_ERR_ARG before any launch: a null p, g,
+ * m or v; n < 0; step < 1; decoupled not 0 or 1; with ema, ema_decay outside [0, 1) or NaN, or [ema, ema + n) overlapping
+ * [p, p + n), g, m or v.  n == 0 is T2_OK without a launch. */
+typedef struct {
+    float* p; const float* g; float* m; float* v; int64_t n; const double* sumsq;
+    float max_norm, lr, beta1, beta2, eps, weight_decay; int step; float grad_scale;
+    float* ema; float ema_decay; int decoupled;
+} T2AdamOpt;
+int t2_adam_step_opt(const T2AdamOpt* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,9 @@
     python main.py --config C --device N train --speech-dir S [--results-dir R] [--resume-ckpt K] [--finetune --finetune-steps n]
                                                   [--guided-attention SIGMA,ALPHA]
                                                   [--mel-loss l2|l1|l1+l2] [--masked-loss | --no-masked-loss] [--stop-weight W]
+                                                  [--ema-decay D] [--decoupled-weight-decay] [--grad-clip NORM]
+                                                  [--lr-schedule multistep|exponential|noam] [--lr-warmup STEPS]
+                                                  [--lr-decay START,STEPS,MIN_LR]
     python main.py --config C --device N say --checkpoint K --text "..." [--out out.npy] [--random-seed s] [--speaker-id i]
     python main.py --config C --device N say --checkpoint K --text-file chapter.txt --out chapter.wav [--expand-numbers] [--level]
                                                   [--attention-window BACK,FWD | --forward-attention] [--durations-out PATH]
@@ -12,7 +15,7 @@
     python main.py --config C --device N test-correlation --speech-dir S --checkpoint K [--hifi-gan-checkpoint G] [--results-dir R]
                                                   [--attention-window BACK,FWD | --forward-attention] [--measure [--smooth-pitch]]
     python main.py --config C --device N measure-correlation --results-dir R [--features a,b,...]
-    (say, test and test-correlation also take --stop-threshold P)
+    (say, test and test-correlation also take --stop-threshold P; they, train-mel-export and duration-export take --ema)
     python main.py --config C --device N train-mel-export --speech-dir S --checkpoint K [--results-dir R]
     python main.py --config C --device N duration-export --speech-dir S --checkpoint K [--results-dir R] [--mode monotonic|argmax]
                                                   [--variances [--pitch-domain log|hz] [--interpolate-pitch] [--frame-level]
@@ -105,6 +108,66 @@ def parse_stop_weight(ctx, param, value):
         raise click.BadParameter(f"expected a finite number > 0 (e.g. 8), got {value!r}") from None
 
 
+def parse_ema_decay(ctx, param, value):
+    """--ema-decay D -> a float with 0 <= D < 1, anything else a usage error."""
+    if value is None:
+        return None
+    from tacotron2_amd.options import check_optimizer_options
+    try:
+        return check_optimizer_options({"ema_decay": float(value)}).ema_decay
+    except ValueError:
+        raise click.BadParameter(f"expected a number with 0 <= D < 1 (e.g. 0.999), got {value!r}") from None
+
+
+def parse_grad_clip(ctx, param, value):
+    """--grad-clip NORM -> a finite float >= 0 (0: no clip), anything else a usage error."""
+    if value is None:
+        return None
+    from tacotron2_amd.options import check_optimizer_options
+    try:
+        return check_optimizer_options({"grad_clip": float(value)}).grad_clip
+    except ValueError:
+        raise click.BadParameter(f"expected a finite number >= 0 (0 switches the clip off, e.g. 1.0), got {value!r}") from None
+
+
+def parse_lr_warmup(ctx, param, value):
+    """--lr-warmup STEPS -> an integer >= 0, anything else a usage error."""
+    if value is None:
+        return None
+    if not re.fullmatch(r"[0-9]+", value.strip()):
+        raise click.BadParameter(f"expected a number of steps >= 0 (e.g. 4000), got {value!r}")
+    return int(value)
+
+
+def parse_lr_decay(ctx, param, value):
+    """--lr-decay START,STEPS,MIN_LR -> (start, steps, min_lr): two integers, start >= 0 and steps >= 1, and a finite number > 0;
+    anything else a usage error."""
+    if value is None:
+        return None
+    parts = [p.strip() for p in value.split(",")]
+    try:
+        if len(parts) != 3 or not all(re.fullmatch(r"[0-9]+", p) for p in parts[:2]):
+            raise ValueError
+        start, steps, min_lr = int(parts[0]), int(parts[1]), float(parts[2])
+        if steps < 1 or not 0.0 < min_lr < float("inf"):
+            raise ValueError
+        return start, steps, min_lr
+    except ValueError:
+        raise click.BadParameter("expected START,STEPS,MIN_LR (two integers, START >= 0 and STEPS >= 1, and a number > 0, "
+                                 f"e.g. 50000,50000,1e-5), got {value!r}") from None
+
+
+ema_option = click.option(
+    "--ema", is_flag=True, default=False,
+    help="Load the checkpoint's EMA weights (written by `train --ema-decay`) instead of the live ones; a checkpoint without them "
+         "is an error. Wins over model.use_ema of the config. Default: off.")
+
+
+def with_ema(cfg: dict, ema: bool) -> dict:
+    """The drivers' arguments with model.use_ema set for the --ema flag (the loaders read it there); unchanged without the flag."""
+    return dict(cfg, model_config=dict(cfg["model_config"], use_ema=True)) if ema else cfg
+
+
 def forward_attention_arg(forward_attention, attention_window):
     """The drivers' forward_attention argument: True for the flag, None (= the config's model.forward_attention) without it; the
     flag together with --attention-window is a usage error."""
@@ -160,16 +223,51 @@ def main(ctx, config, device):
 @click.option("--stop-weight", required=False, type=str, default=None, callback=parse_stop_weight, metavar="W",
               help="Weight of the stop class (the one last frame of an utterance) in the stop-token loss; 5 to 20 is customary "
                    "(ESPnet's bce_pos_weight, on the class that is rare here). Wins over training.loss.stop_weight. Default: 1.")
+@click.option("--ema-decay", required=False, type=str, default=None, callback=parse_ema_decay, metavar="D",
+              help="Keep an exponential moving average of the weights, ema += (1 - D) (p - ema) after every step (0.999 to 0.9999 is "
+                   "customary; the first updates run under min(D, (1 + k) / (10 + k))). Checkpoints carry it as ema_state_dict, "
+                   "validation also reports validation_loss_ema, and say / test / the exports decode from it with --ema. Wins over "
+                   "training.optimizer.ema_decay. Default: 0, off.")
+@click.option("--decoupled-weight-decay/--no-decoupled-weight-decay", default=None,
+              help="AdamW: the weight decay multiplies the weights by 1 - lr * weight_decay in front of the step instead of joining "
+                   "the gradient. Either wins over training.optimizer.decoupled_weight_decay. Default: the config's value, else "
+                   "L2 in the gradient (the reference).")
+@click.option("--grad-clip", required=False, type=str, default=None, callback=parse_grad_clip, metavar="NORM",
+              help="Clip the global gradient norm at NORM; 0 switches the clip off. Wins over training.optimizer.grad_clip. Default: 1.0.")
+@click.option("--lr-schedule", required=False, type=click.Choice(["multistep", "exponential", "noam"]), default=None,
+              help="multistep: a tenth at each of model.scheduler_milestones (the reference); exponential: from lr to MIN_LR over "
+                   "--lr-decay (the Tacotron 2 paper); noam: linear warm-up over --lr-warmup steps to lr, then lr * sqrt(W / step). "
+                   "Wins over training.optimizer.schedule. Default: multistep.")
+@click.option("--lr-warmup", required=False, type=str, default=None, callback=parse_lr_warmup, metavar="STEPS",
+              help="Linear warm-up: the first STEPS steps run at lr * step / STEPS (multistep, exponential); noam's W. Wins over "
+                   "training.optimizer.warmup_steps. Default: 0, none.")
+@click.option("--lr-decay", required=False, type=str, default=None, callback=parse_lr_decay, metavar="START,STEPS,MIN_LR",
+              help="With --lr-schedule exponential: lr until step START, then a geometric decay that reaches MIN_LR after STEPS more "
+                   "steps and stays there (50000,50000,1e-5 is the paper's). Wins over training.optimizer.decay_start / decay_steps / "
+                   "min_lr.")
 def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_checkpoint=None, finetune=False,
           finetune_steps=None, max_steps=None, synthetic=False, guided_attention=None, forward_attention=False, mel_loss=None,
-          masked_loss=None, stop_weight=None):
+          masked_loss=None, stop_weight=None, ema_decay=None, decoupled_weight_decay=None, grad_clip=None, lr_schedule=None,
+          lr_warmup=None, lr_decay=None):
     cfg = config_args(ctx, "Configuration required for training!")
     if finetune and finetune_steps is None:
         raise Exception("If finetuning, --finetune-steps is required!")
+    optimizer = dict(ema_decay=ema_decay, decoupled_weight_decay=decoupled_weight_decay, grad_clip=grad_clip, schedule=lr_schedule,
+                     warmup_steps=lr_warmup)
+    if lr_decay is not None:
+        optimizer.update(decay_start=lr_decay[0], decay_steps=lr_decay[1], min_lr=lr_decay[2])
+    from tacotron2_amd.options import optimizer_options_setting
+    try:        # the combinations the options refuse are usage errors, before torch or the library is loaded
+        tc, mc = cfg["training_config"], cfg["model_config"]
+        optimizer_options_setting(tc, lr=(tc["lr"] / 10 if finetune else tc["lr"]) if "lr" in tc else None,
+                                  milestones=mc.get("scheduler_milestones", []), **optimizer)
+    except ValueError as e:
+        raise click.UsageError(str(e)) from None
     from tacotron2_amd.run.train import do_train
     do_train(**cfg, speech_dir=speech_dir, results_dir=results_dir, resume_ckpt=resume_ckpt, finetune=finetune,
              finetune_steps=finetune_steps, max_steps_override=max_steps, synthetic=synthetic, guided_attention=guided_attention,
-             forward_attention=True if forward_attention else None, mel_loss=mel_loss, masked_loss=masked_loss, stop_weight=stop_weight)
+             forward_attention=True if forward_attention else None, mel_loss=mel_loss, masked_loss=masked_loss, stop_weight=stop_weight,
+             optimizer=optimizer)
 
 
 @main.command()
@@ -206,6 +304,7 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--controls", required=False, type=str, default=None, help="If controls are enabled, a comma-separated list of values to pass into the model. Defaults to all 0 values.")
 @click.option("--description", required=False, type=str, default=None, help="Path of a precomputed description embedding (.pt / .npy, pooler_output of bert-base-uncased); raw text needs the BERT weights (unavailable offline)")
 @decode_options
+@ema_option
 @click.option("--durations-out", required=False, type=str, default=None, metavar="PATH",
               help="Write character timestamps as JSON: per text the encoded symbols, the mel frames each one lasts (the best "
                    "monotonic path through the decode's own alignments), start_s / end_s, focus_rate and feasible. Default: off.")
@@ -230,7 +329,7 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
         forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
         expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000, tempo=None,
-        pitch_shift=None, preserve_formants=False, pitch_range=None):
+        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False):
     if (text is None) == (text_file is None):
         raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
     if text_file is None:
@@ -250,7 +349,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
         except ValueError as e:
             raise click.UsageError(str(e))
     forward_attention = forward_attention_arg(forward_attention, attention_window)
-    common = dict(config_args(ctx, "Configuration required for speech!"), checkpoint=checkpoint, output=out, speaker_id=speaker_id,
+    common = dict(with_ema(config_args(ctx, "Configuration required for speech!"), ema), checkpoint=checkpoint, output=out, speaker_id=speaker_id,
                   hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
                   durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len,
@@ -279,6 +378,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit", required=False, type=int, default=None, help="Only the first n utterances of the test manifest.")
 @decode_options
+@ema_option
 @click.option("--score", is_flag=True, default=False,
               help="Also score every decode against its recording (the manifest's wav column under --speech-dir): mel-cepstral "
                    "distortion under dynamic time warping (MCD-DTW, 13 coefficients, dB), duration ratio, stop failures and "
@@ -290,7 +390,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                    "(YIN with Viterbi smoothing) and compared along the MCD warping path: F0 RMSE and bias in cents, log-F0 "
                    "correlation and voicing-decision error, as f0_scores.csv and four means in scores.json. Default: off.")
 def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_size, max_len, limit, attention_window,
-         forward_attention, stop_threshold=None, score=False, no_audio=False, f0=False):
+         forward_attention, stop_threshold=None, score=False, no_audio=False, f0=False, ema=False):
     """Synthesise the test manifest (run/test.py of the reference): one wav per utterance + failures.csv."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if no_audio and not score:
@@ -299,7 +399,7 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
         raise click.UsageError("--f0 needs --score: the tracks are compared along the path of the MCD score")
     if f0 and no_audio:
         raise click.UsageError("--f0 cannot go with --no-audio: there would be no waveform to track")
-    cfg = config_args(ctx, "Configuration required for testing!")
+    cfg = with_ema(config_args(ctx, "Configuration required for testing!"), ema)
     from tacotron2_amd.run.test import do_test
     do_test(**cfg, speech_dir=speech_dir, checkpoint=checkpoint, hifi_gan_checkpoint=hifi_gan_checkpoint, results_dir=results_dir,
             batch_size=batch_size, max_len=max_len, limit=limit, attention_window=attention_window,
@@ -316,6 +416,7 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
 @click.option("--max-len", required=False, type=int, default=5000, help="Frame cap per utterance (reference: 5000).")
 @click.option("--limit-overrides", required=False, type=int, default=None, help="Only the first n of the 51 control overrides.")
 @decode_options
+@ema_option
 @click.option("--measure", is_flag=True, default=False,
               help="Also measure what comes out, on the GPU: pitch level and range (YIN), intensity, aperiodicity and speaking rate "
                    "of every waveform as prosody.csv in each override directory, and the correlation of every requested control "
@@ -325,12 +426,12 @@ def test(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, batch_si
               help="With --measure: decode every pitch track with the Viterbi smoother before its statistics (no octave jumps in "
                    "the pitch range). Default: off.")
 def test_correlation(ctx, speech_dir, checkpoint, hifi_gan_checkpoint, results_dir, samples_per_speaker, max_len, limit_overrides,
-                     attention_window, forward_attention, stop_threshold=None, measure=False, smooth_pitch=False):
+                     attention_window, forward_attention, stop_threshold=None, measure=False, smooth_pitch=False, ema=False):
     """The test manifest under 51 control-vector overrides (run/test_correlation.py of the reference)."""
     forward_attention = forward_attention_arg(forward_attention, attention_window)
     if smooth_pitch and not measure:
         raise click.UsageError("--smooth-pitch needs --measure: without it no pitch is tracked")
-    cfg = config_args(ctx, "Configuration required for testing!")
+    cfg = with_ema(config_args(ctx, "Configuration required for testing!"), ema)
     from tacotron2_amd.run.test_correlation import do_test_correlation
     given = dict(attention_window=None if attention_window is None else list(attention_window), forward_attention=forward_attention,
                  stop_threshold=stop_threshold)
@@ -378,9 +479,10 @@ def measure_correlation(ctx, results_dir, features=None):
 @click.option("--speech-dir", required=True, type=str, help="A directory containing audio files from the dataset.")
 @click.option("--checkpoint", required=True, type=str, help="A trained Tacotron model checkpoint")
 @click.option("--results-dir", required=False, type=str, default=None, help="The directory to save results. Defaults to the model configuration name with a timestamp.")
-def train_mel_export(ctx, speech_dir, checkpoint, results_dir=None):
+@ema_option
+def train_mel_export(ctx, speech_dir, checkpoint, results_dir=None, ema=False):
     """Teacher-forced post-net mels of the train + val manifests (run/train_mel_export.py of the reference)."""
-    cfg = config_args(ctx, "Configuration required!")
+    cfg = with_ema(config_args(ctx, "Configuration required!"), ema)
     from tacotron2_amd.run.train_mel_export import do_train_mel_export
     do_train_mel_export(**cfg, speech_dir=speech_dir, checkpoint=checkpoint, results_dir=results_dir)
 
@@ -406,8 +508,9 @@ def train_mel_export(ctx, speech_dir, checkpoint, results_dir=None):
               help="With --variances: also write <name>.pitch_frames.npy and <name>.energy_frames.npy, one value per mel frame.")
 @click.option("--no-smooth-pitch", is_flag=True, default=False,
               help="With --variances: the raw YIN track instead of the Viterbi-smoothed one. Default: smoothed.")
+@ema_option
 def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monotonic", variances=False, pitch_domain=None,
-                    interpolate_pitch=False, frame_level=False, no_smooth_pitch=False):
+                    interpolate_pitch=False, frame_level=False, no_smooth_pitch=False, ema=False):
     """Per-character durations (mel frames) of the train + val manifests from teacher-forced alignments, plus durations.csv; with
     --variances also per-character pitch and energy."""
     if not variances:
@@ -415,7 +518,7 @@ def duration_export(ctx, speech_dir, checkpoint, results_dir=None, mode="monoton
                                        ("--frame-level", frame_level), ("--no-smooth-pitch", no_smooth_pitch)) if on]
         if given:
             raise click.UsageError(f"{', '.join(given)} need{'s' if len(given) == 1 else ''} --variances")
-    cfg = config_args(ctx, "Configuration required!")
+    cfg = with_ema(config_args(ctx, "Configuration required!"), ema)
     from tacotron2_amd.run.duration_export import do_duration_export
     do_duration_export(**cfg, speech_dir=speech_dir, checkpoint=checkpoint, results_dir=results_dir, mode=mode, variances=variances, pitch_domain=pitch_domain or "log",
                        interpolate_pitch=interpolate_pitch, frame_level=frame_level, smooth_pitch=not no_smooth_pitch)

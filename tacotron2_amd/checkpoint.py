@@ -11,6 +11,10 @@ not the order of this package's flat buffer: `reference_param_order` restates it
 reference-generated fixtures in tests/test_checkpoint.py).  The flat Adam moments are sliced into per-tensor entries on
 save and gathered back on load; the prosody-controls columns, stored here as separate blocks, are concatenated to the
 reference's shapes (params.CONTROL_SPLITS).
+With optimizer options (options.OptimizerOptions) three things join, none of them with every option at its default:
+`ema_state_dict` (the shadow weights under state_dict's keys and shapes) with `ema` {decay, num_updates};
+param_groups[0]["decoupled_weight_decay"] = True under AdamW; and, for a schedule MultiStepLR cannot state, an `lr_schedulers` entry
+{"t2_schedule": {...}, base_lrs, last_epoch, _step_count, _last_lr} (schedule_state).
 Files are read with torch.load(weights_only=True) only: every value written here is a tensor, number, string, list,
 dict or collections.Counter (MultiStepLR's milestones), all of which that loader accepts.
 """
@@ -22,6 +26,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+from .options import check_optimizer_options
 from .params import CONTROL_SPLITS, ParamStore
 
 LIGHTNING_VERSION = "2.5.2"      # the reference's pinned `lightning` (requirements.txt:8)
@@ -65,8 +70,9 @@ def _moment_views(ps: ParamStore, flat: torch.Tensor) -> Dict[str, torch.Tensor]
 
 
 def optimizer_state(ps: ParamStore, step: int, lr: float, base_lr: float, weight_decay: float, betas=(0.9, 0.999),
-                    eps: float = 1e-8) -> dict:
-    """torch.optim.Adam(...).state_dict() as the reference's optimizer would hold it after `step` updates."""
+                    eps: float = 1e-8, decoupled: bool = False) -> dict:
+    """torch.optim.Adam(...).state_dict() as the reference's optimizer would hold it after `step` updates; decoupled=True:
+    torch.optim.AdamW's, which differs in param_groups[0]["decoupled_weight_decay"] alone."""
     order = reference_param_order(ps.dims)
     state = {}
     if ps.exp_avg is not None and step > 0:
@@ -74,7 +80,7 @@ def optimizer_state(ps: ParamStore, step: int, lr: float, base_lr: float, weight
         for i, name in enumerate(order):
             state[i] = {"step": torch.tensor(float(step)), "exp_avg": m[name], "exp_avg_sq": v[name]}
     group = dict(lr=float(lr), betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                 foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=bool(decoupled),
                  initial_lr=float(base_lr), params=list(range(len(order))))
     return {"state": state, "param_groups": [group]}
 
@@ -84,6 +90,16 @@ def scheduler_state(milestones, base_lr: float, lr: float, step: int) -> dict:
     return {"milestones": Counter(int(m) for m in milestones), "gamma": 0.1, "base_lrs": [float(base_lr)],
             "last_epoch": int(step), "_step_count": int(step) + 1, "_get_lr_called_within_step": False,
             "_last_lr": [float(lr)]}
+
+
+SCHEDULE_KEYS = ("schedule", "warmup_steps", "decay_start", "decay_steps", "min_lr")
+
+
+def schedule_state(opts, milestones, base_lr: float, lr: float, step: int) -> dict:
+    """The `lr_schedulers` entry of a schedule MultiStepLR cannot state (a warm-up, exponential, noam): the option values and the
+    milestones under "t2_schedule", and the scheduler keys both layouts share.  Numbers, strings and lists only."""
+    return {"t2_schedule": dict({k: getattr(opts, k) for k in SCHEDULE_KEYS}, milestones=[int(m) for m in milestones]),
+            "base_lrs": [float(base_lr)], "last_epoch": int(step), "_step_count": int(step) + 1, "_last_lr": [float(lr)]}
 
 
 def lightning_checkpoint(model, trainer=None, epoch: int = 0) -> dict:
@@ -97,9 +113,17 @@ def lightning_checkpoint(model, trainer=None, epoch: int = 0) -> dict:
     if trainer is not None:
         step = int(trainer.global_step)
         lr = trainer.lr_at(step)
-        ck["optimizer_states"] = [optimizer_state(ps, step, lr, trainer.base_lr, trainer.weight_decay)]
-        if trainer.milestones:
+        o = trainer.optimizer_options
+        ck["optimizer_states"] = [optimizer_state(ps, step, lr, trainer.base_lr, trainer.weight_decay,
+                                                  decoupled=o.decoupled_weight_decay)]
+        if o.schedule != "multistep" or o.warmup_steps > 0:
+            ck["lr_schedulers"] = [schedule_state(o, trainer.milestones, trainer.base_lr, lr, step)]
+        elif trainer.milestones:
             ck["lr_schedulers"] = [scheduler_state(trainer.milestones, trainer.base_lr, lr, step)]
+        if trainer.ema_on:
+            # the shadow weights beside the live ones: state_dict stays what a resume needs, ema_state_dict is what --ema decodes from
+            ck["ema_state_dict"] = {k: v.cpu() for k, v in ps.ema_state_dict(prefix="tacotron2.").items()}
+            ck["ema"] = {"decay": float(o.ema_decay), "num_updates": int(trainer.ema_updates)}
     return ck
 
 
@@ -108,6 +132,24 @@ def save_atomic(ck: dict, path: str) -> None:
     tmp = f"{path}.tmp.{os.getpid()}"
     torch.save(ck, tmp)
     os.replace(tmp, path)
+
+
+def _restore_ema(ck: dict, trainer) -> None:
+    """The three resume cases of the EMA: on and in the file - the shadow weights and the counter come back; on and not in the file -
+    the shadow starts from the restored weights (one line says so); off and in the file - dropped (one line)."""
+    ps: ParamStore = trainer.ps
+    sd = ck.get("ema_state_dict")
+    if trainer.ema_on:
+        if sd:
+            ps.load_ema_state_dict(sd, prefix="tacotron2.")
+            trainer.ema_updates = int((ck.get("ema") or {}).get("num_updates", 0))
+        else:
+            ps.init_ema()
+            ps.ema.copy_(ps.flat)
+            trainer.ema_updates = 0
+            print("resume: the checkpoint holds no EMA weights, the EMA starts from the restored weights", flush=True)
+    elif sd:
+        print("resume: the checkpoint's EMA weights are dropped (no ema_decay is configured)", flush=True)
 
 
 def restore_trainer(ck: dict, trainer) -> bool:
@@ -141,8 +183,25 @@ def restore_trainer(ck: dict, trainer) -> bool:
         ps.init_adam()
         ps.exp_avg.copy_(ck["t2_optimizer"]["exp_avg"]); ps.exp_avg_sq.copy_(ck["t2_optimizer"]["exp_avg_sq"])
         found = True
+    _restore_ema(ck, trainer)
     sch = (ck.get("lr_schedulers") or [None])[0]
-    if sch:
+    if sch and "t2_schedule" in sch:
+        # the same rule as for MultiStepLR below: the restored schedule REPLACES the configured one
+        t2 = dict(sch["t2_schedule"])
+        ms = sorted(int(m) for m in t2.pop("milestones", []))
+        before = (trainer.optimizer_options, list(trainer.milestones), trainer.base_lr)
+        trainer.milestones, trainer.base_lr = ms, float(sch["base_lrs"][0])
+        trainer.optimizer_options = check_optimizer_options(dict(trainer.optimizer_options._asdict(), **t2), lr=trainer.base_lr,
+                                                            milestones=ms)
+        if before != (trainer.optimizer_options, ms, trainer.base_lr):
+            print(f"resume: the checkpoint's learning-rate schedule ({t2['schedule']}, base lr {trainer.base_lr:g}) replaces the "
+                  "configured one", flush=True)
+    elif sch:
+        o = trainer.optimizer_options
+        if o.schedule != "multistep" or o.warmup_steps > 0:
+            trainer.optimizer_options = o._replace(schedule="multistep", warmup_steps=0)
+            print(f"resume: the checkpoint's learning-rate schedule (multistep) replaces the configured one ({o.schedule}, "
+                  f"warm-up {o.warmup_steps})", flush=True)
         ms = sorted(int(m) for m, c in dict(sch["milestones"]).items() for _ in range(int(c)))
         # MultiStepLR counts in ITS epochs.  Normally last_epoch == global_step.  A checkpoint the reference wrote after a resume
         # from a scheduler-less checkpoint (the case below) carries a scheduler that was created at that resume: last_epoch counts

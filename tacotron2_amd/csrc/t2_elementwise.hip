@@ -1167,3 +1167,68 @@ extern "C" int t2_adam_step(float* p, const float* g, float* m, float* v, int64_
                        weight_decay, bc1, bc2, grad_scale);
     T2_CHECK_LAUNCH(); return T2_OK;
 }
+
+// t2_adam_step_opt (include/tacotron2_amd.h: T2AdamOpt): decoupled weight decay and the EMA of the parameters as template
+// parameters of ONE body; <false, *> repeats adam_kernel's arithmetic in adam_kernel's order, so p, m and v come out bit for bit.  The
+// EMA reads p' from the register it was just formed in: a fifth buffer read and written, no second pass over p.
+template <bool DECOUPLED, bool EMA>
+__global__ void adam_opt_kernel(float* p, const float* g, float* m, float* v, long n, const double* sumsq, float max_norm, float lr,
+                                float b1, float b2, float eps, float wd, float bc1, float bc2, float gscale, float* ema, float ema_decay) {
+    float clip = 1.f;
+    if (sumsq && !isfinite(*sumsq)) return;    // non-finite gradient norm: skip the step, the EMA included
+    if (sumsq && max_norm > 0.f) {
+        const float tot = (float)sqrt(*sumsq) * gscale;
+        const float c = max_norm / (tot + 1e-6f);
+        clip = c < 1.f ? c : 1.f;
+    }
+    clip *= gscale;
+    const float keep = 1.f - lr * wd;          // AdamW: p * (1 - lr wd) first, then the step
+    const float w = 1.f - ema_decay;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float pv = p[i];
+        float gr;
+        if constexpr (DECOUPLED) gr = g[i] * clip;
+        else gr = g[i] * clip + wd * pv;
+        const float mv = b1 * m[i] + (1.f - b1) * gr;
+        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
+        m[i] = mv; v[i] = vv;
+        float pn;
+        if constexpr (DECOUPLED) pn = pv * keep - lr * (mv / bc1) / (sqrtf(vv / bc2) + eps);
+        else pn = pv - lr * (mv / bc1) / (sqrtf(vv / bc2) + eps);
+        p[i] = pn;
+        if constexpr (EMA) {
+            const float e = ema[i];
+            ema[i] = e + w * (pn - e);
+        }
+    }
+}
+
+static bool adam_overlap(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+    return x < y + len && y < x + len;
+}
+extern "C" int t2_adam_step_opt(const T2AdamOpt* a, void* stream) {
+    (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
+    T2_REQUIRE(a, "t2_adam_step_opt: null");
+    T2_REQUIRE(a->p && a->g && a->m && a->v && a->n >= 0 && a->step >= 1, "t2_adam_step_opt: bad arguments");
+    T2_REQUIRE(a->decoupled == 0 || a->decoupled == 1, "t2_adam_step_opt: decoupled must be 0 or 1");
+    if (a->ema) {
+        T2_REQUIRE(a->ema_decay >= 0.f && a->ema_decay < 1.f, "t2_adam_step_opt: ema_decay must be in [0, 1)");   // (NaN fails both)
+        T2_REQUIRE(!adam_overlap(a->ema, a->p, a->n) && !adam_overlap(a->ema, a->g, a->n) && !adam_overlap(a->ema, a->m, a->n) &&
+                   !adam_overlap(a->ema, a->v, a->n), "t2_adam_step_opt: ema overlaps p, g, m or v");
+    }
+    if (a->n == 0) return T2_OK;
+    const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
+    const dim3 grid(ew_grid(a->n)), block(256);
+    const long n = (long)a->n;
+#define T2_ADAM_OPT(D, E) hipLaunchKernelGGL((adam_opt_kernel<D, E>), grid, block, 0, ST, a->p, a->g, a->m, a->v, n, a->sumsq, a->max_norm, \
+                                             a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, bc1, bc2, a->grad_scale, a->ema, a->ema_decay)
+    if (!a->decoupled && !a->ema)              // no option: the very kernel t2_adam_step launches
+        hipLaunchKernelGGL(adam_kernel, grid, block, 0, ST, a->p, a->g, a->m, a->v, n, a->sumsq, a->max_norm, a->lr, a->beta1, a->beta2,
+                           a->eps, a->weight_decay, bc1, bc2, a->grad_scale);
+    else if (!a->decoupled) T2_ADAM_OPT(false, true);
+    else if (!a->ema) T2_ADAM_OPT(true, false);
+    else T2_ADAM_OPT(true, true);
+#undef T2_ADAM_OPT
+    T2_CHECK_LAUNCH(); return T2_OK;
+}

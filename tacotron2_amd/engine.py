@@ -1478,17 +1478,34 @@ class Engine:
         self.backward_tf(ctx, d_post, dproj, d_align=d_align)
         return loss3
 
-    def adam_step(self, step, lr, weight_decay, max_norm=1.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, ranges=None):
+    def adam_step(self, step, lr, weight_decay, max_norm=1.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, ranges=None,
+                  decoupled=False, ema_decay=None):
         """Global-norm clip + Adam(L2) on the flat buffers.  ranges: optional [(start, end)] element ranges to update (the
-        trainable tensors when some are frozen; the caller zeroes the frozen gradients so the norm excludes them)."""
+        trainable tensors when some are frozen; the caller zeroes the frozen gradients so the norm excludes them).
+        decoupled: AdamW's decay, p * (1 - lr wd) in front of the step, instead of wd * p in the gradient.  ema_decay: a number in
+        [0, 1) moves ps.ema (ParamStore.init_ema) towards the new parameters in the same pass, ema += (1 - d) (p' - ema); None: no
+        EMA.  With both off this is the t2_adam_step call it always was; otherwise t2_adam_step_opt, once per range."""
         ps = self.ps
         ps.init_adam()
         sumsq = self.buf("sumsq", 1, dtype=torch.float64)
         call("t2_sumsq", ps.grad, ps.numel, sumsq, _stream())
+        if not isinstance(decoupled, bool):
+            raise ValueError(f"adam_step: decoupled must be True or False, got {decoupled!r}")
+        if ema_decay is not None:
+            ema_decay = check_rate(ema_decay, "ema_decay")
+            ps.init_ema()
         for a, b in (ranges or [(0, ps.numel)]):
-            call("t2_adam_step", _ptr(ps.flat, a), _ptr(ps.grad, a), _ptr(ps.exp_avg, a), _ptr(ps.exp_avg_sq, a), b - a, sumsq,
-                 float(max_norm), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
-                 float(grad_scale), _stream())
+            if not decoupled and ema_decay is None:
+                call("t2_adam_step", _ptr(ps.flat, a), _ptr(ps.grad, a), _ptr(ps.exp_avg, a), _ptr(ps.exp_avg_sq, a), b - a, sumsq,
+                     float(max_norm), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                     float(grad_scale), _stream())
+            else:
+                call("t2_adam_step_opt", make("T2AdamOpt", p=_ptr(ps.flat, a), g=_ptr(ps.grad, a), m=_ptr(ps.exp_avg, a),
+                                              v=_ptr(ps.exp_avg_sq, a), n=b - a, sumsq=sumsq, max_norm=float(max_norm), lr=float(lr),
+                                              beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
+                                              weight_decay=float(weight_decay), step=int(step), grad_scale=float(grad_scale),
+                                              ema=_ptr(ps.ema, a) if ema_decay is not None else None,
+                                              ema_decay=float(ema_decay or 0.0), decoupled=int(decoupled)), _stream())
         return sumsq
 
     # =============================================================================================

@@ -268,12 +268,18 @@ class TTSModel(nn.Module):
         ck.update(extra or {})
         return ck
 
-    def load_checkpoint_dict(self, ck: dict, strict: bool = True):
-        sd = {k[len("tacotron2."):]: v for k, v in ck["state_dict"].items() if k.startswith("tacotron2.")}
+    def load_checkpoint_dict(self, ck: dict, strict: bool = True, use_ema: bool = False, path: Optional[str] = None):
+        """use_ema=True loads the shadow weights a training run with an EMA wrote beside the live ones (`ema_state_dict`: same keys,
+        same shapes); a checkpoint without them is a KeyError that names `path`."""
+        key = "ema_state_dict" if use_ema else "state_dict"
+        if use_ema and not ck.get(key):
+            raise KeyError(f"{path or 'the checkpoint'} holds no EMA weights (ema_state_dict): it was trained without --ema-decay; "
+                           "load it without use_ema / --ema")
+        sd = {k[len("tacotron2."):]: v for k, v in ck[key].items() if k.startswith("tacotron2.")}
         return self.tacotron2.load_state_dict(sd, strict=strict)
 
     @classmethod
-    def load_from_checkpoint(cls, path: str, map_location=None, device=None, **overrides):
+    def load_from_checkpoint(cls, path: str, map_location=None, device=None, use_ema: bool = False, **overrides):
         ck = torch.load(path, map_location="cpu", weights_only=True)
         hp = dict(ck.get("hyper_parameters", {}))
         # zoneout / cell_dropout change no parameter, so the configured value always loads; a file that recorded another one says so
@@ -284,5 +290,5 @@ class TTSModel(nn.Module):
                    if k in hp or k in ("lr", "weight_decay", "num_chars", "reduction_factor", "zoneout", "cell_dropout")})
         hp = {k: v for k, v in hp.items() if k in cls.__init__.__code__.co_varnames}
         model = cls(device=device, **hp)
-        model.load_checkpoint_dict(ck)
+        model.load_checkpoint_dict(ck, use_ema=use_ema, path=path)
         return model

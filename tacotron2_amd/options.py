@@ -175,3 +175,118 @@ def decode_settings_of(model) -> DecodeSettings:
     """The settings that are on a model (TTSModel's three attributes; load_decode_model puts them there); an object that lacks one
     decodes with its default."""
     return DecodeSettings(*(getattr(model, name, default) for name, default in DecodeSettings()._asdict().items()))
+
+
+LR_SCHEDULES = ("multistep", "exponential", "noam")
+
+
+class OptimizerOptions(NamedTuple):
+    """The options of the update (Trainer(optimizer_options=...)); the defaults are the reference's optimiser - Adam with
+    L2 in the gradient, clip at 1.0, MultiStepLR, no EMA - and are written here only.  ema_decay 0 switches the EMA off; grad_clip 0
+    the clip."""
+    decoupled_weight_decay: bool = False
+    ema_decay: float = 0.0
+    grad_clip: float = 1.0
+    schedule: str = "multistep"
+    warmup_steps: int = 0
+    decay_start: int = 0
+    decay_steps: int = 0
+    min_lr: float = 0.0
+
+
+def _opt_number(v, key: str, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or abs(v) == float("inf"):
+        raise ValueError(f"optimizer options: {key} must be {what}, got {v!r}")
+    return float(v)
+
+
+def _opt_count(v, key: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0:
+        raise ValueError(f"optimizer options: {key} must be an integer >= 0, got {v!r}")
+    return int(v)
+
+
+def check_optimizer_options(opts=None, lr: Optional[float] = None, milestones=()) -> OptimizerOptions:
+    """None, a dict with any of OptimizerOptions' keys, or an OptimizerOptions -> the checked tuple, missing keys at their defaults.
+    `lr` is the base learning rate the `exponential` schedule's min_lr is held against (None: that comparison is left out) and
+    `milestones` the MultiStepLR milestones, which `noam` does not combine with.  Each refusal is a ValueError that names the key."""
+    if opts is None:
+        opts = {}
+    if isinstance(opts, OptimizerOptions):
+        opts = opts._asdict()
+    if not isinstance(opts, dict):
+        raise ValueError(f"optimizer options must be a dict or OptimizerOptions, got {opts!r}")
+    unknown = sorted(set(opts) - set(OptimizerOptions._fields))
+    if unknown:
+        raise ValueError(f"optimizer options: unknown key {unknown[0]!r} (known: {', '.join(OptimizerOptions._fields)})")
+    o = dict(OptimizerOptions()._asdict(), **opts)
+    if not isinstance(o["decoupled_weight_decay"], bool):
+        raise ValueError(f"optimizer options: decoupled_weight_decay must be True or False, got {o['decoupled_weight_decay']!r}")
+    ema = _opt_number(o["ema_decay"], "ema_decay", "a number in [0, 1)")
+    if not 0.0 <= ema < 1.0 or not float(ctypes.c_float(ema).value) < 1.0:
+        raise ValueError(f"optimizer options: ema_decay must be a number in [0, 1) (as a float32 too), got {o['ema_decay']!r}")
+    clip = _opt_number(o["grad_clip"], "grad_clip", "a finite number >= 0")
+    if clip < 0:
+        raise ValueError(f"optimizer options: grad_clip must be >= 0 (0 switches the clip off), got {o['grad_clip']!r}")
+    schedule = o["schedule"]
+    if not isinstance(schedule, str) or schedule not in LR_SCHEDULES:
+        raise ValueError(f"optimizer options: schedule must be one of {', '.join(LR_SCHEDULES)}, got {schedule!r}")
+    warmup, start, steps = (_opt_count(o[k], k) for k in ("warmup_steps", "decay_start", "decay_steps"))
+    min_lr = _opt_number(o["min_lr"], "min_lr", "a finite number >= 0")
+    if min_lr < 0:
+        raise ValueError(f"optimizer options: min_lr must be >= 0, got {o['min_lr']!r}")
+    if schedule == "exponential":
+        if steps < 1:
+            raise ValueError(f"optimizer options: the exponential schedule needs decay_steps >= 1, got {steps!r}")
+        if not min_lr > 0 or (lr is not None and min_lr > float(lr)):
+            raise ValueError(f"optimizer options: the exponential schedule needs 0 < min_lr <= lr"
+                             f"{'' if lr is None else f' = {lr!r}'}, got min_lr {o['min_lr']!r}")
+    if schedule == "noam":
+        if warmup < 1:
+            raise ValueError(f"optimizer options: the noam schedule needs warmup_steps >= 1, got {warmup!r}")
+        if len(list(milestones)) > 0:
+            raise ValueError("optimizer options: the noam schedule does not combine with scheduler milestones "
+                             f"(schedule 'noam', milestones {list(milestones)!r})")
+    return OptimizerOptions(o["decoupled_weight_decay"], ema, clip, schedule, warmup, start, steps, min_lr)
+
+
+def optimizer_options_setting(training_config: dict, lr: Optional[float] = None, milestones=(), **overrides) -> OptimizerOptions:
+    """The options of the update: each keyword of `overrides` that is not None (the command line: --ema-decay, --decoupled-weight-decay /
+    --no-decoupled-weight-decay, --grad-clip, --lr-schedule, --lr-warmup, --lr-decay) wins over its key of
+    `"training": {"optimizer": {"ema_decay": 0.999, "decoupled_weight_decay": true, ...}}`, which wins over the default.  A section of
+    another form or a bad value raises ValueError naming it (check_optimizer_options)."""
+    sec = training_config.get("optimizer")
+    if sec is None:
+        sec = {}
+    if not isinstance(sec, dict):
+        raise ValueError(f"training.optimizer must be an object with keys among {', '.join(OptimizerOptions._fields)}, got {sec!r}")
+    sec = dict(sec)
+    for key, v in overrides.items():
+        if key not in OptimizerOptions._fields:
+            raise ValueError(f"optimizer options: unknown key {key!r}")
+        if v is not None:
+            sec[key] = v
+    return check_optimizer_options(sec, lr=lr, milestones=milestones)
+
+
+def lr_at(base_lr: float, milestones, opts: OptimizerOptions, t: int) -> float:
+    """The learning rate of the 0-based scheduler step t, in Python floats (Trainer.lr_at):
+    multistep base * 0.1^(milestones passed); exponential base until decay_start, then base * (min_lr / base)^min(1, (t - start) / steps);
+    both times min(1, (t + 1) / warmup_steps) under a warm-up; noam base * min((t + 1) / W, sqrt(W / (t + 1))), base the peak at step W."""
+    if opts.schedule == "noam":
+        W = opts.warmup_steps
+        return base_lr * min((t + 1) / W, math.sqrt(W / (t + 1)))
+    if opts.schedule == "exponential":
+        lr = base_lr if t < opts.decay_start else \
+            base_lr * (opts.min_lr / base_lr) ** min(1.0, (t - opts.decay_start) / opts.decay_steps)
+    else:
+        lr = base_lr * (0.1 ** sum(1 for m in milestones if t >= m))
+    if opts.warmup_steps > 0:
+        lr = lr * min(1.0, (t + 1) / opts.warmup_steps)
+    return lr
+
+
+def ema_decay_at(decay: float, k: int) -> float:
+    """The effective decay of the k-th EMA update, k = 1, 2, ...: min(D, (1 + k) / (10 + k)), TensorFlow's num_updates rule - without
+    it a D of 0.9999 holds the random initial weights for 10 000 steps."""
+    return min(float(decay), (1.0 + k) / (10.0 + k))

@@ -148,6 +148,7 @@ class ParamStore:
         self.grad = self._zeros("grad", self.numel) if with_grad else None
         self.exp_avg = None
         self.exp_avg_sq = None
+        self.ema = None
         self.P: Dict[str, torch.Tensor] = {}
         self.G: Dict[str, torch.Tensor] = {}
         for name, shp in man.items():
@@ -189,6 +190,58 @@ class ParamStore:
         if self.exp_avg is None:
             self.exp_avg = self._zeros("exp_avg", self.numel)
             self.exp_avg_sq = self._zeros("exp_avg_sq", self.numel)
+
+    # --- EMA of the parameters --------------------------------------------------------
+    def init_ema(self):
+        """The shadow buffer `ema`, a copy of `flat` (padding included, so that it stays bit-equal there); a second call keeps it."""
+        if self.ema is None:
+            self.ema = self._zeros("ema", self.numel)
+            self.ema.copy_(self.flat)
+
+    def swap_ema(self):
+        """Exchange the contents of `flat` and `ema` in place: every pointer and view stays valid, the model then runs on the shadow
+        weights until the next call.  Three elementwise copies through a temporary; not on the step path."""
+        if self.ema is None:
+            raise RuntimeError("ParamStore.swap_ema: no EMA buffer (init_ema)")
+        tmp = self.flat.clone()
+        self.flat.copy_(self.ema)
+        self.ema.copy_(tmp)
+
+    def ema_state_dict(self, prefix: str = "") -> "OrderedDict[str, torch.Tensor]":
+        """state_dict() with the shadow weights in place of the parameters: same keys, same reference shapes (controls columns
+        re-joined); the BatchNorm buffers are the live ones."""
+        if self.ema is None:
+            raise RuntimeError("ParamStore.ema_state_dict: no EMA buffer (init_ema)")
+        table = {}
+        for name, shp in self.shapes.items():
+            o = self.offsets[name]
+            table[name] = self.ema[o:o + _numel(shp)].view(shp)
+        out = OrderedDict()
+        for name, v in self.reference_layout(table).items():
+            out[prefix + name] = v
+        for name, v in self.Bf.items():
+            out[prefix + name] = v.detach().clone()
+        for name, v in self.num_batches_tracked.items():
+            out[prefix + name] = torch.tensor(v, dtype=torch.int64)
+        return out
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor], prefix: str = ""):
+        """The shadow weights of an ema_state_dict into `ema` (allocated if need be); keys that are no parameter are ignored."""
+        self.init_ema()
+        ctrl = any(n.endswith("#controls") for n in self.P)
+        for name, shp in self.shapes.items():
+            if name.endswith("#controls"):
+                continue
+            if prefix + name not in sd:
+                raise KeyError(f"missing key in ema_state_dict: {prefix + name}")
+            t = torch.as_tensor(sd[prefix + name]).to(torch.float32)
+            if ctrl and name in CONTROL_SPLITS:
+                k0 = shp[1]
+                oc = self.offsets[name + "#controls"]
+                self.ema[oc:oc + t[:, k0:].numel()].copy_(t[:, k0:].reshape(-1))
+                t = t[:, :k0]
+            o = self.offsets[name]
+            self.ema[o:o + _numel(shp)].copy_(t.reshape(-1))
 
     # --- guard bands (tests) ------------------------------------------------------------------------
     def _zeros(self, name: str, n: int) -> torch.Tensor:

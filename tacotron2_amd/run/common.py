@@ -7,7 +7,7 @@ import json
 
 # the resolvers of an option against its config key live in options; run.common.<name> is the same object
 from ..options import (decode_settings, decode_settings_of, guided_attention_setting, loss_options_setting,  # noqa: F401
-                       stop_threshold_setting, train_forward_attention_setting)
+                       optimizer_options_setting, stop_threshold_setting, train_forward_attention_setting)
 
 
 def load_config(path: str) -> dict:
@@ -45,13 +45,24 @@ def sample_rate(pre: dict) -> int:
     return int(pre.get("sample_rate", 22050))
 
 
+def use_ema_setting(model_config: dict, override=None) -> bool:
+    """Decode from the EMA weights of the checkpoint: `override` (True for the --ema flag, None without it) wins over
+    `"model": {"use_ema": true}`; default off.  A value that is not a bool raises ValueError."""
+    v = override if override is not None else model_config.get("use_ema", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"model.use_ema must be true or false, got {v!r}")
+    return v
+
+
 def load_decode_model(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, checkpoint: str, dev,
-                      random_seed=None, attention_window=None, forward_attention=None, stop_threshold=None, **model_overrides):
+                      random_seed=None, attention_window=None, forward_attention=None, stop_threshold=None, ema=None, **model_overrides):
     """The checkpoint as a TTSModel in eval mode, built with model_kwargs of the config (model_overrides on top), seeded with
-    random_seed if there is one, and with decode_settings of the three options on the three attributes free_run reads them from."""
+    random_seed if there is one, and with decode_settings of the three options on the three attributes free_run reads them from.
+    ema (use_ema_setting): the weights are the checkpoint's EMA weights; a file without them is an error that names it."""
     from ..model.tts_model import TTSModel
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
-    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **dict(model_kwargs(cfg), **model_overrides))
+    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, use_ema=use_ema_setting(model_config, ema),
+                                          **dict(model_kwargs(cfg), **model_overrides))
     model.eval()
     if random_seed is not None:
         model.tacotron2._seed = int(random_seed)

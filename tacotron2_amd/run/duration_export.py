@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from ..model.tts_model import TTSModel
-from .common import model_kwargs, train_forward_attention_setting
+from .common import model_kwargs, train_forward_attention_setting, use_ema_setting
 
 MODES = ("monotonic", "argmax")
 CSV_HEADER = ["wav", "n_chars", "n_frames", "focus_rate", "path_logp", "feasible", "argmax_agreement"]
@@ -168,7 +168,7 @@ def do_duration_export(dataset_config: dict, training_config: dict, model_config
     torch.cuda.set_device(dev)
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
-    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **kw)
+    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, use_ema=use_ema_setting(model_config), **kw)
     model.eval()
     # a model trained under forward attention (training.forward_attention) is aligned by the recursion: its alignments need it
     fwd_att = train_forward_attention_setting(training_config)

@@ -15,7 +15,8 @@ import torch.distributed as dist
 
 from ..model.tts_model import TTSModel
 from ..trainer import Trainer
-from .common import guided_attention_setting, loss_options_setting, model_kwargs, train_forward_attention_setting
+from .common import (guided_attention_setting, loss_options_setting, model_kwargs, optimizer_options_setting,
+                     train_forward_attention_setting)
 
 
 def _to_dev(batch, dev):
@@ -34,8 +35,12 @@ def _to_dev(batch, dev):
 def do_train(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
              speech_dir: str, results_dir: Optional[str], resume_ckpt: Optional[str], finetune: bool = False,
              finetune_steps: Optional[int] = None, max_steps_override: Optional[int] = None, synthetic: bool = False,
-             guided_attention=None, forward_attention=None, mel_loss=None, masked_loss=None, stop_weight=None):
-    """mel_loss / masked_loss / stop_weight: the loss options (Trainer(loss_options=...), TTSModel.loss_options): "l2" | "l1" | "l1+l2"
+             guided_attention=None, forward_attention=None, mel_loss=None, masked_loss=None, stop_weight=None, optimizer=None):
+    """optimizer: a dict with any of OptimizerOptions' keys (options.py: decoupled_weight_decay, ema_decay, grad_clip, schedule,
+    warmup_steps, decay_start, decay_steps, min_lr), None values left out - what `main.py train --ema-decay / --decoupled-weight-decay /
+    --grad-clip / --lr-schedule / --lr-warmup / --lr-decay` give; each wins over its key of the config's `training.optimizer`, else the
+    reference's update.  With an EMA every validation pass also runs on the shadow weights and checkpoints carry them.
+    mel_loss / masked_loss / stop_weight: the loss options (Trainer(loss_options=...), TTSModel.loss_options): "l2" | "l1" | "l1+l2"
     mel terms, the mean over valid frames only, the weight of the stop class.  None takes the key of the config's `training.loss`
     (`main.py train --mel-loss / --masked-loss / --stop-weight` win over it), else the reference's loss.
     forward_attention: True trains under the forward-attention prior (Trainer(forward_attention=True)); None takes the config's
@@ -88,13 +93,17 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
     if fwd_att and rank == 0:
         print("forward attention: training under the monotonic prior (decode this model with --forward-attention)", flush=True)
     start_step = 0
+    opt_options = optimizer_options_setting(training_config, lr=kw["lr"], milestones=kw["scheduler_milestones"], **(optimizer or {}))
     # training.sync_batchnorm (not a reference key; Lightning's Trainer(sync_batchnorm=...) name): BatchNorm batch statistics over
     # all ranks' shards, so that N x b utterances give the single-device result on the N*b batch.  Default: per shard.
     tr = Trainer(model.tacotron2.store, lr=kw["lr"], weight_decay=kw["weight_decay"],
                  scheduler_milestones=kw["scheduler_milestones"], max_norm=1.0,
                  sync_bn=bool(training_config.get("sync_batchnorm", False)),
                  overlap_allreduce=bool(training_config.get("overlap_allreduce", False)),
-                 force_collectives=force_dp, guided_attention=guided, forward_attention=fwd_att, loss_options=loss_options)
+                 force_collectives=force_dp, guided_attention=guided, forward_attention=fwd_att, loss_options=loss_options,
+                 optimizer_options=opt_options)
+    if rank == 0 and opt_options != type(opt_options)():
+        print("optimizer: " + " ".join(f"{k} {v}" for k, v in opt_options._asdict().items()), flush=True)
     if world > 1 and os.environ.get("T2_SHARE_GPU") == "1":
         # rehearsal of N ranks on ONE card: persistent launches of different processes cannot promise each other co-residency
         tr.engine.dec_chain = "steps"; tr.engine.enc_chain = "steps"
@@ -186,6 +195,15 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
         model.train()
         return tot / max(n, 1)
 
+    def validate_ema():
+        """The same pass on the EMA weights: flat and ema exchanged in place (the model's views stay valid), and exchanged back
+        before the next step.  The BatchNorm running statistics are the live ones."""
+        tr.ps.swap_ema()
+        try:
+            return validate()
+        finally:
+            tr.ps.swap_ema()
+
     # checkpoint / validation cadence: Lightning checkpoints at the end of every epoch and validates every
     # `val_check_interval` (int: steps, float: fraction of an epoch; fine-tuning forces 1.0, run/train.py:112)
     steps_per_epoch = max(1, len(loader)) if not synthetic else int(training_config["args"].get("checkpoint_every_n_steps", 1000))
@@ -237,9 +255,11 @@ def do_train(dataset_config: dict, training_config: dict, model_config: dict, ex
                       f"{int(frames) * world / max(dt, 1e-9):.0f} mel-frames/s", flush=True)
         if val_loader is not None and (step + 1) % val_every == 0:
             vl = validate()                       # every rank runs it (keeps the ranks in step); rank 0 reports
+            vle = validate_ema() if tr.ema_on else None
             healthy(f"validation after step {step + 1}")
             if rank == 0:
-                print(f"step {step + 1}/{max_steps} validation_loss {vl:.5f}", flush=True)
+                etxt = f" validation_loss_ema {vle:.5f}" if vle is not None else ""
+                print(f"step {step + 1}/{max_steps} validation_loss {vl:.5f}{etxt}", flush=True)
         if rank == 0 and (step + 1) % ckpt_every == 0 and step + 1 < max_steps:
             torch.cuda.synchronize()
             healthy(f"checkpoint after step {step + 1}")

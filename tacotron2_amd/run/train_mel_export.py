@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ..model.tts_model import TTSModel
-from .common import model_kwargs, train_forward_attention_setting
+from .common import model_kwargs, train_forward_attention_setting, use_ema_setting
 
 
 def do_train_mel_export(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
@@ -29,7 +29,7 @@ def do_train_mel_export(dataset_config: dict, training_config: dict, model_confi
     torch.cuda.set_device(dev)
     cfg = dict(dataset=dataset_config, training=training_config, model=model_config, extensions=extensions_config)
     kw = model_kwargs(cfg)
-    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, **kw)
+    model = TTSModel.load_from_checkpoint(checkpoint, device=dev, use_ema=use_ema_setting(model_config), **kw)
     model.eval()
     # a model trained under forward attention (training.forward_attention) is aligned by the recursion: its teacher-forced mels need it
     fwd_att = train_forward_attention_setting(training_config)

@@ -19,14 +19,18 @@ import torch
 import torch.distributed as dist
 
 from .engine import Engine, check_forward_attention, check_guided_attention, check_loss_options, zero_later
+from .options import OptimizerOptions, check_optimizer_options, ema_decay_at, lr_at as schedule_lr_at
 from .params import ParamStore
 
 
 class Trainer:
+    optimizer_options = OptimizerOptions()     # (the reference's update; __init__ replaces it with the checked argument)
+    ema_updates = 0
+
     def __init__(self, ps: ParamStore, lr: float, weight_decay: float, scheduler_milestones: Sequence[int] = (),
                  max_norm: float = 1.0, seed: int = 1234, sync_bn: bool = False, overlap_allreduce: bool = False,
                  force_collectives: bool = False, shape_timeout_s: float = 300.0, guided_attention=None,
-                 forward_attention: bool = False, loss_options=None):
+                 forward_attention: bool = False, loss_options=None, optimizer_options=None):
         self.ps = ps
         self.engine = Engine(ps)
         # (sigma, alpha): the guided-attention loss on the alignments joins the three terms (Engine.loss_and_grads); None = off.
@@ -42,6 +46,16 @@ class Trainer:
         self.last_guided_loss = None     # device float64[1] of the latest step when the term is on (no host read on the step path)
         self.base_lr, self.weight_decay, self.max_norm = lr, weight_decay, max_norm
         self.milestones = sorted(int(m) for m in scheduler_milestones)
+        # OptimizerOptions (options.check_optimizer_options): decoupled weight decay, an EMA of the weights, the clip's
+        # norm and the learning-rate schedule.  None = the reference's update, and then no launch differs.  grad_clip replaces
+        # max_norm only when the options are given.  Under data parallelism nothing changes: every rank applies the same update to
+        # the same p, so the shadow weights agree as the weights do.
+        self.optimizer_options = check_optimizer_options(optimizer_options, lr=lr, milestones=self.milestones)
+        if optimizer_options is not None:
+            self.max_norm = self.optimizer_options.grad_clip
+        self.ema_updates = 0             # k of the EMA's num_updates ramp (options.ema_decay_at), a host counter
+        if self.optimizer_options.ema_decay > 0.0:
+            ps.init_ema()
         self.global_step = 0
         self.seed = seed
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -131,8 +145,16 @@ class Trainer:
         return ranges
 
     def lr_at(self, step: int) -> float:
-        """MultiStepLR(gamma=0.1), stepped once per optimiser step (model/tts_model.py:83-88)."""
-        return self.base_lr * (0.1 ** sum(1 for m in self.milestones if step >= m))
+        """The learning rate of the 0-based scheduler step `step`.  By default MultiStepLR(gamma=0.1), stepped once per optimiser step
+        (model/tts_model.py:83-88); with optimizer options a warm-up on top of it, an exponential decay or Noam (options.lr_at)."""
+        o = self.optimizer_options
+        if o.schedule == "multistep" and o.warmup_steps == 0:
+            return self.base_lr * (0.1 ** sum(1 for m in self.milestones if step >= m))
+        return schedule_lr_at(self.base_lr, self.milestones, o, step)
+
+    @property
+    def ema_on(self) -> bool:
+        return self.optimizer_options.ema_decay > 0.0
 
     def negotiate_shape(self, L: int, T: int):
         """Global (max over ranks) padded text and frame lengths of this step's shards: ONE tiny MAX all-reduce of two host integers
@@ -227,7 +249,19 @@ class Trainer:
             zero_later(ps.G[name])
         self.global_step += 1
         # MultiStepLR: the k-th optimiser step (k = global_step, 1-based) runs after k-1 scheduler steps
-        eng.adam_step(self.global_step, self.lr_at(self.global_step - 1), self.weight_decay, self.max_norm,
-                      grad_scale=1.0 / self.world, ranges=self.trainable_ranges() if self.frozen else None)
+        o = self.optimizer_options
+        if not o.decoupled_weight_decay and not self.ema_on:
+            eng.adam_step(self.global_step, self.lr_at(self.global_step - 1), self.weight_decay, self.max_norm,
+                          grad_scale=1.0 / self.world, ranges=self.trainable_ranges() if self.frozen else None)
+        else:
+            # the k-th EMA update runs under min(D, (1 + k) / (10 + k)).  A step the kernel skips (non-finite norm) still counts: the
+            # host does not read the norm on the step path, and the ramp is a schedule, not a state of the weights
+            d = None
+            if self.ema_on:
+                self.ema_updates += 1
+                d = ema_decay_at(o.ema_decay, self.ema_updates)
+            eng.adam_step(self.global_step, self.lr_at(self.global_step - 1), self.weight_decay, self.max_norm,
+                          grad_scale=1.0 / self.world, ranges=self.trainable_ranges() if self.frozen else None,
+                          decoupled=o.decoupled_weight_decay, ema_decay=d)
         eng.mark("optimizer")
         return loss3, outs
