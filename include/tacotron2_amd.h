@@ -1119,6 +1119,63 @@ typedef struct {
 int t2_psola(const T2Psola* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Programme loudness and true peak of a waveform, and its normalisation: ITU-R BS.1770-4 for one channel (K-weighting, 400 ms blocks
+ * in steps of 100 ms, the absolute and the relative gate, a true peak from 4x oversampling; no reference counterpart;
+ * csrc/t2_loudness.hip, the rule in DESIGN 5.20, restated in float64 in tests/loudness_ref.py).
+ *
+ * t2_loudness: x[b*ldx + i] float32 is a padded batch of B waveforms of finite samples, n[b] (DEVICE int32, 0 <= n[b] <= n_max <= ldx)
+ *   their sample counts; nothing is read from a row at or behind n[b].
+ *   K-WEIGHTING  two biquads in cascade, the shelf b1 / a1 and the high-pass b2 / a2 (a[0] = 1), formed by the HOST in fp64 for the
+ *     row's sample rate (tacotron2_amd/loudness.py: k_weighting).  Each runs as  v = b[0] u + s1;  s1 = b[1] u - a[1] v + s2;
+ *     s2 = b[2] u - a[2] v  in fp64 over [0, n[b]) from s1 = s2 = 0; y is the output of the second.
+ *   HOP ENERGIES  with H samples per hop and N = 4 H:  E[b*lde + h] = the fp64 sum of y^2 over [h H, (h + 1) H) for every whole hop,
+ *     h < n / H.
+ *   BLOCKS  a row with n >= N has J = n / H - 3 blocks  z_j = (((E_j + E_{j+1}) + E_{j+2}) + E_{j+3}) / N.  A row with 0 < n < N is
+ *     ONE block of all its samples, z_0 = (sum of y^2 over [0, n)) / n, and sets the flag `short`.  n == 0: J = 0.
+ *   GATES, in the linear domain:  block j passes the absolute gate iff z_j > abs_gate (the host's 10^((-70 + 0.691) / 10)), and
+ *     the relative one iff it also has z_j > 0.1 * mean(z over the blocks past the absolute gate).
+ *     lufs = -0.691 + 10 log10(mean z over the blocks past both).  Without a block past the absolute gate the row has NO loudness:
+ *     lufs = NaN, the flag `undefined`, gain 1.
+ *   PEAKS  sample_peak = max |x[i]|.  true_peak = the largest magnitude among the 4 n values t2_resample writes for this row with
+ *     U = 4, D = 1 and this table [4][2K]:  for m < 4 n,  i0 = m / 4, p = m % 4,
+ *     sum_{k = -K+1 .. K} table[p][k + K - 1] * x[i0 + k],  one fmaf per tap in ascending k from 0.0f, samples outside [0, n) zero and
+ *     never loaded.  The 4x signal is not written.
+ *   GAIN, in fp64, only with y != NULL (y == NULL: the entry measures, gain = 1 and neither `limited` nor `capped` is set):
+ *     g = 10^((target - lufs) / 20);  g > max_gain: g = max_gain, flag `capped`;  then g * true_peak > ceiling: g = ceiling /
+ *     true_peak, flag `limited` (max_gain and ceiling LINEAR, from the host).  gain[b] = (float) g, and
+ *     y[b*ldy + i] = x[b*ldx + i] * gain[b]  for i < n[b] - one float32 product -,  0.0f for n[b] <= i < ldy.
+ *   stat[b*T2_LOUD_NSTAT + ..] fp64:  0 lufs,  1 gain (before the rounding to float32),  2 true_peak,  3 sample_peak,  4 n_blocks = J,
+ *     5 n_below_abs,  6 n_below_rel (past the absolute gate, not past the relative one),  7 rel_gate_lufs = -0.691 + 10 log10 of the
+ *     relative threshold (NaN without a loudness),  8 momentary_max_lufs = -0.691 + 10 log10(max_j z_j) (-inf for silence, NaN with
+ *     J = 0),  9 flags: bit 0 short, 1 undefined, 2 limited, 3 capped.
+ *   REFUSED on the device, not clamped: a row with n[b] outside 0 .. n_max gets flags = -1; nothing else is written for it (E, gain
+ *     and y included) and x is not read.
+ *   Launches on one stream: the filter and hop energies (one 256-thread workgroup per row: every thread filters a chunk of 32
+ *     samples from a zero state, the 4 end states of the 256 chunks of a pass meet in a scan through the chunk-transition matrix and
+ *     its powers - formed by the entry from a1, a2, b2 in fp64 -, and every thread filters its chunk again from its true state); the
+ *     peaks (grid tiles of 1024 samples x B, the span in LDS as t2_resample stages it, the tile maxima joined by an integer maximum
+ *     on the bits of the non-negative value); gates and gain (one workgroup per row over E); the scaling.  Every sum in a fixed
+ *     order: two calls give bit-identical E, stat, gain and y, and a row's results do not depend on B, ldx, ldy, lde or the other rows.
+ *   T2_ERR_ARG before any launch: a null pointer (x only when n_max > 0, y never: it selects measuring), B < 1 or > 65535, n_max < 0,
+ *     ldx < n_max, H < 1, lde < n_max / H, K outside 1 .. T2_LOUD_MAX_K, ldy < n_max with y, a coefficient, gate, target, max_gain
+ *     or ceiling that is not finite, max_gain or ceiling <= 0. */
+#define T2_LOUD_NSTAT 10
+#define T2_LOUD_MAX_K 4096
+typedef struct {
+    const float* x; int64_t ldx;                        /* rows are read only inside [0, n[b]) */
+    const int32_t* n;                                   /* [B] device */
+    const float* table; int K;                          /* [4][2K] fp32: datasets/resample.plan(sr, 4 sr) */
+    int B, n_max, H;
+    double b1[3], a1[3], b2[3], a2[3];                  /* the K-weighting at the rows' rate, host-made */
+    double abs_gate, target, max_gain, ceiling;         /* linear mean square; LUFS; linear; linear */
+    double* E; int64_t lde;                             /* [B][lde] hop energies */
+    double* stat;                                       /* [B][T2_LOUD_NSTAT] */
+    float* gain;                                        /* [B] */
+    float* y; int64_t ldy;                              /* NULL: measure only */
+} T2Loudness;
+int t2_loudness(const T2Loudness* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

@@ -326,12 +326,26 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
               help="Scale the intonation range about the voice's mean pitch by K, 0 to 2: 0 is a monotone voice, 1 unchanged, 2 twice "
                    "the excursions. Works with any checkpoint; always by TD-PSOLA, so it implies --preserve-formants. Needs a .wav "
                    "target. Default: off.")
+@click.option("--loudness", required=False, type=float, default=None, metavar="LUFS",
+              help="Write the file at this programme loudness, -40 to -5 LUFS (EBU R128: -23, podcasts: -16): measured by ITU-R "
+                   "BS.1770-4 on the GPU on the samples as they are written - behind --tempo, --pitch-shift and --out-sample-rate -, "
+                   "then ONE gain per file, lowered where --true-peak asks for it; no limiter, no compression. With --text-file the "
+                   "loudness is the whole document's. Needs a .wav target. Default: off.")
+@click.option("--true-peak", required=False, type=float, default=None, metavar="DBTP",
+              help="With --loudness: the true peak (4x oversampled) the file may reach, -9 to 0 dBTP; the gain is lowered until it "
+                   "holds. Default: -1.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
         forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
         expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000, tempo=None,
-        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False):
+        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False, loudness=None, true_peak=None):
     if (text is None) == (text_file is None):
         raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
+    if loudness is not None or true_peak is not None:
+        from tacotron2_amd.run.say import loudness_settings
+        try:
+            loudness_settings(loudness, true_peak, wav_target(out, hifi_gan_checkpoint))
+        except ValueError as e:
+            raise click.UsageError(str(e))
     if text_file is None:
         given = [name for name, v in (("--max-chars", max_chars), ("--expand-numbers", expand_numbers or None), ("--pause", pause),
                                       ("--no-trim", no_trim or None), ("--level", level or None), ("--fade-ms", fade_ms),
@@ -353,7 +367,8 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                   hifi_gan_checkpoint=hifi_gan_checkpoint, random_seed=random_seed, controls=controls,
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
                   durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len,
-                  tempo=tempo, pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range)
+                  tempo=tempo, pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range,
+                  loudness=loudness, true_peak=true_peak)
     if text_file is None:
         from tacotron2_amd.run.say import do_say
         do_say(text=text, **common)

@@ -1,5 +1,5 @@
-"""The audio measurements that need no model (DESIGN 5.10 - 5.12, 5.14 - 5.18): pitch tracking, voice quality, their per-utterance
-statistics, resampling, joining, time stretching and pitch change, each one call into libtacotron2_amd.so on the current stream.  The arguments are checked by _args before
+"""The audio measurements that need no model (DESIGN 5.10 - 5.12, 5.14 - 5.18, 5.20): pitch tracking, voice quality, their per-utterance
+statistics, resampling, joining, time stretching, pitch change and loudness, each one call into libtacotron2_amd.so on the current stream.  The arguments are checked by _args before
 a pointer reaches a kernel.  engine re-exports every public name of this module: engine.yin is analysis.yin."""
 from __future__ import annotations
 
@@ -14,6 +14,7 @@ from ._lib import cached, call, make, stream
 from .join import fade_table, join_audio  # noqa: F401  (pieces joined into one waveform, DESIGN 5.16: analysis.join_audio, in join.py)
 from .stretch import hann_table, pitch_shift, time_stretch  # noqa: F401  (WSOLA tempo and pitch, DESIGN 5.17: in stretch.py)
 from .psola import fold_lags, grain_table, pitch_ratio, pitch_shift_psola, psola  # noqa: F401  (TD-PSOLA pitch change, DESIGN 5.18: in psola.py)
+from .loudness import k_weighting, loudness, normalize_loudness  # noqa: F401  (BS.1770 loudness and true peak, DESIGN 5.20: in loudness.py)
 from .variance import VAR_MAX_L, VAR_MAX_T, VAR_NSTAT, VAR_STATS, char_variance  # noqa: F401
 
 PROSODY_MAX_T = 4096        # T2_PROSODY_MAX_T: frames of one utterance in t2_prosody_stats

@@ -203,7 +203,9 @@ class TTSModel(nn.Module):
         trim_frame_length; None: the defaults) and a loaded vocoder object (hifigan.Generator or vocoder.GriffinLim; None: a
         Griffin-Lim for this model's mel bands).  Among the options: tempo=T (0.5 .. 2.0) and pitch_shift=SEMITONES (-12 .. 12), a
         WSOLA stretch of all pieces in one launch in front of the join; preserve_formants=True and pitch_range=K (0 .. 2) change the
-        pitch by TD-PSOLA instead, one launch of each kernel for all pieces.  Loads no checkpoint.  Returns (waveform, plan, per-piece
+        pitch by TD-PSOLA instead, one launch of each kernel for all pieces; loudness=LUFS (-40 .. -5)
+        and true_peak=DBTP (-9 .. 0, default -1) bring the joined waveform to that BS.1770 programme loudness as the last step
+        (DESIGN 5.20).  Loads no checkpoint.  Returns (waveform, plan, per-piece
         dict)."""
         from ..run.say import say_document
         pre = dict(preprocessing or {})

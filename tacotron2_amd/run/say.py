@@ -138,14 +138,74 @@ def scale_records(records: list, voice: Optional[VoicePlan]) -> list:
     return records
 
 
+LOUDNESS_LIMITS, TRUE_PEAK_LIMITS, TRUE_PEAK_DEFAULT = (-40.0, -5.0), (-9.0, 0.0), -1.0      # what `say` offers of analysis.normalize_loudness
+
+
+def loudness_settings(loudness, true_peak, wav_target: bool = True, rate: Optional[int] = None) -> Optional[Tuple[float, float]]:
+    """--loudness LUFS and --true-peak DBTP of `say`, checked before anything is decoded: None when neither is given,
+    else (target, ceiling) for analysis.normalize_loudness, the ceiling -1 dBTP when --true-peak is not given.  rate: the rate the
+    file's header will carry, where it is known; BS.1770's filter is built for 8000 .. 192 000 Hz."""
+    import math
+    from ..loudness import RATE_LIMITS
+    if loudness is None and true_peak is None:
+        return None
+    for name, v, (lo, hi) in (("--loudness", loudness, LOUDNESS_LIMITS), ("--true-peak", true_peak, TRUE_PEAK_LIMITS)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not lo <= v <= hi):
+            raise ValueError(f"{name} must lie in {lo:g} .. {hi:g}, got {v!r}")
+    if loudness is None:
+        raise ValueError("--true-peak needs --loudness: alone it has no gain to bound")
+    if not wav_target:
+        raise ValueError("--loudness and --true-peak need a .wav target or a HiFi-GAN checkpoint: a log-mel has no level to set")
+    if rate is not None and not RATE_LIMITS[0] <= int(rate) <= RATE_LIMITS[1]:
+        raise ValueError(f"--loudness at {rate} Hz: the K-weighting is built for {RATE_LIMITS[0]} .. {RATE_LIMITS[1]} Hz")
+    return float(loudness), TRUE_PEAK_DEFAULT if true_peak is None else float(true_peak)
+
+
+def normalize_rows(waves, rate: int, loud: Tuple[float, float], dev):
+    """The LAST step in front of write_wav: the waveforms as they would be written, at the rate the header will carry, as the rows of
+    ONE analysis.normalize_loudness call.  (the rows cut to their counts, on dev; one dict per row: loudness_lufs - measured, None
+    for a row without a loudness, which keeps the gain 1 and its bits -, gain_db, true_peak_dbtp - after the gain, None for digital
+    silence -, flags)."""
+    import math
+    from .. import analysis
+    buf, n = pack_rows([torch.as_tensor(w).detach().float().reshape(-1) for w in waves], dev)
+    y, stats = analysis.normalize_loudness(buf, n, int(rate), target=loud[0], ceiling=loud[1])
+    lufs, gain, peak, flags = (stats[k].cpu().tolist() for k in ("lufs", "gain", "true_peak", "flags"))
+    db = lambda v: 20.0 * math.log10(v) if v > 0 else None
+    recs = [dict(loudness_lufs=None if math.isnan(lufs[i]) else lufs[i], gain_db=db(gain[i]), true_peak_dbtp=db(gain[i] * peak[i]),
+                 flags=int(flags[i])) for i in range(len(n))]
+    return [y[i, :n[i]] for i in range(len(n))], recs
+
+
+def loudness_line(name: str, rec: dict) -> str:
+    """The line `say` prints per file written with --loudness."""
+    from ..loudness import FLAG_CAPPED, FLAG_LIMITED, FLAG_SHORT, FLAG_UNDEFINED
+    if rec["flags"] & FLAG_UNDEFINED:
+        return f"say: {name}: no loudness (left as it is)"
+    notes = [text for bit, text in ((FLAG_LIMITED, "peak-limited"), (FLAG_CAPPED, "boost capped"), (FLAG_SHORT, "short")) if rec["flags"] & bit]
+    return (f"say: {name}: {rec['loudness_lufs']:.2f} LUFS, gain {rec['gain_db']:+.2f} dB, true peak {rec['true_peak_dbtp']:.2f} dBTP"
+            + "".join(", " + t for t in notes))
+
+
+def loudness_fields(rec: dict) -> dict:
+    """What a --durations-out object gains with --loudness."""
+    return {k: rec[k] for k in ("loudness_lufs", "gain_db", "true_peak_dbtp")}
+
+
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
            description: Optional[str] = None, max_len: int = 5000, attention_window: Optional[Tuple[int, int]] = None,
            forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
            stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-           pitch_shift: Optional[float] = None, preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None):
-    """preserve_formants (with pitch_shift or pitch_range) and pitch_range: 0 .. 2, the intonation range scaled about the mean pitch -
+           pitch_shift: Optional[float] = None, preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None,
+           loudness: Optional[float] = None, true_peak: Optional[float] = None):
+    """loudness: -40 .. -5 LUFS, true_peak: -9 .. 0 dBTP (default -1; only with loudness) - with a `.wav` target every text's waveform,
+    exactly as it would be written (behind the voice chain and out_sample_rate, at the rate of the header), becomes one row of ONE
+    analysis.normalize_loudness call (BS.1770-4) and is written with its gain; one line per file is printed and
+    `durations_out` objects gain `loudness_lufs` (measured), `gain_db` and `true_peak_dbtp` (after the gain).  A text without a
+    loudness (silence) is written as it is.  None: nothing of this runs.
+    preserve_formants (with pitch_shift or pitch_range) and pitch_range: 0 .. 2, the intonation range scaled about the mean pitch -
     the pitch is then changed by TD-PSOLA on the device (analysis.pitch_shift_psola) behind a stretch by the tempo alone:
     the sample count is the stretch's and nothing is resampled; `durations_out` objects gain `preserve_formants` and `pitch_range`.
     tempo: 0.5 .. 2.0, pitch_shift: -12 .. 12 semitones - with a `.wav` target (HiFi-GAN or Griffin-Lim) the vocoded waveform is
@@ -169,6 +229,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         raise ValueError(f"--out-sample-rate needs a .wav target or a HiFi-GAN checkpoint, got {output!r}: a log-mel has no rate")
     resampler = output_resampler(pre, out_sample_rate, dev)
     voice = voice_settings(tempo, pitch_shift, sample_rate(pre), audio, preserve_formants, pitch_range)
+    loud = loudness_settings(loudness, true_peak, audio, sample_rate(pre) if out_sample_rate is None else int(out_sample_rate))
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     _, chars, lens = encode_texts(enc, texts, dev)
@@ -178,9 +239,10 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     frames, _ = emitted_frames(gates, post.shape[1])
     mels = [m[:n] for m, n in zip(post.cpu().numpy(), frames)]
     sr = sample_rate(pre)
-    if durations_out is not None:
+    records = scale_records(duration_records(model, enc, texts, align, lens, frames, sr), voice) if durations_out is not None else None
+    if records is not None and loud is None:
         with open(durations_out, "w") as f:
-            json.dump(scale_records(duration_records(model, enc, texts, align, lens, frames, sr), voice), f)
+            json.dump(records, f)
     if not audio:
         np.save(output, mels[0] if isinstance(text, str) else np.array(mels, dtype=object), allow_pickle=not isinstance(text, str))
         return mels
@@ -194,11 +256,23 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     if voice is not None and voice.active:                # every text's waveform in one padded batch: ONE stretch launch
         rows, n_out = apply_voice(*pack_rows([torch.as_tensor(vocode(m)).detach().float().reshape(-1) for m in mels], dev), voice)
         stretched = [rows[i, :n_out[i]].cpu() for i in range(len(mels))]
+    names = [output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav" for i in range(len(mels))]
+    if loud is not None:                                  # every text as it would be written, in one padded batch: ONE launch
+        from .. import vocoder
+        rate = sr if resampler is None else resampler.sr_out
+        rows, recs = normalize_rows([to_output_rate(vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
+                                     for i, m in enumerate(mels)], rate, loud, dev)
+        for name, row, rec in zip(names, rows, recs):
+            vocoder.write_wav(name, row.cpu(), rate)
+            print(loudness_line(name, rec))
+        if records is not None:
+            with open(durations_out, "w") as f:
+                json.dump([dict(r, **loudness_fields(rec)) for r, rec in zip(records, recs)], f)
+        return mels
     for i, m in enumerate(mels):
         # several texts: `<output without its extension>_<i>.wav`.  Griffin-Lim is reached with a name that ends in ".wav" only, whose
         # last dot is that extension's, so this is the `output[:-4]` of the reference's branch as well
-        name = output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav"
-        write_audio(name, vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
+        write_audio(names[i], vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
     return mels
 
 
@@ -211,17 +285,23 @@ def pack_rows(waves, dev):
     return buf, n
 
 
-def write_audio(name: str, wav, sr: int, resampler, host: bool):
-    """The tail of both drivers: `wav` at sr Hz brought to --out-sample-rate if there is one, then ONE vocoder.write_wav call with the
-    rate the samples then have.  host: do_say's way, which vocodes text by text and writes each text from the host - up and down
-    through Resampler.one; else the document's, whose joined waveform stays on the device through Resampler.batch.  Returns the
-    waveform as written."""
-    from .. import vocoder
+def to_output_rate(wav, sr: int, resampler, host: bool):
+    """`wav` at sr Hz brought to --out-sample-rate if there is one.  host: do_say's way, which vocodes text by text and writes each
+    text from the host - up and down through Resampler.one; else the document's, whose joined waveform stays on the device through
+    Resampler.batch."""
     if resampler is not None and host:
         wav = torch.from_numpy(resampler.one(wav.detach().float().cpu().numpy(), sr))
     elif resampler is not None and wav.numel() > 0:
         out, n_out = resampler.batch(wav[None, :], [int(wav.numel())], sr)
         wav = out[0, :n_out[0]]
+    return wav
+
+
+def write_audio(name: str, wav, sr: int, resampler, host: bool):
+    """The tail of both drivers: to_output_rate, then ONE vocoder.write_wav call with the rate the samples then have.  Returns the
+    waveform as written."""
+    from .. import vocoder
+    wav = to_output_rate(wav, sr, resampler, host)
     vocoder.write_wav(name, wav, sr if resampler is None else resampler.sr_out)
     return wav
 
@@ -235,7 +315,8 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                  trim: bool = True, level: bool = False, fade_ms: float = 5.0, speaker_id: Optional[int] = None,
                  controls: Optional[str] = None, description: Optional[str] = None, random_seed: Optional[int] = None,
                  durations: bool = False, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
-                 preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None):
+                 preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None, loudness: Optional[float] = None,
+                 true_peak: Optional[float] = None):
     """Pieces (datasets.document.Piece, or a text, which is split at the defaults) -> one waveform on the model's device.
     The pieces are sorted by encoded length and decoded in chunks of batch_size through the model's free-running forward, with the
     decode settings that are on the model (common.free_run).  `vocoder` is a loaded hifigan.Generator - each chunk's PADDED batch
@@ -249,10 +330,14 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     effective tempo.  preserve_formants and pitch_range (0 .. 2): the pitch is changed by TD-PSOLA instead (voice_settings), the whole
     buffer through ONE launch of t2_stretch, of the two pitch-tracking kernels and of t2_psola; pauses and times are divided by the
     tempo alone.
+    loudness (-40 .. -5 LUFS) and true_peak (-9 .. 0 dBTP, default -1): the JOINED waveform, as ONE row at the model's rate, is
+    brought to that programme loudness by analysis.normalize_loudness as the last step; `level` keeps moving the pieces
+    towards each other in front of it.  (do_say_document, which may resample behind the join, normalises behind that instead.)
     A piece that ran into max_len without stopping is kept, cut there, and marked stopped=False.
     Returns (y (total,) float32, plan - join_audio's, device tensors -, info): info = dict(pieces, frames, stopped, n, pause,
     waveforms - the per-piece device tensors that went into the join -, chunks, join - the keyword arguments of the join_audio
-    call -, durations - duration_records per piece, or None -, voice - voice_settings, or None)."""
+    call -, durations - duration_records per piece, or None -, voice - voice_settings, or None -, loudness - normalize_rows' record
+    of the document, or None)."""
     from .. import analysis
     from ..datasets.document import split_document
     from ..hifigan import Generator
@@ -266,6 +351,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     dev = next(model.parameters()).device
     sr = sample_rate(pre)
     voice = voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
+    loud = loudness_settings(loudness, true_peak, True, sr)
     texts = [p.text for p in pieces]
     ids, _, _ = encode_texts(enc, texts)
     order = sorted(range(len(ids)), key=lambda i: (len(ids[i]), i))
@@ -297,8 +383,11 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                 keep=int(round(KEEP_S * sr)), fade=int(round(float(fade_ms) * sr / 1000.0)), level=bool(level),
                 ceiling=1.0 if level else 0.0)
     y, _, plan = analysis.join_audio(buf, n, pause, **join)
+    loud_rec = None
+    if loud is not None:
+        (y,), (loud_rec,) = normalize_rows([y], sr, loud, dev)
     return y, plan, dict(pieces=pieces, frames=frames, stopped=stopped, n=n, pause=pause, waveforms=waves, chunks=len(chunks),
-                         join=join, durations=records if durations else None, voice=voice)
+                         join=join, durations=records if durations else None, voice=voice, loudness=loud_rec)
 
 
 def document_records(info: dict, plan: dict, sample_rate: int) -> list:
@@ -341,12 +430,16 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
                     stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, max_chars: int = 190,
                     expand_numbers: bool = False, pause=None, trim: bool = True, level: bool = False, fade_ms: float = 5.0,
                     batch_size: int = 64, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
-                    preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None):
+                    preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None, loudness: Optional[float] = None,
+                    true_peak: Optional[float] = None):
     """`say --text-file`: the file is read, its numbers expanded if asked, split (datasets/document.py) and spoken by say_document;
     the joined waveform is resampled to out_sample_rate if given (one Resampler call) and written by ONE write_wav call.
     tempo, pitch_shift, preserve_formants, pitch_range: say_document's, in front of the join.
+    loudness, true_peak: the joined document, behind the resampling, is ONE row of analysis.normalize_loudness (loudness_settings),
+    so the loudness is the programme's and the ceiling holds for the file; a line is printed, every `durations_out` object gains the
+    document's `loudness_lufs`, `gain_db` and `true_peak_dbtp`, and info["loudness"] holds them.
     durations_out: document_records as a JSON list.  A piece that did not stop is reported on stderr; the exit status stays 0.
-    Returns say_document's (y, plan, info), y as written (after resampling)."""
+    Returns say_document's (y, plan, info), y as written (after resampling and normalisation)."""
     import sys
     import time
     from ..datasets.document import expand_numbers as expand, split_document
@@ -362,6 +455,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     sr = sample_rate(pre)
     resampler = output_resampler(pre, out_sample_rate, dev)
     voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
+    loud = loudness_settings(loudness, true_peak, True, sr if out_sample_rate is None else int(out_sample_rate))
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     with open(text_file, encoding="utf-8") as f:
         text = f.read()
@@ -381,11 +475,19 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     for i, ok in enumerate(info["stopped"]):
         if not ok:
             print(f"say: piece {i} did not stop within --max-len {max_len} frames and is cut there: {pieces[i].text[:40]!r}", file=sys.stderr)
-    if durations_out is not None:
-        with open(durations_out, "w") as f:
-            json.dump(document_records(info, plan_, sr), f)
     seconds = y.numel() / sr
-    y = write_audio(output, y, sr, resampler, host=False)
+    if loud is None:
+        y = write_audio(output, y, sr, resampler, host=False)
+    else:
+        from .. import vocoder
+        rate = sr if resampler is None else resampler.sr_out
+        (y,), (info["loudness"],) = normalize_rows([to_output_rate(y, sr, resampler, host=False)], rate, loud, dev)
+        vocoder.write_wav(output, y, rate)
+        print(loudness_line(output, info["loudness"]))
+    if durations_out is not None:
+        more = loudness_fields(info["loudness"]) if loud is not None else {}
+        with open(durations_out, "w") as f:
+            json.dump([dict(r, **more) for r in document_records(info, plan_, sr)], f)
     torch.cuda.synchronize(dev)
     print(f"say: {len(pieces)} pieces in {info['chunks']} chunks, {seconds:.2f} s of audio in {time.perf_counter() - t_start:.2f} s")
     return y, plan_, info
