@@ -8,7 +8,9 @@ import numbers
 
 import torch
 
-YIN_MAX_SPAN = 4096         # T2_YIN_MAX_SPAN: W + tau_max floats of one frame's span in LDS
+from ._lib import K
+
+YIN_MAX_SPAN = K["YIN_MAX_SPAN"]         # W + tau_max floats of one frame's span in LDS
 
 
 def int_arg(fn: str, name: str, v, lo=None, hi=None) -> int:

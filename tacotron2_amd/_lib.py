@@ -1,5 +1,5 @@
 """ctypes binding of libtacotron2_amd.so, generated at import time from include/tacotron2_amd.h (the header is
-the single source of truth for struct layouts and signatures).
+the single source of truth for struct layouts, signatures and limits: K holds every `#define T2_<NAME> <integer>`).
 
 The product path FAILS LOUDLY when the HIP library is missing: there is no PyTorch/CPU fallback anywhere in
 this package (a silent fallback would void every parity claim).
@@ -60,7 +60,10 @@ def _parse_header(path: str):
                 mm = re.match(r"(const\s+)?(\w+)\s*(\*?)\s*(\w+)?$", a)
                 alist.append((mm.group(2), bool(mm.group(3))))
         funcs[name] = (ret, alist)
-    return structs, order, funcs
+    # `#define T2_<NAME> <integer>` on a line of its own (block comments are gone; a line comment does not start with #)
+    consts = {m.group(1): int(m.group(2), 0)
+              for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+T2_(\w+)[ \t]+([-+]?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", src, flags=re.M)}
+    return structs, order, funcs, consts
 
 
 def _ctype(base: str, is_ptr: bool, structs_c: dict):
@@ -73,7 +76,7 @@ def _ctype(base: str, is_ptr: bool, structs_c: dict):
     raise T2Error(f"unknown C type {base}")
 
 
-_structs, _order, _funcs = _parse_header(HEADER)
+_structs, _order, _funcs, K = _parse_header(HEADER)
 S: dict = {}
 for _name in _order:
     _fields = []

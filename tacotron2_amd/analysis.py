@@ -9,7 +9,7 @@ import torch
 
 from . import _args
 from ._args import YIN_MAX_SPAN
-from ._lib import cached, call, make, stream
+from ._lib import K, cached, call, make, stream
 # per-character pitch and energy on the duration grid: analysis.char_variance, written in variance.py
 from .join import fade_table, join_audio  # noqa: F401  (pieces joined into one waveform, DESIGN 5.16: analysis.join_audio, in join.py)
 from .stretch import hann_table, pitch_shift, time_stretch  # noqa: F401  (WSOLA tempo and pitch, DESIGN 5.17: in stretch.py)
@@ -17,8 +17,8 @@ from .psola import fold_lags, grain_table, pitch_ratio, pitch_shift_psola, psola
 from .loudness import k_weighting, loudness, normalize_loudness  # noqa: F401  (BS.1770 loudness and true peak, DESIGN 5.20: in loudness.py)
 from .variance import VAR_MAX_L, VAR_MAX_T, VAR_NSTAT, VAR_STATS, char_variance  # noqa: F401
 
-PROSODY_MAX_T = 4096        # T2_PROSODY_MAX_T: frames of one utterance in t2_prosody_stats
-PROSODY_NSTAT = 8           # T2_PROSODY_NSTAT
+PROSODY_MAX_T = K["PROSODY_MAX_T"]        # frames of one utterance in t2_prosody_stats
+PROSODY_NSTAT = K["PROSODY_NSTAT"]
 YIN_DEFAULTS = dict(sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, thr=0.1, vthr=0.3, power_floor=1e-10)
 
 
@@ -67,8 +67,8 @@ def prosody_stats(f0, aper, power, n, hop=256, span=1024 + 367):
     return out
 
 
-VQ_MAX_CYCLES = 32          # T2_VQ_MAX_CYCLES: cycles matched per frame in t2_voice_quality
-CORPUS_NSTAT = 12           # T2_CORPUS_NSTAT
+VQ_MAX_CYCLES = K["VQ_MAX_CYCLES"]        # cycles matched per frame in t2_voice_quality
+CORPUS_NSTAT = K["CORPUS_NSTAT"]
 
 
 def voice_quality(wav, n, f0, sr=22050, hop=256, W=1024, fmin=60.0, fmax=500.0, n_max=None, return_cycles=False):
@@ -111,8 +111,8 @@ def corpus_stats(f0, power, jitter, shimmer, nhr, hnr_db, cycles, n, hop=256, sp
     return out
 
 
-PITCH_MAX_STATES = 4096     # T2_PITCH_MAX_STATES: voiced states (integer lags) of t2_pitch_viterbi
-F0_NSTAT = 12               # T2_F0_NSTAT
+PITCH_MAX_STATES = K["PITCH_MAX_STATES"]  # voiced states (integer lags) of t2_pitch_viterbi
+F0_NSTAT = K["F0_NSTAT"]
 # w: transition cost per octave of lag change; max_jump: the largest allowed change in octaves per frame; u: local cost of the
 # unvoiced state (YIN's voicing threshold: a frame whose best lag is worse than that is cheaper unvoiced); c_sw: a voicing switch
 VITERBI_DEFAULTS = dict(w=1.0, max_jump=0.25, u=YIN_DEFAULTS["vthr"], c_sw=0.15)
@@ -166,7 +166,8 @@ def f0_path_stats(path, path_len, f0_a, n_a, f0_b, n_b, hop=256, span=1024 + 367
     unvoiced -, n_a and n_b the sample counts, hop and span = W + tau_max of the yin call (the validity rule of prosody_stats; cells
     outside a track count as invalid).  (B, 12) float64 rows [scored cells, both voiced, only a voiced, only b voiced, sum d, sum d^2
     with d = 1200 (log2 fa - log2 fb) cents over the both-voiced cells, sum la, sum lb, sum la^2, sum lb^2, sum la lb with la =
-    log2 fa, 0]; f0_figures turns a row into RMSE, bias, correlation and voicing error."""
+    log2 fa, 0]; f0_figures turns a row into RMSE, bias, correlation and voicing error.  Sums in fp64 in a fixed order (per thread, a shuffle
+    tree, the waves in order: t2m_sums_to_thread0 of csrc/t2_measure.hpp)."""
     fn = "f0_path_stats"
     if not torch.is_tensor(path) or path.dim() != 3 or path.shape[2] != 2 or path.dtype != torch.int32 or not path.is_contiguous():
         raise ValueError("f0_path_stats: path must be a contiguous int32 (B, P, 2) tensor")

@@ -11,18 +11,16 @@
 //     position of the row's maximum.
 // Both modes make the argmax pass (focus rate, agreement with the argmax).  The counts are LDS integers (they reuse the Q
 // rows once the recurrence is done); the block writes them out as dur.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
-
-#define ST ((hipStream_t)stream)
 
 __device__ __forceinline__ double la_of(float a) { return log((double)fmaxf(a, 1e-8f)); }
 
 // dynamic LDS: [0, 64) 8 doubles of wave partials; then mode 1: Q[2][L] doubles, mode 0: L ints.  cnt[L] ints alias Q.
 __global__ __launch_bounds__(256) void align_durations_kernel(T2AlignDur a) {
     extern __shared__ double lds[];
-    double* red = lds;
+    double (*red)[4] = reinterpret_cast<double (*)[4]>(lds);         // [2][4 waves]
     double* Q = lds + 8;
     int* cnt = reinterpret_cast<int*>(lds + 8);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(256) void align_durations_kernel(T2AlignDur a) {
     __syncthreads();
 
     // argmax pass, one wave per step: the row's maximum (focus rate) and its lowest position
-    double focus = 0.0, lasum = 0.0;
+    double sum[2] = {0.0, 0.0};                    // focus, lasum: lane 0 of every wave adds, the other lanes hold 0
     for (int s = w; s < Sb; s += 4) {
         const float* row = al + s * lds_;
         float v = -__builtin_inff();
@@ -81,28 +79,23 @@ __global__ __launch_bounds__(256) void align_durations_kernel(T2AlignDur a) {
             const float x = row[n];
             if (x > v || i == 0x7fffffff) { v = x; i = n; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(v, o, 64);
-            const int oi = __shfl_xor(i, o, 64);
-            if (oi != 0x7fffffff && (i == 0x7fffffff || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
-        }
+        t2m_wave_pick(v, i, [](float ov, int oi, float mv, int mi) {
+            return oi != 0x7fffffff && (mi == 0x7fffffff || ov > mv || (ov == mv && oi < mi));
+        });
         if (lane == 0) {
-            focus += (double)v;
+            sum[0] += (double)v;
             if (mono) {
                 back[(long)s * L + i] |= 2;       // bit 1: this cell is the step's argmax (read by the backtrack below)
             } else {
                 atomicAdd(&cnt[i], s < Sb - 1 ? r : wlast);
-                lasum += la_of(v);
+                sum[1] += la_of(v);
             }
         }
     }
-    if (lane == 0) { red[2 * w] = focus; red[2 * w + 1] = lasum; }
-    __syncthreads();
+    t2m_sums_to_thread0(sum, red);
 
     if (tid == 0) {
-        focus = red[0] + red[2] + red[4] + red[6];
-        lasum = red[1] + red[3] + red[5] + red[7];
+        double focus = sum[0], lasum = sum[1];
         int agree = Sb;
         if (mono) {               // backtrack from (Sb - 1, Nb - 1)
             agree = 0;

@@ -9,11 +9,10 @@
 //     independent of D: the distances of diagonal k+1 are computed BEFORE the barrier of diagonal k, so no global load sits
 //     between a barrier and the LDS reads that depend on it.  fp64 D: totals reach ~1e5 over a few thousand cells, where an fp32
 //     ulp (8e-3) is the size of real decision margins.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define DTW_THREADS 256
 #define DTW_MAXC (T2_DTW_MAX_T / DTW_THREADS)      // cells of one diagonal a thread can own
 

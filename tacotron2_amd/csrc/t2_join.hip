@@ -14,33 +14,14 @@
 //           writes nothing (nothing is clamped; the rows that are out of range are never read).
 //   write   grid (chunks, B): y[off + i] = x[s0 + i] * (gain * e) - two float multiplications, nothing to contract - and the zeros of
 //           the pause.  A shortened fade (len < 2 fade) samples the SAME table, at (2 i + 1) fade / (2 fl).
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define JN_FRAME_WAVES 4
 #define JN_ROW_THREADS 1024
+#define JN_ROW_WAVES (JN_ROW_THREADS / 64)
 #define JN_CHUNK 1024              // outputs of one workgroup of the write launch per round
-
-template <typename T, typename Op>
-__device__ __forceinline__ T jn_block_reduce(T v, Op op, T* red) {      // red: blockDim.x / 64 values; every thread gets the result
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    T s = red[0];
-    for (int i = 1; i < nw; ++i) s = op(s, red[i]);
-    return s;
-}
-struct JnSum { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
-struct JnMaxD { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
-struct JnMinI { __device__ long long operator()(long long a, long long b) const { return a < b ? a : b; } };
-struct JnMaxI { __device__ long long operator()(long long a, long long b) const { return a > b ? a : b; } };
-
-__device__ __forceinline__ bool jn_row_ok(const T2Join& p, int b) { const int n = p.n[b]; return n >= 0 && n <= p.n_max; }
 
 __global__ __launch_bounds__(JN_FRAME_WAVES * 64) void join_energy_kernel(T2Join p) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -61,11 +42,11 @@ __global__ __launch_bounds__(JN_FRAME_WAVES * 64) void join_energy_kernel(T2Join
 }
 
 __global__ __launch_bounds__(JN_ROW_THREADS) void join_span_kernel(T2Join p, double factor) {
-    __shared__ double redd[JN_ROW_THREADS / 64];
-    __shared__ long long redi[JN_ROW_THREADS / 64];
+    __shared__ double redd[JN_ROW_WAVES];
+    __shared__ long long redi[JN_ROW_WAVES];
     const int b = blockIdx.x, tid = threadIdx.x;
     int64_t s0 = 0, s1 = 0;
-    if (jn_row_ok(p, b)) {
+    if (t2m_count_ok(p.n[b], p.n_max)) {
         const int64_t n = p.n[b];
         s1 = n;
         if (p.trim && n >= p.F) {
@@ -73,13 +54,13 @@ __global__ __launch_bounds__(JN_ROW_THREADS) void join_span_kernel(T2Join p, dou
             const int64_t nfr = n / p.H + 1;
             double m = 0.0;
             for (int64_t f = tid; f < nfr; f += JN_ROW_THREADS) m = fmax(m, e[f]);
-            m = jn_block_reduce(m, JnMaxD(), redd);
+            m = t2m_block_reduce<JN_ROW_WAVES>(m, T2mFmax(), redd);
             const double thr = m * factor;
             long long fa = INT64_MAX, fz = -1;
             for (int64_t f = tid; f < nfr; f += JN_ROW_THREADS)
                 if (e[f] > thr) { fa = f < fa ? f : fa; fz = f > fz ? f : fz; }
-            fa = jn_block_reduce(fa, JnMinI(), redi);
-            fz = jn_block_reduce(fz, JnMaxI(), redi);
+            fa = t2m_block_reduce<JN_ROW_WAVES>(fa, T2mMin(), redi);
+            fz = t2m_block_reduce<JN_ROW_WAVES>(fz, T2mMax(), redi);
             if (!(m > 0.0) || fz < 0) {
                 s0 = s1 = 0;
             } else {
@@ -98,8 +79,8 @@ __global__ __launch_bounds__(JN_ROW_THREADS) void join_span_kernel(T2Join p, dou
         ss += v * v;
         pk = fmax(pk, fabs(v));
     }
-    ss = jn_block_reduce(ss, JnSum(), redd);
-    pk = jn_block_reduce(pk, JnMaxD(), redd);
+    ss = t2m_block_reduce<JN_ROW_WAVES>(ss, T2mSum(), redd);
+    pk = t2m_block_reduce<JN_ROW_WAVES>(pk, T2mFmax(), redd);
     if (tid == 0) {
         p.s0[b] = (int32_t)s0;
         p.len[b] = (int32_t)(s1 - s0);
@@ -117,24 +98,24 @@ __device__ __forceinline__ double jn_gain(const T2Join& p, int b, double rms_doc
 }
 
 __global__ __launch_bounds__(JN_ROW_THREADS) void join_plan_kernel(T2Join p) {
-    __shared__ double redd[JN_ROW_THREADS / 64];
-    __shared__ long long redi[JN_ROW_THREADS / 64];
+    __shared__ double redd[JN_ROW_WAVES];
+    __shared__ long long redi[JN_ROW_WAVES];
     __shared__ long long sc[2][JN_ROW_THREADS];
     const int tid = threadIdx.x, B = p.B;
     double S = 0.0;
     long long L = 0, bad = 0;
     for (int b = tid; b < B; b += JN_ROW_THREADS) {
-        if (!jn_row_ok(p, b) || p.pause[b] < 0) bad = 1;
+        if (!t2m_count_ok(p.n[b], p.n_max) || p.pause[b] < 0) bad = 1;
         S += p.stat[2 * (int64_t)b];
         L += p.len[b];
     }
-    S = jn_block_reduce(S, JnSum(), redd);
-    L = jn_block_reduce(L, JnSum(), redi);
-    bad = jn_block_reduce(bad, JnMaxI(), redi);
+    S = t2m_block_reduce<JN_ROW_WAVES>(S, T2mSum(), redd);
+    L = t2m_block_reduce<JN_ROW_WAVES>(L, T2mSum(), redi);
+    bad = t2m_block_reduce<JN_ROW_WAVES>(bad, T2mMax(), redi);
     const double rms_doc = L > 0 ? sqrt(S / (double)L) : 0.0;
     double pk = 0.0;
     for (int b = tid; b < B; b += JN_ROW_THREADS) pk = fmax(pk, jn_gain(p, b, rms_doc) * p.stat[2 * (int64_t)b + 1]);
-    pk = jn_block_reduce(pk, JnMaxD(), redd);
+    pk = t2m_block_reduce<JN_ROW_WAVES>(pk, T2mFmax(), redd);
     const bool limit = p.ceiling > 0.0 && pk > p.ceiling;
     const double scale = limit ? p.ceiling / pk : 1.0;
     for (int b = tid; b < B; b += JN_ROW_THREADS) {

@@ -23,12 +23,12 @@
 //   gate    one 256-thread workgroup per row over E: the blocks, the two gates, the loudness, the gain.
 //   scale   grid (chunks, B): y = x * gain, zeros behind n.  Only with y != NULL.
 #include <math.h>
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define LD_THREADS 256
+#define LD_WAVES (LD_THREADS / 64)
 #define LD_CHUNK 32
 #define LD_PASS (LD_THREADS * LD_CHUNK)
 #define LD_STEPS 8                 // log2(LD_THREADS)
@@ -39,23 +39,6 @@ namespace {
 #define LS_CHUNK 1024
 
 struct LdTrans { double m[LD_STEPS][16]; };     // m[k] = T^(32 * 2^k), row-major, over the state (s1, s2 of the shelf, s1, s2 of the high-pass)
-
-template <typename T, typename Op>
-__device__ __forceinline__ T ld_block_reduce(T v, Op op, T* red) {      // red: LD_THREADS / 64 values; every thread gets the result
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    T s = red[0];
-    for (int i = 1; i < LD_THREADS / 64; ++i) s = op(s, red[i]);
-    return s;
-}
-struct LdSum { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
-struct LdMaxD { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
-
-__device__ __forceinline__ bool ld_row_ok(const T2Loudness& p, int b) { const int n = p.n[b]; return n >= 0 && n <= p.n_max; }
 
 struct LdCoef { double b10, b11, b12, a11, a12, b20, b21, b22, a21, a22; };
 
@@ -77,7 +60,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_filter_kernel(T2Loudness p, L
     float* xs = reinterpret_cast<float*>(sc + 2 * LD_THREADS * 4);      // [LD_ROWS]
     __shared__ double open[2];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (!ld_row_ok(p, b)) return;
+    if (!t2m_count_ok(p.n[b], p.n_max)) return;
     const int64_t n = p.n[b], H = p.H;
     const float* x = p.x + (int64_t)b * p.ldx;
     double* E = p.E + (int64_t)b * p.lde;
@@ -162,7 +145,7 @@ __global__ __launch_bounds__(256) void loud_peak_kernel(T2Loudness p) {
     extern __shared__ __attribute__((aligned(16))) float lp_xs[];
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x;
-    if (!ld_row_ok(p, b)) return;
+    if (!t2m_count_ok(p.n[b], p.n_max)) return;
     const int64_t n = p.n[b], tile0 = (int64_t)blockIdx.x * LP_TILE;
     if (tile0 >= n) return;                                             // (uniform) behind the row: nothing is read
     const int K = p.K;
@@ -197,11 +180,11 @@ __global__ __launch_bounds__(256) void loud_peak_kernel(T2Loudness p) {
 }
 
 __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(T2Loudness p) {
-    __shared__ double redd[LD_THREADS / 64];
-    __shared__ long long redi[LD_THREADS / 64];
+    __shared__ double redd[LD_WAVES];
+    __shared__ long long redi[LD_WAVES];
     const int b = blockIdx.x, tid = threadIdx.x;
     double* st = p.stat + (int64_t)b * T2_LOUD_NSTAT;
-    if (!ld_row_ok(p, b)) {
+    if (!t2m_count_ok(p.n[b], p.n_max)) {
         if (tid == 0) st[9] = -1.0;
         return;
     }
@@ -225,9 +208,9 @@ __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(T2Loudness p) {
         zmax = fmax(zmax, zj);
         if (zj > p.abs_gate) { sum_a += zj; ++cnt_a; }
     }
-    sum_a = ld_block_reduce(sum_a, LdSum(), redd);
-    cnt_a = ld_block_reduce(cnt_a, LdSum(), redi);
-    zmax = ld_block_reduce(zmax, LdMaxD(), redd);
+    sum_a = t2m_block_reduce<LD_WAVES>(sum_a, T2mSum(), redd);
+    cnt_a = t2m_block_reduce<LD_WAVES>(cnt_a, T2mSum(), redi);
+    zmax = t2m_block_reduce<LD_WAVES>(zmax, T2mFmax(), redd);
     const double nan = __builtin_nan("");
     double lufs = nan, rel_lufs = nan, g = 1.0;
     long long cnt_r = 0;
@@ -241,8 +224,8 @@ __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(T2Loudness p) {
             const double zj = z(j);
             if (zj > p.abs_gate && zj > thr) { sum_r += zj; ++cnt_r; }
         }
-        sum_r = ld_block_reduce(sum_r, LdSum(), redd);
-        cnt_r = ld_block_reduce(cnt_r, LdSum(), redi);
+        sum_r = t2m_block_reduce<LD_WAVES>(sum_r, T2mSum(), redd);
+        cnt_r = t2m_block_reduce<LD_WAVES>(cnt_r, T2mSum(), redi);
         lufs = -0.691 + 10.0 * log10(sum_r / (double)cnt_r);            // (cnt_r >= 1: the largest block is above a tenth of the mean)
         rel_lufs = -0.691 + 10.0 * log10(thr);
         if (p.y) {
@@ -266,7 +249,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(T2Loudness p) {
 
 __global__ __launch_bounds__(256) void loud_scale_kernel(T2Loudness p) {
     const int b = blockIdx.y;
-    if (!ld_row_ok(p, b)) return;
+    if (!t2m_count_ok(p.n[b], p.n_max)) return;
     const int64_t n = p.n[b];
     const float gain = p.gain[b];
     const float* x = p.x + (int64_t)b * p.ldx;

@@ -11,36 +11,17 @@
 //     loaded BEFORE the barrier of frame t, so no global load sits between a barrier and the LDS reads that depend on it.  The back
 //     pointers go to global memory (uint16), thread 0 walks them back (T dependent loads), then the block forms f0 and aper.
 //   t2_f0_path_stats: ONE workgroup per pair strides over the path's cells; counts and fp64 sums by wave shuffles, then in wave order.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define PV_THREADS 256
 #define PV_WAVES (PV_THREADS / T2_WAVE)
 #define PV_NONE 0x7fffffff
 #define PV_CHUNK 8
 
+// (value, index) minimum, ties to the lower index
 __device__ __forceinline__ bool pv_better(double ov, int oi, double mv, int mi) { return ov < mv || (ov == mv && oi < mi); }
-
-// (value, index) minimum over the block's four wave partials, in wave order
-__device__ __forceinline__ void pv_combine(const double* v, const int* i, double* mv_out, int* mi_out) {
-    double mv = v[0];
-    int mi = i[0];
-#pragma unroll
-    for (int r = 1; r < PV_WAVES; ++r)
-        if (pv_better(v[r], i[r], mv, mi)) { mv = v[r]; mi = i[r]; }
-    *mv_out = mv; *mi_out = mi;
-}
-
-__device__ __forceinline__ void pv_wave_min(double& mv, int& mi) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const double ov = __shfl_xor(mv, s, T2_WAVE);
-        const int oi = __shfl_xor(mi, s, T2_WAVE);
-        if (pv_better(ov, oi, mv, mi)) { mv = ov; mi = oi; }
-    }
-}
 
 // MAXC = the voiced targets one thread can own: N <= MAXC * 256.  dynamic LDS: D[2][N+1] doubles, then lw[N]
 template <int MAXC>
@@ -152,14 +133,14 @@ __global__ __launch_bounds__(PV_THREADS) void pitch_viterbi_kernel(T2PitchViterb
                 if (cand < mv) { mv = cand; mi = k; }    // (k ascends with c: a later one wins only when strictly smaller)
             }
         }
-        pv_wave_min(mv, mi);
+        t2m_wave_pick(mv, mi, pv_better);
         if (lane == 0) { wv[pc][w] = mv; wi[pc][w] = mi; }
         if (tid == PV_THREADS - 1) {                     // target U: U first, then the voiced predecessors ascending
             if (t == 0) {
                 Dc[N] = p.u;
             } else {
                 double vv; int vi;
-                pv_combine(wv[pp], wi[pp], &vv, &vi);
+                t2m_combine_picks<PV_WAVES>(wv[pp], wi[pp], vv, vi, pv_better);
                 double best = Dp[N] + 0.0;
                 int arg = N;
                 if (vv < best && vi < N) { best = vv; arg = vi; }
@@ -180,13 +161,13 @@ __global__ __launch_bounds__(PV_THREADS) void pitch_viterbi_kernel(T2PitchViterb
             const double d = Dl[k];
             if (d < mv) { mv = d; mi = k; }
         }
-        pv_wave_min(mv, mi);
+        t2m_wave_pick(mv, mi, pv_better);
         if (lane == 0) { wv[pl ^ 1][w] = mv; wi[pl ^ 1][w] = mi; }       // (the other parity: last read in front of the last barrier)
     }
     __syncthreads();
     if (tid == 0) {
         double vv; int vi;
-        pv_combine(wv[pl ^ 1], wi[pl ^ 1], &vv, &vi);
+        t2m_combine_picks<PV_WAVES>(wv[pl ^ 1], wi[pl ^ 1], vv, vi, pv_better);
         int s = vi < N ? vi : N;
         double best = s < N ? vv : Dl[N];
         if (Dl[N] < best) { best = Dl[N]; s = N; }
@@ -214,14 +195,14 @@ __global__ __launch_bounds__(PV_THREADS) void pitch_viterbi_kernel(T2PitchViterb
 }
 
 __device__ __forceinline__ bool f0_valid(long t, int T, int hop, int S, long n) {
-    const long s0 = t * hop - S / 2;
-    return t >= 0 && t < T && s0 >= 0 && s0 + S <= n;
+    long s0;
+    return t >= 0 && t < T && t2m_frame_valid(t, hop, S, n, &s0);
 }
 
 __global__ __launch_bounds__(PV_THREADS) void f0_path_stats_kernel(T2F0PathStats p) {
     __shared__ double redd[7][PV_WAVES];
     __shared__ int redn[4][PV_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(p.path_len[b], 0), p.P);
     double* out = p.out + (long)b * T2_F0_NSTAT;
     if (n == 0) {                                        // (uniform) nothing is read
@@ -251,29 +232,10 @@ __global__ __launch_bounds__(PV_THREADS) void f0_path_stats_kernel(T2F0PathStats
             ++cnt[3];
         }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) cnt[q] += __shfl_xor(cnt[q], m, T2_WAVE);
-        if (lane == 0) redn[q][w] = cnt[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        const double v = t2_wave_sum_d(s[q]);
-        if (lane == 0) redd[q][w] = v;
-    }
-    __syncthreads();
+    t2m_sums_to_thread0(cnt, s, redn, redd);
     if (tid == 0) {
-        for (int q = 0; q < 4; ++q) {
-            int m = 0;
-            for (int r = 0; r < PV_WAVES; ++r) m += redn[q][r];
-            out[q] = (double)m;
-        }
-        for (int q = 0; q < 7; ++q) {
-            double m = 0.0;
-            for (int r = 0; r < PV_WAVES; ++r) m += redd[q][r];
-            out[4 + q] = m;
-        }
+        for (int q = 0; q < 4; ++q) out[q] = (double)cnt[q];
+        for (int q = 0; q < 7; ++q) out[4 + q] = s[q];
         out[11] = 0.0;
     }
 }

@@ -14,19 +14,15 @@
 //   t2_voice_quality: ONE workgroup per (frame, utterance), the same span in LDS; one thread per (cycle, lag) pair sums its product
 //     left to right, the window energies are a running sum, the picks and the frame's means short serial walks (see vq_kernel).
 //   t2_corpus_stats: ONE workgroup per utterance; counts and fp64 sums per thread, a shuffle tree, then the waves in order.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define PR_THREADS 256
 #define PR_WAVES (PR_THREADS / T2_WAVE)
 
-__device__ __forceinline__ bool yin_valid(long t, int hop, int S, long nb, long* s0_out) {
-    const long s0 = t * hop - S / 2;
-    *s0_out = s0;
-    return s0 >= 0 && s0 + S <= nb;
-}
+// (value, index) minimum, ties to the lower index
+__device__ __forceinline__ bool yin_better(float ov, int oi, float mv, int mi) { return ov < mv || (ov == mv && oi < mi); }
 
 __global__ __launch_bounds__(PR_THREADS) void yin_kernel(T2Yin p, int T) {
     extern __shared__ float lds[];
@@ -41,7 +37,7 @@ __global__ __launch_bounds__(PR_THREADS) void yin_kernel(T2Yin p, int T) {
     long nb = p.n[b];
     nb = nb < 0 ? 0 : (nb > p.n_max ? p.n_max : nb);
     long s0;
-    if (!yin_valid(t, p.hop, S, nb, &s0)) {           // (uniform over the workgroup) nothing is read
+    if (!t2m_frame_valid(t, p.hop, S, nb, &s0)) {           // (uniform over the workgroup) nothing is read
         if (tid == 0) { p.f0[o] = 0.f; p.aper[o] = 1.f; p.power[o] = 0.f; }
         if (p.cmnd) for (int k = tid; k < NT; k += PR_THREADS) p.cmnd[o * NT + k] = 1.f;
         return;
@@ -120,20 +116,13 @@ __global__ __launch_bounds__(PR_THREADS) void yin_kernel(T2Yin p, int T) {
         if (v < p.thr && c < first) first = c;
         if (v < mv) { mv = v; mi = c; }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const int of = __shfl_xor(first, s, T2_WAVE), oi = __shfl_xor(mi, s, T2_WAVE);
-        const float ov = __shfl_xor(mv, s, T2_WAVE);
-        first = min(first, of);
-        if (ov < mv || (ov == mv && oi < mi)) { mv = ov; mi = oi; }
-    }
+    first = t2m_wave_reduce(first, T2mMin());
+    t2m_wave_pick(mv, mi, yin_better);
     if (lane == 0) { red_f[w] = first; red_v[w] = mv; red_i[w] = mi; }
     __syncthreads();
     if (tid == 0) {
-        for (int r = 1; r < PR_WAVES; ++r) {
-            first = min(first, red_f[r]);
-            if (red_v[r] < mv || (red_v[r] == mv && red_i[r] < mi)) { mv = red_v[r]; mi = red_i[r]; }
-        }
+        for (int r = 1; r < PR_WAVES; ++r) first = min(first, red_f[r]);
+        t2m_combine_picks<PR_WAVES>(red_v, red_i, mv, mi, yin_better);
         int c = mi;
         if (first != 0x7fffffff) {
             c = first;
@@ -156,42 +145,31 @@ __global__ __launch_bounds__(PR_THREADS) void prosody_stats_kernel(T2ProsodyStat
     __shared__ float v[T2_PROSODY_MAX_T];              // f0 of the voiced frames, 0 elsewhere
     __shared__ double redd[3][PR_WAVES];
     __shared__ int redn[2][PR_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, T = p.T;
+    const int b = blockIdx.x, tid = threadIdx.x, T = p.T;
     const long nb = p.n[b] < 0 ? 0 : p.n[b];
     const float* f0 = p.f0 + (long)b * T;
     const float* ap = p.aper + (long)b * T;
     const float* pw = p.power + (long)b * T;
-    int n_valid = 0, n_voiced = 0;
-    double s_lf = 0.0, s_db = 0.0, s_ap = 0.0;
+    int cnt[2] = {0, 0};                               // valid, voiced
+    double m[3] = {0.0, 0.0, 0.0};                     // log f0, 10 log10 power, aperiodicity over the voiced frames
     for (int t = tid; t < T; t += PR_THREADS) {
         long s0;
-        const bool valid = yin_valid(t, p.hop, p.S, nb, &s0);
+        const bool valid = t2m_frame_valid(t, p.hop, p.S, nb, &s0);
         const float f = valid ? f0[t] : 0.f;
         const bool voiced = f > 0.f;
         v[t] = voiced ? f : 0.f;
-        n_valid += valid;
+        cnt[0] += valid;
         if (voiced) {
-            ++n_voiced;
-            s_lf += (double)logf(f);
-            s_db += (double)(10.f * log10f(pw[t]));
-            s_ap += (double)ap[t];
+            ++cnt[1];
+            m[0] += (double)logf(f);
+            m[1] += (double)(10.f * log10f(pw[t]));
+            m[2] += (double)ap[t];
         }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        n_valid += __shfl_xor(n_valid, s, T2_WAVE);
-        n_voiced += __shfl_xor(n_voiced, s, T2_WAVE);
-    }
-    s_lf = t2_wave_sum_d(s_lf); s_db = t2_wave_sum_d(s_db); s_ap = t2_wave_sum_d(s_ap);
-    if (lane == 0) { redn[0][w] = n_valid; redn[1][w] = n_voiced; redd[0][w] = s_lf; redd[1][w] = s_db; redd[2][w] = s_ap; }
-    __syncthreads();
-    n_valid = 0; n_voiced = 0;
-    for (int r = 0; r < PR_WAVES; ++r) { n_valid += redn[0][r]; n_voiced += redn[1][r]; }
+    t2m_sums_to_thread0(cnt, m, redn, redd);
+    const int n_valid = cnt[0], n_voiced = cnt[1];     // (in every thread)
     float* out = p.out + (long)b * T2_PROSODY_NSTAT;
     if (tid == 0) {
-        double m[3] = {0.0, 0.0, 0.0};
-        for (int q = 0; q < 3; ++q)
-            for (int r = 0; r < PR_WAVES; ++r) m[q] += redd[q][r];
         const float nan = __builtin_nanf("");
         out[0] = (float)n_valid; out[1] = (float)n_voiced;
         out[2] = n_voiced ? (float)(m[0] / n_voiced) : nan;
@@ -234,7 +212,7 @@ __global__ __launch_bounds__(PR_THREADS) void vq_kernel(T2VoiceQuality p, int T,
     nb = nb < 0 ? 0 : (nb > p.n_max ? p.n_max : nb);
     long s0;
     int K = 0, L = 0, d = 0;
-    if (yin_valid(t, p.hop, S, nb, &s0)) {             // (uniform over the workgroup)
+    if (t2m_frame_valid(t, p.hop, S, nb, &s0)) {             // (uniform over the workgroup)
         const float f = p.f0[o];
         if (f > 0.f) {
             const float q = fminf(fmaxf((float)p.sr / f, (float)p.tau_min), (float)(p.tau_max - 1));
@@ -339,14 +317,14 @@ __global__ __launch_bounds__(PR_THREADS) void vq_kernel(T2VoiceQuality p, int T,
 __global__ __launch_bounds__(PR_THREADS) void corpus_stats_kernel(T2CorpusStats p) {
     __shared__ double redd[6][PR_WAVES];
     __shared__ int redn[4][PR_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, T = p.T;
+    const int b = blockIdx.x, tid = threadIdx.x, T = p.T;
     const long nb = p.n[b] < 0 ? 0 : p.n[b];
     const long r0 = (long)b * T;
     int cnt[4] = {0, 0, 0, 0};                         // valid, voiced, measured, loud
     double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // f0, jitter, shimmer, nhr, hnr_db, 10 log10 power
     for (int t = tid; t < T; t += PR_THREADS) {
         long s0;
-        if (!yin_valid(t, p.hop, p.S, nb, &s0)) continue;          // an invalid frame is not read
+        if (!t2m_frame_valid(t, p.hop, p.S, nb, &s0)) continue;          // an invalid frame is not read
         ++cnt[0];
         const float f = p.f0[r0 + t], pw = p.power[r0 + t];
         if (f > 0.f) { ++cnt[1]; s[0] += (double)f; }
@@ -357,32 +335,40 @@ __global__ __launch_bounds__(PR_THREADS) void corpus_stats_kernel(T2CorpusStats 
         }
         if (pw > p.power_floor) { ++cnt[3]; s[5] += (double)(10.f * log10f(pw)); }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt[q] += __shfl_xor(cnt[q], o, T2_WAVE);
-        if (lane == 0) redn[q][w] = cnt[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        s[q] = t2_wave_sum_d(s[q]);
-        if (lane == 0) redd[q][w] = s[q];
-    }
-    __syncthreads();
+    t2m_sums_to_thread0(cnt, s, redn, redd);
     if (tid == 0) {
-        int n4[4] = {0, 0, 0, 0};
-        double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int r = 0; r < PR_WAVES; ++r) {
-            for (int q = 0; q < 4; ++q) n4[q] += redn[q][r];
-            for (int q = 0; q < 6; ++q) m[q] += redd[q][r];
-        }
         float* out = p.out + (long)b * T2_CORPUS_NSTAT;
-        for (int q = 0; q < 4; ++q) out[q] = (float)n4[q];
-        out[4] = n4[1] ? (float)(m[0] / n4[1]) : 0.f;
-        for (int q = 1; q < 5; ++q) out[4 + q] = n4[2] ? (float)(m[q] / n4[2]) : 0.f;
-        out[9] = n4[3] ? (float)(m[5] / n4[3]) : 0.f;
+        for (int q = 0; q < 4; ++q) out[q] = (float)cnt[q];
+        out[4] = cnt[1] ? (float)(s[0] / cnt[1]) : 0.f;
+        for (int q = 1; q < 5; ++q) out[4 + q] = cnt[2] ? (float)(s[q] / cnt[2]) : 0.f;
+        out[9] = cnt[3] ? (float)(s[5] / cnt[3]) : 0.f;
         out[10] = 0.f; out[11] = 0.f;
     }
+}
+
+// The frame geometry t2_yin and t2_voice_quality share (G: T2Yin or T2VoiceQuality); *T_out = the frames of a padded row.
+template <typename G>
+int pr_geometry(const char* name, const G* a, int64_t* T_out) {
+#define PR_REQUIRE(cond, text)                                                \
+    do {                                                                      \
+        if (!(cond)) {                                                        \
+            char msg[96];                                                     \
+            snprintf(msg, sizeof(msg), "%s: %s", name, text);                 \
+            T2_REQUIRE(false, msg);                                           \
+        }                                                                     \
+    } while (0)
+    PR_REQUIRE(a->B >= 1 && a->B <= 65535, "B outside 1 .. 65535");
+    PR_REQUIRE(a->n_max >= 0, "n_max < 0");
+    PR_REQUIRE(a->hop >= 1 && a->sr >= 1, "need hop, sr >= 1");
+    PR_REQUIRE(a->W >= 16, "W below 16");
+    PR_REQUIRE(a->tau_min >= 2, "tau_min below 2");
+    PR_REQUIRE(a->tau_max > a->tau_min + 1, "need tau_max > tau_min + 1");
+    PR_REQUIRE((int64_t)a->W + a->tau_max <= T2_YIN_MAX_SPAN, "W + tau_max above T2_YIN_MAX_SPAN (4096)");
+    PR_REQUIRE(a->ld_wav >= a->n_max, "ld_wav < n_max");
+    *T_out = 1 + a->n_max / a->hop;
+    PR_REQUIRE(*T_out <= 0x7fffffff, "more than 2^31 - 1 frames");
+#undef PR_REQUIRE
+    return T2_OK;
 }
 
 }  // namespace
@@ -390,16 +376,8 @@ __global__ __launch_bounds__(PR_THREADS) void corpus_stats_kernel(T2CorpusStats 
 extern "C" int t2_voice_quality(const T2VoiceQuality* a, void* stream) {
     (void)hipGetLastError();
     T2_REQUIRE(a && a->wav && a->n && a->f0 && a->jitter && a->shimmer && a->nhr && a->hnr_db && a->cycles, "t2_voice_quality: null");
-    T2_REQUIRE(a->B >= 1 && a->B <= 65535, "t2_voice_quality: B outside 1 .. 65535");
-    T2_REQUIRE(a->n_max >= 0, "t2_voice_quality: n_max < 0");
-    T2_REQUIRE(a->hop >= 1 && a->sr >= 1, "t2_voice_quality: need hop, sr >= 1");
-    T2_REQUIRE(a->W >= 16, "t2_voice_quality: W below 16");
-    T2_REQUIRE(a->tau_min >= 2, "t2_voice_quality: tau_min below 2");
-    T2_REQUIRE(a->tau_max > a->tau_min + 1, "t2_voice_quality: need tau_max > tau_min + 1");
-    T2_REQUIRE((int64_t)a->W + a->tau_max <= T2_YIN_MAX_SPAN, "t2_voice_quality: W + tau_max above T2_YIN_MAX_SPAN (4096)");
-    T2_REQUIRE(a->ld_wav >= a->n_max, "t2_voice_quality: ld_wav < n_max");
-    const int64_t T = 1 + a->n_max / a->hop;
-    T2_REQUIRE(T <= 0x7fffffff, "t2_voice_quality: more than 2^31 - 1 frames");
+    int64_t T;
+    T2_TRY(pr_geometry("t2_voice_quality", a, &T));
     // pairs of one frame: K <= S / L cycles of 2 d + 1 <= L / 4 + 3 lags for L >= 16 (<= S/4 + 3 S/16), 32 cycles of 5 lags below
     const int S = a->W + a->tau_max, cap = S / 2 + 160;
     const size_t bytes = ((size_t)S + 2 * (size_t)cap) * sizeof(float);
@@ -422,16 +400,8 @@ extern "C" int t2_corpus_stats(const T2CorpusStats* a, void* stream) {
 extern "C" int t2_yin(const T2Yin* a, void* stream) {
     (void)hipGetLastError();   // drop stale sticky errors of other HIP users in this thread: only OUR launches are checked
     T2_REQUIRE(a && a->wav && a->n && a->f0 && a->aper && a->power, "t2_yin: null");
-    T2_REQUIRE(a->B >= 1 && a->B <= 65535, "t2_yin: B outside 1 .. 65535");
-    T2_REQUIRE(a->n_max >= 0, "t2_yin: n_max < 0");
-    T2_REQUIRE(a->hop >= 1 && a->sr >= 1, "t2_yin: need hop, sr >= 1");
-    T2_REQUIRE(a->W >= 16, "t2_yin: W below 16");
-    T2_REQUIRE(a->tau_min >= 2, "t2_yin: tau_min below 2");
-    T2_REQUIRE(a->tau_max > a->tau_min + 1, "t2_yin: need tau_max > tau_min + 1");
-    T2_REQUIRE((int64_t)a->W + a->tau_max <= T2_YIN_MAX_SPAN, "t2_yin: W + tau_max above T2_YIN_MAX_SPAN (4096)");
-    T2_REQUIRE(a->ld_wav >= a->n_max, "t2_yin: ld_wav < n_max");
-    const int64_t T = 1 + a->n_max / a->hop;
-    T2_REQUIRE(T <= 0x7fffffff, "t2_yin: more than 2^31 - 1 frames");
+    int64_t T;
+    T2_TRY(pr_geometry("t2_yin", a, &T));
     const size_t bytes = ((size_t)a->W + a->tau_max + (size_t)PR_WAVES * (a->tau_max + 1)) * sizeof(float);
     T2_REQUIRE(t2_allow_lds(yin_kernel, bytes), "t2_yin: LDS request refused");
     hipLaunchKernelGGL(yin_kernel, dim3((unsigned)T, (unsigned)a->B), dim3(PR_THREADS), bytes, ST, *a, (int)T);

@@ -13,11 +13,10 @@
 //   sweep   all threads gather: a binary search for the first grain that can reach sample i (r_j > i - gmax, gmax the row's largest
 //           mark spacing), then the grains in ascending j up to r_j >= i + gmax.  Products and sums by __fmul_rn / __fadd_rn, nothing
 //           fused, one IEEE division.  a, r and kmap are read back from global memory behind the barrier that ends chain 2.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define PS_THREADS 1024
 #define PS_PIECE 16384                                                    // samples of one staged piece (64 KB)
 #define PS_LAGS (PS_PIECE / 16 + 2)                                       // frames under one piece at the smallest hop, 16
@@ -31,7 +30,7 @@ __global__ __launch_bounds__(PS_THREADS) void psola_kernel(T2Psola p) {
     __shared__ int st[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = p.n[b];
-    if (n < 0 || n > p.n_max) {                                           // refused, not clamped: the row is neither read nor written
+    if (!t2m_count_ok(n, p.n_max)) {                                      // refused, not clamped: the row is neither read nor written
         if (tid == 0) p.n_marks[b] = -1;
         return;
     }
@@ -90,12 +89,7 @@ __global__ __launch_bounds__(PS_THREADS) void psola_kernel(T2Psola p) {
                             const float v = xs[i - base];
                             if (bi == INT_MAX || v > bv) { bv = v; bi = i; }
                         }
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) {
-                            const float ov = __shfl_xor(bv, o, 64);
-                            const int oi = __shfl_xor(bi, o, 64);
-                            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-                        }
+                        t2m_wave_pick(bv, bi, [](float ov, int oi, float v, int i) { return ov > v || (ov == v && oi < i); });
                         m = __builtin_amdgcn_readfirstlane(bi);           // (lane 0 scanned lo itself: an index inside the window)
                     }
                 }

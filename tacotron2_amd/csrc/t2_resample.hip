@@ -14,11 +14,10 @@
 //   guarded global loads (resample_kernel<.., false>).
 //   m D is formed in 64 bits (ten minutes at 48 kHz with D = 320 pass 2^31); i0 and p of an output are one 64-bit division each.
 //   Blocks at or behind n_out[b] only write zeros, up to ldy: the log-mel pass wants each row zero-filled behind its utterance.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define RS_THREADS 256
 #define RS_PER_THREAD 4
 #define RS_BLOCK (RS_THREADS * RS_PER_THREAD)

@@ -15,27 +15,14 @@
 //           2 (D - |d|) + (d < 0), so the smaller |d| wins, then the negative one.  Every thread holds p_m afterwards.
 //   sweep   y[j] = w[Hs + i] x~[p_m + i] + w[i] x~[p_{m+1} - Hs + i] for j = m Hs + i < n_out, two products and one sum in fp32, nothing
 //           fused; zeros behind n_out up to ldy.  pos is read back from global memory behind the barrier that ends the chain.
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
 #define SR_THREADS 1024
+#define SR_WAVES (SR_THREADS / 64)
 #define SR_T_LEN (T2_STRETCH_MAX_N + 8)                                   // the template, zero padded to whole chunks of 8
 #define SR_R_LEN (T2_STRETCH_MAX_N + 2 * T2_STRETCH_MAX_D + 32)          // the region and the zeros a thread's last reads run into
-
-__device__ __forceinline__ long long sr_block_max(long long v, long long* red) {     // every thread gets the result
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const long long u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    long long s = red[0];
-#pragma unroll
-    for (int i = 1; i < SR_THREADS / 64; ++i) s = red[i] > s ? red[i] : s;
-    return s;
-}
 
 __device__ __forceinline__ short sr_quant(const float* x, int64_t i, int64_t n, double peak) {
     if (i < 0 || i >= n || !(peak > 0.0)) return 0;
@@ -56,10 +43,10 @@ __global__ __launch_bounds__(SR_THREADS) void stretch_kernel(T2Stretch p) {
     __shared__ __attribute__((aligned(16))) short T[SR_T_LEN];
     __shared__ __attribute__((aligned(16))) short R[SR_R_LEN];
     __shared__ int part[4 * SR_THREADS];
-    __shared__ long long red[SR_THREADS / 64];
+    __shared__ long long red[SR_WAVES];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nb = p.n[b];
-    if (nb < 0 || nb > p.n_max) {                                         // refused, not clamped: the row is neither read nor written
+    if (!t2m_count_ok(nb, p.n_max)) {                                     // refused, not clamped: the row is neither read nor written
         if (tid == 0) p.n_out[b] = -1;
         return;
     }
@@ -75,7 +62,8 @@ __global__ __launch_bounds__(SR_THREADS) void stretch_kernel(T2Stretch p) {
     // ---- peak ----
     float pk = 0.f;
     for (int64_t i = tid; i < n; i += SR_THREADS) pk = fmaxf(pk, fabsf(x[i]));
-    const double peak = (double)__builtin_bit_cast(float, (int)sr_block_max((long long)__builtin_bit_cast(int, pk), red));
+    const double peak =
+        (double)__builtin_bit_cast(float, (int)t2m_block_reduce<SR_WAVES, SR_WAVES>((long long)__builtin_bit_cast(int, pk), T2mMax(), red));
     // (|x| >= 0: the bit patterns of non-negative floats order as integers)
 
     // ---- chain ----
@@ -117,7 +105,7 @@ __global__ __launch_bounds__(SR_THREADS) void stretch_kernel(T2Stretch p) {
             const long long k2 = (long long)sc * 4294967296LL + rank;
             key = k2 > key ? k2 : key;
         }
-        key = sr_block_max(key, red);
+        key = t2m_block_reduce<SR_WAVES, SR_WAVES>(key, T2mMax(), red);
         const int rank = (int)(key & 0xffffffffLL);
         const int ad = D - rank / 2;
         prev = a + ((rank & 1) ? -ad : ad);

@@ -15,13 +15,11 @@
 //   5. the per-utterance sums: thread-strided partials, a wave butterfly, the four wave partials in order.
 // q and e stay in LDS as doubles between the passes: 2 * 8 * T + 4 * (L + 1) bytes = 80 KB at both caps, plus 4.8 KB of small
 // arrays (reduction partials, chunk totals, chunk voicing, voicing bits).
-#include "t2_common.hpp"
+#include "t2_measure.hpp"
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
-constexpr int kRed = 32;        // doubles: 4 waves x 8 partial sums
+constexpr int kRed = 32;        // doubles: 8 sums x 4 wave partials
 constexpr int kChunks = 256;    // one chunk per thread
 
 __host__ __device__ inline size_t variance_lds_bytes(int T, int L) {
@@ -30,16 +28,10 @@ __host__ __device__ inline size_t variance_lds_bytes(int T, int L) {
            4 * (size_t)(L + 1);
 }
 
-// the sum of v over the block in a fixed order, to thread 0 (other threads get a partial); slot 0 .. 7 of red, no barrier inside
-__device__ __forceinline__ void wave_partial(double v, double* red, int slot, int lane, int w) {
-    v = t2_wave_sum_d(v);
-    if (lane == 0) red[w * 8 + slot] = v;
-}
-
 __global__ __launch_bounds__(256) void char_variance_kernel(T2CharVariance a) {
     extern __shared__ double lds[];
     const int T = a.T, L = a.L, M = a.M;
-    double* red = lds;
+    double (*red)[4] = reinterpret_cast<double (*)[4]>(lds);
     long long* part = reinterpret_cast<long long*>(lds + kRed);
     int* edge = reinterpret_cast<int*>(lds + kRed + kChunks);                 // [0, 256) first voiced of a chunk, [256, 512) last
     unsigned long long* vbits = reinterpret_cast<unsigned long long*>(lds + kRed + kChunks + kChunks);
@@ -177,27 +169,19 @@ __global__ __launch_bounds__(256) void char_variance_kernel(T2CharVariance a) {
     }
 
     // 5. the utterance's sums
-    double nvoiced = 0.0, sp = 0.0, sp2 = 0.0, sq = 0.0, sq2 = 0.0, se = 0.0, se2 = 0.0;
+    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, (double)unvoiced_chars};    // voiced, p, p^2, q, q^2, e, e^2, unvoiced chars
     for (int t = tid; t < Fb; t += 256) {
         const double qt = q[t], et = e[t];
-        if (VOICED(t)) { nvoiced += 1.0; sp += qt; sp2 += qt * qt; }
-        sq += qt; sq2 += qt * qt;
-        se += et; se2 += et * et;
+        if (VOICED(t)) { s[0] += 1.0; s[1] += qt; s[2] += qt * qt; }
+        s[3] += qt; s[4] += qt * qt;
+        s[5] += et; s[6] += et * et;
     }
-    wave_partial(nvoiced, red, 0, lane, w);
-    wave_partial(sp, red, 1, lane, w);
-    wave_partial(sp2, red, 2, lane, w);
-    wave_partial(sq, red, 3, lane, w);
-    wave_partial(sq2, red, 4, lane, w);
-    wave_partial(se, red, 5, lane, w);
-    wave_partial(se2, red, 6, lane, w);
-    wave_partial((double)unvoiced_chars, red, 7, lane, w);
-    __syncthreads();
-    if (tid < 8) {
-        const double v = ((red[tid] + red[8 + tid]) + red[16 + tid]) + red[24 + tid];
-        stats[tid < 7 ? 1 + tid : 9] = v;
+    t2m_sums_to_thread0(s, red);
+    if (tid == 0) {
+        stats[0] = (double)Fb;
+        for (int k = 0; k < 7; ++k) stats[1 + k] = s[k];
+        stats[8] = consistent; stats[9] = s[7];
     }
-    if (tid == 8) { stats[0] = (double)Fb; stats[8] = consistent; }
 #undef VOICED
 }
 

@@ -1716,7 +1716,7 @@ class Engine:
     # =============================================================================================
     # per-character durations from alignments (include/tacotron2_amd.h: t2_align_durations)
     # =============================================================================================
-    ALIGN_MAX_L = 4096          # T2_ALIGN_MAX_L: two fp64 rows of the search in LDS
+    ALIGN_MAX_L = _lib.K["ALIGN_MAX_L"]        # two fp64 rows of the search in LDS
     DURATION_MODES = {"argmax": 0, "monotonic": 1}
 
     def durations(self, align, chars_len, frames_len, mode="monotonic"):
@@ -1757,8 +1757,8 @@ class Engine:
     # objective scoring: mel-cepstral distortion under dynamic time warping (include/tacotron2_amd.h: t2_mel_cepstra, t2_dtw;
     # DESIGN 5.9)
     # =============================================================================================
-    DTW_MAX_T = 4096            # T2_DTW_MAX_T: three fp64 rows and three int32 rows of the recurrence in LDS
-    DTW_MAX_K = 32              # T2_DTW_MAX_K
+    DTW_MAX_T = _lib.K["DTW_MAX_T"]            # three fp64 rows and three int32 rows of the recurrence in LDS
+    DTW_MAX_K = _lib.K["DTW_MAX_K"]
     DTW_BACK_BYTES = 256 << 20  # the `back` workspace of one t2_dtw call with a path stays at or below this
     MCD_SCALE = 10.0 * math.sqrt(2.0) / math.log(10.0)
 

@@ -9,9 +9,9 @@ import math
 import torch
 
 from . import _args
-from ._lib import cached, call, make, stream
+from ._lib import K, cached, call, make, stream
 
-NSTAT = 10                                  # T2_LOUD_NSTAT
+NSTAT = K["LOUD_NSTAT"]
 STATS = ("lufs", "gain", "true_peak", "sample_peak", "n_blocks", "n_below_abs", "n_below_rel", "rel_gate_lufs",
          "momentary_max_lufs", "flags")     # the columns of stat
 FLAG_SHORT, FLAG_UNDEFINED, FLAG_LIMITED, FLAG_CAPPED = 1, 2, 4, 8

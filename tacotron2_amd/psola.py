@@ -10,13 +10,13 @@ import math
 import torch
 
 from . import _args
-from ._lib import cached, call, make, stream
+from ._lib import K, cached, call, make, stream
 from .stretch import MAX_SAMPLES, SEMITONE_RANGE
 
-LAG_RANGE = (16, 4096)                      # T2_PSOLA_MIN_LAG, T2_PSOLA_MAX_LAG: voiced lags, and the unvoiced spacing
+LAG_RANGE = (K["PSOLA_MIN_LAG"], K["PSOLA_MAX_LAG"])      # voiced lags, and the unvoiced spacing
 RHO_ONE = 65536                             # Q16
-RHO_RANGE = (16384, 262144)                 # T2_PSOLA_MIN_RHO, T2_PSOLA_MAX_RHO: 1/4 .. 4
-SYN_TAIL = 10256                            # T2_PSOLA_SYN_TAIL
+RHO_RANGE = (K["PSOLA_MIN_RHO"], K["PSOLA_MAX_RHO"])      # 1/4 .. 4
+SYN_TAIL = K["PSOLA_SYN_TAIL"]
 PITCH_RANGE_RANGE = (0.0, 2.0)
 
 

@@ -9,9 +9,9 @@ import math
 import torch
 
 from . import _args
-from ._lib import cached, call, make, stream
+from ._lib import K, cached, call, make, stream
 
-MAX_FRAME, MAX_TOLERANCE = 2048, 1024       # T2_STRETCH_MAX_N, T2_STRETCH_MAX_D
+MAX_FRAME, MAX_TOLERANCE = K["STRETCH_MAX_N"], K["STRETCH_MAX_D"]
 MAX_SAMPLES = 1 << 27                       # t2_stretch's n_max, and t2_psola's
 TEMPO_RANGE = (0.25, 4.0)
 RATIO_RANGE = (0.125, 8.0)                  # t2_stretch's P / Q: what a pitch shift may ask of the stretch (4 x 2 octaves is refused)

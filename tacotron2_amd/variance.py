@@ -6,11 +6,11 @@ from __future__ import annotations
 import torch
 
 from . import _args
-from ._lib import call, make
+from ._lib import K, call, make
 
-VAR_MAX_T = 4096            # T2_VAR_MAX_T: frames of one utterance (q and e as doubles in LDS)
-VAR_MAX_L = 4096            # T2_VAR_MAX_L: characters of one utterance
-VAR_NSTAT = 10              # T2_VAR_NSTAT
+VAR_MAX_T = K["VAR_MAX_T"]            # frames of one utterance (q and e as doubles in LDS)
+VAR_MAX_L = K["VAR_MAX_L"]            # characters of one utterance
+VAR_NSTAT = K["VAR_NSTAT"]
 VAR_STATS = ["n_frames", "n_voiced", "sum_p", "sum_p2", "sum_q", "sum_q2", "sum_e", "sum_e2", "consistent", "chars_unvoiced"]
 
 

@@ -134,6 +134,22 @@ def test_a_tie_stays_on_the_character():
     assert dur.tolist() == [[1, 3]] and stats[0, 2] == 1.0 and abs(stats[0, 0] - 0.5) <= STATS_TOL
 
 
+def test_argmax_of_equal_maxima_is_the_lowest_position():
+    """L = 130, argmax mode: a wave's lane l scans positions l, l + 64, l + 128.  Step 0 has equal maxima at 5 and 70 (lanes 5 and 6:
+    the shuffle walk decides), step 1 at 5 and 69 (both lane 5: its serial scan decides), step 2 at 70 and 129 (lanes 6 and 1, the
+    higher lane holding the lower position).  The lower position wins each time, as numpy's argmax."""
+    dev = _dev()
+    a = np.full((1, 3, 130), 0.001, dtype=np.float32)
+    a[0, 0, [5, 70]], a[0, 1, [5, 69]], a[0, 2, [70, 129]] = 0.25, 0.25, 0.25
+    rd, rs, _ = R.durations_batch(a, [130], [3], 1, "argmax")
+    assert rd[0, 5] == 2 and rd[0, 70] == 1 and rd.sum() == 3
+    dur, stats = _kernel(torch.from_numpy(a).to(dev), [130], [3], 1, "argmax", dev)
+    assert np.array_equal(dur, rd), np.nonzero(dur[0])[0].tolist()
+    assert float(np.abs(stats.astype(np.float64) - rs).max()) <= STATS_TOL
+    dur, stats = _kernel(torch.from_numpy(a).to(dev), [130], [3], 1, "monotonic", dev)      # (3 steps < 130 characters: the argmax fall-back)
+    assert np.array_equal(dur, rd) and stats[0, 2] == 0.0
+
+
 def test_staircase_alignment_gives_back_its_durations():
     dev = _dev()
     d = np.array([3, 1, 4, 1, 5, 9, 2, 6, 5, 3, 5], dtype=np.int32)

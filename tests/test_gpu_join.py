@@ -209,6 +209,34 @@ def test_rows_do_not_depend_on_the_batch_around_them():
         assert np.array_equal(_bits(y3[a:a + k]), _bits(y5[b:b + k]))
 
 
+def test_a_device_count_out_of_range_refuses_the_batch_with_nothing_written():
+    """The C entry itself: one n[b] of -1 or n_max + 1 gives total = -1 and y keeps its prefill (the batch is one document: no row of
+    it is written); the same block with the row's own count writes what the wrapper writes."""
+    from tacotron2_amd import _lib
+    x, n = _rows([(7000, 1000, 6000, 0.1), (2000, 100, 1500, 0.2), (6500, 3000, 6500, 0.05)], 21)
+    wav, pause, B, ld = _poison(x, n), [5, 0, 9], 3, x.shape[1]
+    cap, lde = sum(n) + sum(pause), ld // H + 1
+    want, total, _ = _join(wav, n, pause)
+
+    def run(counts):
+        t = lambda *shape, dtype: torch.empty(*shape, dtype=dtype, device=DEV)
+        out = dict(total=torch.full((1,), 77, dtype=torch.int64, device=DEV), y=torch.full((cap,), -7.0, device=DEV))
+        a = _lib.make("T2Join", x=wav, ldx=wav.stride(0), n=torch.tensor(counts, dtype=torch.int32, device=DEV),
+                      pause=torch.tensor(pause, dtype=torch.int32, device=DEV), w=None, B=B, n_max=ld, trim=1, F=F, H=H, keep=0, fade=0,
+                      level=0, top_db=60.0, max_gain=2.0, ceiling=0.0, energy=t(B, lde, dtype=torch.float64), lde=lde,
+                      stat=t(B, 2, dtype=torch.float64), off=t(B, dtype=torch.int64), s0=t(B, dtype=torch.int32),
+                      len=t(B, dtype=torch.int32), gain=t(B, dtype=torch.float32), cap=cap, **out)
+        _lib.call("t2_join", a, _lib.stream())
+        torch.cuda.synchronize()
+        return int(out["total"].item()), out["y"].cpu().numpy()
+
+    for bad in (-1, ld + 1):
+        t, y = run([n[0], bad, n[2]])
+        assert t == -1 and (y == -7.0).all(), (bad, t)
+    t, y = run(n)
+    assert t == total and np.array_equal(_bits(y[:t]), _bits(want))
+
+
 # ---- arguments ----------------------------------------------------------------------------------------------------------------------------
 def test_the_wrapper_refuses_bad_arguments():
     from tacotron2_amd import analysis, engine

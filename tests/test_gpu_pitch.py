@@ -308,6 +308,23 @@ def test_stats_hand_made_paths_batch_of_three():
     check_stats("clipped", got, path[:2], [Pn, 0], f0_a[:2], n_a[:2], f0_b[:2], n_b[:2], hop, S)
 
 
+@pytest.mark.parametrize("Pn", [1, 63, 64, 65, 255, 256, 257])
+def test_stats_at_the_wave_and_block_edges(Pn):
+    """Path lengths at which a lane, a wave or the second round of the 256-thread block is empty or holds one cell.  B = 2, hop = S = 1
+    (every frame inside n is valid): the first pair scores all Pn cells, the second has n = 0 on both sides - no valid frame, NaN in
+    its tracks - and scores none."""
+    rng = np.random.default_rng(300 + Pn)
+    Ta, Tb = 40, 30
+    f0_a = rng.choice(np.array([0, 98.5, 131.25, 220, 402.7], np.float32), size=(2, Ta))
+    f0_b = rng.choice(np.array([0, 101.5, 120.25, 233, 390.1], np.float32), size=(2, Tb))
+    path = np.stack([rng.integers(0, Ta, size=(2, Pn)), rng.integers(0, Tb, size=(2, Pn))], axis=-1).astype(np.int32)
+    f0_a[0, path[0, Pn - 1, 0]], f0_b[0, path[0, Pn - 1, 1]] = 220.0, 233.0            # the last cell is voiced on both sides
+    f0_a[1], f0_b[1] = np.nan, np.nan
+    got = run_stats(path, [Pn, Pn], f0_a, [Ta, 0], f0_b, [Tb, 0], 1, 1)
+    check_stats(f"edge P={Pn}", got, path, [Pn, Pn], f0_a, [Ta, 0], f0_b, [Tb, 0], 1, 1)
+    assert got[0, 0] == Pn and got[0, 1] >= 1 and not got[1].any()
+
+
 def test_stats_bad_arguments():
     from tacotron2_amd import _lib
     lib = _lib.lib()

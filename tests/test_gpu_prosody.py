@@ -113,6 +113,26 @@ def test_yin_is_reproducible_and_cmnd_is_optional(name):
         assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("thr", [0.1, 0.0])
+def test_yin_pulse_train_exact_ties_across_lanes_and_waves(thr):
+    """One valid frame of a pulse train of exact period 100 at the default geometry (lags 44 .. 366 searched): the difference function,
+    and so cmnd, is exactly 0 at lags 100, 200 and 300 - candidates of wave 0, of wave 2 and of wave 0's second round of the 256-thread
+    pick.  thr = 0.1 takes the "first under the threshold" path, thr = 0 the argmin path: both must give the lowest, lag 100."""
+    x = np.zeros(1500, np.float32)                          # frames 0 .. 5; only t = 3 (samples 73 .. 1463) lies inside the row
+    x[::100] = 0.5
+    cfg = dict(DEFAULT, thr=thr)
+    ref, tol = R.tolerances([x], **cfg)
+    f0, aper, power, cm = run_yin([x], cfg)
+    assert ref["valid"][0].tolist() == [False, False, False, True, False, False] and ref["tau"][0, 3] == 100 and ref["voiced"][0, 3]
+    assert [c for c in range(44, 367) if cm[0, 3, c] == 0] == [100, 200, 300] and (cm[0, 3, 44:367] >= 0).all()
+    assert R.pick(cm[0, 3], 44, 367, thr) == 100 and aper[0, 3] == 0
+    print(f"thr {thr}: f0 {f0[0, 3]!r}, reference {ref['f0'][0, 3]!r}, tolerance {tol['f0']:.3e}")
+    assert abs(f0[0, 3] - ref["f0"][0, 3]) <= tol["f0"] * ref["f0"][0, 3]
+    assert abs(cfg["sr"] / f0[0, 3] - 100) <= 1 + 1e-4
+    inv = ~ref["valid"][0]
+    assert (f0[0, inv] == 0).all() and (aper[0, inv] == 1).all() and (power[0, inv] == 0).all()
+
+
 def test_yin_bad_arguments_return_the_code_without_a_launch():
     from tacotron2_amd import _lib
     lib = _lib.lib()
@@ -210,6 +230,24 @@ def test_prosody_stats_small_and_ties_by_index():
     _check_stats(got, f0, aper, power, [7], 1, 1)
     assert got[0].tolist()[:2] == [7.0, 5.0] and got[0, 3] == 100 and got[0, 4] == 300 and got[0, 6] == 0.125
     assert abs(got[0, 5] + 20.0) < 1e-5
+
+
+EDGE_LENGTHS = [1, 63, 64, 65, 255, 256, 257]       # a lane, a wave or the block's second round is empty or holds one frame
+
+
+@pytest.mark.parametrize("T", EDGE_LENGTHS)
+def test_prosody_stats_at_the_wave_and_block_edges(T):
+    """B = 2, hop = S = 1 (every frame inside n is valid): the first utterance has all T frames, the second n = 0 - no valid frame,
+    NaN in its inputs.  Counts exact, sums within the bound of the hand-made tracks."""
+    rng = np.random.default_rng(100 + T)
+    f0 = rng.choice(np.array([0, 90.5, 120.25, 200, 333.3, 410], np.float32), size=(2, T))
+    f0[0, T - 1] = 151.0                                    # the last frame is voiced: a sum that drops it is wrong
+    aper = rng.uniform(0.01, 0.3, size=(2, T)).astype(np.float32)
+    power = (10.0 ** rng.uniform(-4, -1, size=(2, T))).astype(np.float32)
+    f0[1], aper[1], power[1] = np.nan, np.nan, np.nan
+    got = run_stats(f0, aper, power, [T, 0], 1, 1)
+    _check_stats(got, np.nan_to_num(f0, nan=0.0), aper, power, [T, 0], 1, 1)
+    assert got[0, 0] == T and 1 <= got[0, 1] <= T and got[1, 0] == 0 and got[1, 1] == 0
 
 
 def test_prosody_stats_bad_arguments():

@@ -195,6 +195,20 @@ def test_refused_rows_keep_their_prefill_and_the_others_are_right(voiced):
     _row_ok(out, 3, rows[3], lag[3].cpu().numpy(), rho2[3].cpu().numpy())
 
 
+def test_rows_beside_a_refused_count_keep_their_bits(voiced):
+    rows = [voiced[:3000], voiced[:2500], voiced[:2800]]
+    wav, n = _device_rows(rows)
+    lag, rho = _tracks([np.full(_frames(k), 100) for k in n], [Q[0.794]] * 3, _frames(3000))
+    _, good = _abi(wav, torch.tensor(n, dtype=torch.int32, device=DEV), 3000, lag, rho)
+    for bad in (-1, 3001):                                  # one below 0, one above n_max
+        rc, out = _abi(wav, torch.tensor([n[0], bad, n[2]], dtype=torch.int32, device=DEV), 3000, lag, rho)
+        assert rc == 0 and out["n_marks"][1] == -1 and out["n_syn"][1] == SENTINEL
+        assert all((out[k][1] == SENTINEL).all() for k in ("y", "a", "r", "kmap"))
+        for b in (0, 2):
+            for k in out:
+                assert out[k][b].tobytes() == good[k][b].tobytes(), (bad, b, k)
+
+
 def test_two_calls_are_bit_identical_and_rows_do_not_depend_on_the_batch(voiced):
     rows = [voiced[:5000], voiced[200:3201]]
     wav, n = _device_rows(rows)

@@ -198,6 +198,17 @@ def test_a_count_out_of_range_is_refused_with_nothing_written():
             assert np.array_equal(pos[b, :len(want_pos)], want_pos) and np.abs(y[b, :n_out[b]] - want_y).max() <= 2.0 ** -21 * np.abs(rows[b]).max()
 
 
+def test_rows_beside_a_refused_count_keep_their_bits():
+    rows = [_noise(300, 1), _noise(200, 2), _noise(250, 3)]
+    wav, n = _device_rows(rows)
+    _, y0, pos0, n_out0 = _abi(wav, torch.tensor(n, dtype=torch.int32, device=DEV), 300, 800, 1000, 16, 4)
+    for bad in (-1, 301):                                   # one below 0, one above n_max
+        rc, y, pos, n_out = _abi(wav, torch.tensor([n[0], bad, n[2]], dtype=torch.int32, device=DEV), 300, 800, 1000, 16, 4)
+        assert rc == 0 and n_out[1] == -1 and (y[1] == SENTINEL).all() and (pos[1] == SENTINEL).all()
+        for b in (0, 2):
+            assert n_out[b] == n_out0[b] and np.array_equal(pos[b], pos0[b]) and np.array_equal(y[b].view(np.uint32), y0[b].view(np.uint32))
+
+
 def test_bad_operand_blocks_return_an_error_before_any_launch():
     from tacotron2_amd import _lib
     lib = _lib.lib()

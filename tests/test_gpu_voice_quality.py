@@ -247,6 +247,29 @@ def test_corpus_stats_on_the_kernels_own_outputs():
     assert (out[2] == 0).all()                                # the all-empty utterance
 
 
+@pytest.mark.parametrize("T", [1, 63, 64, 65, 255, 256, 257])
+def test_corpus_stats_at_the_wave_and_block_edges(T):
+    """The lengths at which a lane, a wave or the second round of the 256-thread block is empty or holds one frame.  B = 2, hop = S = 1
+    (every frame inside n is valid): all T frames of the first utterance, none of the second (n = 0, NaN in its inputs).  Counts
+    exact, means within 1e-6 relative, as on the kernel's own outputs."""
+    rng = np.random.default_rng(200 + T)
+    f0 = rng.choice(np.array([0, 98.5, 131.25, 220, 402.7], np.float32), size=(2, T))
+    power = (10.0 ** rng.uniform(-12, -1, size=(2, T))).astype(np.float32)              # some frames under the floor of 1e-10
+    vq = {q: rng.uniform(0.001, 0.2, size=(2, T)).astype(np.float32) for q in OUTS}
+    vq["cycles"] = rng.integers(0, 4, size=(2, T)).astype(np.int32)
+    f0[0, T - 1], power[0, T - 1], vq["cycles"][0, T - 1] = 220.0, 1e-3, 3             # the last frame counts everywhere
+    f0[1], power[1], vq["cycles"][1] = np.nan, np.nan, 9
+    for q in OUTS:
+        vq[q][1] = np.nan
+    out = run_corpus(f0, power, vq, [T, 0], 1, 1)
+    for b, n in enumerate([T, 0]):
+        want = V.corpus_stats(f0[b], power[b], {k: v[b] for k, v in vq.items()}, np.arange(T) < n)
+        assert out[b, :4].tolist() == want[:4] and out[b, 10] == 0 and out[b, 11] == 0, (b, out[b], want)
+        for k in range(4, 10):
+            assert abs(out[b, k] - want[k]) <= 1e-6 * abs(want[k]), (b, k, out[b, k], want[k])
+    assert out[0, 0] == T and out[0, 1] >= 1 and out[0, 2] >= 1 and out[0, 3] >= 1 and (out[1] == 0).all()
+
+
 def test_corpus_stats_bad_arguments():
     from tacotron2_amd import _lib
     lib = _lib.lib()
