@@ -1176,6 +1176,57 @@ typedef struct {
 int t2_loudness(const T2Loudness* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Look-ahead true-peak limiter of a padded batch of waveforms (no reference counterpart; csrc/t2_limit.hip, the rule in DESIGN 5.21,
+ * restated sequentially in float64 in tests/limiter_ref.py).  It holds the true peak t2_loudness measures under a ceiling with a gain
+ * that moves, where t2_loudness's own bound turns the whole row down.
+ *
+ * t2_limit: x[b*ldx + i] float32 is a padded batch of B waveforms of finite samples v, already at their target gain, n[b] (DEVICE
+ *   int32, 0 <= n[b] <= n_max) their sample counts; nothing is read from a row at or behind n[b].  ceiling c LINEAR, fp64; L the
+ *   look-ahead in samples, 1 .. 2048; a the release coefficient in (0, 1), host-made in fp64 as exp(-1 / (release_s * sr)); table
+ *   [4][2K] as t2_loudness takes it.  Per row:
+ *   1 ENVELOPE  P[i] = max(|v[i]|, |u[4i]|, .., |u[4i+3]|), u the 4 n values t2_resample writes for this row with U = 4, D = 1 and this
+ *     table, in t2_loudness's arithmetic: one fmaf per tap in ascending k from 0.0f, samples outside [0, n) zero and never loaded.
+ *     env[i] = max(P[i-1], P[i]), P[-1] = 0: a value between the samples i and i + 1 is made of both, so both carry its reduction.
+ *     env[b*lde + i] float32 is written for i < n[b].
+ *   2 REQUIRED GAIN  r[i] = (double)env[i] > c ? (float)(c / (double)env[i]) : 1.0f - one fp64 division, rounded once.
+ *   3 LOOK-AHEAD  h[i] = min r[k] over i <= k <= min(i + L, n - 1): exact.
+ *   4 RELEASE, in fp64:  e[i] = min(h[i], a * e[i-1] + (1 - a)),  e[m] = h[0] for every m < 0: the limiter is already down when the
+ *     row starts (with e = 1 in front of the row a peak inside the first L samples would break the bound of step 5).
+ *   5 ATTACK  s[i] = (e[i-L] + .. + e[i]) / (L + 1) in fp64.  Every term is at most h of its own index, which is at most r[i], so
+ *     s[i] <= r[i] up to the rounding of the sum.  A row with no env[i] > c has s == 1 exactly.  curve[b*ldc + i] = (float)s[i], i < n[b].
+ *   6 APPLY  w[i] = v[i] * curve[i], one float32 product.
+ *   7 TRIM  the gain now moves between samples, so the 4x values of w can pass c by a hair.  peak_after = max_i P[i] of w (step 1,
+ *     the same taps).  peak_after > c:  t = the largest float32 with (double)t * peak_after <= c,  y[i] = w[i] * t;  else t = 1 and
+ *     y = w bit for bit.  y[b*ldy + i] = 0.0f for n[b] <= i < ldy.
+ *   stat[b*8 + ..] fp64:  0 in_peak = max env,  1 n_over = the count of env[i] > c,  2 min_gain = min s,  3 peak_after,  4 trim = t,
+ *     5 flags: bit 0 active (n_over > 0), bit 1 trimmed,  6, 7: 0.
+ *   REFUSED on the device, not clamped: a row with n[b] outside 0 .. n_max gets flags = -1; nothing else is written for it (env,
+ *     curve and y included) and x is not read.
+ *   Launches on one stream, plain: the envelope (grid tiles of 1024 samples x B, the span in LDS as t2_loudness's peak launch stages
+ *     it); the curve (one 256-thread workgroup per row in passes of 4096 samples with a halo of L on both sides: the sliding minimum
+ *     by doubling in LDS, the release chunked - every thread runs 16 samples from the neutral state e = 1, the chunk ends meet in a
+ *     scan over d = 1 - e, d_end[t] = max(local_end[t], a^16 d_end[t-1]) - a carried d that is not zero is held where the fp64
+ *     recurrence itself stops, about tau / 2 ulps under 1 -, and every thread runs its chunk again from its true state -, the box sum; the last L values of e and the release state are carried from pass to pass; a row without a sample above c
+ *     gets curve = 1 and skips all of it); apply and the peak of w (the envelope's grid; the maxima joined by an integer maximum on
+ *     the bits of the non-negative value); the trim.  Two calls give bit-identical env, curve, y and stat, and a row's results do not
+ *     depend on B, the leading dimensions or the other rows.
+ *   T2_ERR_ARG before any launch: a null pointer (x only when n_max > 0), B < 1 or > 65535, n_max < 0, ldx, lde, ldc or ldy < n_max,
+ *     K outside 1 .. T2_LOUD_MAX_K, L outside 1 .. 2048, a not in (0, 1), a ceiling that is not finite or <= 0. */
+enum { T2_LIMIT_NSTAT = 8, T2_LIMIT_MAX_L = 2048 };
+typedef struct {
+    const float* x; int64_t ldx;                        /* rows are read only inside [0, n[b]) */
+    const int32_t* n;                                   /* [B] device */
+    const float* table; int K;                          /* [4][2K] fp32: datasets/resample.plan(sr, 4 sr) */
+    int B, n_max, L;
+    double a, ceiling;                                  /* release coefficient; linear */
+    float* env; int64_t lde;                            /* [B][lde] */
+    float* curve; int64_t ldc;                          /* [B][ldc] */
+    float* y; int64_t ldy;                              /* [B][ldy], zeros behind n[b] */
+    double* stat;                                       /* [B][8] */
+} T2Limit;
+int t2_limit(const T2Limit* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

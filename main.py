@@ -334,16 +334,22 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
 @click.option("--true-peak", required=False, type=float, default=None, metavar="DBTP",
               help="With --loudness: the true peak (4x oversampled) the file may reach, -9 to 0 dBTP; the gain is lowered until it "
                    "holds. Default: -1.")
+@click.option("--limiter", is_flag=True, default=False,
+              help="With --loudness: hold --true-peak with a look-ahead true-peak limiter on the GPU (5 ms look-ahead, 50 ms release) "
+                   "instead of a lower gain for the whole file, so a file with a few tall peaks comes out at the loudness asked for; "
+                   "the line tells the limited samples, the largest reduction and the loudness reached. Default: off.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
         forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
         expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000, tempo=None,
-        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False, loudness=None, true_peak=None):
+        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False, loudness=None, true_peak=None, limiter=False):
     if (text is None) == (text_file is None):
         raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
-    if loudness is not None or true_peak is not None:
-        from tacotron2_amd.run.say import loudness_settings
+    limiter = True if limiter else None
+    if loudness is not None or true_peak is not None or limiter:
+        from tacotron2_amd.run.say import limiter_settings, loudness_settings
         try:
             loudness_settings(loudness, true_peak, wav_target(out, hifi_gan_checkpoint))
+            limiter_settings(limiter, loudness)
         except ValueError as e:
             raise click.UsageError(str(e))
     if text_file is None:
@@ -368,7 +374,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
                   durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len,
                   tempo=tempo, pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range,
-                  loudness=loudness, true_peak=true_peak)
+                  loudness=loudness, true_peak=true_peak, limiter=limiter)
     if text_file is None:
         from tacotron2_amd.run.say import do_say
         do_say(text=text, **common)

@@ -15,6 +15,7 @@ from .join import fade_table, join_audio  # noqa: F401  (pieces joined into one 
 from .stretch import hann_table, pitch_shift, time_stretch  # noqa: F401  (WSOLA tempo and pitch, DESIGN 5.17: in stretch.py)
 from .psola import fold_lags, grain_table, pitch_ratio, pitch_shift_psola, psola  # noqa: F401  (TD-PSOLA pitch change, DESIGN 5.18: in psola.py)
 from .loudness import k_weighting, loudness, normalize_loudness  # noqa: F401  (BS.1770 loudness and true peak, DESIGN 5.20: in loudness.py)
+from .limiter import limit_peaks  # noqa: F401  (look-ahead true-peak limiter, DESIGN 5.21: in limiter.py)
 from .variance import VAR_MAX_L, VAR_MAX_T, VAR_NSTAT, VAR_STATS, char_variance  # noqa: F401
 
 PROSODY_MAX_T = K["PROSODY_MAX_T"]        # frames of one utterance in t2_prosody_stats

@@ -163,12 +163,7 @@ __global__ __launch_bounds__(256) void loud_peak_kernel(T2Loudness p) {
         if (tile0 + o >= n) break;
         const float* xr = lp_xs + o;                                    // the sample of tap -K+1
         sp = fmaxf(sp, fabsf(xr[K - 1]));
-        for (int ph = 0; ph < 4; ++ph) {
-            const float* h = p.table + (int64_t)ph * (2 * K);
-            float acc = 0.f;
-            for (int k = 0; k < 2 * K; ++k) acc = fmaf(h[k], xr[k], acc);
-            tp = fmaxf(tp, fabsf(acc));
-        }
+        tp = fmaxf(tp, t2m_peak4(p.table, K, xr));
     }
     tp = t2_block_max(tp, red);
     sp = t2_block_max(sp, red);

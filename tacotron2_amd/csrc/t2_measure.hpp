@@ -1,4 +1,4 @@
-// Shared pieces of the model-free measurement kernels (t2_align, t2_dtw, t2_join, t2_loudness, t2_pitch, t2_prosody, t2_psola,
+// Shared pieces of the model-free measurement kernels (t2_align, t2_dtw, t2_join, t2_limit, t2_loudness, t2_pitch, t2_prosody, t2_psola,
 // t2_resample, t2_stretch, t2_variance): their reductions, the frame rule and the count rule.  None of it is on the training
 // step's path.  Every reduction walks the wave with __shfl_xor at offsets 32, 16, .., 1 and then the waves in order 0 .. NW - 1:
 // one fixed association, so float sums keep their bits from launch to launch (t2_wave_sum of t2_common.hpp has another order).
@@ -88,6 +88,19 @@ __device__ __forceinline__ void t2m_combine_picks(const V* rv, const int* ri, V&
 #pragma unroll
     for (int r = 1; r < NW; ++r)
         if (better(rv[r], ri[r], v, i)) { v = rv[r]; i = ri[r]; }
+}
+
+// The largest magnitude among the 4 values t2_resample writes behind one input sample with U = 4, D = 1 (the true peak of t2_loudness
+// and t2_limit): table [4][2K], xr the sample of tap -K+1 in a staged span; one fmaf per tap in ascending k from 0.0f.
+__device__ __forceinline__ float t2m_peak4(const float* table, int K, const float* xr) {
+    float tp = 0.f;
+    for (int ph = 0; ph < 4; ++ph) {
+        const float* h = table + (int64_t)ph * (2 * K);
+        float acc = 0.f;
+        for (int k = 0; k < 2 * K; ++k) acc = fmaf(h[k], xr[k], acc);
+        tp = fmaxf(tp, fabsf(acc));
+    }
+    return tp;
 }
 
 // Frame t of hop `hop` and span S is valid when its span [s0, s0 + S), s0 = t hop - S / 2, lies inside the row's n samples.

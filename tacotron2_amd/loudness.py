@@ -56,7 +56,8 @@ def _limited(fn: str, name: str, v, limits) -> float:
     return v
 
 
-def _run(fn: str, wav, n, sample_rate, target, ceiling, max_gain_db, write: bool):
+def _run(fn: str, wav, n, sample_rate, target, ceiling, max_gain_db, write: bool, lift: bool = False):
+    """lift: the ceiling is checked and then lifted out of reach, so the gain is bounded by max_gain_db alone (the limiter path)."""
     B, ld, ldx = _args.wav_rows(fn, "wav", wav)
     sr = _args.int_arg(fn, "sample_rate", sample_rate, *RATE_LIMITS)
     target = _limited(fn, "target", target, TARGET_LIMITS)
@@ -77,7 +78,7 @@ def _run(fn: str, wav, n, sample_rate, target, ceiling, max_gain_db, write: bool
         gain = torch.empty(B, dtype=torch.float32, device=dev)
         y = torch.empty(B, ld, dtype=torch.float32, device=dev) if write else None
         a = make("T2Loudness", x=wav if ld > 0 else None, ldx=ldx, n=n32, table=table, K=K, B=B, n_max=ld, H=H, b1=b1, a1=a1, b2=b2,
-                 a2=a2, abs_gate=ABS_GATE, target=target, max_gain=10.0 ** (max_gain_db / 20.0), ceiling=10.0 ** (ceiling / 20.0),
+                 a2=a2, abs_gate=ABS_GATE, target=target, max_gain=10.0 ** (max_gain_db / 20.0), ceiling=1.7e308 if lift else 10.0 ** (ceiling / 20.0),
                  E=E, lde=lde, stat=stat, gain=gain, y=y if write and ld > 0 else None, ldy=ld)
         call("t2_loudness", a, stream())
         if n_sum is None and bool((stat[:, 9] < 0).any()):             # (device counts: the kernel's refusal is the one extra read)
@@ -100,11 +101,29 @@ def loudness(wav, n, sample_rate):
     return stats
 
 
-def normalize_loudness(wav, n, sample_rate, target=-23.0, ceiling=-1.0, max_gain_db=MAX_GAIN_DB):
+def normalize_loudness(wav, n, sample_rate, target=-23.0, ceiling=-1.0, max_gain_db=MAX_GAIN_DB, limiter=None):
     """A padded batch brought to `target` LUFS (C-ABI t2_loudness, DESIGN 5.20): wav, n and sample_rate as loudness takes them;
     target in -70 .. 0 LUFS, ceiling in -40 .. 0 dBTP, max_gain_db in 0 .. 120.  Every row is multiplied by ONE gain,
     10^((target - lufs) / 20), lowered to max_gain_db (flag bit 3, capped) and then until gain * true_peak is at most the ceiling
     (flag bit 2, limited): a plain gain, no limiter, no compression.  A row without a loudness keeps the gain 1.  Returns (y, stats):
-    y of wav's shape, zeros behind n[b]; stats = loudness's dict - the MEASURED values of wav, not of y - plus gain (float32)."""
-    y, gain, stats = _run("normalize_loudness", wav, n, sample_rate, target, ceiling, max_gain_db, True)
-    return y, dict(stats, gain=gain)
+    y of wav's shape, zeros behind n[b]; stats = loudness's dict - the MEASURED values of wav, not of y - plus gain (float32).
+    limiter: None - the above, nothing else runs.  True, or a dict of lookahead_ms / release_ms (limiter.limit_peaks), holds the
+    ceiling with a look-ahead limiter instead, three library calls: t2_loudness with the ceiling lifted out of reach, so
+    the gain is bounded by max_gain_db alone and `limited` is never set; t2_limit on that waveform with the ceiling; t2_loudness once
+    more, measuring.  stats then also holds limit_peaks' in_peak, n_over, min_gain, peak_after, trim and its flags as limiter_flags,
+    and output_lufs and output_true_peak, measured on y.  A row without a loudness keeps its bits through all three."""
+    if limiter is None:
+        y, gain, stats = _run("normalize_loudness", wav, n, sample_rate, target, ceiling, max_gain_db, True)
+        return y, dict(stats, gain=gain)
+    from . import limiter as lim
+    fn = "normalize_loudness"
+    if limiter is True:
+        limiter = {}
+    if not isinstance(limiter, dict) or set(limiter) - {"lookahead_ms", "release_ms"}:
+        raise ValueError(f"{fn}: limiter must be None, True or a dict of lookahead_ms / release_ms, got {limiter!r}")
+    lim.settings(fn, sample_rate, **limiter)                             # (checked in front of the first launch)
+    g, gain, stats = _run(fn, wav, n, sample_rate, target, ceiling, max_gain_db, True, lift=True)
+    y, more = lim.limit_peaks(g, n, sample_rate, ceiling=ceiling, **limiter)
+    _, _, after = _run(fn, y, n, sample_rate, target, ceiling, max_gain_db, False)
+    more["limiter_flags"] = more.pop("flags")
+    return y, dict(stats, gain=gain, output_lufs=after["lufs"], output_true_peak=after["true_peak"], **more)

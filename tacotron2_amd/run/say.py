@@ -161,19 +161,38 @@ def loudness_settings(loudness, true_peak, wav_target: bool = True, rate: Option
     return float(loudness), TRUE_PEAK_DEFAULT if true_peak is None else float(true_peak)
 
 
-def normalize_rows(waves, rate: int, loud: Tuple[float, float], dev):
+def limiter_settings(limiter, loudness) -> bool:
+    """--limiter of `say`, checked before anything is decoded, beside loudness_settings: whether the ceiling of
+    --loudness is held by the look-ahead limiter instead of a lower gain."""
+    if limiter is None or limiter is False:
+        return False
+    if limiter is not True:
+        raise ValueError(f"--limiter is a flag, got {limiter!r}")
+    if loudness is None:
+        raise ValueError("--limiter needs --loudness: it holds the ceiling of that gain")
+    return True
+
+
+def normalize_rows(waves, rate: int, loud: Tuple[float, float], dev, limiter: bool = False):
     """The LAST step in front of write_wav: the waveforms as they would be written, at the rate the header will carry, as the rows of
     ONE analysis.normalize_loudness call.  (the rows cut to their counts, on dev; one dict per row: loudness_lufs - measured, None
     for a row without a loudness, which keeps the gain 1 and its bits -, gain_db, true_peak_dbtp - after the gain, None for digital
-    silence -, flags)."""
+    silence -, flags).  limiter: that call's limiter=True - t2_loudness, t2_limit, t2_loudness -; a row's dict then also holds
+    limited_samples, limiter_max_reduction_db and output_lufs (None without a loudness), and true_peak_dbtp is measured on the
+    limited row."""
     import math
     from .. import analysis
     buf, n = pack_rows([torch.as_tensor(w).detach().float().reshape(-1) for w in waves], dev)
-    y, stats = analysis.normalize_loudness(buf, n, int(rate), target=loud[0], ceiling=loud[1])
+    y, stats = analysis.normalize_loudness(buf, n, int(rate), target=loud[0], ceiling=loud[1], limiter=True if limiter else None)
     lufs, gain, peak, flags = (stats[k].cpu().tolist() for k in ("lufs", "gain", "true_peak", "flags"))
     db = lambda v: 20.0 * math.log10(v) if v > 0 else None
     recs = [dict(loudness_lufs=None if math.isnan(lufs[i]) else lufs[i], gain_db=db(gain[i]), true_peak_dbtp=db(gain[i] * peak[i]),
                  flags=int(flags[i])) for i in range(len(n))]
+    if limiter:
+        over, low, out, out_peak = (stats[k].cpu().tolist() for k in ("n_over", "min_gain", "output_lufs", "output_true_peak"))
+        for i, rec in enumerate(recs):
+            rec.update(limited_samples=int(over[i]), limiter_max_reduction_db=-20.0 * math.log10(low[i]) + 0.0,
+                       output_lufs=None if math.isnan(out[i]) else out[i], true_peak_dbtp=db(out_peak[i]))
     return [y[i, :n[i]] for i in range(len(n))], recs
 
 
@@ -183,13 +202,18 @@ def loudness_line(name: str, rec: dict) -> str:
     if rec["flags"] & FLAG_UNDEFINED:
         return f"say: {name}: no loudness (left as it is)"
     notes = [text for bit, text in ((FLAG_LIMITED, "peak-limited"), (FLAG_CAPPED, "boost capped"), (FLAG_SHORT, "short")) if rec["flags"] & bit]
-    return (f"say: {name}: {rec['loudness_lufs']:.2f} LUFS, gain {rec['gain_db']:+.2f} dB, true peak {rec['true_peak_dbtp']:.2f} dBTP"
+    limited = ""
+    if "limited_samples" in rec:                          # --limiter: what the limiter did and what was reached
+        limited = (f"limited {rec['limited_samples']} samples by up to {rec['limiter_max_reduction_db']:.2f} dB, "
+                   f"now {rec['output_lufs']:.2f} LUFS, ")
+    return (f"say: {name}: {rec['loudness_lufs']:.2f} LUFS, gain {rec['gain_db']:+.2f} dB, {limited}true peak {rec['true_peak_dbtp']:.2f} dBTP"
             + "".join(", " + t for t in notes))
 
 
 def loudness_fields(rec: dict) -> dict:
-    """What a --durations-out object gains with --loudness."""
-    return {k: rec[k] for k in ("loudness_lufs", "gain_db", "true_peak_dbtp")}
+    """What a --durations-out object gains with --loudness, and with --limiter."""
+    return {k: rec[k] for k in ("loudness_lufs", "gain_db", "true_peak_dbtp", "limited_samples", "limiter_max_reduction_db", "output_lufs")
+            if k in rec}
 
 
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
@@ -199,8 +223,12 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
            forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
            stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, tempo: Optional[float] = None,
            pitch_shift: Optional[float] = None, preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None,
-           loudness: Optional[float] = None, true_peak: Optional[float] = None):
-    """loudness: -40 .. -5 LUFS, true_peak: -9 .. 0 dBTP (default -1; only with loudness) - with a `.wav` target every text's waveform,
+           loudness: Optional[float] = None, true_peak: Optional[float] = None, limiter: Optional[bool] = None):
+    """limiter (only with loudness): the ceiling is held by the look-ahead true-peak limiter (analysis.normalize_loudness(limiter=True),
+    DESIGN 5.21: t2_loudness, t2_limit, t2_loudness) where the gain alone would be lowered; the line then tells the limited samples,
+    the largest reduction and the loudness reached, and `durations_out` objects gain `limited_samples`, `limiter_max_reduction_db`
+    and `output_lufs`.  None: nothing of this runs.
+    loudness: -40 .. -5 LUFS, true_peak: -9 .. 0 dBTP (default -1; only with loudness) - with a `.wav` target every text's waveform,
     exactly as it would be written (behind the voice chain and out_sample_rate, at the rate of the header), becomes one row of ONE
     analysis.normalize_loudness call (BS.1770-4) and is written with its gain; one line per file is printed and
     `durations_out` objects gain `loudness_lufs` (measured), `gain_db` and `true_peak_dbtp` (after the gain).  A text without a
@@ -230,6 +258,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     resampler = output_resampler(pre, out_sample_rate, dev)
     voice = voice_settings(tempo, pitch_shift, sample_rate(pre), audio, preserve_formants, pitch_range)
     loud = loudness_settings(loudness, true_peak, audio, sample_rate(pre) if out_sample_rate is None else int(out_sample_rate))
+    limiter = limiter_settings(limiter, loudness)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     _, chars, lens = encode_texts(enc, texts, dev)
@@ -261,7 +290,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         from .. import vocoder
         rate = sr if resampler is None else resampler.sr_out
         rows, recs = normalize_rows([to_output_rate(vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
-                                     for i, m in enumerate(mels)], rate, loud, dev)
+                                     for i, m in enumerate(mels)], rate, loud, dev, limiter)
         for name, row, rec in zip(names, rows, recs):
             vocoder.write_wav(name, row.cpu(), rate)
             print(loudness_line(name, rec))
@@ -316,7 +345,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                  controls: Optional[str] = None, description: Optional[str] = None, random_seed: Optional[int] = None,
                  durations: bool = False, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
                  preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None, loudness: Optional[float] = None,
-                 true_peak: Optional[float] = None):
+                 true_peak: Optional[float] = None, limiter: Optional[bool] = None):
     """Pieces (datasets.document.Piece, or a text, which is split at the defaults) -> one waveform on the model's device.
     The pieces are sorted by encoded length and decoded in chunks of batch_size through the model's free-running forward, with the
     decode settings that are on the model (common.free_run).  `vocoder` is a loaded hifigan.Generator - each chunk's PADDED batch
@@ -333,6 +362,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     loudness (-40 .. -5 LUFS) and true_peak (-9 .. 0 dBTP, default -1): the JOINED waveform, as ONE row at the model's rate, is
     brought to that programme loudness by analysis.normalize_loudness as the last step; `level` keeps moving the pieces
     towards each other in front of it.  (do_say_document, which may resample behind the join, normalises behind that instead.)
+    limiter (only with loudness): normalize_rows' limiter - the ceiling is held by the look-ahead limiter.
     A piece that ran into max_len without stopping is kept, cut there, and marked stopped=False.
     Returns (y (total,) float32, plan - join_audio's, device tensors -, info): info = dict(pieces, frames, stopped, n, pause,
     waveforms - the per-piece device tensors that went into the join -, chunks, join - the keyword arguments of the join_audio
@@ -352,6 +382,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     sr = sample_rate(pre)
     voice = voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
     loud = loudness_settings(loudness, true_peak, True, sr)
+    limiter = limiter_settings(limiter, loudness)
     texts = [p.text for p in pieces]
     ids, _, _ = encode_texts(enc, texts)
     order = sorted(range(len(ids)), key=lambda i: (len(ids[i]), i))
@@ -385,7 +416,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     y, _, plan = analysis.join_audio(buf, n, pause, **join)
     loud_rec = None
     if loud is not None:
-        (y,), (loud_rec,) = normalize_rows([y], sr, loud, dev)
+        (y,), (loud_rec,) = normalize_rows([y], sr, loud, dev, limiter)
     return y, plan, dict(pieces=pieces, frames=frames, stopped=stopped, n=n, pause=pause, waveforms=waves, chunks=len(chunks),
                          join=join, durations=records if durations else None, voice=voice, loudness=loud_rec)
 
@@ -431,13 +462,14 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
                     expand_numbers: bool = False, pause=None, trim: bool = True, level: bool = False, fade_ms: float = 5.0,
                     batch_size: int = 64, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
                     preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None, loudness: Optional[float] = None,
-                    true_peak: Optional[float] = None):
+                    true_peak: Optional[float] = None, limiter: Optional[bool] = None):
     """`say --text-file`: the file is read, its numbers expanded if asked, split (datasets/document.py) and spoken by say_document;
     the joined waveform is resampled to out_sample_rate if given (one Resampler call) and written by ONE write_wav call.
     tempo, pitch_shift, preserve_formants, pitch_range: say_document's, in front of the join.
     loudness, true_peak: the joined document, behind the resampling, is ONE row of analysis.normalize_loudness (loudness_settings),
     so the loudness is the programme's and the ceiling holds for the file; a line is printed, every `durations_out` object gains the
     document's `loudness_lufs`, `gain_db` and `true_peak_dbtp`, and info["loudness"] holds them.
+    limiter (only with loudness): the joined document is limited as that one row (normalize_rows' limiter).
     durations_out: document_records as a JSON list.  A piece that did not stop is reported on stderr; the exit status stays 0.
     Returns say_document's (y, plan, info), y as written (after resampling and normalisation)."""
     import sys
@@ -456,6 +488,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     resampler = output_resampler(pre, out_sample_rate, dev)
     voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
     loud = loudness_settings(loudness, true_peak, True, sr if out_sample_rate is None else int(out_sample_rate))
+    limiter = limiter_settings(limiter, loudness)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     with open(text_file, encoding="utf-8") as f:
         text = f.read()
@@ -481,7 +514,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     else:
         from .. import vocoder
         rate = sr if resampler is None else resampler.sr_out
-        (y,), (info["loudness"],) = normalize_rows([to_output_rate(y, sr, resampler, host=False)], rate, loud, dev)
+        (y,), (info["loudness"],) = normalize_rows([to_output_rate(y, sr, resampler, host=False)], rate, loud, dev, limiter)
         vocoder.write_wav(output, y, rate)
         print(loudness_line(output, info["loudness"]))
     if durations_out is not None:

@@ -1,5 +1,5 @@
-"""One sha256 per output tensor of fixed-seed cases through the 15 entries of the model-free measurement kernels (t2_align, t2_dtw,
-t2_join, t2_loudness, t2_pitch, t2_prosody, t2_psola, t2_resample, t2_stretch, t2_variance), through the C ABI only (_lib.make and
+"""One sha256 per output tensor of fixed-seed cases through the 16 entries of the model-free measurement kernels (t2_align, t2_dtw,
+t2_join, t2_limit, t2_loudness, t2_pitch, t2_prosody, t2_psola, t2_resample, t2_stretch, t2_variance), through the C ABI only (_lib.make and
 _lib.call), so that the same file runs against two builds of the library (T2_LIB_PATH selects one) and their outputs can be compared
 bit for bit.  Every entry runs on a ragged batch of 3 and on a single row, with every optional output requested; outputs start as
 zeros, so what a kernel leaves unwritten is the same in both builds.  The tables come from the package's host-side helpers.
@@ -128,7 +128,7 @@ def pitch_chain(case, g, n):
 
 
 def audio_chain(case, wav, n):
-    """stretch, join, loudness (with the normalised copy) and resample of the same rows."""
+    """stretch, join, loudness (with the normalised copy), the limiter on that copy and resample of the same rows."""
     B, ld = len(n), max(n)
     n32 = i32(n)
     N, D, P, Q = 512, 128, 1250, 1000
@@ -158,6 +158,11 @@ def audio_chain(case, wav, n):
                                        b1=b1, a1=a1, b2=b2, a2=a2, abs_gate=ABS_GATE, target=-23.0, max_gain=10.0 ** 1.5,
                                        ceiling=10.0 ** (-1.0 / 20.0), E=E, lde=lde, stat=stat, gain=gain, y=y, ldy=ld), stream())
     record(f"{case}.loudness", E=E, stat=stat, gain=gain, y=y)
+    env, curve, out, stat = zeros(B, ld), zeros(B, ld), zeros(B, ld), zeros(B, 8, dtype=torch.float64)      # a ceiling the copy passes often
+    _lib.call("t2_limit", _lib.make("T2Limit", x=y, ldx=ld, n=n32, table=torch.from_numpy(table).to(DEV), K=Kt, B=B, n_max=ld, L=110,
+                                    a=math.exp(-1.0 / (0.05 * SR)), ceiling=0.1, env=env, lde=ld, curve=curve, ldc=ld, y=out, ldy=ld, stat=stat),
+              stream())
+    record(f"{case}.limit", env=env, curve=curve, y=out, stat=stat)
     U, D, Kt, table = plan(SR, 16000)
     n_out = [-((-v * U) // D) for v in n]
     ldy = (max(n_out) + 63) // 64 * 64
@@ -216,7 +221,7 @@ def main():
     differ = []
     for name, t in OUT.items():
         line = f"{hashlib.sha256(t.numpy().tobytes()).hexdigest()}  {name}  {str(t.dtype)[6:]}{tuple(t.shape)}  {int(t.count_nonzero())} non-zero"
-        if other is not None and not same(other[name], t):
+        if other is not None and name in other and not same(other[name], t):      # (an entry the other build lacks is not compared)
             differ.append(name)
             line += f"  DIFFERS: max abs difference {float((other[name].double() - t.double()).abs().nan_to_num(nan=0.0).max()):.3e}"
         print(line)
