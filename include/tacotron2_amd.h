@@ -1227,6 +1227,55 @@ typedef struct {
 int t2_limit(const T2Limit* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Spectral subtraction of a stationary bias spectrum - a vocoder's own buzz - from a padded batch of waveforms (the method of the
+ * denoisers that ship with other Tacotron 2 / HiFi-GAN toolchains; no reference counterpart; csrc/t2_denoise.hip, the rule in DESIGN
+ * 5.22, restated in float64 in tests/denoise_ref.py).
+ *
+ * t2_denoise: x[b*ldx + i] float32 is a padded batch of B waveforms of finite samples, n[b] (DEVICE int32, 0 <= n[b] <= n_max) their
+ *   sample counts; nothing is read from a row at or behind n[b].  The geometry is fixed: N = T2_DENOISE_NFFT = 1024, hop H =
+ *   T2_DENOISE_HOP = 256, win [1024] the periodic Hann window and tw [768][2] = (cos, sin) of 2 pi k / 1024, both fp32 tables made
+ *   by the host in float64; bias [513] float32, strength a float >= 0.  Per row, with n = n[b]:
+ *   SHORT  n <= 512 cannot be reflected: y[i] = x[i] bit for bit, no frame is formed (F = 0, gated = 0, no mag row), flag `short`.
+ *   FRAMING  else the row is reflect-padded by 512 samples on both sides at its OWN length, p[j] = x[|j - 512|] in front and
+ *     x[2 (n - 1) - (j - 512)] behind, and has F = 1 + n / 256 frames; frame t is p[256 t .. 256 t + 1024), that is the samples
+ *     256 t - 512 .. 256 t + 511 of the row.  Every sample i < n lies under at least two frames with a positive window.
+ *   PER FRAME  a[j] = p[256 t + j] * win[j];  Z = the 1024-point DFT of a;  per bin k <= 512:  m = sqrtf(fmaf(re, re, im * im)),
+ *     thr = strength * bias[k] (one float32 product),  g = m > thr ? (m - thr) / m : 0,  Z[k] and Z[1024 - k] scaled by g;
+ *     c = the real part of the inverse DFT / 1024;  the frame's term at j is (c[j] * win[j]).
+ *     mag[(b*f_max + t)*ldm + k] = m, the magnitude BEFORE the gate, when mag is given.
+ *   OVERLAP-ADD  y[i] = (the sum of the terms of the frames over i, in ASCENDING t, from 0.0f) / (the sum over the same frames, in
+ *     the same order, of the float32 products win * win), i < n: the divisor is formed from the frames that exist and is not 1.5
+ *     near the row's ends (its minimum: tests/denoise_ref.py).  y[b*ldy + i] = 0.0f for n[b] <= i < ldy.  bias == 0 is the
+ *     identity up to the rounding of the two transforms.
+ *   y == NULL is ANALYSIS mode: mag alone is written (and stat 0 and 2); there is no inverse transform and bias is not read.
+ *   gated[b] int32 = the bins of the row with g == 0 (0 in analysis mode);  stat[b*4 + ..] fp64:  0 F,  1 gated,  2 flags: bit 0
+ *     short,  3: 0.  gated and stat are zeroed by the entry itself in front of the launch.
+ *   REFUSED on the device, not clamped: a row with n[b] outside 0 .. n_max gets flags = -1; nothing else is written for it (y and
+ *     mag included; its gated and the rest of its stat keep the entry's zeros) and x is not read.
+ *   ONE launch, grid (tiles of 16 hops = 4096 samples, B), 256 threads: a workgroup stages the samples its frames touch in LDS,
+ *     runs the 19 frames that reach its tile one after another through a radix-4 FFT in LDS, adds them into an LDS tile and writes
+ *     its samples once; the three halo frames are computed again by the neighbouring tile; a frame is counted and its mag row
+ *     written by ONE workgroup, the tile that owns it.  The float sums have a fixed order and the counts are integer atomics:
+ *     two calls give bit-identical y, mag, gated and stat, and a row's results do not depend on B, the leading dimensions or the
+ *     other rows.
+ *   T2_ERR_ARG before any launch: a null pointer (x only when n_max > 0; bias only with y; y and mag may each be NULL, not both),
+ *     B < 1 or > 65535, n_max < 0, ldx < n_max, a strength that is negative or not finite, with y: ldy < n_max, with mag:
+ *     ldm < 513 or f_max < 1 + n_max / 256. */
+enum { T2_DENOISE_NFFT = 1024, T2_DENOISE_HOP = 256, T2_DENOISE_NSTAT = 4 };
+typedef struct {
+    const float* x; int64_t ldx;                        /* rows are read only inside [0, n[b]) */
+    const int32_t* n;                                   /* [B] device */
+    int B, n_max;
+    const float* win; const float* tw;                  /* [1024]; [768][2]: host-made in float64 */
+    const float* bias; float strength;                  /* [513] */
+    float* y; int64_t ldy;                              /* [B][ldy], zeros behind n[b]; NULL: analysis mode */
+    float* mag; int64_t ldm; int f_max;                 /* [B][f_max][ldm]; NULL: not written */
+    int32_t* gated;                                     /* [B] */
+    double* stat;                                       /* [B][4] */
+} T2Denoise;
+int t2_denoise(const T2Denoise* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Log-mel front-end (datasets/tts_dataset.py:166-168,204; definition restated from datasets/prosody_dataset.py:39-50,67):
  * wav [n] fp32 -> out [frames = 1 + n/hop][n_mels] natural-log mel.  basis [2*(n_fft/2+1)][n_fft] = window-folded
  * [cos ; -sin] DFT rows, fb [n_mels][ldm] mel filterbank rows zero-padded to ldm = round_up(n_fft/2+1, 4) (both built by the

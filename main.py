@@ -338,10 +338,15 @@ def train(ctx, speech_dir, results_dir=None, resume_ckpt=None, prosody_model_che
               help="With --loudness: hold --true-peak with a look-ahead true-peak limiter on the GPU (5 ms look-ahead, 50 ms release) "
                    "instead of a lower gain for the whole file, so a file with a few tall peaks comes out at the loudness asked for; "
                    "the line tells the limited samples, the largest reduction and the loudness reached. Default: off.")
+@click.option("--denoise", required=False, type=float, default=None, metavar="STRENGTH",
+              help="Take the HiFi-GAN generator's own stationary buzz off the waveform, 0 to 1: the spectrum of a vocoded all-zero mel, "
+                   "times STRENGTH, is subtracted from every frame's magnitudes on the GPU - the first step behind the vocoder, in "
+                   "front of --tempo, --pitch-shift, --out-sample-rate and --loudness. NVIDIA's defaults are 0.01 for HiFi-GAN and 0.1 "
+                   "for WaveGlow. Needs --hifi-gan-checkpoint and a .wav target. Default: off.")
 def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed, controls, description, attention_window,
         forward_attention, durations_out=None, stop_threshold=None, out_sample_rate=None, text_file=None, max_chars=None,
         expand_numbers=False, pause=None, no_trim=False, level=False, fade_ms=None, batch_size=None, max_len=5000, tempo=None,
-        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False, loudness=None, true_peak=None, limiter=False):
+        pitch_shift=None, preserve_formants=False, pitch_range=None, ema=False, loudness=None, true_peak=None, limiter=False, denoise=None):
     if (text is None) == (text_file is None):
         raise click.UsageError("say needs exactly one of --text and --text-file" + (", got both" if text is not None else ""))
     limiter = True if limiter else None
@@ -350,6 +355,12 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
         try:
             loudness_settings(loudness, true_peak, wav_target(out, hifi_gan_checkpoint))
             limiter_settings(limiter, loudness)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    if denoise is not None:
+        from tacotron2_amd.run.say import denoise_settings
+        try:
+            denoise_settings(denoise, hifi_gan_checkpoint, out)
         except ValueError as e:
             raise click.UsageError(str(e))
     if text_file is None:
@@ -374,7 +385,7 @@ def say(ctx, checkpoint, text, out, speaker_id, hifi_gan_checkpoint, random_seed
                   description=description, attention_window=attention_window, forward_attention=forward_attention,
                   durations_out=durations_out, stop_threshold=stop_threshold, out_sample_rate=out_sample_rate, max_len=max_len,
                   tempo=tempo, pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range,
-                  loudness=loudness, true_peak=true_peak, limiter=limiter)
+                  loudness=loudness, true_peak=true_peak, limiter=limiter, denoise=denoise)
     if text_file is None:
         from tacotron2_amd.run.say import do_say
         do_say(text=text, **common)

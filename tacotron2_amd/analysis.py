@@ -16,6 +16,7 @@ from .stretch import hann_table, pitch_shift, time_stretch  # noqa: F401  (WSOLA
 from .psola import fold_lags, grain_table, pitch_ratio, pitch_shift_psola, psola  # noqa: F401  (TD-PSOLA pitch change, DESIGN 5.18: in psola.py)
 from .loudness import k_weighting, loudness, normalize_loudness  # noqa: F401  (BS.1770 loudness and true peak, DESIGN 5.20: in loudness.py)
 from .limiter import limit_peaks  # noqa: F401  (look-ahead true-peak limiter, DESIGN 5.21: in limiter.py)
+from .denoise import denoise, stft_magnitudes, vocoder_bias  # noqa: F401  (vocoder-bias spectral subtraction, DESIGN 5.22: in denoise.py)
 from .variance import VAR_MAX_L, VAR_MAX_T, VAR_NSTAT, VAR_STATS, char_variance  # noqa: F401
 
 PROSODY_MAX_T = K["PROSODY_MAX_T"]        # frames of one utterance in t2_prosody_stats

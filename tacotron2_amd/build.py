@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtacotron2_amd.so")
 SOURCES = ["t2_error.cpp", "t2_gemm.hip", "t2_lstm.hip", "t2_attention.hip", "t2_elementwise.hip", "t2_logmel.hip",
            "t2_infer.hip", "t2_align.hip", "t2_dtw.hip", "t2_prosody.hip", "t2_pitch.hip", "t2_resample.hip", "t2_variance.hip",
-           "t2_join.hip", "t2_stretch.hip", "t2_psola.hip", "t2_loudness.hip", "t2_limit.hip"]
+           "t2_join.hip", "t2_stretch.hip", "t2_psola.hip", "t2_loudness.hip", "t2_limit.hip", "t2_denoise.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

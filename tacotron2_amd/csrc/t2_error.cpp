@@ -17,6 +17,7 @@ extern "C" int t2_sizeof(const char* name) {
     T2_SZ(T2AlignDur); T2_SZ(T2AttnZone); T2_SZ(T2LossOpts); T2_SZ(T2MelCeps); T2_SZ(T2Dtw);
     T2_SZ(T2Yin); T2_SZ(T2ProsodyStats); T2_SZ(T2VoiceQuality); T2_SZ(T2CorpusStats); T2_SZ(T2PitchViterbi); T2_SZ(T2F0PathStats);
     T2_SZ(T2Resample); T2_SZ(T2CharVariance); T2_SZ(T2Join); T2_SZ(T2Stretch); T2_SZ(T2Psola); T2_SZ(T2Loudness); T2_SZ(T2Limit);
+    T2_SZ(T2Denoise);
     T2_SZ(T2AdamOpt);
 #undef T2_SZ
     return -1;

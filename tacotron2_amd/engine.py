@@ -26,9 +26,9 @@ from . import _args
 from ._lib import call, make, stream as _stream  # noqa: F401  (hifigan and the model import _stream from here)
 # the documented module API: the model-free measurements live in analysis, and engine.<name> is the same object
 from .analysis import (CORPUS_NSTAT, F0_NSTAT, PITCH_MAX_STATES, PROSODY_MAX_T, PROSODY_NSTAT, VITERBI_DEFAULTS, VQ_MAX_CYCLES,  # noqa: F401
-                       YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, f0_figures, f0_path_stats, fade_table, fold_lags, join_audio,
-                       k_weighting, limit_peaks, loudness, normalize_loudness, pitch_ratio, pitch_shift, pitch_shift_psola, pitch_viterbi, prosody_stats, psola, resample, time_stretch,
-                       voice_quality, yin, yin_lags)
+                       YIN_DEFAULTS, YIN_MAX_SPAN, _RESAMPLERS, corpus_stats, denoise, f0_figures, f0_path_stats, fade_table, fold_lags, join_audio,
+                       k_weighting, limit_peaks, loudness, normalize_loudness, pitch_ratio, pitch_shift, pitch_shift_psola, pitch_viterbi, prosody_stats, psola, resample, stft_magnitudes, time_stretch,
+                       vocoder_bias, voice_quality, yin, yin_lags)
 # likewise the option checks, which live in options (no torch, no library) and are served from here as before
 from .options import (LOSS_DEFAULTS, MEL_LOSSES, check_attention_window, check_forward_attention, check_guided_attention,  # noqa: F401
                       check_loss_options, check_rate, check_stop_threshold, stop_logit)

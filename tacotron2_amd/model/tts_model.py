@@ -205,7 +205,8 @@ class TTSModel(nn.Module):
         WSOLA stretch of all pieces in one launch in front of the join; preserve_formants=True and pitch_range=K (0 .. 2) change the
         pitch by TD-PSOLA instead, one launch of each kernel for all pieces; loudness=LUFS (-40 .. -5)
         and true_peak=DBTP (-9 .. 0, default -1) bring the joined waveform to that BS.1770 programme loudness as the last step
-        (DESIGN 5.20), and limiter=True holds that ceiling with the look-ahead true-peak limiter.  Loads no checkpoint.  Returns (waveform, plan, per-piece
+        (DESIGN 5.20), and limiter=True holds that ceiling with the look-ahead true-peak limiter; denoise=STRENGTH (0 .. 1, with a
+        hifigan.Generator) takes that generator's own bias spectrum off each chunk as the first step behind it.  Loads no checkpoint.  Returns (waveform, plan, per-piece
         dict)."""
         from ..run.say import say_document
         pre = dict(preprocessing or {})

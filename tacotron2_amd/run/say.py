@@ -216,6 +216,43 @@ def loudness_fields(rec: dict) -> dict:
             if k in rec}
 
 
+def denoise_settings(denoise, hifi_gan_checkpoint, output=None) -> Optional[float]:
+    """--denoise STRENGTH of `say`, checked before anything is decoded: None when it is not given or 0 - nothing runs
+    then -, else the strength, 0 .. 1, for analysis.denoise.  The bias that is taken off is the HiFi-GAN generator's own (Griffin-Lim
+    has no learned bias to remove), and the result is a waveform, so a `.npy` name is refused whatever vocodes."""
+    import math
+    from ..denoise import STRENGTH_LIMITS
+    if denoise is None:
+        return None
+    lo, hi = STRENGTH_LIMITS
+    if isinstance(denoise, bool) or not isinstance(denoise, (int, float)) or not math.isfinite(denoise) or not lo <= denoise <= hi:
+        raise ValueError(f"--denoise must lie in {lo:g} .. {hi:g}, got {denoise!r}")
+    if hifi_gan_checkpoint is None:
+        raise ValueError("--denoise needs --hifi-gan-checkpoint: it removes that generator's bias, and Griffin-Lim has none to remove")
+    if output is not None and str(output).endswith(".npy"):
+        raise ValueError(f"--denoise needs a .wav target, got {output!r}: a log-mel has no vocoder bias")
+    return float(denoise) if denoise > 0 else None
+
+
+def denoise_batch(gen, buf: torch.Tensor, n: List[int], strength: float):
+    """The FIRST step behind the generator: a padded batch (B, ld) on the device, exactly as vocoded and at the model's rate, through
+    ONE analysis.denoise call with the generator's own bias (analysis.vocoder_bias: computed once per generator, one t2_denoise call
+    in analysis mode).  (the denoised batch, the gated fraction per row as host numbers)."""
+    from .. import analysis
+    y, stats = analysis.denoise(buf, n, analysis.vocoder_bias(gen), strength)
+    return y, stats["gated_fraction"].cpu().tolist()
+
+
+def denoise_line(name: str, strength: float, fraction: float) -> str:
+    """The line `say` prints per file written with --denoise."""
+    return f"say: {name}: denoise {strength:g}, {100.0 * fraction:.2f} % of bins gated"
+
+
+def denoise_fields(strength: float, fraction: float) -> dict:
+    """What a --durations-out object gains with --denoise."""
+    return dict(denoise_strength=strength, denoise_gated_fraction=fraction)
+
+
 def do_say(dataset_config: dict, training_config: dict, model_config: dict, extensions_config: dict, device: int,
            checkpoint: str, text: Union[str, List[str]], output: str, hifi_gan_checkpoint: Optional[str] = None,
            random_seed: Optional[int] = None, speaker_id: Optional[int] = None, controls: Optional[str] = None,
@@ -223,8 +260,13 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
            forward_attention: Optional[bool] = None, durations_out: Optional[str] = None,
            stop_threshold: Optional[float] = None, out_sample_rate: Optional[int] = None, tempo: Optional[float] = None,
            pitch_shift: Optional[float] = None, preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None,
-           loudness: Optional[float] = None, true_peak: Optional[float] = None, limiter: Optional[bool] = None):
-    """limiter (only with loudness): the ceiling is held by the look-ahead true-peak limiter (analysis.normalize_loudness(limiter=True),
+           loudness: Optional[float] = None, true_peak: Optional[float] = None, limiter: Optional[bool] = None,
+           denoise: Optional[float] = None):
+    """denoise: 0 .. 1 (only with a HiFi-GAN checkpoint and a `.wav` name) - every text's waveform exactly as vocoded, at the model's
+    rate, becomes one row of ONE analysis.denoise call with the generator's own bias spectrum (analysis.vocoder_bias),
+    in front of the voice chain, out_sample_rate and loudness; one line per file is printed and `durations_out` objects gain
+    `denoise_strength` and `denoise_gated_fraction`.  None or 0: nothing of this runs.
+    limiter (only with loudness): the ceiling is held by the look-ahead true-peak limiter (analysis.normalize_loudness(limiter=True),
     DESIGN 5.21: t2_loudness, t2_limit, t2_loudness) where the gain alone would be lowered; the line then tells the limited samples,
     the largest reduction and the loudness reached, and `durations_out` objects gain `limited_samples`, `limiter_max_reduction_db`
     and `output_lufs`.  None: nothing of this runs.
@@ -259,6 +301,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     voice = voice_settings(tempo, pitch_shift, sample_rate(pre), audio, preserve_formants, pitch_range)
     loud = loudness_settings(loudness, true_peak, audio, sample_rate(pre) if out_sample_rate is None else int(out_sample_rate))
     limiter = limiter_settings(limiter, loudness)
+    den = denoise_settings(denoise, hifi_gan_checkpoint, output)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)   # run/say.py: no abbreviations
     texts = [text] if isinstance(text, str) else list(text)
     _, chars, lens = encode_texts(enc, texts, dev)
@@ -269,7 +312,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     mels = [m[:n] for m, n in zip(post.cpu().numpy(), frames)]
     sr = sample_rate(pre)
     records = scale_records(duration_records(model, enc, texts, align, lens, frames, sr), voice) if durations_out is not None else None
-    if records is not None and loud is None:
+    if records is not None and loud is None and den is None:
         with open(durations_out, "w") as f:
             json.dump(records, f)
     if not audio:
@@ -281,16 +324,29 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
         vocode = lambda m: gen(torch.from_numpy(np.ascontiguousarray(m.T)).to(dev))[0, 0].cpu()
     else:
         vocode = lambda m: gl.mel_to_audio(torch.from_numpy(m), seed=int(random_seed or 0))
+    names = [output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav" for i in range(len(mels))]
+    clean = None
+    wave = lambda i: vocode(mels[i]) if clean is None else clean[i]      # text i behind the vocoder, and behind --denoise
+    if den is not None:                                   # every text's waveform as vocoded, in one padded batch: ONE denoise launch
+        buf, n = pack_rows([torch.as_tensor(vocode(m)).detach().float().reshape(-1) for m in mels], dev)
+        buf, gated = denoise_batch(gen, buf, n, den)
+        clean = [buf[i, :n[i]].cpu() for i in range(len(mels))]
+        for name, frac in zip(names, gated):
+            print(denoise_line(name, den, frac))
+        if records is not None:
+            records = [dict(r, **denoise_fields(den, frac)) for r, frac in zip(records, gated)]
+            if loud is None:
+                with open(durations_out, "w") as f:
+                    json.dump(records, f)
     stretched = None
     if voice is not None and voice.active:                # every text's waveform in one padded batch: ONE stretch launch
-        rows, n_out = apply_voice(*pack_rows([torch.as_tensor(vocode(m)).detach().float().reshape(-1) for m in mels], dev), voice)
+        rows, n_out = apply_voice(*pack_rows([torch.as_tensor(wave(i)).detach().float().reshape(-1) for i in range(len(mels))], dev), voice)
         stretched = [rows[i, :n_out[i]].cpu() for i in range(len(mels))]
-    names = [output if isinstance(text, str) else f"{output.rsplit('.', 1)[0]}_{i}.wav" for i in range(len(mels))]
     if loud is not None:                                  # every text as it would be written, in one padded batch: ONE launch
         from .. import vocoder
         rate = sr if resampler is None else resampler.sr_out
-        rows, recs = normalize_rows([to_output_rate(vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
-                                     for i, m in enumerate(mels)], rate, loud, dev, limiter)
+        rows, recs = normalize_rows([to_output_rate(wave(i) if stretched is None else stretched[i], sr, resampler, host=True)
+                                     for i in range(len(mels))], rate, loud, dev, limiter)
         for name, row, rec in zip(names, rows, recs):
             vocoder.write_wav(name, row.cpu(), rate)
             print(loudness_line(name, rec))
@@ -301,7 +357,7 @@ def do_say(dataset_config: dict, training_config: dict, model_config: dict, exte
     for i, m in enumerate(mels):
         # several texts: `<output without its extension>_<i>.wav`.  Griffin-Lim is reached with a name that ends in ".wav" only, whose
         # last dot is that extension's, so this is the `output[:-4]` of the reference's branch as well
-        write_audio(names[i], vocode(m) if stretched is None else stretched[i], sr, resampler, host=True)
+        write_audio(names[i], wave(i) if stretched is None else stretched[i], sr, resampler, host=True)
     return mels
 
 
@@ -345,7 +401,7 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                  controls: Optional[str] = None, description: Optional[str] = None, random_seed: Optional[int] = None,
                  durations: bool = False, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
                  preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None, loudness: Optional[float] = None,
-                 true_peak: Optional[float] = None, limiter: Optional[bool] = None):
+                 true_peak: Optional[float] = None, limiter: Optional[bool] = None, denoise: Optional[float] = None):
     """Pieces (datasets.document.Piece, or a text, which is split at the defaults) -> one waveform on the model's device.
     The pieces are sorted by encoded length and decoded in chunks of batch_size through the model's free-running forward, with the
     decode settings that are on the model (common.free_run).  `vocoder` is a loaded hifigan.Generator - each chunk's PADDED batch
@@ -363,11 +419,14 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     brought to that programme loudness by analysis.normalize_loudness as the last step; `level` keeps moving the pieces
     towards each other in front of it.  (do_say_document, which may resample behind the join, normalises behind that instead.)
     limiter (only with loudness): normalize_rows' limiter - the ceiling is held by the look-ahead limiter.
+    denoise (0 .. 1, only with a hifigan.Generator): each chunk's padded batch, cut at frames * 256, goes through ONE analysis.denoise
+    call with the generator's own bias (denoise_batch) as the first step behind the generator, in front of everything above.
     A piece that ran into max_len without stopping is kept, cut there, and marked stopped=False.
     Returns (y (total,) float32, plan - join_audio's, device tensors -, info): info = dict(pieces, frames, stopped, n, pause,
     waveforms - the per-piece device tensors that went into the join -, chunks, join - the keyword arguments of the join_audio
     call -, durations - duration_records per piece, or None -, voice - voice_settings, or None -, loudness - normalize_rows' record
-    of the document, or None)."""
+    of the document, or None -, denoise - None, or dict(strength, gated_fraction - of the document's bins -, pieces - the gated
+    fraction per piece))."""
     from .. import analysis
     from ..datasets.document import split_document
     from ..hifigan import Generator
@@ -383,12 +442,13 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     voice = voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
     loud = loudness_settings(loudness, true_peak, True, sr)
     limiter = limiter_settings(limiter, loudness)
+    den = denoise_settings(denoise, True if isinstance(vocoder, Generator) else None)
     texts = [p.text for p in pieces]
     ids, _, _ = encode_texts(enc, texts)
     order = sorted(range(len(ids)), key=lambda i: (len(ids[i]), i))
     chunks = [order[k:k + batch_size] for k in range(0, len(order), batch_size)]
     P = len(pieces)
-    waves, frames, stopped, records = [None] * P, [0] * P, [False] * P, [None] * P
+    waves, frames, stopped, records, gated = [None] * P, [0] * P, [False] * P, [None] * P, [0.0] * P
     for ch in chunks:
         chars, lens = pad_ids([ids[i] for i in ch], dev)
         post, gates, align = free_run(model, chars, lens, max_len, **conditioning(model, len(ch), dev, speaker_id, controls, description))
@@ -398,6 +458,10 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
                 records[i] = rec
         if isinstance(vocoder, Generator):
             rows = vocoder(post.transpose(1, 2))[:, 0]                        # the padded batch in one call
+            if den is not None:
+                rows, fractions = denoise_batch(vocoder, rows, [f * 256 for f in fr], den)
+                for k, i in enumerate(ch):
+                    gated[i] = fractions[k]
             out = [rows[k, :fr[k] * 256] for k in range(len(ch))]
         else:
             out = [torch.as_tensor(vocoder.mel_to_audio(post[k, :fr[k]], seed=int(random_seed or 0))).float().reshape(-1).to(dev)
@@ -417,8 +481,12 @@ def say_document(model, pieces, enc: TextEncoder, pre: dict, vocoder, max_len: i
     loud_rec = None
     if loud is not None:
         (y,), (loud_rec,) = normalize_rows([y], sr, loud, dev, limiter)
+    den_rec = None
+    if den is not None:                                   # (a piece of f mel frames has 1 + f frames of bins, none when it is copied)
+        rows_of = [1 + f if f * 256 > 512 else 0 for f in frames]
+        den_rec = dict(strength=den, gated_fraction=sum(g * r for g, r in zip(gated, rows_of)) / max(sum(rows_of), 1), pieces=gated)
     return y, plan, dict(pieces=pieces, frames=frames, stopped=stopped, n=n, pause=pause, waveforms=waves, chunks=len(chunks),
-                         join=join, durations=records if durations else None, voice=voice, loudness=loud_rec)
+                         join=join, durations=records if durations else None, voice=voice, loudness=loud_rec, denoise=den_rec)
 
 
 def document_records(info: dict, plan: dict, sample_rate: int) -> list:
@@ -462,7 +530,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
                     expand_numbers: bool = False, pause=None, trim: bool = True, level: bool = False, fade_ms: float = 5.0,
                     batch_size: int = 64, tempo: Optional[float] = None, pitch_shift: Optional[float] = None,
                     preserve_formants: Optional[bool] = None, pitch_range: Optional[float] = None, loudness: Optional[float] = None,
-                    true_peak: Optional[float] = None, limiter: Optional[bool] = None):
+                    true_peak: Optional[float] = None, limiter: Optional[bool] = None, denoise: Optional[float] = None):
     """`say --text-file`: the file is read, its numbers expanded if asked, split (datasets/document.py) and spoken by say_document;
     the joined waveform is resampled to out_sample_rate if given (one Resampler call) and written by ONE write_wav call.
     tempo, pitch_shift, preserve_formants, pitch_range: say_document's, in front of the join.
@@ -470,6 +538,8 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     so the loudness is the programme's and the ceiling holds for the file; a line is printed, every `durations_out` object gains the
     document's `loudness_lufs`, `gain_db` and `true_peak_dbtp`, and info["loudness"] holds them.
     limiter (only with loudness): the joined document is limited as that one row (normalize_rows' limiter).
+    denoise: say_document's, per chunk in front of everything else; a line is printed, every `durations_out` object gains
+    `denoise_strength` and its piece's `denoise_gated_fraction`, and info["denoise"] holds them.
     durations_out: document_records as a JSON list.  A piece that did not stop is reported on stderr; the exit status stays 0.
     Returns say_document's (y, plan, info), y as written (after resampling and normalisation)."""
     import sys
@@ -489,6 +559,7 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     voice_settings(tempo, pitch_shift, sr, True, preserve_formants, pitch_range)
     loud = loudness_settings(loudness, true_peak, True, sr if out_sample_rate is None else int(out_sample_rate))
     limiter = limiter_settings(limiter, loudness)
+    denoise_settings(denoise, hifi_gan_checkpoint, output)
     enc = TextEncoder(pre["allowed_chars"], pre.get("end_token"), expand_abbrev=False)
     with open(text_file, encoding="utf-8") as f:
         text = f.read()
@@ -504,7 +575,9 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
     y, plan_, info = say_document(model, pieces, enc, pre, gen if gen is not None else gl, max_len=max_len, batch_size=batch_size,
                                   pauses=pauses, trim=trim, level=level, fade_ms=fade_ms, speaker_id=speaker_id, controls=controls,
                                   description=description, random_seed=random_seed, durations=durations_out is not None, tempo=tempo,
-                                  pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range)
+                                  pitch_shift=pitch_shift, preserve_formants=preserve_formants, pitch_range=pitch_range, denoise=denoise)
+    if info["denoise"] is not None:
+        print(denoise_line(output, info["denoise"]["strength"], info["denoise"]["gated_fraction"]))
     for i, ok in enumerate(info["stopped"]):
         if not ok:
             print(f"say: piece {i} did not stop within --max-len {max_len} frames and is cut there: {pieces[i].text[:40]!r}", file=sys.stderr)
@@ -519,8 +592,11 @@ def do_say_document(dataset_config: dict, training_config: dict, model_config: d
         print(loudness_line(output, info["loudness"]))
     if durations_out is not None:
         more = loudness_fields(info["loudness"]) if loud is not None else {}
+        den, recs = info["denoise"], document_records(info, plan_, sr)
+        if den is not None:
+            recs = [dict(r, **denoise_fields(den["strength"], frac)) for r, frac in zip(recs, den["pieces"])]
         with open(durations_out, "w") as f:
-            json.dump([dict(r, **more) for r in document_records(info, plan_, sr)], f)
+            json.dump([dict(r, **more) for r in recs], f)
     torch.cuda.synchronize(dev)
     print(f"say: {len(pieces)} pieces in {info['chunks']} chunks, {seconds:.2f} s of audio in {time.perf_counter() - t_start:.2f} s")
     return y, plan_, info
