@@ -53,18 +53,32 @@ def _hip_train_and_compare(d, P, case, dev, kw_cpu=None, kw_dev=None, grad_tol=3
     torch.cuda.synchronize()
     if guard_bytes:
         assert eng.guard_check() == []
+    _compare_train_step(eng, ps, outs, ctx, loss3, (ref, loss, grads, new_stats), grad_tol=grad_tol)
+    return eng, ps
+
+
+def _compare_train_step(eng, ps, outs, ctx, loss3, reference, grad_tol=3e-4):
+    """The comparison half of _hip_train_and_compare, for callers that drive the step themselves (tests/test_gpu_engine_reuse.py: one
+    engine over many steps): the persistent launches' flag, then outputs, masked gates, alignments, loss, EVERY parameter gradient and
+    the BatchNorm running statistics of `ps` against reference = (outputs, loss, gradients, new_stats) of the oracle.  Returns the
+    measured figures (printed before anything is asserted)."""
+    ref, loss, grads, new_stats = reference
     eng.check_persistent_kernels()
+    sd = ps.state_dict()
+    fig = dict(mel_l1=l1(outs[0], ref[0]), post_l1=l1(outs[1], ref[1]), mel_max=mx(outs[0], ref[0]), post_max=mx(outs[1], ref[1]),
+               align_max=mx(outs[3], ref[3]), loss_rel=abs(float(loss3.sum()) - loss) / max(1.0, abs(loss)),
+               bn_max=max([mx(sd[k], v) for k, v in new_stats.items() if not k.endswith("num_batches_tracked")], default=0.0))
+    print(f"train step (B,L,T)=({ctx['B']},{ctx['L']},{ctx['T']}): " + ", ".join(f"{k} {v:.2e}" for k, v in fig.items()))
     assert l1(outs[0], ref[0]) < MEL_L1_TOL and l1(outs[1], ref[1]) < MEL_L1_TOL, (l1(outs[0], ref[0]), l1(outs[1], ref[1]))
     assert mx(outs[0], ref[0]) < 1e-3 and mx(outs[1], ref[1]) < 2e-3
     assert mx(outs[3], ref[3]) < 2e-5
     assert ((outs[2].cpu() == -1000.0) == (ref[2] == -1000.0)).all()
     assert abs(float(loss3.sum()) - loss) < 2e-5 * max(1.0, abs(loss))
     _grad_check(ps, grads, tol=grad_tol)
-    sd = ps.state_dict()
     for k, v in new_stats.items():
         if not k.endswith("num_batches_tracked"):
             assert mx(sd[k], v) < 1e-5, k
-    return eng, ps
+    return fig
 
 
 @pytest.mark.parametrize("B,L,T", [(3, 32, 16), (17, 29, 13)])

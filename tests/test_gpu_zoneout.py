@@ -417,15 +417,10 @@ def test_training_step_against_float64(dev, B, r, dec_chain):
     _grad_report(ps, _ref_grads(c, tot), label)
 
 
-def test_training_step_with_forward_and_guided_attention(dev):
-    from tests.test_gpu_reduction_factor import _check_outputs, _grad_report
-    B, L, T, r = 3, 21, 10, 2
-    c = _train_case(B, L, T, r, 431, True)
-    (ci, lens, mel, tl, gate, m), o = c[2], c[5]
-    sigma, alpha = 0.4, 1.0
+def _guided_term(al, lens, tl, r, sigma, alpha):
+    """The guided-attention term on the reference's alignments (closed form of tests/reduction_ref.py, differentiable here)."""
+    B = al.shape[0]
     steps = RR.steps_of(tl.to(torch.int64), r)
-    S, al = o[3].shape[1], o[3]
-    # the guided-attention term on the reference's alignments (closed form of tests/reduction_ref.py, differentiable here)
     g_tot = torch.zeros((), dtype=torch.float64)
     for b in range(B):
         Nb, Tb = int(lens[b]), int(steps[b])
@@ -434,6 +429,16 @@ def test_training_step_with_forward_and_guided_attention(dev):
         g_tot = g_tot + ((1.0 - torch.exp(-((ll - ss) ** 2) / (2.0 * sigma * sigma))) * al[b, :Tb, :Nb]).sum() / (Nb * Tb)
     g_tot = alpha / B * g_tot
     assert abs(float(g_tot.detach()) - RR.guided_mask_sum(al.detach(), lens, tl, r, sigma, alpha)) < 1e-12
+    return g_tot
+
+
+def test_training_step_with_forward_and_guided_attention(dev):
+    from tests.test_gpu_reduction_factor import _check_outputs, _grad_report
+    B, L, T, r = 3, 21, 10, 2
+    c = _train_case(B, L, T, r, 431, True)
+    (ci, lens, mel, tl, gate, m), o = c[2], c[5]
+    sigma, alpha = 0.4, 1.0
+    g_tot = _guided_term(o[3], lens, tl, r, sigma, alpha)
     tot, bce, ml, pl = R.tts_loss(o[0], o[1], o[2], mel.double(), gate.double())
     eng, ps, outs, loss3, _ = _engine_step(c, dev, guided=(sigma, alpha), forward_attention=True)
     _check_outputs(outs, o, "zoneout + forward + guided attention")
